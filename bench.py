@@ -11,8 +11,14 @@ synthetic wideband int16 IQ (default 2^26 samples = 256 MiB) for every channel a
           the kernel; each rank demodulates only its own contiguous channel range - no other collective.
 
 Metric (BASELINE.json): input IQ MSamp/s x channels demodulated, whole job.  The JSON line also carries
-the HBM roofline of the dominant kernel (algorithmic bytes / HIP-event kernel time), the compute roofline of
-the kernel variant in use next to it, and - on rank 0 at N = 1 - the oracle's CPU path timed on the host cores.
+the HBM roofline of the dominant kernel (algorithmic bytes / HIP-event kernel time) and the compute roofline of
+the kernel variant in use next to it, both from the timed launches themselves.
+
+A plain run sets up, settles, warms up, times --steps launches and prints the line.  --full adds everything that
+takes work of its own behind the timed region: the self-check of the last timed launch against the oracle
+(`verified`), the board sample, and - on rank 0 at N = 1 - the oracle's CPU path timed on the host cores, the
+float32 path, the block-size series, end to end, the FLEX chain, the other geometries, the north-star shape and
+the device-group path.  --dump-outputs DIR writes the last timed launch's PCM (bench.py --help).
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ SIMDS = 1024                # 256 CUs x 4
 MFMA_ISSUE_CYCLES = 16      # v_mfma_i32_16x16x64_i8: 4 passes x 4 cycles
 VALU_ISSUE_CYCLES = 3       # mean issue cost of the kernels' other vector instructions (profiles/r02_ubench_ops.txt: 2 .. 4)
 FP32_VECTOR_PEAK_TFLOPS = 157.3  # packed FP32 on the vector ALUs: 256 CU x 256 flop/clk x 2.4 GHz
+DUMP_BYTES = 48 << 20       # --dump-outputs: float32 bytes written at most, all files of a run together
 
 
 def parse():
@@ -73,6 +80,13 @@ def parse():
     ap.add_argument("--no-chain", action="store_true", help="skip the device-resident FLEX chain line")
     ap.add_argument("--no-series", action="store_true", help="skip the block-size series and the host-fed end-to-end line")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the self-check against the oracle, the board sample, the CPU baseline, the "
+                         "float32 path, the block-size series, end to end, the FLEX chain, the other geometries, the north-star shape, "
+                         "the device-group comparison and, at N > 1, the one-GPU line (the --no-* flags above thin it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the PCM the last timed step left on the device as DIR/*.npy (float32; a fixed, seeded sample of "
+                         "its columns when the whole would exceed %d MB)" % (DUMP_BYTES >> 20))
     return ap.parse_args()
 
 
@@ -164,6 +178,36 @@ def verify_last_block(pkg, eng, fs, decim, taps, offs, gains, outputs_before):
     return {"verified": bad == 0, "mismatches": bad, "outputs_checked": checked, "channels": chans, "windows": wins,
             "outputs_before_block": int(outputs_before),
             "how": "last timed launch's PCM in HBM vs oracle/mfm_oracle.c on the same input window, bit-exact"}
+
+
+def dump_outputs(out_dir, name, engines, max_bytes):
+    """--dump-outputs: the PCM the last timed launch of each engine left in HBM, the engines' channels one after the other, as
+    out_dir/<name>.npy in float32 (int16 values, exact), shape (channels, outputs).  Above max_bytes only a fixed, seeded choice
+    of output columns is kept (the same columns on every row; the same choice for the same arguments on every run).  Runs
+    after the timed region and before anything launches again."""
+    import ctypes as C
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    views = [eng.last_output_device()[:3] for eng in engines]
+    rows = sum(eng.nr_channels for eng in engines)
+    nout = views[0][2]
+    assert all(v[2] == nout for v in views), [v[2] for v in views]
+    cols = None
+    if rows * nout * 4 > max_bytes:
+        k = max(1, max_bytes // (4 * rows))
+        cols = np.sort(np.random.default_rng(0x6d666d).choice(nout, size=k, replace=False))
+    out = np.empty((rows, nout if cols is None else len(cols)), np.float32)
+    row = np.empty(nout, np.int16)
+    r = 0
+    for eng, (dptr, stride, _) in zip(engines, views):
+        for c in range(eng.nr_channels):
+            rc = hip.hipMemcpy(row.ctypes.data, C.c_void_p(dptr + 2 * stride * c), 2 * nout, 2)
+            if rc != 0:
+                raise SystemExit(f"hipMemcpy of PCM row {r} failed: {rc}")
+            out[r] = row if cols is None else row[cols]
+            r += 1
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), out)
 
 
 def cpu_baseline(pkg, fs, decim, taps, offs, gains, target_s):
@@ -957,11 +1001,12 @@ def hip_memcpy_h2d(dst_ptr, arr):
         raise SystemExit("hipMemcpy (host to device) failed")
 
 
-def group_run(pkg, args, devices, shared, fs, decim, taps, offs, gains, block, steps, warmup, settle_s):
+def group_run(pkg, args, devices, shared, fs, decim, taps, offs, gains, block, steps, warmup, settle_s, full=True, dump_dir=None):
     """One pass of the protocol through the library's device group (mfm_group_*; csrc/mfm_group.hip): the channels are cut into
     contiguous shards, one engine per device, every block goes from the root's input buffer to the others by the library's own
     RCCL exchange (scatter + all-gather) and is submitted on every shard - what host/mfm_receiver.c runs for "gpuDevices": [..].
-    One process, one host thread.  Blocks are resident in the root's HBM buffers before the timed region."""
+    One process, one host thread.  Blocks are resident in the root's HBM buffers before the timed region.  `full`: the self-check
+    against the oracle and the board sample behind the timed region; `dump_dir`: --dump-outputs of the last timed block."""
     b = pkg.binding
     S = len(devices)
     g = b.Group(fs, decim, block, devices=tuple(devices),
@@ -1006,6 +1051,8 @@ def group_run(pkg, args, devices, shared, fs, decim, taps, offs, gains, block, s
     st1 = [g.stats(s) for s in range(g.nr_shards)]
     eng0 = g.shard_engine(0)
     cycles = launch_clocks(eng0, min(steps, 1024))
+    if dump_dir:
+        dump_outputs(dump_dir, "pcm", [g.shard_engine(s) for s in range(g.nr_shards)], DUMP_BYTES)
     uses, nblk, moved = g.exchange_info()
     shards = []
     for s in range(g.nr_shards):
@@ -1020,7 +1067,7 @@ def group_run(pkg, args, devices, shared, fs, decim, taps, offs, gains, block, s
     # every shard's last block against the oracle, on the input THAT shard's launch read: a wrong scatter or all-gather offset
     # corrupts the input of the non-root shards only
     per_shard = []
-    for s in range(g.nr_shards):
+    for s in range(g.nr_shards if full else 0):
         lo_s, n_s, _ = g.shard_info(s)
         eng_s = g.shard_engine(s)
         n_last = eng_s.last_output_device()[2]
@@ -1028,26 +1075,30 @@ def group_run(pkg, args, devices, shared, fs, decim, taps, offs, gains, block, s
                               g.stats(s)["outputs"] - n_last)
         v["shard"] = s
         per_shard.append(v)
-    verified = dict(per_shard[0])
-    verified["verified"] = all(v["verified"] for v in per_shard)
-    verified["shards_verified"] = [bool(v["verified"]) for v in per_shard]
-    if not verified["verified"]:
-        verified["failed_shards"] = [v for v in per_shard if not v["verified"]]
+    verified = {"verified": None, "how": "not checked: bench.py --full runs the self-check"}
+    if per_shard:
+        verified = dict(per_shard[0])
+        verified["verified"] = all(v["verified"] for v in per_shard)
+        verified["shards_verified"] = [bool(v["verified"]) for v in per_shard]
+        if not verified["verified"]:
+            verified["failed_shards"] = [v for v in per_shard if not v["verified"]]
     detail = [g.exchange_detail(s) for s in range(g.nr_shards)]
-    sampler = BoardSampler(0)   # behind the timed region and the self-check, while the same steps run again (see main())
-    k, started, t_load = 0, False, time.perf_counter()
-    while k < 16 or ((not started or sampler.thread.is_alive()) and k < 40000):
-        step()
-        k += 1
-        if k % 64 == 0:
-            g.sync()
-        if not started and time.perf_counter() - t_load >= BOARD_SAMPLE_AFTER_S:
-            sampler.start()
-            started = True
-    g.sync()
-    smi = sampler.result()
-    if smi is not None:
-        smi["when"] = "after %.1f s of further back-to-back steps of the same workload behind the timed region" % BOARD_SAMPLE_AFTER_S
+    smi = None
+    if full:
+        sampler = BoardSampler(0)   # behind the timed region and the self-check, while the same steps run again (see main())
+        k, started, t_load = 0, False, time.perf_counter()
+        while k < 16 or ((not started or sampler.thread.is_alive()) and k < 40000):
+            step()
+            k += 1
+            if k % 64 == 0:
+                g.sync()
+            if not started and time.perf_counter() - t_load >= BOARD_SAMPLE_AFTER_S:
+                sampler.start()
+                started = True
+        g.sync()
+        smi = sampler.result()
+        if smi is not None:
+            smi["when"] = "after %.1f s of further back-to-back steps of the same workload behind the timed region" % BOARD_SAMPLE_AFTER_S
     try:
         rccl_file = b.rccl_library() if uses else None
     except Exception as exc:   # (a group that exchanges has loaded it: this cannot fail there)
@@ -1070,7 +1121,8 @@ def group_main(args, pkg, devices, shared, world_for_line):
     fs, decim, taps, offs, gains = pkg.synth.plan(args.config, nr_channels=total_ch)
     block = 1 << args.block_log2
     T = len(taps)
-    r = group_run(pkg, args, devices, shared, fs, decim, taps, offs, gains, block, args.steps, args.warmup, args.settle_seconds)
+    r = group_run(pkg, args, devices, shared, fs, decim, taps, offs, gains, block, args.steps, args.warmup, args.settle_seconds,
+                  full=args.full, dump_dir=args.dump_outputs)
     dt = r["dt"]
     sh0 = r["shards"][0]
     k_ms = max(sh["kernel_ms"] for sh in r["shards"])
@@ -1081,7 +1133,7 @@ def group_main(args, pkg, devices, shared, world_for_line):
     kname = {0: "mfm_channel_kernel", 1: "mfm_channel_kernel_mfma", 2: "mfm_channel_kernel_v3"}[sh0["kernel_variant"]]
     need = 4.0 * block / (k_ms * 1e-3) / 1e9 if S > 1 else 0.0
     single = None
-    if S > 1:
+    if S > 1 and args.full:
         # the same per-GPU shape on ONE device of the same node, same run, same protocol: what "N x one GPU" means for this line
         fs1, decim1, taps1, offs1, gains1 = pkg.synth.plan(args.config, nr_channels=cpg)
         r1 = group_run(pkg, args, devices[:1], False, fs1, decim1, taps1, offs1, gains1, block, args.steps, args.warmup, args.settle_seconds)
@@ -1179,7 +1231,7 @@ def main():
                 except Exception:
                     pass
                 print(json.dumps(line), flush=True)
-                if not line["verified"]:
+                if line["verified"] is False:
                     raise SystemExit(f"bench.py: the timed kernel's output differs from the oracle: {line['verification']}")
             return
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1315,6 +1367,9 @@ def main():
     cycles = launch_clocks(eng, min(args.steps, 1024)) if rank == 0 else None
     if use_dist:
         dt = pkg.dist.max_over_ranks(dt, device="cuda")
+    if args.dump_outputs:
+        # (before anything launches again: the self-check and the board sample below read / overwrite the last block's PCM)
+        dump_outputs(args.dump_outputs, "pcm" if world == 1 else f"pcm_rank{rank}", [eng], DUMP_BYTES // world)
 
     launches = st1["launches"] - st0["launches"]
     timed = st1["timed_launches"] - st0["timed_launches"]  # MFM_F_TIMING_SPARSE: one launch in four carries the event pair
@@ -1367,7 +1422,7 @@ def main():
 
     # (the self-check first: it reads what the LAST TIMED launch left in HBM)
     verified = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_last = eng.last_output_device()[2]
         verified = verify_last_block(pkg, eng, fs, decim, taps, offs, gains, eng.stats()["outputs"] - n_last)
 
@@ -1376,7 +1431,7 @@ def main():
     # third of `value` (tools/r05/step_overheads.sh: ms_per_step 0.121 -> 0.180).  The clock the timed launches really ran
     # at is in `clocks` (stamped by the kernel itself); this is the board's own reading of the same sustained state.
     smi = None
-    if os.environ.get("BENCH_NO_BOARD_SAMPLE") != "1":
+    if args.full and os.environ.get("BENCH_NO_BOARD_SAMPLE") != "1":
         sampler = BoardSampler(local_rank) if rank == 0 else None
         # The read starts only after BOARD_SAMPLE_AFTER_S of back-to-back steps - the host work between the timed region and
         # this loop (the self-check: tenths of a second) lets the board's power reading, a moving average over a few hundred ms,
@@ -1439,7 +1494,8 @@ def main():
                          "sclk_mhz_in_launches": (cycles or {}).get("sclk_mhz_effective"),
                          "board_power_w": (smi or {}).get("power_w"), "board_power_cap_w": (smi or {}).get("power_cap_w"),
                          "simd_busy_fraction": (ceiling or {}).get("simd_busy_fraction")},
-            "verified": verified["verified"], "verification": verified,
+            "verified": verified["verified"] if verified else None,
+            "verification": verified or {"how": "not checked: bench.py --full runs the self-check"},
             "rotators": {"exact_channels": st1["rot_exact_channels"], "channels": len(offs)},
             "protocol": {"settle_seconds": args.settle_seconds, "settle_steps": settle_steps + 8,
                          "warmup_steps": args.warmup, "timed_steps": args.steps},
@@ -1465,20 +1521,20 @@ def main():
                          "grid": st1["grid_last"], "rot_table_entries": st1["rot_table_entries"],
                          "k_steps": st1["k_steps"], "tap_hi_mask": st1["tap_hi_mask"], "taps_resident": st1["taps_resident"]},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(pkg, fs, decim, taps, offs, gains, args.cpu_seconds)
 
     eng.close()
-    if rank == 0 and world == 1 and not args.no_fp32:
+    if rank == 0 and world == 1 and args.full and not args.no_fp32:
         # BASELINE configs[4] "fp32 vs int16 IQ path": the same channels on float32 IQ, outside the timed region,
         # reported next to the headline (never part of `value`)
         line["fp32_iq_path"] = fp32_path(pkg, torch, fs, decim, taps, offs, gains, line["roofline"]["kernel_ms"],
                                          block, block_log2=args.block_log2)
-    if rank == 0 and world == 1 and not args.no_series:
+    if rank == 0 and world == 1 and args.full and not args.no_series:
         # SURVEY.md 8(d)'s own protocol (2^20-sample blocks, >= 64 per timing; host-fed end to end), outside the timed region
         line["block_series"] = block_series(pkg, torch, fs, decim, taps, offs, gains)
         line["end_to_end"] = end_to_end(pkg, fs, decim, taps, offs, gains)
-    if rank == 0 and world == 1 and not args.no_chain and decim == 96:
+    if rank == 0 and world == 1 and args.full and not args.no_chain and decim == 96:
         line["flex_chain"] = flex_chain(pkg, torch, fs, decim, taps, offs, gains, block)
         if line["roofline"]["kernel"].startswith("mfm_channel_kernel_v3"):
             line["ingest_8bit"] = ingest_8bit(pkg, fs, decim, taps, offs, gains, block, line["roofline"]["kernel_ms"])
@@ -1506,7 +1562,7 @@ def main():
         except Exception:
             pass
         print(json.dumps(line), flush=True)
-        if not line["verified"]:
+        if line["verified"] is False:
             raise SystemExit(f"bench.py: the timed kernel's output differs from the oracle: {line['verification']}")
 
 

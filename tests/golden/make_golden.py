@@ -5,6 +5,8 @@ for the reference-built part; `make -C oracle` first).
   atan2_ref.npz   inputs (y, x) and the bit patterns returned by the REFERENCE's own fast_atan2f
                   object code (oracle/_ref/libref_fast_atan2f.so, built from
                   /root/reference/multifm/fast_atan2f.c).  This is what pins the oracle's fast_atan2f.
+  atan2_ref_dense.npz the bits the same object code returns for tests/test_oracle_atan2.py's dense_inputs() ("dense")
+                  and knot_inputs() ("knots"): the reference side of those tests where oracle/_ref cannot be built.
   path_oracle.npz a small end-to-end vector (IQ in -> filtered IQ + PCM out, 3 channels) produced by
                   the ORACLE.  It is a regression pin for the restatement, not reference output: the
                   reference's FIR / discriminator sources need TSL headers the image lacks.
@@ -48,6 +50,15 @@ def atan2_inputs(seed=11):
     return np.concatenate(parts, axis=0)
 
 
+def atan2_dense(ref):
+    from test_oracle_atan2 import dense_inputs, knot_inputs
+    out = {}
+    for name, yx in (("dense", dense_inputs()), ("knots", knot_inputs())):
+        out[name] = np.array([ref.fast_atan2f(float(y), float(x)) for y, x in yx], dtype=np.float32).view(np.uint32)
+    np.savez_compressed(os.path.join(HERE, "atan2_ref_dense.npz"), **out)
+    print("atan2_ref_dense.npz:", {k: v.shape[0] for k, v in out.items()}, "answers from the reference object code")
+
+
 def main():
     ref = ora.ref_atan2()
     if ref is None:
@@ -56,6 +67,7 @@ def main():
     out = np.array([ref.fast_atan2f(float(y), float(x)) for y, x in yx], dtype=np.float32)
     np.savez_compressed(os.path.join(HERE, "atan2_ref.npz"), yx=yx, bits=out.view(np.uint32))
     print("atan2_ref.npz:", yx.shape[0], "vectors from the reference object code")
+    atan2_dense(ref)
 
     pkg = load_package()
     fs, decim = 2400000, 96

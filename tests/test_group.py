@@ -266,7 +266,7 @@ def test_bench_runs_its_distributed_path_on_one_rank(pkg):
     """bench.py with BENCH_FORCE_DIST=1: process group on RCCL, in-place broadcast of the block into the engine's
     input buffer, submit behind it - the N > 1 code path of the bench on the one GPU of the box."""
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
-    r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                         "--settle-seconds", "0", "--no-cpu-baseline", "--no-fp32", "--block-log2", "22"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -289,7 +289,7 @@ def test_bench_group_path_over_the_fake_transport(tmp_path, shards):
     assert r.returncode == 0, r.stderr[-2000:]
     env = dict(os.environ, LD_LIBRARY_PATH=str(tmp_path) + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
     r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--group-shards", str(shards), "--channels-per-gpu", "40",
-                        "--steps", "5", "--warmup", "2", "--settle-seconds", "0", "--block-log2", "21"],
+                        "--steps", "5", "--warmup", "2", "--settle-seconds", "0", "--block-log2", "21", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -326,7 +326,7 @@ def test_bench_group_path_as_the_driver_launches_it(tmp_path):
     env = dict(os.environ, MFM_RCCL_LIBRARY=str(so))
     r = subprocess.run(["python3", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--group-shards", "2",
-                        "--channels-per-gpu", "40", "--steps", "5", "--warmup", "2", "--settle-seconds", "0", "--block-log2", "21"],
+                        "--channels-per-gpu", "40", "--steps", "5", "--warmup", "2", "--settle-seconds", "0", "--block-log2", "21", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -358,7 +358,7 @@ def test_bench_line_carries_the_group_path_and_the_north_star_shape():
     """the N = 1 line: `group_path` - the same workload through mfm_group_* on one device - the same rate as `value` (loosely here: small
     blocks; 2 % at the driver's size), and `north_star_shape` - 1024 channels on the one GPU - with its matrix-instruction bound"""
     r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--settle-seconds", "0.3",
-                        "--no-cpu-baseline", "--no-fp32", "--no-series", "--block-log2", "24"],
+                        "--full", "--no-cpu-baseline", "--no-fp32", "--no-series", "--block-log2", "24"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -381,7 +381,7 @@ def test_bench_exchanges_8bit_blocks_as_bytes(pkg):
     RTL-SDR delivers, the exchange moves 2 bytes per sample instead of 4, the matrix kernel reads the bytes, and the line's
     self-check widens the launch's input as multifm/rtl_sdr_if.c:146-148 does before it asks the oracle."""
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29543")
-    r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                         "--settle-seconds", "0", "--no-cpu-baseline", "--no-fp32", "--no-chain", "--no-series", "--block-log2", "22",
                         "--input", "rtlsdr_u8"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

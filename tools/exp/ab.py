@@ -4,7 +4,7 @@
     python tools/exp/ab.py [--reps 6] [--bench-args "..."] [--metric kernel_ms|cycles|ms_per_step] base=<lib.so> cand=<lib.so> ...
 
 Every repetition runs every variant once, in rotating order (variant i first in repetition i, so that no variant always runs on a
-cold or a warm board), each as `bench.py --no-cpu-baseline --no-fp32 --no-chain --no-series --steps 200 --warmup 20
+cold or a warm board), each as `bench.py --full --no-cpu-baseline --no-fp32 --no-chain --no-series --steps 200 --warmup 20
 --settle-seconds 0.5 <bench args>` with MFM_LIB pointing at the variant's library.  Per variant: mean, standard deviation
 (n - 1), min, max of the metric over the repetitions.  Against the FIRST variant (the baseline) a candidate is
 
@@ -33,7 +33,7 @@ def run_once(spec, bench_args, metric):
         extra = spec[len("flags:"):].split()
     elif spec:
         env["MFM_LIB"] = os.path.abspath(spec)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-fp32", "--no-chain", "--no-series", "--steps", "200",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-fp32", "--no-chain", "--no-series", "--steps", "200",
            "--warmup", "20", "--settle-seconds", "0.5"] + bench_args + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]

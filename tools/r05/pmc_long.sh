@@ -5,7 +5,7 @@ PLAN=${1:-cfg5_airspy}; NCH=${2:-256}; shift 2
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05/pmc_${PLAN}_${NCH}; rm -rf $O; mkdir -p $O
 for k in auto mfma1 v3l1; do
-P="python3 bench.py --config $PLAN --channels-per-gpu $NCH --kernel $k --steps 8 --warmup 3 --settle-seconds 0.3 --no-cpu-baseline --no-fp32 --no-chain --no-series $*"
+P="python3 bench.py --full --config $PLAN --channels-per-gpu $NCH --kernel $k --steps 8 --warmup 3 --settle-seconds 0.3 --no-cpu-baseline --no-fp32 --no-chain --no-series $*"
 timeout 300 rocprofv3 --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $O/${k}_p1 -o p -- $P > $O/${k}_p1.log 2>&1
 timeout 300 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_MFMA --kernel-trace --output-format csv -d $O/${k}_p2 -o p -- $P > $O/${k}_p2.log 2>&1
 timeout 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_COEXEC_CYCLES SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_CVT --kernel-trace --output-format csv -d $O/${k}_p3 -o p -- $P > $O/${k}_p3.log 2>&1

@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05/traffic1024; rm -rf $O; mkdir -p $O
 N="--no-cpu-baseline --no-fp32 --no-chain --no-series --steps 6 --warmup 2 --settle-seconds 0.3 --channels-per-gpu 1024"
 for plan in cfg3_1024ch cfg3_1024ch_grid; do
-  timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${plan}_fetch -o f -- python3 bench.py --config $plan $N > $O/${plan}_fetch.log 2>&1
-  timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${plan}_write -o w -- python3 bench.py --config $plan $N > $O/${plan}_write.log 2>&1
+  timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${plan}_fetch -o f -- python3 bench.py --full --config $plan $N > $O/${plan}_fetch.log 2>&1
+  timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${plan}_write -o w -- python3 bench.py --full --config $plan $N > $O/${plan}_write.log 2>&1
 done
 python3 - <<'PY'
 import csv, glob, json, sys, os
