@@ -649,6 +649,61 @@ int mfm_flex_fetch_events(struct mfm_flex *f, struct mfm_flex_event *events, siz
                           struct mfm_flex_frame_words *frames, size_t max_frames, size_t *nr_frames);
 
 /*
+ * ---- AIS stage: slicer / preamble detector / NRZI + HDLC bit recovery / FCS check ------------------------------
+ * Replaces, for ALL channels at once and on PCM that is still in HBM (48 000 Hz, i.e. the resampler's output):
+ *
+ *   ais_demod_on_pcm                  ais/ais_demod.c:215-258   state machine SEARCH_SYNC -> RECEIVING
+ *   _ais_demod_detect_handle_sample   ais/ais_demod.c:114-158   five preamble registers, 3 of 5 within 2 bits
+ *   _ais_demod_packet_rx_sample       ais/ais_demod.c:160-213   NRZI, unstuffing, end flag / 1280-bit cut
+ *   _ais_crc16                        ais/ais_demod.c:19-36     CRC-16, reflected 0x8408, init 0xffff, inverted
+ *
+ * Output is one event per candidate packet, i.e. per packet end with current_bit / 8 >= 4 (:190-191), whether its
+ * FCS holds or not.  Decoding the message (ais/ais_decode.c) stays on the host (tsl-sdr_amd/host/mfm_ais.c).
+ *
+ * Conventions kept: bit = (sample > 0); detector bit = !(b[s] ^ b[s-5]); the first packet bit is read four samples
+ * after the matching sample, then one every five; packet bits LSB first into bytes; the FCS is the little-endian
+ * pair after nr_bytes - 2 bytes of data.
+ */
+struct mfm_ais_event {
+    uint32_t channel;
+    uint32_t fcs_valid;     /* 1: the CRC over bytes[0 .. nr_bytes - 2) equals bytes[nr_bytes - 2] | bytes[nr_bytes - 1] << 8 */
+    uint32_t nr_bytes;      /* current_bit / 8 at the packet end, the two FCS bytes included (4 .. 160) */
+    uint32_t reserved;      /* 0 */
+    uint64_t sample;        /* index (per channel, since creation) of the PCM sample that ended the packet */
+    uint64_t start_sample;  /* index of the sample where the preamble matched */
+    uint8_t bytes[160];     /* the packet buffer as the reference holds it (a partial last byte included, zeros after) */
+};
+
+struct mfm_ais; /* opaque */
+
+struct mfm_ais_config {
+    uint32_t abi_version;    /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_in_samples; /* most PCM samples per channel one process call may carry */
+    uint32_t max_events;     /* per channel and call; 0 = max_in_samples / 160 + 16 (cannot overflow) */
+    uint32_t flags;          /* 0 */
+};
+
+int mfm_ais_create(struct mfm_ais **pp, const struct mfm_ais_config *cfg);
+void mfm_ais_destroy(struct mfm_ais **pp);
+/*
+ * Consume nr_in PCM samples per channel, laid out [channel][in_stride] in device memory (for instance the
+ * output of mfm_resampler_process_device).  Work is queued on `stream`; no host synchronisation.  The events of
+ * THIS call replace those of the previous one.  A packet that is still being received at the end of a call is
+ * carried over on the device: events do not depend on how a stream is cut into calls.
+ */
+int mfm_ais_process_device(struct mfm_ais *p, const int16_t *d_pcm, size_t in_stride, size_t nr_in, void *stream);
+/* Host convenience: same from host memory, synchronous. */
+int mfm_ais_process_host(struct mfm_ais *p, const int16_t *pcm, size_t in_stride, size_t nr_in);
+/*
+ * Wait for the last process call and copy its events: channels ascending, stream order within a channel.
+ * MFM_E_NOMEM when `max_events` is too small (nothing copied, *nr_events = needed), MFM_E_STATE when a channel
+ * overflowed its device-side event list (only possible with a caller-chosen max_events).
+ */
+int mfm_ais_fetch_events(struct mfm_ais *p, struct mfm_ais_event *out, size_t max_events, size_t *nr_events);
+
+/*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
  *   mm_init      pager/mueller_muller.c:10-33
  *   mm_process   pager/mueller_muller.c:41-115

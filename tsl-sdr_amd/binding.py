@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "mfm_group_sync", "mfm_group_get_stats", "mfm_group_exchange_info", "mfm_group_exchange_detail", "mfm_group_rccl_library",
     "mfm_flex_create", "mfm_flex_destroy", "mfm_flex_process_device", "mfm_flex_process_host", "mfm_flex_fetch_events",
     "mfm_mm_create", "mfm_mm_destroy", "mfm_mm_max_decisions", "mfm_mm_process_device", "mfm_mm_process_host",
+    "mfm_ais_create", "mfm_ais_destroy", "mfm_ais_process_device", "mfm_ais_process_host", "mfm_ais_fetch_events",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -131,6 +132,21 @@ class PocsagEvent(C.Structure):
 # numpy view of struct mfm_pocsag_event (160 bytes)
 POCSAG_EVENT_DTYPE = np.dtype([("type", "<u4"), ("baud", "<u4"), ("channel", "<u4"), ("aux", "<u4"), ("sample", "<u8"),
                                ("nr_ok", "<u4"), ("fail_mask", "<u4"), ("raw", "<u4", (16,)), ("corrected", "<u4", (16,))])
+
+
+class AisConfig(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32),
+                ("max_in_samples", C.c_uint32), ("max_events", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class AisEvent(C.Structure):
+    _fields_ = [("channel", C.c_uint32), ("fcs_valid", C.c_uint32), ("nr_bytes", C.c_uint32), ("reserved", C.c_uint32),
+                ("sample", C.c_uint64), ("start_sample", C.c_uint64), ("bytes", C.c_uint8 * 160)]
+
+
+# numpy view of struct mfm_ais_event (192 bytes)
+AIS_EVENT_DTYPE = np.dtype([("channel", "<u4"), ("fcs_valid", "<u4"), ("nr_bytes", "<u4"), ("reserved", "<u4"),
+                            ("sample", "<u8"), ("start_sample", "<u8"), ("bytes", "u1", (160,))])
 
 
 class FlexConfig(C.Structure):
@@ -290,6 +306,12 @@ def load_library():
     lib.mfm_pocsag_process_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.mfm_pocsag_process_host.argtypes = [vp, i16p, C.c_size_t, C.c_size_t]
     lib.mfm_pocsag_fetch_events.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.mfm_ais_create.argtypes = [C.POINTER(vp), C.POINTER(AisConfig)]
+    lib.mfm_ais_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_ais_destroy.restype = None
+    lib.mfm_ais_process_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.mfm_ais_process_host.argtypes = [vp, i16p, C.c_size_t, C.c_size_t]
+    lib.mfm_ais_fetch_events.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.mfm_flex_create.argtypes = [C.POINTER(vp), C.POINTER(FlexConfig)]
     lib.mfm_flex_destroy.argtypes = [C.POINTER(vp)]
     lib.mfm_flex_destroy.restype = None
@@ -897,6 +919,54 @@ class Pocsag:
         rc = self.lib.mfm_pocsag_fetch_events(self.h, out.ctypes.data, cap, C.byref(n))
         if rc < 0:
             raise MfmError(rc, "mfm_pocsag_fetch_events", self.lib.mfm_strerror(rc).decode())
+        return out[:n.value].copy()
+
+
+class Ais:
+    """mfm_ais: AIS slicer / preamble detector / NRZI + HDLC bit recovery / FCS check for all channels of a 48 000 Hz
+    PCM block.  One event per candidate packet (AIS_EVENT_DTYPE), CRC rejects included (fcs_valid = 0)."""
+
+    def __init__(self, nr_channels, max_in_samples, device=0, max_events=0):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        cfg = AisConfig(MFM_ABI_VERSION, device, nr_channels, max_in_samples, max_events, 0)
+        rc = self.lib.mfm_ais_create(C.byref(self.h), C.byref(cfg))
+        if rc < 0:
+            raise MfmError(rc, "mfm_ais_create", self.lib.mfm_strerror(rc).decode())
+        self.nr_channels = nr_channels
+        self.max_events = max_events or (max_in_samples // 160 + 16)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_ais_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process_host(self, pcm):
+        """pcm: int16 [C][n]; returns the events of this call as a structured array (AIS_EVENT_DTYPE)"""
+        a = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.nr_channels, -1)
+        rc = self.lib.mfm_ais_process_host(self.h, _i16p(a), a.shape[1], a.shape[1])
+        if rc < 0:
+            raise MfmError(rc, "mfm_ais_process_host", self.lib.mfm_strerror(rc).decode())
+        return self.fetch_events()
+
+    def process_device(self, d_pcm, in_stride, nr_in, stream=None):
+        rc = self.lib.mfm_ais_process_device(self.h, C.c_void_p(d_pcm), in_stride, nr_in, C.c_void_p(stream or 0))
+        if rc < 0:
+            raise MfmError(rc, "mfm_ais_process_device", self.lib.mfm_strerror(rc).decode())
+
+    def fetch_events(self):
+        cap = self.nr_channels * self.max_events
+        out = np.zeros(cap, AIS_EVENT_DTYPE)
+        n = C.c_size_t()
+        rc = self.lib.mfm_ais_fetch_events(self.h, out.ctypes.data, cap, C.byref(n))
+        if rc < 0:
+            raise MfmError(rc, "mfm_ais_fetch_events", self.lib.mfm_strerror(rc).decode())
         return out[:n.value].copy()
 
 

@@ -240,6 +240,150 @@ def pocsag_fm_iq(bits, baud, sample_rate_hz, carrier_hz, deviation_hz=4500.0, am
     return out
 
 
+# ---- synthetic AIS ---------------------------------------------------------------------------------------
+# Written from the published frame layout: 24-bit 0101.. preamble, 0x7e flag, HDLC-stuffed payload + FCS, 0x7e
+# flag, NRZI (a 0 is a transition), 9600 bit/s, at 48 kHz five samples per bit.  Byte order and bit order are the
+# ones the reference's receiver assembles: bytes LSB first on the air (ais/ais_demod.c:176), fields MSB first across
+# bytes (ais/ais_decode.c:21-46), the FCS little-endian after the payload (:192).
+
+AIS_RATE = 48000
+AIS_SPB = 5
+AIS_FLAG = 0x7E
+
+
+def ais_crc16(data):
+    """CRC-16/X-25: reflected 0x8408, init 0xffff, inverted (ais/ais_demod.c:19-36)"""
+    crc = 0xFFFF
+    for b in bytes(data):
+        crc ^= b
+        for _ in range(8):
+            crc = (crc >> 1) ^ 0x8408 if crc & 1 else crc >> 1
+    return crc ^ 0xFFFF
+
+
+def ais_payload(fields, nr_bits):
+    """bytes from (offset, width, value) fields, MSB first across bytes; negative values two's complement"""
+    acc = 0
+    for off, width, value in fields:
+        acc |= (int(value) & ((1 << width) - 1)) << (nr_bits - off - width)
+    nbytes = (nr_bits + 7) // 8
+    return (acc << (8 * nbytes - nr_bits)).to_bytes(nbytes, "big")
+
+
+def ais_sixbit(text, nr_chars):
+    """6-bit text as the decoder reads it back (v > 0x1f ? v : v + 0x40): '@'..'_' -> 0..31, ' '..'?' -> 32..63"""
+    out = []
+    for ch in text.ljust(nr_chars, "@")[:nr_chars]:
+        v = ord(ch)
+        out.append(v - 0x40 if v >= 0x40 else v)
+    return out
+
+
+def ais_type1(mmsi, nav_stat=0, rot=0, sog=0, pos_acc=0, lon=0, lat=0, course=0, heading=0, seconds=0, repeat=0,
+              msg_type=1):
+    """position report (types 1-3): lon / lat in 1/10000 minute, sog / course in tenths; 168 bits"""
+    f = [(0, 6, msg_type), (6, 2, repeat), (8, 30, mmsi), (38, 4, nav_stat), (42, 8, rot), (50, 10, sog),
+         (60, 1, pos_acc), (61, 28, lon), (89, 27, lat), (116, 12, course), (128, 9, heading), (137, 6, seconds)]
+    return ais_payload(f, 168)
+
+
+def ais_type4(mmsi, year=2026, month=1, day=1, hour=0, minute=0, second=0, lon=0, lat=0, epfd=1, repeat=0):
+    """base station report; 168 bits"""
+    f = [(0, 6, 4), (6, 2, repeat), (8, 30, mmsi), (38, 14, year), (52, 4, month), (56, 5, day), (61, 5, hour),
+         (66, 6, minute), (72, 6, second), (78, 1, 1), (79, 28, lon), (107, 27, lat), (134, 4, epfd)]
+    return ais_payload(f, 168)
+
+
+def ais_type5(mmsi, version=0, imo=0, callsign="", ship_name="", ship_type=0, bow=0, stern=0, port=0, starboard=0,
+              fix=1, eta_month=0, eta_day=0, eta_hour=24, eta_minute=60, draught=0, destination="", repeat=0):
+    """static and voyage related data; 424 bits"""
+    f = [(0, 6, 5), (6, 2, repeat), (8, 30, mmsi), (38, 2, version), (40, 30, imo)]
+    f += [(70 + 6 * i, 6, v) for i, v in enumerate(ais_sixbit(callsign, 7))]
+    f += [(112 + 6 * i, 6, v) for i, v in enumerate(ais_sixbit(ship_name, 20))]
+    f += [(232, 8, ship_type), (240, 9, bow), (249, 9, stern), (258, 6, port), (264, 6, starboard), (270, 4, fix),
+          (274, 4, eta_month), (278, 5, eta_day), (283, 5, eta_hour), (288, 6, eta_minute), (294, 8, draught)]
+    f += [(302 + 6 * i, 6, v) for i, v in enumerate(ais_sixbit(destination, 20))]
+    return ais_payload(f, 424)
+
+
+def ais_stuff(bits):
+    """HDLC: a 0 after every five 1s in a row"""
+    out, ones = [], 0
+    for b in bits:
+        out.append(b)
+        ones = ones + 1 if b else 0
+        if ones == 5:
+            out.append(0)
+            ones = 0
+    return out
+
+
+def ais_frame_bits(payload, fcs=None, preamble_bits=24, end_flag=True):
+    """on-air bits (before NRZI) of one packet: preamble, flag, stuffed payload + FCS (LSB first), flag"""
+    payload = bytes(payload)
+    if fcs is None:
+        fcs = ais_crc16(payload)
+    body = payload + bytes([fcs & 0xFF, (fcs >> 8) & 0xFF])
+    data = [(b >> k) & 1 for b in body for k in range(8)]
+    flag = [(AIS_FLAG >> k) & 1 for k in range(8)]
+    bits = [i & 1 for i in range(preamble_bits)] + flag + ais_stuff(data)
+    if end_flag:
+        bits += flag
+    return np.array(bits, dtype=np.uint8)
+
+
+def ais_bits(frames, gap_bits=0, lead_bits=0, trail_bits=0):
+    """frames one after the other, `gap_bits` 1s (no transition) between them"""
+    parts = [np.ones(lead_bits, np.uint8)]
+    for k, fr in enumerate(frames):
+        if k:
+            parts.append(np.ones(gap_bits, np.uint8))
+        parts.append(np.asarray(fr, np.uint8))
+    parts.append(np.ones(trail_bits, np.uint8))
+    return np.concatenate(parts)
+
+
+def ais_nrzi(bits, level=0):
+    """levels: a 0 toggles, a 1 keeps"""
+    out = np.empty(len(bits), np.uint8)
+    for k, b in enumerate(bits):
+        if not b:
+            level ^= 1
+        out[k] = level
+    return out
+
+
+def ais_pcm(bits, amplitude=8000, noise=0.0, lead=0, trail=0, phase=0, seed=0, flip=None, level=0):
+    """48 kHz PCM, five samples per bit: level 1 -> +amplitude (the slicer is sample > 0).  `flip`: on-air bit
+    indices to invert; lead / trail: noise-only samples before / after; phase: 0..4 extra samples of lead."""
+    b = np.array(bits, dtype=np.uint8)
+    if flip is not None and len(flip):
+        b[np.asarray(flip)] ^= 1
+    lv = ais_nrzi(b, level)
+    sig = np.repeat(np.where(lv == 1, amplitude, -amplitude), AIS_SPB).astype(np.float64)
+    x = np.concatenate([np.zeros(lead + phase), sig, np.zeros(trail)])
+    if noise > 0:
+        x = x + np.random.RandomState(seed).normal(0.0, noise, size=x.size)
+    return np.clip(np.round(x), -32768, 32767).astype(np.int16)
+
+
+def ais_fm_iq(bits, sample_rate_hz, carrier_hz, deviation_hz=2400.0, amplitude=9000.0, lead=0, trail=0, noise=200.0,
+              seed=0, level=0):
+    """GMSK-less 2-FSK at `carrier_hz` from the tuner centre: NRZI level 1 -> +deviation (positive PCM)."""
+    spb = int(round(sample_rate_hz / 9600))
+    lv = ais_nrzi(np.asarray(bits, np.uint8), level)
+    f = np.concatenate([np.zeros(lead), np.repeat(np.where(lv == 1, deviation_hz, -deviation_hz), spb),
+                        np.zeros(trail)]) + carrier_hz
+    ph = 2.0 * np.pi * np.cumsum(f) / sample_rate_hz
+    rng = np.random.RandomState(seed)
+    i = amplitude * np.cos(ph) + rng.normal(0.0, noise, size=ph.size)
+    q = amplitude * np.sin(ph) + rng.normal(0.0, noise, size=ph.size)
+    out = np.empty((ph.size, 2), np.int16)
+    out[:, 0] = np.clip(np.round(i), -32768, 32767)
+    out[:, 1] = np.clip(np.round(q), -32768, 32767)
+    return out
+
+
 # ---- synthetic FLEX (SURVEY.md section 8f row 4) ------------------------------------------------------------
 # Written from the published frame layout, not from the decoder: 115.2 ms sync 1 at 1600 bit/s 2-FSK (32 bits of
 # 1010.., A = mode code + 0x5939, B = 0x5555, inverted A, the frame information word), 25 ms sync 2 at the frame's
