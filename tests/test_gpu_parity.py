@@ -657,7 +657,7 @@ def test_bench_shapes_against_the_oracle(pkg, ora, shape):
     block = 1 << log2
     n = block + 54321
     iq = _tiled_iq(pkg, n, fs, offs[:: max(1, nch // 6)][:6], seed=log2 + nch)
-    threads = os.cpu_count() or 8
+    threads = min(16, os.cpu_count() or 8)
     eng = _mk_engine(pkg, fs, decim, taps, offs, gains, max_block=block, want_iq=False)
     st = eng.stats()
     if shape.startswith("exact_grid"):
