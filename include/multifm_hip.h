@@ -822,6 +822,11 @@ int mfm_devtest_discriminate(int variant, const int32_t *s_re, const int32_t *s_
  * differs: a device with another reciprocal table is accepted only if not one quotient is off. */
 #define MFM_RCP_TABLE_HASH_GFX950 0x706d94bc005bcc1aull /* (read off an MI355X: tests/test_gpu_parity.py checks it there) */
 int mfm_devtest_rcp_table(int device, uint64_t *hash, uint64_t counts[4], uint64_t *sweep_bad, uint64_t *sweep_tried);
+/* The kernel form mfm_engine_commit() would choose for this engine's channels, planned on the host without a device: the
+ * fields kernel_variant, slice_channels, taps_resident, outputs_per_tile, k_steps, tap_hi_mask, lds_bytes, rot_exact_channels
+ * and rot_fast_slices as mfm_engine_get_stats() reports them after commit, the others 0.  Before commit only; a plan that
+ * commit would refuse returns the same error. */
+int mfm_hosttwin_kernel_form(struct mfm_engine *e, struct mfm_stats *st);
 /* the device's table-driven BCH(31,21) decode (syndrome bytes -> 1024-entry flip table), on the host */
 int mfm_hosttwin_bch3121_decode(uint32_t *word);
 

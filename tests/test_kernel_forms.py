@@ -1,11 +1,12 @@
 """Which kernel form the channel engine picks at commit, and parity of every form it picks.
 
-The engine (csrc/mfm_engine.hip, commit_locked) chooses among the v_dot2 kernel, the first-generation matrix kernel, the
-second generation's layouts on 64-channel slices, and the long-filter kernel (mfm_kernel_v3l.hip) with one or two row blocks
-per wave; PCM stores go through with system scope ("write-through") from 512 channels on unless MFM_F_PCM_WRITE_BACK.  A
+The engine's planner (csrc/mfm_plan.hip, plan_channel_kernel) chooses among the v_dot2 kernel, the first-generation matrix
+kernel, the second generation's layouts on 64-channel slices, and the long-filter kernel (mfm_kernel_v3l.hip) with one or two
+row blocks per wave; PCM stores go through with system scope ("write-through") from 512 channels on unless MFM_F_PCM_WRITE_BACK.  A
 PCM block is bit-exact only if the form that ran is, so:
-  1. a selection table pins, for each configuration, the form stats() reports after commit (no kernel runs), with the
-     expected values written out from the documented rules - a form that quietly falls back to another fails here;
+  1. a selection table pins, for each configuration, the form the planner picks - on the host through
+     mfm_hosttwin_kernel_form, and as stats() reports it after commit on the GPU (no kernel runs) - with the expected values
+     written out from the documented rules: a form that quietly falls back to another fails here;
   2. every form the table selects runs against the oracle, bit-exact, with its form asserted first."""
 import ctypes as C
 import json
@@ -15,8 +16,6 @@ import numpy as np
 import pytest
 
 from test_gpu_parity import _ingest_8bit, _mk_engine, _oracle_tables
-
-pytestmark = pytest.mark.gpu
 
 # the oracle's thread pool: a job on the GPU machines may use 16 CPUs, whatever os.cpu_count() says
 THREADS = min(16, os.cpu_count() or 8)
@@ -68,8 +67,11 @@ def _big_taps(pkg):
 
 # Selection table: (id, geometry, flags, expected stats).  Expected: kernel_variant (0 v_dot2, 1 first generation, 2 second),
 # slice_channels, taps_resident, outputs_per_tile, k_steps, popcount(tap_hi_mask) (None: not pinned).  The rules they follow
-# (mfm_engine.hip commit_locked, the mfm_stats comments in include/multifm_hip.h, mfm3l_fits / mfm3l_instance_ptr in
-# mfm_kernel_v3l.hip):
+# (mfm_plan.hip plan_channel_kernel, the mfm_stats comments in include/multifm_hip.h, mfm3l_fits / mfm3l_instance_ptr in
+# mfm_kernel_v3l.hip), in the order the planner applies them (each may replace what the ones before it chose):
+#   [dot2]  the v_dot2 kernel: MFM_F_FORCE_DOT2, a tap beyond 32639, or a padded filter beyond 16 k-steps; 128 outputs per
+#           tile (two per lane) where the tile fits 53 KiB of LDS
+#   [v1]    the first generation: 62-output tiles (two 31-output iterations) where they fit, else 31
 #   [sub]   D % 32 == 0, <= 4 k-steps: second generation, sub-plane layout, slices of 64, taps not "resident" (layout 3 only)
 #   [crow]  D % 8 == 0, D % 32 != 0, <= 4 k-steps: the chunk-row layout, slices of 64
 #   [pad25] D = 25, <= 150 taps: padded-row layout 2, six k-steps, slices of 64
@@ -80,9 +82,6 @@ def _big_taps(pkg):
 #   [s128]  the [sub] geometry with 4 k-steps at >= 512 channels (kSlice128MinChannels) or MFM_F_SLICE_128, not with
 #           MFM_F_SLICE_64 / MFM_F_FORCE_MFMA_V1: the long-filter kernel with rb = 2, ng = 4 (whole-tile images, built for
 #           KQ = 4 with 0, 2 and 4 held high planes: 8 (4 + nh) + 16 <= 128 holds for all) - unless <= 64 channels (one row block)
-#   [v1]    the first generation: 62-output tiles (two 31-output iterations) where they fit, else 31
-#   [dot2]  the v_dot2 kernel: MFM_F_FORCE_DOT2, a tap beyond 32639, or a padded filter beyond 16 k-steps; 128 outputs per
-#           tile (two per lane) where the tile fits 53 KiB of LDS
 SELECTION = [
     # ---- every channel-engine configuration under tests/golden/reference_etc/ (multifm_decimate.json configures the
     #      rational resampler only), with its own filter file and channel list
@@ -149,21 +148,49 @@ SELECTION = [
 ]
 
 
-@pytest.mark.parametrize("row", SELECTION, ids=[r[0] for r in SELECTION])
-def test_selection_table(pkg, row):
+FORM_FIELDS = ("kernel_variant", "slice_channels", "taps_resident", "outputs_per_tile", "k_steps", "tap_hi_mask", "lds_bytes",
+               "rot_exact_channels", "rot_fast_slices")
+
+
+def _selection_engine(pkg, row):
+    """the row's engine with its channels added, not committed"""
     name, geom, flags, want = row
     fs, decim, taps, offs, gains = geom(pkg)
     eng = pkg.Engine(fs, decim, 1 << 16, device=0, flags=flags)
     gains = gains if gains is not None else [1.0] * len(offs)
     for o, g in zip(offs, gains):
         eng.add_channel(int(o), taps, float(g))
-    eng.commit()
-    st = eng.stats()
-    eng.close()
+    return eng
+
+
+def _check_form(row, st):
+    name, _, _, want = row
     got = (st["kernel_variant"], st["slice_channels"], st["taps_resident"], st["outputs_per_tile"], st["k_steps"],
            bin(st["tap_hi_mask"]).count("1"))
     want = tuple(g if w is None else w for w, g in zip(want, got))
     assert got == want, f"{name}: (variant, slice, resident, outputs/tile, k-steps, high planes) {got}, expected {want}"
+
+
+@pytest.mark.parametrize("row", SELECTION, ids=[r[0] for r in SELECTION])
+def test_selection_table_host(pkg, row):
+    """the planner on the host, without a device (mfm_hosttwin_kernel_form)"""
+    eng = _selection_engine(pkg, row)
+    st = eng.kernel_form()
+    eng.close()
+    _check_form(row, st)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("row", SELECTION, ids=[r[0] for r in SELECTION])
+def test_selection_table(pkg, row):
+    """what commit chose, as stats() reports it - and that it is what the host twin planned"""
+    eng = _selection_engine(pkg, row)
+    twin = eng.kernel_form()
+    eng.commit()
+    st = eng.stats()
+    eng.close()
+    _check_form(row, st)
+    assert {k: st[k] for k in FORM_FIELDS} == {k: twin[k] for k in FORM_FIELDS}, row[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------- parity
@@ -232,6 +259,7 @@ def _run_parity(pkg, ora, fs, decim, taps, offs, iq, flags, variant, slices, gai
     return st
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("nch", [512, 513, 1000, 1024])
 def test_slice128_by_default(pkg, ora, nch):
     """From kSlice128MinChannels on, 128-tap filters run on 128-channel slices; partial last slices (513: one channel, 1000:
@@ -243,6 +271,7 @@ def test_slice128_by_default(pkg, ora, nch):
     assert 0 < st["rot_exact_channels"] < nch
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("nch,iq_chan", [(129, None), (200, 77), (384, None)])
 def test_slice128_forced(pkg, ora, nch, iq_chan):
     """MFM_F_SLICE_128 below 512 channels; with a filtered-IQ consumer on one channel the rb = 2 instance keeps running (its
@@ -265,6 +294,7 @@ def test_slice128_forced(pkg, ora, nch, iq_chan):
         assert q is not None and np.array_equal(q[iq_chan], refq[iq_chan]), "filtered IQ differs"
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("nch", [512, 1024])
 @pytest.mark.parametrize("fmt", [1, 2, 3])
 def test_slice128_on_bytes(pkg, ora, fmt, nch):
@@ -283,6 +313,7 @@ def test_slice128_on_bytes(pkg, ora, fmt, nch):
     _assert_equal(got, want, f"bytes fmt {fmt}, {nch} channels")
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("n_hi", [0, 2, 3, 4])
 def test_slice128_high_byte_planes(pkg, ora, n_hi):
     """Tap sets with 0, 2, 3 and 4 high-byte k-steps on 128-channel slices (instances for 0, 2 and 4 held planes)."""
@@ -310,6 +341,7 @@ def _device_only(pkg, eng, iq, block):
     return np.concatenate(outs, axis=1)
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("geom", ["cfg3", "cfg5"])
 def test_pcm_store_policy(pkg, ora, geom):
     """At 512 channels (kPcmWriteThroughMinChannels) PCM stores go through with system scope unless MFM_F_PCM_WRITE_BACK:
@@ -340,6 +372,7 @@ def test_pcm_store_policy(pkg, ora, geom):
             eng.close()
             _assert_equal(pcm, ref, f"{geom} device view, flags {flags:#x}")
 
+@pytest.mark.gpu
 
 def test_slice128_gathered_and_overlapped(pkg, ora):
     """MFM_F_GATHER | MFM_F_OVERLAP with coalesce_samples on 128-channel slices: launch boundaries at the gathered counts,
@@ -386,6 +419,7 @@ def test_slice128_gathered_and_overlapped(pkg, ora):
     assert st["submits"] == k and st["pending_samples"] == 0 and 2 <= st["launches"] <= n // 100000 + 1, st
 
 
+@pytest.mark.gpu
 @pytest.mark.parametrize("row", ["d25_t170_130", "d30_t150_130", "d24_t140_130", "d150_t300_130", "d96_t256_130_one_rb"])
 def test_fallback_geometries(pkg, ora, row):
     """Parity of the fallback rows of the selection table, in the form the table pins."""

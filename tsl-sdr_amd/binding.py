@@ -43,7 +43,7 @@ ABI_SYMBOLS = [
     "mfm_engine_submit", "mfm_engine_push", "mfm_engine_push_bytes", "mfm_engine_fetch", "mfm_engine_release",
     "mfm_engine_last_output_device", "mfm_engine_sync", "mfm_engine_reset", "mfm_engine_get_stats",
     "mfm_engine_stream", "mfm_engine_get_launch_ms", "mfm_engine_get_launch_cycles", "mfm_group_acquire_input", "mfm_group_submit", "mfm_group_shard_engine", "mfm_link_probe", "mfm_link_probe_runs", "mfm_engine_push_pinned_run", "mfm_group_push_pinned_run", "mfm_engine_input_room", "mfm_group_replay_arena", "mfm_strerror", "mfm_last_error", "mfm_hosttwin_discriminate", "mfm_hosttwin_discriminate_batch", "mfm_hosttwin_r14",
-    "mfm_hosttwin_pcm_range", "mfm_hosttwin_atan_table", "mfm_hosttwin_atan_table_ok",
+    "mfm_hosttwin_pcm_range", "mfm_hosttwin_atan_table", "mfm_hosttwin_atan_table_ok", "mfm_hosttwin_kernel_form",
     "mfm_resampler_create", "mfm_resampler_destroy", "mfm_resampler_max_out", "mfm_resampler_process_device",
     "mfm_resampler_process_host", "mfm_resampler_process_host_to_device",
     "mfm_pocsag_create", "mfm_pocsag_destroy", "mfm_pocsag_process_device", "mfm_pocsag_process_host",
@@ -299,6 +299,7 @@ def load_library():
     lib.mfm_hosttwin_atan_table.argtypes = [C.POINTER(C.c_float)]
     lib.mfm_hosttwin_atan_table.restype = None
     lib.mfm_hosttwin_atan_table_ok.restype = C.c_int
+    lib.mfm_hosttwin_kernel_form.argtypes = [vp, C.POINTER(Stats)]
     u32p = C.POINTER(C.c_uint32)
     lib.mfm_pocsag_create.argtypes = [C.POINTER(vp), C.POINTER(PocsagConfig)]
     lib.mfm_pocsag_destroy.argtypes = [C.POINTER(vp)]
@@ -545,6 +546,12 @@ class Engine:
     def stats(self):
         st = Stats()
         self._chk(self.lib.mfm_engine_get_stats(self.h, C.byref(st)), "mfm_engine_get_stats")
+        return {k: getattr(st, k) for k, _ in Stats._fields_}
+
+    def kernel_form(self):
+        """before commit: the form stats() will report after it (kernel_variant, slice_channels, ...), planned on the host"""
+        st = Stats()
+        self._chk(self.lib.mfm_hosttwin_kernel_form(self.h, C.byref(st)), "mfm_hosttwin_kernel_form")
         return {k: getattr(st, k) for k, _ in Stats._fields_}
 
     def launch_ms(self, last=4096):

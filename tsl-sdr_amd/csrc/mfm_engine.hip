@@ -25,23 +25,17 @@
 #include "mfm_kernel.h"
 #include "mfm_numerics.h"
 #include "mfm_taps.h"
+#include "mfm_plan.h"
 #include "mfm_engine_internal.h"
 
-/* every kernel file exports a pair: select (which template instance runs a launch description; asked at commit, where the
- * instance's LDS limit is raised once) and launch (through that pointer) */
-extern "C" hipError_t mfm_select_channel_kernel(int opl, int dbg_iq, const void **kfn_out);
+/* every kernel file exports a pair: select (which template instance runs a launch description: mfm_plan.hip, at commit) and
+ * launch (through that pointer) */
 extern "C" hipError_t mfm_launch_channel_kernel(const void *kfn, const mfm_launch *L, uint32_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t mfm_select_channel_kernel_mfma(const mfm_launch_mfma *L, int dbg_iq, const void **kfn_out,
-                                                     uint32_t *waves_per_simd_out);
 extern "C" hipError_t mfm_launch_channel_kernel_mfma(const void *kfn, const mfm_launch_mfma *L, uint32_t lds_bytes,
                                                      uint32_t grid, hipStream_t stream);
 extern "C" hipError_t mfm_disc_test_dot2(const int *s_re, const int *s_im, int *pcm, uint32_t n, const float2 *lut, hipStream_t stream);
 extern "C" hipError_t mfm_disc_test_mfma(const int *s_re, const int *s_im, int *pcm, uint32_t n, const float2 *lut, hipStream_t stream);
 extern "C" hipError_t mfm_disc_test_v3(const int *s_re, const int *s_im, int *pcm, uint32_t n, const float2 *lut, hipStream_t stream);
-extern "C" hipError_t mfm_select_channel_kernel_v3(const mfm_launch_v3 *L, int dbg_iq, const void **kfn_out);
-extern "C" uint32_t mfm_rot_entry_bytes_v3(void);
-extern "C" uint32_t mfm_sp_pitch_v3(void);
-extern "C" uint32_t mfm_v3l_wg_per_cu(const mfm_launch_v3 *L);
 extern "C" hipError_t mfm_launch_channel_kernel_v3(const void *kfn, const mfm_launch_v3 *L, uint32_t lds_bytes, uint32_t grid,
                                                    hipStream_t stream);
 
@@ -68,6 +62,25 @@ int fail(int code, const char *fmt, ...)
         }                                                                                                    \
     } while (0)
 
+#define MFM_TRY(expr)                                                                                        \
+    do {                                                                                                     \
+        const int rc_ = (expr);                                                                              \
+        if (rc_ != MFM_OK) {                                                                                 \
+            return rc_;                                                                                      \
+        }                                                                                                    \
+    } while (0)
+
+/* a device copy of a host table */
+template <class P, class T>
+int upload(P **dst, const std::vector<T> &v)
+{
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, v.size() * sizeof(T)));
+    *dst = static_cast<P *>(d);
+    HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return MFM_OK;
+}
+
 /* FNV-1a of the 257 float bit patterns of the fast_atan2f table */
 constexpr uint64_t MFM_ATAN_TABLE_FNV1A = 0x674d1aab1787b44bull;
 
@@ -77,71 +90,6 @@ constexpr int kTimingPairs = 256; /* event pairs kept before the oldest is folde
 constexpr uint64_t kSparseTiming = 4; /* MFM_F_TIMING_SPARSE: one launch in this many is bracketed */
 constexpr uint64_t kCycleRing = 1024; /* launches whose shader-clock stamps are kept (mfm_engine_get_launch_cycles) */
 constexpr size_t kLaunchRing = 4096; /* per-launch durations kept for mfm_engine_get_launch_ms() */
-constexpr uint32_t kMaxOutputsPerTile = 128;
-/* 128-tap filters: slices of 128 channels from this many channels on (below, slices of 64: MFM_F_SLICE_128 / _64 override) */
-constexpr uint32_t kSlice128MinChannels = 512; /* the measured crossover (profiles/r06_slice128_ab.txt): +1.8 % at 128, +1.7 % at 256,
-                                                 -0.6 % at 512, -0.8 % at 768, -1.4 % at 1024 channels */
-/* second-generation kernels: PCM stores with system scope from this many channels per launch on (profiles/r05_store_policy.txt,
- * r06_hbm_traffic_1024ch.json: L2-miss traffic 1.27 -> 1.16 x algorithmic at 1024 channels at unchanged time; +0.4 % time at 256
- * channels and 1.5-5 % at 64, where there is nothing to gain: profiles/r06_ab_store_policy.txt) */
-constexpr uint32_t kPcmWriteThroughMinChannels = 512;
-constexpr uint64_t kMaxRotEntries = 1ull << 26; /* per distinct increment: 512 MiB of table */
-
-struct Channel {
-    std::vector<int16_t> cre, cim;
-    int16_t incr_re = 0, incr_im = 0;
-    bool want_iq = false;
-    /* rotator table placement */
-    uint64_t rot_base = 0;
-    uint32_t mu = 0, lam = 1;
-};
-
-inline void rot_step(int16_t &rr, int16_t &ri, int16_t ir, int16_t ii)
-{
-    /* filter/direct_fir.c:166-167 -> filter/complex.h:51-62 */
-    const int32_t a = rr, b = ri;
-    const int16_t nr = (int16_t)mfm_r14_wide(a * ir - b * ii);
-    const int16_t ni = (int16_t)mfm_r14_wide(a * ii + b * ir);
-    rr = nr;
-    ri = ni;
-}
-
-/* Brent's cycle finder on the rotator recurrence started at (16384, 0) (direct_fir.c:78-79). */
-bool rot_cycle(int16_t ir, int16_t ii, uint64_t limit, uint32_t *mu_out, uint32_t *lam_out)
-{
-    int16_t tr = 16384, ti = 0, hr = 16384, hi = 0;
-    uint64_t power = 1, lam = 1;
-    rot_step(hr, hi, ir, ii);
-    while (!(tr == hr && ti == hi)) {
-        if (power == lam) {
-            tr = hr;
-            ti = hi;
-            power *= 2;
-            lam = 0;
-        }
-        rot_step(hr, hi, ir, ii);
-        lam++;
-        if (lam > limit) {
-            return false;
-        }
-    }
-    tr = 16384, ti = 0, hr = 16384, hi = 0;
-    for (uint64_t i = 0; i < lam; i++) {
-        rot_step(hr, hi, ir, ii);
-    }
-    uint64_t mu = 0;
-    while (!(tr == hr && ti == hi)) {
-        rot_step(tr, ti, ir, ii);
-        rot_step(hr, hi, ir, ii);
-        mu++;
-        if (mu > limit) {
-            return false;
-        }
-    }
-    *mu_out = (uint32_t)mu;
-    *lam_out = (uint32_t)lam;
-    return true;
-}
 
 struct OutSlot {
     int16_t *d_pcm = nullptr;
@@ -163,45 +111,14 @@ struct mfm_engine {
     bool committed = false;
     bool any_iq = false;
 
-    /* geometry */
-    int opl = 2;
-    uint32_t rs2 = 0, lds_bytes = 0, lut_off = 0, nchunks = 0, ngroups = 0, gpw = 0, nslices = 0;
-    uint32_t cap_in = 0;     /* samples per input buffer */
-    uint32_t out_stride = 0; /* outputs per channel one submit can produce (even) */
-
-    /* matrix-core path (mfm_kernel_mfma.hip) */
-    bool use_mfma = false;
-    uint32_t m_row_bytes = 0, m_nstage = 0;
-    bool slice128 = false;        /* 128-tap filters on 128-channel slices (layout 3, two row blocks per wave) */
-    uint32_t m_ks = 0, m_ot = 0, m_rs = 0, m_plane_bytes = 0, m_lut_off = 0, m_krow_off = 0, m_nrb = 0,
-             m_nslices = 0, m_lds_bytes = 0, m_wg_per_cu = 1;
-    uint32_t m_wg_fmt[4] = { 1, 1, 1, 1 }; /* workgroups per CU of the instance each input format runs (select_kernels) */
-    bool m_resident_taps = false;
-    bool m_fixed_planes = false;
-    uint32_t m_ah_mask = 0; /* k-steps whose high-byte tap plane is not all zero */
-    uint32_t m_kq_used = 0; /* k-steps that hold taps at all */
-    /* second-generation matrix kernel (mfm_kernel_v3.hip): same tap fragments, its own LDS image */
-    bool use_v3 = false;
-    uint32_t v_rs = 0, v_sp_pitch = 0, v_nstage4 = 0, v_lds_bytes = 0, v_wg_per_cu = 1, v_cross[4] = { 0, 0, 0, 0 },
-             v_within[4] = { 0, 0, 0, 0 };
-    uint32_t v_layout = 0, v_t_per = 0, v_t_pitch = 0; /* mfm_launch_v3::layout: chunk rows for decimations % 32 != 0 */
-    /* layout 3, long filters (mfm_kernel_v3l.hip): plain rows; v_rs = row stride, v_plane = bytes of one byte plane */
-    uint32_t v_plane = 0, v_ng = 0, v_nstage_p = 0, v_sta_bytes = 0, v_rb = 1;
-    uint32_t v_shift = 0, v_copy_pitch = 0; /* decimations 1, 2, 4: 8 / D shifted copies of the image, this many bytes apart */
-    uint32_t v_nslices = 0; /* channel slices of the second-generation launches: of 64 channels, or of 128 (v_rb = 2) */
-    uint32_t v_kq = 0, v_nh = 0, v_kperm[4] = { 0, 0, 0, 0 }; /* the instance's k-step count, k-steps with a high-byte tap plane,
-                                                                 and the order the k-steps are laid out in (mfm_launch_v3::kperm) */
-    uint32_t *d_afrag = nullptr;
-    int32_t *d_krow = nullptr;
-    int32_t *d_krow8[4] = { nullptr, nullptr, nullptr, nullptr }; /* [MFM_IN_*]: row constants of the 8-bit input forms */
-    bool raw8_ok = false; /* the matrix kernels can read 8-bit input as it is (IN8 forms of mfm_kernel_v3.hip, mfm_kernel_mfma.hip) */
-    uint32_t v_rc = 0; /* the lowest rotator class (MFM_RC_*) among the channels: selects the kernel instance */
-    uint32_t rot_exact_channels = 0, rot_fast_slices = 0;
-    /* the kernel instance that runs a block of input format MFM_IN_* (selected, and its LDS limit raised, at commit) */
-    const void *kfn[4] = { nullptr, nullptr, nullptr, nullptr };
+    /* which kernel runs and how (mfm_plan.h); at commit its launch descriptions get the device tables below */
+    KernelPlan plan;
 
     /* device tables */
     uint32_t *d_coef = nullptr, *d_tapoff = nullptr;
+    uint32_t *d_afrag = nullptr;
+    int32_t *d_krow = nullptr;
+    int32_t *d_krow8[4] = { nullptr, nullptr, nullptr, nullptr }; /* [MFM_IN_*]: row constants of the 8-bit input forms */
     mfm_chan_info *d_info = nullptr;
     uint2 *d_rot = nullptr;
     float2 *d_lut = nullptr;
@@ -289,118 +206,6 @@ struct mfm_engine {
 };
 
 namespace {
-
-/* The geometry half of a launch description - everything commit fixed, per input format; submit adds the block (input
- * address and counts, chunking, output slot, carried state).  Also what the kernel files' select functions look at. */
-void fill_v3(const mfm_engine *e, int fmt, mfm_launch_v3 &V)
-{
-    V.decim = e->cfg.decimation;
-    V.x_last4 = e->v_shift ? e->cap_in - 1u : (e->cap_in - 4u) & ~3u;
-    V.kq = e->m_ks;
-    V.rs = e->v_rs;
-    V.sp_pitch = e->v_sp_pitch;
-    V.plane_pitch = 4u * e->v_sp_pitch;
-    V.buf_pitch = 8u * e->v_sp_pitch;
-    V.nstage4 = e->v_nstage4;
-    V.lut_off = 16u * e->v_sp_pitch;
-    V.sta_off = V.lut_off + 2048u;
-    for (int k = 0; k < 4; k++) {
-        V.cross[k] = e->v_cross[k];
-        V.within[k] = e->v_within[k];
-    }
-    V.layout = e->v_layout;
-    V.t_per = e->v_t_per;
-    V.t_pitch = e->v_t_pitch;
-    if (3u == e->v_layout) {
-        /* long filters: [two buffers of two byte planes | atan table | staging offsets | transposition areas + per-wave constants] */
-        V.plane_pitch = e->v_plane;
-        V.buf_pitch = 2u * e->v_plane;
-        V.lut_off = 4u * e->v_plane;
-        V.sta_off = V.lut_off + 2048u;
-        V.tp_off = V.sta_off + e->v_sta_bytes;
-        V.row_bytes = e->m_row_bytes;
-        V.split_rows = (e->cfg.decimation % 4u) != 0u ? 1u : 0u;
-        V.kq = e->v_kq;
-        V.kq_used = e->m_kq_used;
-        V.nh = e->v_nh;
-        for (int k = 0; k < 4; k++) {
-            V.kperm[k] = e->v_kperm[k];
-        }
-        V.ng = e->v_ng;
-        V.rb = e->v_rb;
-        V.nstage_p = e->v_nstage_p;
-        V.shift = e->v_shift;
-        if (e->v_shift) {
-            V.sp_pitch = e->v_copy_pitch;
-        }
-    }
-    V.nslices = e->v_nslices;
-    V.nrb = e->m_nrb;
-    V.nchan = (uint32_t)e->chans.size();
-    V.pcm_scope = (V.nchan >= kPcmWriteThroughMinChannels && !(e->cfg.flags & MFM_F_PCM_WRITE_BACK)) ? 1u : 0u;
-    V.out_stride = e->out_stride;
-    V.ah_mask = e->m_ah_mask;
-    V.rc = e->v_rc;
-    V.afrag = e->d_afrag;
-    V.krow = e->d_krow;
-    V.info = e->d_info;
-    V.rot = e->d_rot;
-    V.lut = e->d_lut;
-    if (fmt != MFM_IN_CS16) {
-        /* the buffer holds 2-byte samples: twice as many fit, a 16-byte chunk is 8 of them */
-        V.in8 = fmt == MFM_IN_RTLSDR_U8 ? 7u : 14u;
-        V.in8_xor = fmt == MFM_IN_RTLSDR_U8 ? 0x80808080u : 0u;
-        V.krow = e->d_krow8[fmt];
-        V.nstage4 = 2u == e->v_layout ? (73u * 25u + 7u + 7u) / 8u : e->v_nstage4 / 2u;
-        V.x_last4 = (2u * e->cap_in - 8u) & ~7u;
-        if (3u == e->v_layout) {
-            /* a staging chunk stays 4 samples there - an 8-byte load */
-            V.nstage4 = e->v_nstage4;
-            V.x_last4 = (2u * e->cap_in - 4u) & ~3u;
-            if (e->v_shift) {
-                V.x_last4 = 2u * e->cap_in - 1u; /* one-sample loads */
-            }
-        }
-    }
-}
-
-void fill_mfma(const mfm_engine *e, int fmt, mfm_launch_mfma &M)
-{
-    const uint32_t C = (uint32_t)e->chans.size(), D = e->cfg.decimation;
-    M.decim = D;
-    M.x_last4 = (e->cap_in - 4u) & ~3u;
-    M.kq = e->m_ks;
-    M.kq_used = e->m_kq_used;
-    M.ot = e->m_ot;
-    M.nstage = e->m_nstage;
-    M.rs = e->m_rs;
-    M.row_bytes = e->m_row_bytes;
-    M.split_rows = (D % 4u) != 0u ? 1u : 0u;
-    M.plane_bytes = e->m_plane_bytes;
-    M.fixed_planes = e->m_fixed_planes ? 1u : 0u;
-    M.lut_off = e->m_lut_off;
-    M.sta_off = e->m_lut_off + 2048u;
-    M.bof_off = M.sta_off + ((M.nstage / 4u + MFM_MFMA_NW * 64u - 1u) / (MFM_MFMA_NW * 64u)) * MFM_MFMA_NW * 64u * 4u;
-    M.tbl_off = C <= 256u ? M.bof_off + (e->m_ks > MFM_MFMA_KQ_MAX ? 2048u : 0u) : 0u;
-    M.nslices = e->m_nslices;
-    M.nrb = e->m_nrb;
-    M.nchan = C;
-    M.out_stride = e->out_stride;
-    M.ah_mask = e->m_ah_mask;
-    M.stream_taps = (e->cfg.flags & MFM_F_STREAM_TAPS) ? 1u : 0u;
-    M.afrag = e->d_afrag;
-    M.krow = e->d_krow;
-    M.info = e->d_info;
-    M.rot = e->d_rot;
-    M.lut = e->d_lut;
-    if (fmt != MFM_IN_CS16) {
-        /* the buffer holds 2-byte samples: twice as many fit; a staging chunk (4 samples) is an 8-byte load */
-        M.in8 = fmt == MFM_IN_RTLSDR_U8 ? 7u : 14u;
-        M.in8_xor = fmt == MFM_IN_RTLSDR_U8 ? 0x80808080u : 0u;
-        M.krow = e->d_krow8[fmt];
-        M.x_last4 = (2u * e->cap_in - 4u) & ~3u;
-    }
-}
 
 /* The dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to a kernel instance on a device, not to an
  * engine: two engines of one process can share an instance with different image sizes (first-generation kernels with
@@ -580,47 +385,6 @@ int division_selftest(int device, int variant)
 }
 
 
-/* which instance runs blocks of each input format; its LDS limit is raised here, once (commit, on the engine's device) */
-int select_kernels(mfm_engine *e)
-{
-    for (int fmt = MFM_IN_CS16; fmt <= MFM_IN_RTLSDR_U8; fmt++) {
-        e->kfn[fmt] = nullptr;
-        if (fmt != MFM_IN_CS16 && !e->raw8_ok) {
-            continue;
-        }
-        const void *fn = nullptr;
-        uint32_t lds = 0;
-        if (e->use_v3) {
-            mfm_launch_v3 V{};
-            fill_v3(e, fmt, V);
-            HIP_TRY(mfm_select_channel_kernel_v3(&V, e->any_iq ? 1 : 0, &fn));
-            lds = e->v_lds_bytes;
-        } else if (e->use_mfma) {
-            mfm_launch_mfma M{};
-            fill_mfma(e, fmt, M);
-            uint32_t wps = 4;
-            HIP_TRY(mfm_select_channel_kernel_mfma(&M, e->any_iq ? 1 : 0, &fn, &wps));
-            lds = e->m_lds_bytes;
-            /* a resident long-filter instance takes a SIMD's registers with two waves: one workgroup per CU */
-            e->m_wg_fmt[fmt] = wps < 4u ? 1u : e->m_wg_per_cu;
-            if (fmt == MFM_IN_CS16) {
-                e->m_resident_taps = wps < 4u;
-            }
-        } else {
-            HIP_TRY(mfm_select_channel_kernel(e->opl, e->any_iq ? 1 : 0, &fn));
-            lds = e->lds_bytes;
-        }
-        {
-            const int rc = raise_lds_limit(e->cfg.device, fn, lds);
-            if (rc != MFM_OK) {
-                return rc;
-            }
-        }
-        e->kfn[fmt] = fn;
-    }
-    return MFM_OK;
-}
-
 int fold_timing(mfm_engine *e, bool all)
 {
     while (e->t_tail < e->t_head && (all || e->t_head - e->t_tail >= (uint64_t)kTimingPairs)) {
@@ -639,6 +403,38 @@ int fold_timing(mfm_engine *e, bool all)
     return MFM_OK;
 }
 
+template <class P>
+void free_dev(P *&p)
+{
+    (void)hipFree(p);
+    p = nullptr;
+}
+
+template <class P>
+void free_host(P *&p)
+{
+    if (p) {
+        (void)hipHostFree(p);
+    }
+    p = nullptr;
+}
+
+void free_event(hipEvent_t &ev)
+{
+    if (ev) {
+        (void)hipEventDestroy(ev);
+    }
+    ev = nullptr;
+}
+
+void free_stream(hipStream_t &s)
+{
+    if (s) {
+        (void)hipStreamDestroy(s);
+    }
+    s = nullptr;
+}
+
 void free_device(mfm_engine *e)
 {
     if (!e->committed) {
@@ -646,132 +442,67 @@ void free_device(mfm_engine *e)
     }
     (void)hipSetDevice(e->cfg.device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(e->d_coef);
-    (void)hipFree(e->d_tapoff);
-    (void)hipFree(e->d_afrag);
-    (void)hipFree(e->d_krow);
-    for (int i = 0; i < 4; i++) {
-        (void)hipFree(e->d_krow8[i]);
-        e->d_krow8[i] = nullptr;
+    free_dev(e->d_coef);
+    free_dev(e->d_tapoff);
+    free_dev(e->d_afrag);
+    free_dev(e->d_krow);
+    for (int32_t *&k : e->d_krow8) {
+        free_dev(k);
     }
-    (void)hipFree(e->d_tailtmp);
-    e->d_tailtmp = nullptr;
-    (void)hipFree(e->d_info);
-    (void)hipFree(e->d_rot);
-    (void)hipFree(e->d_cyc);
-    (void)hipFree(e->d_lut);
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(e->d_state[i]);
+    free_dev(e->d_tailtmp);
+    free_dev(e->d_info);
+    free_dev(e->d_rot);
+    free_dev(e->d_cyc);
+    free_dev(e->d_lut);
+    for (mfm_chan_state *&s : e->d_state) {
+        free_dev(s);
     }
     for (int i = 0; i < kMaxInBufs; i++) {
         if (e->own_in) {
             (void)hipFree(e->d_in[i]);
         }
-        if (e->d_raw[i]) {
-            (void)hipFree(e->d_raw[i]);
-        }
-        if (e->h_in[i]) {
-            (void)hipHostFree(e->h_in[i]);
-        }
-        if (e->in_free[i]) {
-            (void)hipEventDestroy(e->in_free[i]);
-        }
+        e->d_in[i] = nullptr;
+        free_dev(e->d_raw[i]);
+        free_host(e->h_in[i]);
+        free_event(e->in_free[i]);
+        e->in_free_wait[i] = nullptr; /* (in_free[i] or a timing event) */
+        free_event(e->tail_done[i]);
+        e->tail_pending[i] = false;
     }
-    for (int i = 0; i < kOutSlots; i++) {
-        OutSlot &s = e->slots[i];
-        (void)hipFree(s.d_pcm);
-        (void)hipFree(s.d_iq);
-        if (s.h_pcm) {
-            (void)hipHostFree(s.h_pcm);
-        }
-        if (s.h_iq) {
-            (void)hipHostFree(s.h_iq);
-        }
-        if (s.ready) {
-            (void)hipEventDestroy(s.ready);
-        }
+    for (OutSlot &s : e->slots) {
+        free_dev(s.d_pcm);
+        free_dev(s.d_iq);
+        free_host(s.h_pcm);
+        free_host(s.h_iq);
+        free_event(s.ready);
+        s = OutSlot();
     }
-    if (e->timing_events) {
-        for (int i = 0; i < kTimingPairs; i++) {
-            if (e->t0[i]) {
-                (void)hipEventDestroy(e->t0[i]);
-            }
-            if (e->t1[i]) {
-                (void)hipEventDestroy(e->t1[i]);
-            }
-        }
+    for (int i = 0; i < kTimingPairs; i++) {
+        free_event(e->t0[i]);
+        free_event(e->t1[i]);
     }
-    if (e->in_ready) {
-        (void)hipEventDestroy(e->in_ready);
-    }
+    e->timing_events = false;
     for (uint64_t i = 0; i < mfm_engine::kCopyRing; i++) {
-        if (e->copy_ev[i]) {
-            (void)hipEventDestroy(e->copy_ev[i]);
-            e->copy_ev[i] = nullptr;
-        }
+        free_event(e->copy_ev[i]);
         e->copy_ev_seq[i] = 0;
     }
     e->copy_seq = e->copy_done_seq = e->copy_ev_next = 0;
     e->wait_copy_stream = false;
-    if (e->kernel_done) {
-        (void)hipEventDestroy(e->kernel_done);
-    }
-    if (e->s_in) {
-        (void)hipStreamDestroy(e->s_in);
-    }
-    if (e->cs[1] && e->cs[1] != e->s_compute) {
-        (void)hipStreamDestroy(e->cs[1]);
+    free_event(e->in_ready);
+    free_event(e->kernel_done);
+    if (e->cs[1] != e->s_compute) {
+        free_stream(e->cs[1]);
     }
     e->cs[0] = e->cs[1] = e->s_last = nullptr;
-    for (int i = 0; i < kMaxInBufs; i++) {
-        if (e->tail_done[i]) {
-            (void)hipEventDestroy(e->tail_done[i]);
-            e->tail_done[i] = nullptr;
-        }
-        e->tail_pending[i] = false;
-    }
-    if (e->s_compute) {
-        (void)hipStreamDestroy(e->s_compute);
-    }
-    if (e->s_out) {
-        (void)hipStreamDestroy(e->s_out);
-    }
-    e->d_coef = e->d_tapoff = e->d_afrag = nullptr;
-    e->d_krow = nullptr;
-    e->d_info = nullptr;
-    e->d_rot = nullptr;
-    e->d_cyc = nullptr;
-    e->d_lut = nullptr;
-    for (int i = 0; i < 2; i++) {
-        e->d_state[i] = nullptr;
-    }
-    for (int i = 0; i < kMaxInBufs; i++) {
-        e->d_in[i] = nullptr;
-        e->d_raw[i] = nullptr;
-        e->h_in[i] = nullptr;
-        e->in_free[i] = e->in_free_wait[i] = nullptr;
-    }
-    for (int i = 0; i < kOutSlots; i++) {
-        e->slots[i] = OutSlot();
-    }
-    e->in_ready = e->kernel_done = nullptr;
-    e->s_in = e->s_compute = e->s_out = nullptr;
-    e->timing_events = false;
+    free_stream(e->s_in);
+    free_stream(e->s_compute);
+    free_stream(e->s_out);
     e->committed = false;
-}
-
-uint64_t input_capacity(uint32_t max_block, uint32_t coalesce, uint32_t nr_taps)
-{
-    /* history tail (< nr_taps samples) + block + one 16-byte staging chunk of slack (a chunk that starts on the last
-     * real sample must still be readable in place: decimations that are not multiples of 4 start their chunks at any
-     * sample), rounded to 64 samples.  A coalescing engine launches once coalesce_samples have gathered: fewer than that
-     * plus one more block of any size always fit. */
-    return ((uint64_t)max_block + coalesce + 2ull * nr_taps + 4u + 63u) & ~63ull; /* 2 x: history tail + mfm_engine::hist (<= taps) */
 }
 
 int write_state_fresh(mfm_engine *e)
 {
-    std::vector<mfm_chan_state> st(e->ngroups * MFM_CG);
+    std::vector<mfm_chan_state> st(e->plan.ngroups * MFM_CG);
     for (auto &s : st) {
         s.carry_q = 0; /* fm_demod.c: last sample starts at 0 (TZAALLOC, :29) */
         s.kb = 0;
@@ -1023,6 +754,8 @@ int mfm_engine_commit(struct mfm_engine *e)
     return rc;
 }
 
+/* Device setup for the plan (mfm_plan.h): the device check, the plan and its host tables, streams and events, the uploads,
+ * input buffers and output slots, the launch descriptions' device pointers and each instance's LDS limit. */
 static int commit_locked(struct mfm_engine *e)
 {
     if (e->chans.empty()) {
@@ -1038,629 +771,13 @@ static int commit_locked(struct mfm_engine *e)
     }
     HIP_TRY(hipSetDevice(e->cfg.device));
 
-    const uint32_t T = e->nr_taps, D = e->cfg.decimation, C = (uint32_t)e->chans.size();
-    const bool dev_only = (e->cfg.flags & MFM_F_DEVICE_ONLY) != 0;
-
-    /* ---- geometry: outputs per lane, LDS tile ---- */
-    const uint32_t qrows = (T + D - 1) / D;
-    auto tile_dwords = [&](int opl, uint32_t *rs2) {
-        const uint32_t rows = 64u * opl - 1u + qrows;
-        *rs2 = rows | 1u; /* odd stride: transposing stores hit 32 different banks */
-        return (uint64_t)D * *rs2;
-    };
-    uint32_t rs2 = 0;
-    int opl = 2;
-    uint64_t dw = tile_dwords(2, &rs2);
-    if ((dw + 512) * 4 > 53 * 1024) {
-        opl = 1;
-        dw = tile_dwords(1, &rs2);
-    }
-    if ((dw + 512) * 4 > 160 * 1024) {
-        return fail(MFM_E_INVAL, "decimation %u needs a %llu-byte LDS tile (> 160 KiB)", D,
-                    (unsigned long long)(dw + 512) * 4);
-    }
-    e->opl = opl;
-    e->rs2 = rs2;
-    e->lut_off = (uint32_t)((dw + 3) & ~3ull);
-    e->lds_bytes = (e->lut_off + 512) * 4;
-    e->nchunks = (T + MFM_TG - 1) / MFM_TG;
-    e->ngroups = (C + MFM_CG - 1) / MFM_CG;
-    e->gpw = std::min<uint32_t>(MFM_NW, e->ngroups);
-    e->nslices = (e->ngroups + e->gpw - 1) / e->gpw;
-    e->cap_in = (uint32_t)input_capacity(e->cfg.max_block_samples, e->cfg.coalesce_samples, T);
+    KernelPlan &p = e->plan;
+    HostTables t;
+    MFM_TRY(plan_channel_kernel(e->cfg, e->chans, e->nr_taps, p));
+    MFM_TRY(build_host_tables(p, e->chans, t));
+    const bool v3 = 2u == p.variant, dev_only = (e->cfg.flags & MFM_F_DEVICE_ONLY) != 0;
     e->nbuf = e->cfg.coalesce_samples ? 3 : 2;
-    /* a multiple of 8 outputs: channel rows of the PCM buffer start 16-byte aligned (8-byte PCM / 16-byte IQ stores) */
-    e->out_stride = ((e->cap_in - T) / D + 1 + 7) & ~7u;
-    e->any_iq = false;
-    for (const Channel &c : e->chans) {
-        e->any_iq |= c.want_iq;
-    }
-    /* the kernels address outputs with 32-bit byte offsets from the buffer base: 2 bytes per PCM sample, 4 per
-     * filtered-IQ sample, plus the dump slots behind the last row */
-    const uint64_t out_limit = e->any_iq ? (1ull << 30) : (1ull << 31);
-    if ((uint64_t)C * e->out_stride + 64 >= out_limit) {
-        return fail(MFM_E_INVAL, "channels x outputs per block = %llu exceeds %llu (use smaller blocks)",
-                    (unsigned long long)C * e->out_stride, (unsigned long long)out_limit);
-    }
-
-    /* ---- tap table: [group][chunk][tap in chunk][channel in group]{(cr,-ci),(ci,cr)} ---- */
-    const size_t coef_dwords = (size_t)e->ngroups * e->nchunks * MFM_TG * MFM_CG * 2;
-    std::vector<uint32_t> coef(coef_dwords, 0u);
-    for (uint32_t c = 0; c < C; c++) {
-        const Channel &ch = e->chans[c];
-        const uint32_t g = c / MFM_CG, cc = c % MFM_CG;
-        for (uint32_t i = 0; i < T; i++) {
-            const uint32_t chunk = i / MFM_TG, k = i % MFM_TG;
-            const size_t at = ((((size_t)g * e->nchunks + chunk) * MFM_TG + k) * MFM_CG + cc) * 2;
-            const int32_t cr = ch.cre[i], ci = ch.cim[i];
-            coef[at + 0] = mfm_pack16(cr, -ci);
-            coef[at + 1] = mfm_pack16(ci, cr);
-        }
-    }
-    std::vector<uint32_t> tapoff((size_t)e->nchunks * MFM_TG, 0u);
-    for (uint32_t i = 0; i < T; i++) {
-        tapoff[i] = ((i % D) * rs2 + i / D) * 4u;
-    }
-
-    /* ---- matrix-core path.  An LDS row (the D samples between two outputs) is 2*D plane bytes; the B fragments are
-     *      16-byte reads, so rows are padded to 16-byte multiples when D is not a multiple of 8, and the taps (the A
-     *      operand) carry zeros over the padding: decimation 25 of etc/pocsag_rtlsdr.json = rows of 50 + 14 bytes,
-     *      128 taps = 5 full rows + 3 taps = 326 elements -> 6 k-steps instead of 4.  Usable while at least 3/4 of a
-     *      row is samples, the padded filter fits the 16 k-steps of the streaming variant and every tap splits into
-     *      two signed bytes. ---- */
-    std::vector<uint32_t> afrag;
-    std::vector<int32_t> krow;
-    /* decimations 1, 2, 4 (etc/multifm_file.json: 1): rows shorter than a fragment - the long-filter kernel keeps 8 / D shifted
-     * copies of the image instead of padding them (mfm_kernel_v3l.hip, SHIFT); the window is then the unpadded 2 T elements */
-    const bool shift_geo = (1u == D || 2u == D || 4u == D) && T <= 512u && !(e->cfg.flags & (MFM_F_FORCE_MFMA_V1 | MFM_F_FORCE_DOT2));
-    const uint32_t row_bytes_p = shift_geo ? 2u * D : (2u * D + 15u) & ~15u;
-    const uint32_t k_elems = ((T - 1u) / D) * row_bytes_p + 2u * ((T - 1u) % D) + 2u; /* element index of the last tap + 1 */
-    e->use_mfma = 8u * D >= 3u * row_bytes_p && k_elems <= 64u * MFM_MFMA_KQ_STREAM_MAX &&
-                  !(e->cfg.flags & MFM_F_FORCE_DOT2);
-    for (const Channel &ch : e->chans) {
-        for (uint32_t i = 0; i < T && e->use_mfma; i++) {
-            if (ch.cre[i] > 32639 || ch.cim[i] > 32639 || ch.cim[i] < -32639) {
-                e->use_mfma = false; /* 256*Wh + Wl with both in int8 needs W <= 32639 */
-            }
-        }
-    }
-    if (e->use_mfma) {
-        uint32_t kq = 1;
-        while (64u * kq < k_elems) {
-            kq *= 2;
-        }
-        e->m_kq_used = (k_elems + 63u) / 64u;
-        const uint32_t row_bytes = row_bytes_p;
-        const bool padded = row_bytes_p != 2u * D;
-        /* LDS row stride: an ODD multiple of 32 bytes.  tools/ubench_lds.hip: the B-fragment read pattern (lane
-         * 16 kg + n reads 16 bytes at n * rs + 16 kg) runs at the full ds_read_b128 rate for rs = 224 and at 76-81 %
-         * of it for 80, 144, 176, 192, 208, 272 - odd multiples of 16 bytes are not enough. */
-        uint32_t rs_m = (row_bytes + 31u) / 32u * 32u;
-        if (((rs_m / 32u) & 1u) == 0u) {
-            rs_m += 32u;
-        }
-        uint32_t ot = 0, plane = 0, lds = 0;
-        const uint32_t want[] = { 2u * 31u, 31u }; /* new outputs per tile: two 31-output iterations, or one for large decimations */
-        for (uint32_t cand : want) {
-            /* samples a tile stages: its outputs' rows plus the rows the last window reaches into */
-            const uint32_t nst = padded ? ((cand * D + ((64u * kq + row_bytes - 1u) / row_bytes) * D) + 3u) & ~3u
-                                        : ((cand * D + 32u * kq) + 3u) & ~3u;
-            const uint32_t rows = (nst + D - 1u) / D;
-            const uint32_t pb = rows * rs_m;
-            /* two staging buffers x two byte planes + atan LUT + staging offsets + rotator constants of up to 256 channels */
-            const uint32_t nch_t = (nst / 4u + MFM_MFMA_NW * 64u - 1u) / (MFM_MFMA_NW * 64u); /* staging chunks per thread */
-            const uint32_t need = 4u * pb + 2048u + nch_t * MFM_MFMA_NW * 64u * 4u + (kq > MFM_MFMA_KQ_MAX ? 2048u : 0u) +
-                                  (C <= 256u ? 32u * C : 0u);
-            /* up to 80 KB two workgroups share a CU; beyond that one per CU is still far better than the v_dot2 kernel */
-            /* the kernels are built for up to 4 chunks per thread with two iterations, up to MFM_M_CH_MAX with one
-             * (and then only for 128-tap-class and longer filters) */
-            const uint32_t nch_max = cand == 62u ? 4u : MFM_M_CH_MAX;
-            if (cand == 31u && kq < MFM_MFMA_KQ_MAX) {
-                continue;
-            }
-            if (need <= 150u * 1024u && nch_t <= nch_max) {
-                ot = cand;
-                plane = pb;
-                lds = need;
-                break;
-            }
-        }
-        if (0 == ot) {
-            e->use_mfma = false;
-        } else {
-            e->m_ks = kq;
-            e->m_row_bytes = row_bytes;
-            e->m_nstage = padded ? ((ot * D + ((64u * kq + row_bytes - 1u) / row_bytes) * D) + 3u) & ~3u
-                                 : ((ot * D + 32u * kq) + 3u) & ~3u;
-            e->m_ot = ot;
-            e->m_rs = rs_m;
-            e->m_plane_bytes = plane;
-            e->m_lut_off = 4u * plane;
-            e->m_lds_bytes = lds;
-            /* planes at a fixed 16 KiB pitch when they fit and two workgroups still share a CU: the kernel then
-             * reaches the low-byte plane and the second staging buffer through instruction immediates */
-            e->m_fixed_planes = false;
-            if (plane <= MFM_M_PLANE_DIST && kq <= MFM_MFMA_KQ_MAX && ot == 62u) { /* streaming / single-iteration variants: packed planes */
-                const uint32_t lds_fixed = 4u * MFM_M_PLANE_DIST + (lds - 4u * plane);
-                if (2u * lds_fixed <= 160u * 1024u) {
-                    e->m_fixed_planes = true;
-                    e->m_lut_off = 4u * MFM_M_PLANE_DIST;
-                    e->m_lds_bytes = lds_fixed;
-                    lds = lds_fixed;
-                }
-            }
-            e->m_nrb = (2u * C + 15u) / 16u;
-            e->m_nslices = (e->m_nrb + MFM_MFMA_NW - 1u) / MFM_MFMA_NW;
-            e->m_wg_per_cu = std::max(1u, std::min(2u, (160u * 1024u) / lds));
-
-        }
-    }
-
-    /* ---- second-generation matrix kernel: 64-output tiles, four sub-planes per byte plane (mfm_kernel.h) ---- */
-    e->use_v3 = false;
-    e->v_layout = 0;
-    e->v_shift = 0;
-    e->v_rb = 1;
-    if (e->use_mfma && !(e->cfg.flags & MFM_F_FORCE_MFMA_V1) && e->m_ks <= 4u && D % 8u == 0u && (2u * D) % 64u != 0u) {
-        /* decimations that are multiples of 8 but not of 32 (40: etc/multifm.json, etc/multifm_1ch.json): the chunk-row
-         * layout (mfm_kernel.h).  t_per = chunks of four outputs; slots: one per four staged rows, plus the window's reach */
-        const uint32_t kq = e->m_ks, row_bytes = 2u * D, cpo = D / 8u, per = 4u * cpo;
-        const uint32_t extra = (64u * kq - 1u) / row_bytes;
-        const uint32_t rows = MFM_V3_LEAD + MFM_V3_OT + extra;
-        const uint32_t nchunks16 = (rows * row_bytes + 15u) / 16u;
-        const uint32_t x_max = cpo * 3u + 4u * (kq - 1u);
-        const uint32_t pitch = std::max((nchunks16 + per - 1u) / per + 1u, 16u + 1u + x_max / per + 1u);
-        const uint32_t plane = ((per + 3u) * pitch * 16u + 63u) & ~63u;
-        const uint32_t nstage4 = rows * D / 4u; /* D % 8 == 0 */
-        const uint32_t nch = (nstage4 + 511u) / 512u;
-        const uint32_t lds = 4u * plane + 2048u + nch * 512u * 4u + 1024u + 2048u + nch * 512u * 4u;
-        if (nch <= MFM_V3_CH_MAX && lds <= 160u * 1024u) {
-            e->use_v3 = true;
-            e->v_layout = 1;
-            e->v_t_per = per;
-            e->v_t_pitch = pitch;
-            e->v_rs = 0;
-            e->v_sp_pitch = plane / 4u; /* plane pitch = 4 * sp_pitch, buffer pitch = 8 * sp_pitch, as in the sub-plane layout */
-            e->v_nstage4 = nstage4;
-            e->v_lds_bytes = lds;
-            e->v_wg_per_cu = std::max(1u, std::min(2u, (160u * 1024u) / lds));
-            for (uint32_t k = 0; k < 4; k++) {
-                e->v_cross[k] = e->v_within[k] = 0;
-            }
-        }
-    }
-    if (e->use_mfma && !(e->cfg.flags & MFM_F_FORCE_MFMA_V1) && e->m_ks <= 4u && (2u * D) % 64u == 0u) {
-        const uint32_t kq = e->m_ks, row_bytes = 2u * D;
-        uint32_t rs_v = (row_bytes + 31u) / 32u * 32u;
-        if (((rs_v / 32u) & 1u) == 0u) {
-            rs_v += 32u; /* odd multiple of 32 bytes: the B-fragment read pattern runs at the full ds_read_b128 rate */
-        }
-        const uint32_t extra = (64u * kq - 1u) / row_bytes; /* rows the last output's window reaches past the tile */
-        const uint32_t rows = MFM_V3_LEAD + MFM_V3_OT + extra;
-        const uint32_t sr = (rows + 3u) / 4u;
-        uint32_t sp = sr * rs_v;
-        sp = sp <= mfm_sp_pitch_v3() ? mfm_sp_pitch_v3() : (sp + 63u) & ~63u;
-        const uint32_t nstage4 = rows * D / 4u; /* D % 16 == 0 here */
-        const uint32_t nch = (nstage4 + 511u) / 512u;
-        const uint32_t lds = 16u * sp + 2048u + nch * 512u * 4u + 1024u + 2048u; /* image, atan table, staging offsets, row constants + fold constants, exact-rotator table */
-        if (nch <= MFM_V3_CH_MAX && lds <= 160u * 1024u) {
-            e->use_v3 = true;
-            e->v_rs = rs_v;
-            e->v_sp_pitch = sp;
-            e->v_nstage4 = nstage4;
-            e->v_lds_bytes = lds;
-            e->v_wg_per_cu = std::max(1u, std::min(2u, (160u * 1024u) / lds));
-#ifdef MFM_EXP_ONE_WG_PER_CU /* occupancy experiment (tools/exp/snapeng.sh): LDS padded so that one workgroup fits a CU */
-            e->v_lds_bytes = 100u * 1024u;
-            e->v_wg_per_cu = 1u;
-#endif
-            for (uint32_t k = 0; k < 4; k++) {
-                e->v_cross[k] = k < kq ? (64u * k) / row_bytes : 0u;
-                e->v_within[k] = k < kq ? (64u * k) % row_bytes : 0u;
-            }
-        }
-    }
-
-    if (e->use_mfma && !(e->cfg.flags & MFM_F_FORCE_MFMA_V1) && 25u == D && T <= 150u) {
-        /* decimation 25 (etc/pocsag_rtlsdr.json) on the second generation: rows of 50 plane bytes padded to 64, so that a k-step
-         * is exactly one row and a window of up to 150 taps spans six of them (layout 2, mfm_kernel.h); sub-planes at the fixed
-         * pitch, the image staged sample by sample.  The tap fragments are laid out for six k-steps. */
-        e->use_v3 = true;
-        e->v_layout = 2;
-        e->v_rs = 96u;
-        e->v_sp_pitch = mfm_sp_pitch_v3();
-        e->v_nstage4 = (73u * 25u + 3u + 3u) / 4u; /* 16-byte chunks covering the image wherever it starts inside the first one */
-        e->v_lds_bytes = 16u * mfm_sp_pitch_v3() + 2048u + 4u * 512u * 4u + 1024u + 2048u;
-        e->v_wg_per_cu = 2u;
-        for (uint32_t k = 0; k < 4; k++) {
-            e->v_cross[k] = k;
-            e->v_within[k] = 0;
-        }
-        e->m_ks = 6u;
-        e->m_kq_used = 6u;
-    }
-
-    if (shift_geo && e->use_mfma) {
-        /* ---- decimations 1, 2, 4 on the long-filter kernel's shifted copies (mfm_kernel_v3l.hip, SHIFT): whole-tile images of
-         *      8 / D copies, one row block per wave; the first generation's geometry above does not apply to rows this short ---- */
-        const uint32_t kq_inst = e->m_kq_used <= 4u ? 4u : e->m_kq_used <= 8u ? 8u : 16u;
-        uint32_t hi_mask = 0;
-        for (const Channel &ch : e->chans) {
-            for (uint32_t i = 0; i < T; i++) {
-                for (int32_t w : { (int32_t)ch.cre[i], (int32_t)ch.cim[i], -(int32_t)ch.cim[i] }) {
-                    const int32_t wl = (int8_t)(w & 0xff);
-                    if (((w - wl) >> 8) != 0) {
-                        hi_mask |= 1u << ((2u * i) / 64u);
-                    }
-                }
-            }
-        }
-        const uint32_t nc = 8u / D;
-        const uint32_t img_samples = 63u * D + T;                       /* what the tile's 64 windows cover */
-        const uint32_t read_bytes = 2u * D * 63u + 64u * kq_inst + 16u; /* ... and what the instance's fragment reads touch */
-        /* bytes between two copies: at least the copy, and 2 D (mod 16) sixteen-byte units - the sixteen columns of a fragment read
-         * (copy n % nc, offset 16 (n / nc)) then fall into sixteen different groups of four LDS banks */
-        uint32_t cp16 = (std::max(2u * img_samples, read_bytes) + 15u) / 16u;
-        while (cp16 % 16u != (2u * D) % 16u) {
-            cp16++;
-        }
-        const uint32_t plane = nc * cp16 * 16u;
-        const uint32_t aux = 8u * 8u * MFM_V3L_TP * 4u + 512u + 2048u;
-        const uint32_t lds = 4u * plane + 2048u + 2048u + aux;
-        mfm_launch_v3 probe{};
-        probe.layout = 3u;
-        probe.shift = 1u;
-        probe.kq = kq_inst;
-        probe.kq_used = e->m_kq_used;
-        probe.nh = (uint32_t)__builtin_popcount(hi_mask);
-        probe.ng = 4u;
-        probe.rb = 1u;
-        probe.nstage4 = img_samples;
-        const void *fn = nullptr;
-        if (img_samples <= 4u * 512u && lds <= 160u * 1024u && mfm_select_channel_kernel_v3(&probe, 0, &fn) == hipSuccess) {
-            e->use_v3 = true;
-            e->v_layout = 3u;
-            e->v_shift = 1u;
-            e->v_copy_pitch = cp16 * 16u;
-            e->v_rs = 2u * D;
-            e->v_plane = plane;
-            e->v_sp_pitch = 0;
-            e->v_ng = 4u;
-            e->v_rb = 1u;
-            e->v_nstage4 = img_samples;
-            e->v_nstage_p = T;
-            e->v_sta_bytes = 2048u;
-            e->v_lds_bytes = lds;
-            e->v_wg_per_cu = 1u; /* (per input format at launch time: mfm_v3l_wg_per_cu) */
-            e->v_kq = kq_inst;
-            e->v_nh = probe.nh;
-            uint8_t order[16] = { 0 };
-            uint32_t at = 0;
-            for (uint32_t k = 0; k < e->m_kq_used; k++) {
-                if ((hi_mask >> k) & 1u) {
-                    order[at++] = (uint8_t)k;
-                }
-            }
-            for (uint32_t k = 0; k < kq_inst; k++) {
-                if (!((hi_mask >> k) & 1u)) {
-                    order[at++] = (uint8_t)k;
-                }
-            }
-            for (int w = 0; w < 4; w++) {
-                e->v_kperm[w] = (uint32_t)order[4 * w] | ((uint32_t)order[4 * w + 1] << 8) | ((uint32_t)order[4 * w + 2] << 16) |
-                                ((uint32_t)order[4 * w + 3] << 24);
-            }
-        } else {
-            e->use_mfma = false; /* the v_dot2 kernel */
-        }
-    }
-    /* ---- filters of 129..512 taps on the second-generation structure (layout 3, mfm_kernel_v3l.hip): the first
-     *      generation's image - plain rows of m_row_bytes plane bytes at stride m_rs, any decimation - holding a whole
-     *      64-output tile, or half of one when two whole ones do not fit LDS (decimation 400 of configs[4]: 112 KB per
-     *      image of both planes); same tap fragments, same row constants.
-     *      And (round 6) 128-tap filters on SLICES OF 128 CHANNELS where there are that many: two row blocks per wave share
-     *      every B fragment and every staged image - half the LDS traffic and half the staging work per (channel, output) of
-     *      the 64-channel layouts above, for two waves per SIMD instead of four.  multifm/receiver.c:195-244 builds as many
-     *      channels as the configuration lists; north_star's shape is 1024 of them on one GPU. ---- */
-    struct l3_cand { uint32_t rb, ng; };
-    auto plan_layout3 = [&](const l3_cand *cand, size_t nr_cand) -> bool {
-        const uint32_t row_bytes = e->m_row_bytes, rs_l = e->m_rs;
-        const uint32_t kq_inst = mfm_v3l_built_kq(e->m_kq_used);
-        /* k-steps whose high-byte tap plane is not all zero (what m_ah_mask will say once the fragments are built) */
-        uint32_t hi_mask = 0;
-        for (const Channel &ch : e->chans) {
-            for (uint32_t i = 0; i < T; i++) {
-                const uint32_t kst = ((i / D) * row_bytes + 2u * (i % D)) / 64u;
-                for (int32_t w : { (int32_t)ch.cre[i], (int32_t)ch.cim[i], -(int32_t)ch.cim[i] }) {
-                    const int32_t wl = (int8_t)(w & 0xff);
-                    if (((w - wl) >> 8) != 0) {
-                        hi_mask |= 1u << kst;
-                    }
-                }
-            }
-        }
-        const uint32_t reach = (k_elems - 1u) / row_bytes;                       /* rows the last window reaches past its own */
-        const uint32_t reach_read = (64u * kq_inst - 1u) / row_bytes + 1u;       /* ... and what the instance's fragment reads touch */
-        /* (row blocks per wave, column groups per image), best first: slices of 128 channels - half the staging work and
-         * half the B-fragment traffic per (channel, output) - where there are more than 64 channels and two row blocks' taps
-         * fit 128 registers, on quarter-tile images; else slices of 64 on whole- or half-tile images */
-        const uint32_t nh_inst = mfm_v3l_built_nh(kq_inst, (uint32_t)__builtin_popcount(hi_mask));
-        for (size_t ci = 0; ci < nr_cand; ci++) {
-            const uint32_t ng = cand[ci].ng, rbw = cand[ci].rb;
-            if (2u == rbw && (e->m_nrb <= 8u || 8u * (kq_inst + nh_inst) > 128u || (e->cfg.flags & MFM_F_V3L_ONE_ROW_BLOCK))) {
-                continue;
-            }
-            const uint32_t opi = 16u * ng;
-            const uint32_t plane_used = (opi + std::max(reach, reach_read)) * rs_l;
-            const uint32_t plane = mfm_v3l_plane_pitch(rbw); /* a constant: the low plane's reads are "high plane + immediate" */
-            const uint32_t nstage4 = ((opi + reach) * D + 3u) / 4u;
-            const uint32_t nch = (nstage4 + 511u) / 512u;
-            if (nch > MFM_V3_CH_MAX || plane_used > plane || kq_inst > e->m_ks) {
-                continue;
-            }
-            /* the instance's count of chunks (a surplus chunk is loaded and not stored); 16-bit offsets where no chunk straddles rows */
-            const uint32_t sta = mfm_v3l_built_nch(nch) * ((D % 4u) != 0u ? 1536u : 1024u); /* 16-bit offsets (+ a byte per chunk: rows split) */
-            const uint32_t aux = 8u * 8u * rbw * MFM_V3L_TP * 4u + 512u * rbw + 2048u * rbw;
-            const uint32_t lds = 4u * plane + 2048u + sta + aux;
-            if (lds > 160u * 1024u) {
-                continue;
-            }
-            /* is the int16 instance for this geometry built?  (All are but a few that would need more than 256 registers.)  It
-             * must be known HERE: the second generation orders its rows by rotator class, the first does not. */
-            mfm_launch_v3 probe{};
-            probe.layout = 3u;
-            probe.kq = kq_inst;
-            probe.kq_used = e->m_kq_used;
-            probe.nh = (uint32_t)__builtin_popcount(hi_mask);
-            probe.ng = ng;
-            probe.rb = rbw;
-            probe.nstage4 = nstage4;
-            probe.split_rows = (D % 4u) != 0u ? 1u : 0u; /* (sample-by-sample staging: instances of their own, one row block per wave) */
-            probe.ah_mask = hi_mask;
-            const void *fn = nullptr;
-            if (mfm_select_channel_kernel_v3(&probe, 0, &fn) != hipSuccess) {
-                continue;
-            }
-            e->v_rb = rbw;
-            e->use_v3 = true;
-            e->v_layout = 3u;
-            e->v_rs = rs_l;
-            e->v_plane = plane;
-            e->v_sp_pitch = 0;
-            e->v_ng = ng;
-            e->v_nstage4 = nstage4;
-            e->v_nstage_p = ((1u + reach) * D + 3u) / 4u;
-            e->v_sta_bytes = sta;
-            e->v_lds_bytes = lds;
-            e->v_wg_per_cu = 1u; /* two waves per SIMD hold a long filter's taps: one workgroup per CU */
-            e->v_kq = kq_inst;
-            e->v_nh = probe.nh;
-            {
-                /* the order the k-steps are multiplied in: those with a high-byte tap plane first, then the others that
-                 * hold taps, then - up to the instance's count - steps of zero taps */
-                uint8_t order[16] = { 0 };
-                uint32_t at = 0;
-                for (uint32_t k = 0; k < e->m_kq_used; k++) {
-                    if ((hi_mask >> k) & 1u) {
-                        order[at++] = (uint8_t)k;
-                    }
-                }
-                for (uint32_t k = 0; k < kq_inst; k++) {
-                    if (!((hi_mask >> k) & 1u)) {
-                        order[at++] = (uint8_t)k;
-                    }
-                }
-                for (int w = 0; w < 4; w++) {
-                    e->v_kperm[w] = (uint32_t)order[4 * w] | ((uint32_t)order[4 * w + 1] << 8) | ((uint32_t)order[4 * w + 2] << 16) |
-                                    ((uint32_t)order[4 * w + 3] << 24);
-                }
-            }
-            return true;
-        }
-        return false;
-    };
-    if (e->use_mfma && !e->use_v3 && !(e->cfg.flags & (MFM_F_FORCE_MFMA_V1 | MFM_F_STREAM_TAPS)) && e->m_ks >= 8u &&
-        e->m_ks <= MFM_V3L_KQ_MAX) {
-        /* (row blocks per wave, column groups per image), best first: slices of 128 channels on quarter-tile images where there
-         * are more than 64 channels and two row blocks' taps fit 128 registers; else slices of 64 on whole- or half-tile images */
-        const l3_cand cand[3] = { { 2u, 1u }, { 1u, 4u }, { 1u, 2u } };
-        plan_layout3(cand, 3);
-    }
-    e->slice128 = false;
-    if (e->use_mfma && e->use_v3 && 0u == e->v_layout && 4u == e->m_ks && (2u * D) % 64u == 0u &&
-        !(e->cfg.flags & (MFM_F_FORCE_MFMA_V1 | MFM_F_SLICE_64)) &&
-        ((e->cfg.flags & MFM_F_SLICE_128) || C >= kSlice128MinChannels)) {
-        /* the sub-plane layout above stays what runs when the instance is not built (more than two high-byte tap planes) */
-        const l3_cand cand[1] = { { 2u, 4u } };
-        e->slice128 = plan_layout3(cand, 1);
-    }
-
-    e->v_nslices = (e->use_v3 && 3u == e->v_layout) ? (e->m_nrb + 8u * e->v_rb - 1u) / (8u * e->v_rb) : e->m_nslices;
-
-    /* ---- rotator classes and row order (filter/direct_fir.c:151-172,406-413).  An increment of exactly (16384, 0) - every
-     *      channel whose offset is a multiple of the output rate, e.g. a 25 kHz grid at 2.4 MS/s / 96 - leaves the rotator at
-     *      (16384, 0) for ever, and r14(f * 16384) = f: nothing to do.  An increment of (-16384, 0) - offsets at odd
-     *      multiples of half the output rate - makes it alternate between (16384, 0) and (-16384, 0), and r14(f * -16384)
-     *      = -f with the int16 cast's wrap: one packed multiply by +-1.  An increment of (0, +-16384) - offsets at odd
-     *      multiples of a quarter of the output rate - walks the four axis points: r14(f * rot) = f * j^m, a swap of
-     *      the halves and two signs.  Everything else is the general case (two Q14
-     *      dot products against the tabulated rotator and a second rounding).  The second-generation kernel runs a
-     *      64-channel slice without the table loads and the derotation arithmetic when all its channels are exact, so
-     *      the rows are ordered by class (stable); where a row's PCM goes is in its mfm_chan_info. ---- */
-    auto chan_class = [](const Channel &ch) -> uint32_t {
-        if ((ch.incr_re == 16384 && ch.incr_im == 0) || (ch.incr_re == 0 && ch.incr_im == 0)) {
-            return MFM_RC_IDENT; /* direct_fir.c:406 skips the derotation altogether for a zero increment */
-        }
-        if (ch.incr_re == -16384 && ch.incr_im == 0) {
-            return MFM_RC_FLIP;
-        }
-        return (ch.incr_re == 0 && (ch.incr_im == 16384 || ch.incr_im == -16384)) ? MFM_RC_QUARTER : MFM_RC_GENERAL;
-    };
-    /* quarter turns per output: rot after k outputs = j^(turns * k) * 16384 for the exact classes */
-    auto chan_turns = [](const Channel &ch) -> uint32_t {
-        return ch.incr_im == 16384 ? 1u : ch.incr_im == -16384 ? 3u : ch.incr_re == -16384 ? 2u : 0u;
-    };
-    std::vector<uint32_t> perm(C);
-    for (uint32_t c = 0; c < C; c++) {
-        perm[c] = c;
-    }
-    if (e->use_v3) {
-        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
-            return chan_class(e->chans[a]) > chan_class(e->chans[b]);
-        });
-    }
-    e->rot_exact_channels = 0;
-    for (uint32_t c = 0; c < C; c++) {
-        e->rot_exact_channels += chan_class(e->chans[c]) != MFM_RC_GENERAL ? 1u : 0u;
-    }
-    e->v_rc = MFM_RC_IDENT;
-    e->rot_fast_slices = 0;
-    for (uint32_t sl = 0; sl < e->m_nslices && e->use_v3; sl++) {
-        uint32_t cls = MFM_RC_IDENT; /* rows past the last channel have zero taps and store nothing */
-        for (uint32_t c = sl * 64u; c < std::min(C, sl * 64u + 64u); c++) {
-            cls = std::min(cls, chan_class(e->chans[perm[c]]));
-        }
-        e->v_rc = std::min(e->v_rc, cls);
-        e->rot_fast_slices += cls != MFM_RC_GENERAL ? 1u : 0u;
-    }
-    if (!e->use_v3 || e->any_iq || e->v_layout >= 2u) {
-        e->v_rc = MFM_RC_GENERAL; /* the exact-rotator instances are built without the filtered-IQ output, and for the
-                                     sub-plane / chunk-row geometries only */
-    }
-
-    if (e->use_mfma) {
-        const uint32_t kq = e->m_ks, row_bytes = e->m_row_bytes;
-            /* W[2c] = (cr0,-ci0,cr1,-ci1..), W[2c+1] = (ci0,cr0,ci1,cr1..) (filter/complex.h:40-46) */
-            const uint32_t K = 64u * kq;
-            auto w_at = [&](uint32_t row, uint32_t k) -> int32_t {
-                /* element k of a window = byte k % row_bytes of LDS row k / row_bytes: sample (k / row_bytes) * D +
-                 * (k % row_bytes) / 2 while the byte is inside the 2 * D sample bytes, padding (zero tap) behind them */
-                const uint32_t c = row / 2u, pos = k % row_bytes, i = (k / row_bytes) * D + pos / 2u;
-                if (c >= C || pos >= 2u * D || i >= T) {
-                    return 0;
-                }
-                const int32_t cr = e->chans[perm[c]].cre[i], ci = e->chans[perm[c]].cim[i];
-                if (row & 1u) {
-                    return (k & 1u) ? cr : ci;
-                }
-                return (k & 1u) ? -ci : cr;
-            };
-            /* v_mfma_i32_16x16x64_i8 A operand: lane (kg = lane >> 4, i = lane & 15) holds row i,
-             * elements 64*kq + 16*kg + j, j = 0..15 */
-            e->m_ah_mask = 0;
-            afrag.assign((size_t)e->m_nrb * kq * 2 * 64 * 4, 0u);
-            krow.assign((size_t)e->m_nrb * 16, 0);
-            uint8_t *ab = reinterpret_cast<uint8_t *>(afrag.data());
-            for (uint32_t rb = 0; rb < e->m_nrb; rb++) {
-                for (uint32_t i = 0; i < 16; i++) {
-                    const uint32_t row = rb * 16u + i;
-                    uint32_t sum = 0;
-                    for (uint32_t k = 0; k < K; k++) {
-                        const int32_t w = w_at(row, k);
-                        sum += (uint32_t)w;
-                        const int32_t wl = (int8_t)(w & 0xff);
-                        const int32_t wh = (w - wl) >> 8;
-                        const uint32_t kst = k / 64u, gg = (k % 64u) / 16u, j = k % 16u;
-                        const uint32_t ln = gg * 16u + i;
-                        const size_t base = ((((size_t)rb * kq + kst) * 2u) * 64u + ln) * 16u + j;
-                        if (wh != 0) {
-                            e->m_ah_mask |= 1u << kst;
-                        }
-                        ab[base] = (uint8_t)(int8_t)wh;              /* plane 0: high bytes */
-                        ab[base + 64u * 16u] = (uint8_t)(int8_t)wl;  /* plane 1: low bytes */
-                    }
-                    /* El = (e & 255) - 128 puts 128 * sum(W) into every product sum; 8192 is the rounding
-                     * bias of the first round_q30_q15 (filter/complex.h:30-34), added here once */
-                    krow[(size_t)rb * 16 + i] = (int32_t)(128u * sum + 8192u);
-                }
-            }
-    }
-
-    if (e->use_v3 && 3u == e->v_layout) {
-        /* the long-filter kernel's fragments: v_kq k-steps per row block, in the order v_kperm */
-        if (e->m_ah_mask != ([&] { uint32_t m = 0; for (uint32_t j = 0; j < e->v_nh; j++) { m |= 1u << ((e->v_kperm[j >> 2] >> (8u * (j & 3u))) & 0xffu); } return m; })()) {
-            return fail(MFM_E_INVAL, "internal: the tap-plane mask changed between planning and building the fragments");
-        }
-        const size_t step_dw = 2u * 64u * 4u; /* dwords of one k-step: two planes x 64 lanes x 16 bytes */
-        std::vector<uint32_t> af3((size_t)e->m_nrb * e->v_kq * step_dw, 0u);
-        for (uint32_t rb = 0; rb < e->m_nrb; rb++) {
-            for (uint32_t j = 0; j < e->v_kq; j++) {
-                const uint32_t src = (e->v_kperm[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-                if (src < e->m_ks) { /* (a step past the laid-out ones holds zero taps) */
-                    memcpy(&af3[((size_t)rb * e->v_kq + j) * step_dw], &afrag[((size_t)rb * e->m_ks + src) * step_dw], step_dw * 4u);
-                }
-            }
-        }
-        afrag.swap(af3);
-    }
-
-    /* ---- rotator tables (one per distinct increment) ---- */
-    std::map<std::pair<int16_t, int16_t>, std::pair<uint64_t, std::pair<uint32_t, uint32_t>>> seen;
-    std::vector<uint2> rot;
-    for (Channel &ch : e->chans) {
-        const auto key = std::make_pair(ch.incr_re, ch.incr_im);
-        auto it = seen.find(key);
-        if (it == seen.end()) {
-            uint32_t mu = 0, lam = 1;
-            int16_t ir = ch.incr_re, ii = ch.incr_im;
-            if (0 == ir && 0 == ii) {
-                /* direct_fir.c:406 skips derotation for a zero increment; a constant (16384,0)
-                 * rotator is the identity through both Q14 roundings */
-                ir = 16384;
-                ii = 0;
-            }
-            if (!rot_cycle(ir, ii, kMaxRotEntries, &mu, &lam)) {
-                return fail(MFM_E_INVAL, "rotator (%d,%d) has no cycle within %llu steps", ir, ii,
-                            (unsigned long long)kMaxRotEntries);
-            }
-            /* unroll short cycles to at least one tile's worth of entries: a multiple of a period is
-             * a period, and the kernels then fold an index with one conditional subtraction */
-            lam = lam * ((kMaxOutputsPerTile + lam - 1) / lam);
-            const uint64_t n = (uint64_t)mu + lam + kMaxOutputsPerTile;
-            const uint64_t base = rot.size() + 1; /* one dummy entry in front: index -1 is readable */
-            rot.resize(rot.size() + 1 + n);
-            rot[base - 1] = make_uint2(0, 0);
-            int16_t rr = 16384, ri = 0;
-            for (uint64_t k = 0; k < n; k++) {
-                if (ri == INT16_MIN) {
-                    return fail(MFM_E_INVAL, "rotator state reached -32768");
-                }
-                rot[base + k] = make_uint2(mfm_pack16(rr, -(int32_t)ri), mfm_pack16(ri, rr));
-                rot_step(rr, ri, ir, ii);
-            }
-            it = seen.emplace(key, std::make_pair(base, std::make_pair(mu, lam))).first;
-        }
-        ch.rot_base = it->second.first;
-        ch.mu = it->second.second.first;
-        ch.lam = it->second.second.second;
-    }
-    e->rot_entries = rot.size();
-    if (rot.size() >= (1ull << 29)) {
-        return fail(MFM_E_INVAL, "rotator tables need %zu entries (limit 2^29: byte offsets are 32-bit)", rot.size());
-    }
-
-    std::vector<mfm_chan_info> info((size_t)e->ngroups * MFM_CG);
-    memset(info.data(), 0, info.size() * sizeof(mfm_chan_info));
-    for (uint32_t c = 0; c < C; c++) {
-        const Channel &ch = e->chans[perm[c]];
-        info[c].rot_base = ch.rot_base;
-        info[c].mu = ch.mu;
-        info[c].lam = ch.lam;
-        info[c].lam_magic = (uint32_t)std::min<uint64_t>(0xffffffffull, (1ull << 32) / ch.lam);
-        info[c].out_row = perm[c];
-        info[c].rot_class = chan_class(ch) | (chan_class(ch) != MFM_RC_GENERAL ? chan_turns(ch) << 4 : 0u);
-    }
-
-    /* ---- atan LUT: fast_atan2f.c:14-81, entries atan(i/255) at 7 significant digits ---- */
-    float tbl[257];
-    mfm_hosttwin_atan_table(tbl);
-    if (!mfm_hosttwin_atan_table_ok()) {
-        return fail(MFM_E_INVAL, "atan table self-check failed (host libm rounds atan() differently)");
-    }
-    std::vector<float2> lut(256);
-    for (int i = 0; i < 256; i++) {
-        lut[i] = make_float2(tbl[i], tbl[i + 1] - tbl[i]);
-    }
+    e->rot_entries = t.rot.size() + t.rot4.size();
 
     /* ---- device allocations ---- */
     e->committed = true; /* from here free_device() releases whatever was allocated */
@@ -1668,7 +785,7 @@ static int commit_locked(struct mfm_engine *e)
     HIP_TRY(hipStreamCreateWithFlags(&e->s_compute, hipStreamNonBlocking));
     e->cs[0] = e->cs[1] = e->s_last = e->s_compute;
     e->ncs = 1;
-    if ((e->cfg.flags & MFM_F_OVERLAP) && e->use_v3) {
+    if ((e->cfg.flags & MFM_F_OVERLAP) && v3) {
         HIP_TRY(hipStreamCreateWithFlags(&e->cs[1], hipStreamNonBlocking));
         e->ncs = 2;
         for (int i = 0; i < kMaxInBufs; i++) {
@@ -1679,62 +796,27 @@ static int commit_locked(struct mfm_engine *e)
     HIP_TRY(hipEventCreateWithFlags(&e->in_ready, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&e->kernel_done, hipEventDisableTiming));
 
-    HIP_TRY(hipMalloc(&e->d_coef, coef.size() * 4));
-    HIP_TRY(hipMemcpy(e->d_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&e->d_tapoff, tapoff.size() * 4));
-    HIP_TRY(hipMemcpy(e->d_tapoff, tapoff.data(), tapoff.size() * 4, hipMemcpyHostToDevice));
-    if (e->use_mfma) {
-        HIP_TRY(hipMalloc(&e->d_afrag, afrag.size() * 4));
-        HIP_TRY(hipMemcpy(e->d_afrag, afrag.data(), afrag.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc(&e->d_krow, krow.size() * 4));
-        HIP_TRY(hipMemcpy(e->d_krow, krow.data(), krow.size() * 4, hipMemcpyHostToDevice));
+    MFM_TRY(upload(&e->d_coef, t.coef));
+    MFM_TRY(upload(&e->d_tapoff, t.tapoff));
+    if (p.variant >= 1u) {
+        MFM_TRY(upload(&e->d_afrag, t.afrag));
+        MFM_TRY(upload(&e->d_krow, t.krow));
     }
-    /* 8-bit input read as it is (mfm_kernel_v3.hip, IN8): x = alpha * s + beta with s the byte as int8, so the row
-     * constant is (beta * sum(W) + 8192) / alpha - exact for all three forms.  krow = 128 * sum(W) + 8192. */
-    /* both matrix kernels have the form for it (not built for the filtered-IQ debug output) */
-    e->raw8_ok = e->use_mfma && (!e->use_v3 || (e->v_nstage4 / 2u + 511u) / 512u <= 4u) && !e->any_iq &&
-                !(e->cfg.flags & MFM_F_WIDEN_8BIT);
-    if (e->raw8_ok) {
-        std::vector<int32_t> k8(krow.size());
+    if (p.raw8_ok) {
         for (int fmt = MFM_IN_CS8; fmt <= MFM_IN_RTLSDR_U8; fmt++) {
-            for (size_t i = 0; i < krow.size(); i++) {
-                const uint32_t sum = (uint32_t)(((int64_t)krow[i] - 8192) / 128); /* |sum(W)| < 2^24: no wrap in krow */
-                k8[i] = fmt == MFM_IN_RTLSDR_U8 ? (int32_t)(sum + 64u)                  /* (128 * sum + 8192) / 128 */
-                        : fmt == MFM_IN_CU8     ? (int32_t)(8192u - 127u * sum)           /* beta = -127 */
-                                                : 8192;                                    /* cs8: beta = 0 */
-            }
-            HIP_TRY(hipMalloc(&e->d_krow8[fmt], k8.size() * 4));
-            HIP_TRY(hipMemcpy(e->d_krow8[fmt], k8.data(), k8.size() * 4, hipMemcpyHostToDevice));
+            MFM_TRY(upload(&e->d_krow8[fmt], t.krow8[fmt]));
         }
-        HIP_TRY(hipMalloc(&e->d_tailtmp, ((size_t)T + D + 16u) * 2u));
+        HIP_TRY(hipMalloc(&e->d_tailtmp, ((size_t)p.T + p.D + 16u) * 2u));
     }
-    HIP_TRY(hipMalloc(&e->d_info, info.size() * sizeof(mfm_chan_info)));
-    HIP_TRY(hipMemcpy(e->d_info, info.data(), info.size() * sizeof(mfm_chan_info), hipMemcpyHostToDevice));
-    if (e->use_v3 && mfm_rot_entry_bytes_v3() == 4u) {
-        /* the second-generation kernel's build takes 4-byte entries (rr | ri << 16): half the table bytes per output */
-        std::vector<uint32_t> rot4(rot.size());
-        for (size_t i = 0; i < rot.size(); i++) {
-            rot4[i] = mfm_pack16(mfm_lo16(rot[i].x), mfm_lo16(rot[i].y)); /* {(rr, -ri), (ri, rr)} -> (rr, ri) */
-        }
-        HIP_TRY(hipMalloc(&e->d_rot, rot4.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(e->d_rot, rot4.data(), rot4.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    } else {
-        HIP_TRY(hipMalloc(&e->d_rot, rot.size() * sizeof(uint2)));
-        HIP_TRY(hipMemcpy(e->d_rot, rot.data(), rot.size() * sizeof(uint2), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMalloc(&e->d_lut, lut.size() * sizeof(float2)));
-    HIP_TRY(hipMemcpy(e->d_lut, lut.data(), lut.size() * sizeof(float2), hipMemcpyHostToDevice));
+    MFM_TRY(upload(&e->d_info, t.info));
+    MFM_TRY(t.rot4.empty() ? upload(&e->d_rot, t.rot) : upload(&e->d_rot, t.rot4));
+    MFM_TRY(upload(&e->d_lut, t.lut));
     for (int i = 0; i < 2; i++) {
-        HIP_TRY(hipMalloc(&e->d_state[i], info.size() * sizeof(mfm_chan_state)));
+        HIP_TRY(hipMalloc(&e->d_state[i], t.info.size() * sizeof(mfm_chan_state)));
     }
-    {
-        int rc = write_state_fresh(e);
-        if (rc != MFM_OK) {
-            return rc;
-        }
-    }
+    MFM_TRY(write_state_fresh(e));
 
-    const size_t in_bytes = (size_t)e->cap_in * 4;
+    const size_t in_bytes = (size_t)p.cap_in * 4;
     e->own_in = e->cfg.ext_input[0] == nullptr;
     for (int i = 0; i < e->nbuf; i++) {
         if (e->own_in) {
@@ -1748,22 +830,22 @@ static int commit_locked(struct mfm_engine *e)
     e->nslots = dev_only ? 2 : kOutSlots;
     for (int i = 0; i < e->nslots; i++) {
         OutSlot &s = e->slots[i];
-        const size_t pcm_bytes = (size_t)C * e->out_stride * sizeof(int16_t);
+        const size_t pcm_bytes = (size_t)p.C * p.out_stride * sizeof(int16_t);
         /* + a dump slot per lane behind the last channel row: the MFMA kernel stores unconditionally and sends
          * what is not an output there */
         HIP_TRY(hipMalloc(&s.d_pcm, pcm_bytes + 64 * sizeof(int16_t)));
-        if (e->any_iq) {
+        if (p.any_iq) {
             HIP_TRY(hipMalloc(&s.d_iq, pcm_bytes * 2 + 64 * sizeof(uint32_t)));
         }
         if (!dev_only) {
             HIP_TRY(hipHostMalloc(&s.h_pcm, pcm_bytes, hipHostMallocDefault));
-            if (e->any_iq) {
+            if (p.any_iq) {
                 HIP_TRY(hipHostMalloc(&s.h_iq, pcm_bytes * 2, hipHostMallocDefault));
             }
         }
         HIP_TRY(hipEventCreateWithFlags(&s.ready, hipEventDisableTiming));
     }
-    if ((e->cfg.flags & MFM_F_TIMING) && e->use_v3) {
+    if ((e->cfg.flags & MFM_F_TIMING) && v3) {
         HIP_TRY(hipMalloc(&e->d_cyc, kCycleRing * 2 * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(e->d_cyc, 0, kCycleRing * 2 * sizeof(unsigned long long)));
     }
@@ -1774,15 +856,24 @@ static int commit_locked(struct mfm_engine *e)
             HIP_TRY(hipEventCreate(&e->t1[i]));
         }
     }
-    {
-        int rc = select_kernels(e);
-        if (rc == MFM_OK) {
-            rc = division_selftest(e->cfg.device, e->use_v3 ? 2 : e->use_mfma ? 1 : 0);
-        }
-        if (rc != MFM_OK) {
-            return rc;
+
+    /* the launch descriptions get the device tables; the instance of each format its LDS limit (on this device, once) */
+    for (int fmt = MFM_IN_CS16; fmt <= MFM_IN_RTLSDR_U8; fmt++) {
+        FormatPlan &f = p.fmt[fmt];
+        const int32_t *krow = fmt == MFM_IN_CS16 ? e->d_krow : e->d_krow8[fmt];
+        f.L.coef = e->d_coef;
+        f.L.tapoff = e->d_tapoff;
+        f.M.afrag = f.V.afrag = e->d_afrag;
+        f.M.krow = f.V.krow = krow;
+        f.L.info = f.M.info = f.V.info = e->d_info;
+        f.L.rot = f.M.rot = e->d_rot;
+        f.V.rot = e->d_rot;
+        f.L.lut = f.M.lut = f.V.lut = e->d_lut;
+        if (f.kfn) {
+            MFM_TRY(raise_lds_limit(e->cfg.device, f.kfn, f.lds_bytes));
         }
     }
+    MFM_TRY(division_selftest(e->cfg.device, (int)p.variant));
     HIP_TRY(hipDeviceSynchronize());
     return MFM_OK;
 }
@@ -1866,7 +957,7 @@ void plan_block(mfm_engine *e, size_t nr_samples, SubmitPlan *p, bool locked)
 int launch_locked(mfm_engine *e)
 {
     const uint32_t T = e->nr_taps, D = e->cfg.decimation, C = (uint32_t)e->chans.size();
-    const bool dev_only = (e->cfg.flags & MFM_F_DEVICE_ONLY) != 0;
+    const bool dev_only = (e->cfg.flags & MFM_F_DEVICE_ONLY) != 0, v3 = 2u == e->plan.variant;
     const int cur = e->cur_in, nxt = (cur + 1) % e->nbuf;
     const uint32_t n_avail = e->tail + e->pend;
     const uint32_t n_new = n_avail >= T ? (n_avail - T) / D + 1 : 0;
@@ -1879,13 +970,13 @@ int launch_locked(mfm_engine *e)
      * moves into); a launch of one tile per slot or less costs more in the extra packets of the carry (a copy, two events)
      * than it gains: it keeps the carry in the kernel and the next launch stays behind it on the same stream. */
     bool two = false;
-    if (e->ncs > 1u && e->use_v3 && n_new) {
-        const uint32_t ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT, slots = 256u * e->v_wg_per_cu;
+    if (e->ncs > 1u && v3 && n_new) {
+        const uint32_t ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT, slots = 256u * e->plan.v_wg_per_cu;
         /* ... and only when what its carry copy reads - the last consumed row and the unconsumed samples behind it - lies
          * behind the [hist | tail] front of this buffer, which the previous launch's carry wrote on the OTHER stream: the
          * copy below is then ordered behind everything it reads (the H2D copies, through in_ready) without a wait of its
          * own.  True for every launch of more than a tile per slot; spelled out so that it does not rest on that. */
-        two = (uint64_t)ntiles * e->v_nslices > slots && (uint64_t)n_new * D >= (uint64_t)e->tail + D;
+        two = (uint64_t)ntiles * e->plan.v_nslices > slots && (uint64_t)n_new * D >= (uint64_t)e->tail + D;
     }
     hipStream_t S_after = two ? e->cs[e->si ^ 1u] : S;
     if (e->ncs > 1u && !two && e->in_free_wait[nxt]) {
@@ -1914,32 +1005,9 @@ int launch_locked(mfm_engine *e)
     bool tail_in_kernel = false;
     hipEvent_t timing_end = nullptr;
     if (n_new) {
-        const uint32_t ot = 64u * e->opl;
-        mfm_launch L{};
-        L.x = e->d_in[cur];
-        L.n_avail = n_avail;
-        L.n_new = n_new;
-        L.decim = D;
-        L.nchunks = e->nchunks;
-        L.nstage = (ot - 1) * D + T;
-        L.rs2 = e->rs2;
-        L.lut_off = e->lut_off;
-        L.ngroups = e->ngroups;
-        L.gpw = e->gpw;
-        L.nslices = e->nslices;
-        L.ntiles = (n_new + ot - 2) / (ot - 1);
-        L.nchan = C;
-        L.out_stride = e->out_stride;
-        L.coef = e->d_coef;
-        L.tapoff = e->d_tapoff;
-        L.info = e->d_info;
-        L.rot = e->d_rot;
-        L.st_in = e->d_state[e->parity];
-        L.st_out = e->d_state[e->parity ^ 1];
-        L.lut = e->d_lut;
-        L.pcm = slot->d_pcm;
-        L.iq_dbg = e->any_iq ? slot->d_iq : nullptr;
-
+        const FormatPlan &f = e->plan.fmt[fmt]; /* (8-bit blocks stay bytes on the matrix kernels only) */
+        mfm_chan_state *const st_in = e->d_state[e->parity], *const st_out = e->d_state[e->parity ^ 1];
+        uint32_t *const iq_dbg = e->plan.any_iq ? slot->d_iq : nullptr;
         if (!dev_only) {
             /* the previous D2H out of this slot must have drained before the kernel rewrites it */
             HIP_TRY(hipStreamWaitEvent(S, slot->ready, 0));
@@ -1958,9 +1026,11 @@ int launch_locked(mfm_engine *e)
             ti = (int)(e->t_head % kTimingPairs);
             HIP_TRY(hipEventRecord(e->t0[ti], S));
         }
-        if (e->use_v3) {
-            mfm_launch_v3 V{};
-            fill_v3(e, fmt, V);
+        if (raw8) {
+            e->launches_8bit++;
+        }
+        if (v3) {
+            mfm_launch_v3 V = f.V;
             V.x = e->d_in[cur];
             V.n_avail = n_avail;
             V.n_new = n_new;
@@ -1969,9 +1039,7 @@ int launch_locked(mfm_engine *e)
             V.ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT;
             /* chunks of consecutive tiles, `rounds` per workgroup slot and slice, lengths equal to within one tile
              * (a chunk pays one extra column group) */
-            /* (the long-filter kernel's small 8-bit instances are built for two workgroups per CU, the others for one) */
-            const uint32_t wg_per_cu = (3u == e->v_layout && 2u * e->v_lds_bytes <= 160u * 1024u) ? mfm_v3l_wg_per_cu(&V) : e->v_wg_per_cu;
-            const uint32_t slots = 256u * wg_per_cu;
+            const uint32_t slots = 256u * f.wg_per_cu;
             /* (a multiple of 8: the items are dealt chunk-major over the eight XCDs - item = 8 * (chunk / 8 * nslices + slice) +
              * chunk % 8, mfm3_decode_item - so a chunk count that is not one leaves holes in the last group of eight, the grid
              * overflows the slots and a few workgroups run a SECOND chunk while the others are done: with 3, 5, 6 or 12 slices
@@ -1992,7 +1060,7 @@ int launch_locked(mfm_engine *e)
                 tail_in_kernel = false;
             }
             V.pcm = slot->d_pcm;
-            V.iq_dbg = L.iq_dbg;
+            V.iq_dbg = iq_dbg;
             if (e->d_cyc) {
                 V.cyc = e->d_cyc + 2u * (e->launches % kCycleRing);
                 V.cyc_tag = (uint32_t)((e->launches + 1u) & 0xffffffu);
@@ -2000,38 +1068,38 @@ int launch_locked(mfm_engine *e)
                  * holds an older launch's stamp when its turn comes, whatever the 24-bit tags compare like after 2^24 launches */
                 V.cyc_clear = e->d_cyc + 2u * ((e->launches + kCycleRing / 2u) % kCycleRing);
             }
-            if (raw8) {
-                e->launches_8bit++;
-            }
-            const uint32_t grid = std::min(V.nitems, slots);
-            HIP_TRY(mfm_launch_channel_kernel_v3(e->kfn[fmt], &V, e->v_lds_bytes, grid, S));
-            L.ntiles = grid; /* for grid_last below */
-            L.nslices = 1;
-        } else if (e->use_mfma) {
-            mfm_launch_mfma M{};
-            fill_mfma(e, fmt, M);
+            e->grid_last = std::min(V.nitems, slots);
+            HIP_TRY(mfm_launch_channel_kernel_v3(f.kfn, &V, f.lds_bytes, e->grid_last, S));
+        } else if (1u == e->plan.variant) {
+            mfm_launch_mfma M = f.M;
             M.x = e->d_in[cur];
             M.n_avail = n_avail;
             M.n_new = n_new;
-            M.ntiles = (n_new + e->m_ot - 1u) / e->m_ot;
+            M.ntiles = (n_new + M.ot - 1u) / M.ot;
             M.nitems = ((M.ntiles + 7u) / 8u) * 8u * M.nslices;
             M.tail_src = n_new * D;
             M.tail_n = n_avail - n_new * D;
             M.tail_dst = e->d_in[nxt];
             tail_in_kernel = true;
-            M.st_in = L.st_in;
-            M.st_out = L.st_out;
+            M.st_in = st_in;
+            M.st_out = st_out;
             M.pcm = slot->d_pcm;
-            M.iq_dbg = L.iq_dbg;
-            if (raw8) {
-                e->launches_8bit++;
-            }
-            const uint32_t grid = std::min(M.nitems, 256u * e->m_wg_fmt[fmt]);
-            HIP_TRY(mfm_launch_channel_kernel_mfma(e->kfn[fmt], &M, e->m_lds_bytes, grid, S));
-            L.ntiles = grid; /* for grid_last below */
-            L.nslices = 1;
+            M.iq_dbg = iq_dbg;
+            e->grid_last = std::min(M.nitems, 256u * f.wg_per_cu);
+            HIP_TRY(mfm_launch_channel_kernel_mfma(f.kfn, &M, f.lds_bytes, e->grid_last, S));
         } else {
-            HIP_TRY(mfm_launch_channel_kernel(e->kfn[MFM_IN_CS16], &L, e->lds_bytes, S));
+            mfm_launch L = f.L;
+            const uint32_t ot = 64u * e->plan.opl;
+            L.x = e->d_in[cur];
+            L.n_avail = n_avail;
+            L.n_new = n_new;
+            L.ntiles = (n_new + ot - 2) / (ot - 1);
+            L.st_in = st_in;
+            L.st_out = st_out;
+            L.pcm = slot->d_pcm;
+            L.iq_dbg = iq_dbg;
+            e->grid_last = ((L.ntiles + 7) / 8) * 8 * L.nslices;
+            HIP_TRY(mfm_launch_channel_kernel(f.kfn, &L, f.lds_bytes, S));
         }
         if (timing) {
             HIP_TRY(hipEventRecord(e->t1[ti], S));
@@ -2040,14 +1108,13 @@ int launch_locked(mfm_engine *e)
         }
         e->parity ^= 1;
         e->launches++;
-        e->grid_last = e->use_mfma ? L.ntiles : ((L.ntiles + 7) / 8) * 8 * L.nslices;
     }
 
     /* carry the unconsumed tail (and, for the second-generation kernel, the last consumed row in front of it) to the front
      * of the next staging buffer (the MFMA kernels have done it themselves) */
     const uint32_t consumed = n_new * D;
     const uint32_t new_tail = n_avail - consumed;
-    const uint32_t new_hist = (e->use_v3 && n_new) ? D : e->hist;
+    const uint32_t new_hist = (v3 && n_new) ? D : e->hist;
     if (new_hist + new_tail && !tail_in_kernel) {
         const size_t ss = raw8 ? 2 : 4;
         if (two && e->in_free_wait[nxt]) {
@@ -2086,10 +1153,10 @@ int launch_locked(mfm_engine *e)
         } else {
             HIP_TRY(hipEventRecord(e->kernel_done, S));
             HIP_TRY(hipStreamWaitEvent(e->s_out, e->kernel_done, 0));
-            const size_t row = (size_t)e->out_stride * sizeof(int16_t);
+            const size_t row = (size_t)e->plan.out_stride * sizeof(int16_t);
             HIP_TRY(hipMemcpy2DAsync(slot->h_pcm, row, slot->d_pcm, row, (size_t)n_new * sizeof(int16_t), C,
                                      hipMemcpyDeviceToHost, e->s_out));
-            if (e->any_iq) {
+            if (e->plan.any_iq) {
                 HIP_TRY(hipMemcpy2DAsync(slot->h_iq, row * 2, slot->d_iq, row * 2, (size_t)n_new * 4, C,
                                          hipMemcpyDeviceToHost, e->s_out));
             }
@@ -2160,7 +1227,7 @@ int mfm_engine_acquire_input(struct mfm_engine *e, void **d_dst, size_t *capacit
     }
     *d_dst = e->d_in[e->cur_in] + e->hist + e->tail + e->pend;
     if (capacity_samples) {
-        *capacity_samples = std::min<size_t>(e->cap_in - e->hist - e->tail - e->pend, e->cfg.max_block_samples);
+        *capacity_samples = std::min<size_t>(e->plan.cap_in - e->hist - e->tail - e->pend, e->cfg.max_block_samples);
     }
     return MFM_OK;
 }
@@ -2170,7 +1237,7 @@ int mfm_engine_can_take_bytes(struct mfm_engine *e, int format, size_t nr_sample
 {
     /* not a cu8 block of odd length (file_if.c:146-150 widens its last sample differently), not behind a history or
      * behind accepted blocks of another format */
-    if (!e || !e->committed || !e->raw8_ok || !(format == MFM_IN_CS8 || format == MFM_IN_CU8 || format == MFM_IN_RTLSDR_U8) ||
+    if (!e || !e->committed || !e->plan.raw8_ok || !(format == MFM_IN_CS8 || format == MFM_IN_CU8 || format == MFM_IN_RTLSDR_U8) ||
         (format == MFM_IN_CU8 && (nr_samples & 1u))) {
         return 0;
     }
@@ -2209,7 +1276,7 @@ int mfm_engine_acquire_input_bytes(struct mfm_engine *e, int format, void **d_ds
     e->in_fmt[e->cur_in] = format;
     *d_dst = reinterpret_cast<uint8_t *>(e->d_in[e->cur_in]) + ((size_t)e->hist + e->tail + e->pend) * 2;
     if (capacity_samples) {
-        *capacity_samples = std::min<size_t>(e->cap_in - e->hist - e->tail - e->pend, e->cfg.max_block_samples); /* the block limit is that of int16 blocks */
+        *capacity_samples = std::min<size_t>(e->plan.cap_in - e->hist - e->tail - e->pend, e->cfg.max_block_samples); /* the block limit is that of int16 blocks */
     }
     return MFM_OK;
 }
@@ -2236,7 +1303,7 @@ static int submit_impl(struct mfm_engine *e, size_t nr_samples, void *producer_s
         /* receiver_sample_buf_deliver() treats an empty buffer as a bug (receiver.c:84) */
         return fail(MFM_E_INVAL, "empty block");
     }
-    if (nr_samples > (size_t)e->cap_in - e->hist - e->tail - e->pend || (!run && nr_samples > e->cfg.max_block_samples)) {
+    if (nr_samples > (size_t)e->plan.cap_in - e->hist - e->tail - e->pend || (!run && nr_samples > e->cfg.max_block_samples)) {
         return fail(MFM_E_INVAL, "block of %zu samples exceeds max_block_samples %u", nr_samples,
                     e->cfg.max_block_samples);
     }
@@ -2390,7 +1457,7 @@ int mfm_engine_stage(struct mfm_engine *e, const void *data, size_t nr_samples, 
     }
     const int cur = e->cur_in;
     if (!pinned && !e->h_in[cur]) {
-        HIP_TRY(hipHostMalloc(&e->h_in[cur], (size_t)e->cap_in * 4, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(&e->h_in[cur], (size_t)e->plan.cap_in * 4, hipHostMallocDefault));
     }
     /* acquire_input() waited for the kernel that consumed the previous contents of this buffer, so the copies out of
      * h_in[cur] that fed it are done; blocks accepted since then sit in front of this one, as they do on the device */
@@ -2408,7 +1475,7 @@ int mfm_engine_stage(struct mfm_engine *e, const void *data, size_t nr_samples, 
         HIP_TRY(hipMemcpyAsync(dst, h, nr_samples * 4, hipMemcpyHostToDevice, e->s_in));
     } else {
         if (!e->d_raw[cur]) {
-            HIP_TRY(hipMalloc(&e->d_raw[cur], (size_t)e->cap_in * 2 + 64));
+            HIP_TRY(hipMalloc(&e->d_raw[cur], (size_t)e->plan.cap_in * 2 + 64));
         }
         /* the unpack kernels of the previous use of d_raw[cur] ran before the kernel acquire_input() waited for */
         uint16_t *draw = e->d_raw[cur] + ((e->pend + 7u) & ~7u); /* the unpack kernel reads 16-byte groups */
@@ -2501,7 +1568,7 @@ size_t mfm_engine_input_room(struct mfm_engine *e)
         return 0;
     }
     std::lock_guard<std::mutex> guard(e->mu);
-    return (size_t)e->cap_in - e->hist - e->tail - e->pend;
+    return (size_t)e->plan.cap_in - e->hist - e->tail - e->pend;
 }
 
 /*
@@ -2797,7 +1864,7 @@ int mfm_engine_fetch(struct mfm_engine *e, struct mfm_block *blk)
     s.state = OutSlot::FETCHED;
     blk->first_output = s.first_output;
     blk->nr_outputs = s.nr_outputs;
-    blk->stride = e->out_stride;
+    blk->stride = e->plan.out_stride;
     blk->pcm = s.h_pcm;
     blk->iq = reinterpret_cast<const int16_t *>(s.h_iq);
     return MFM_OK;
@@ -2832,7 +1899,7 @@ int mfm_engine_last_output_device(struct mfm_engine *e, void **d_pcm, size_t *st
         *d_pcm = s.d_pcm;
     }
     if (stride) {
-        *stride = e->out_stride;
+        *stride = e->plan.out_stride;
     }
     if (nr_outputs) {
         *nr_outputs = s.nr_outputs;
@@ -2904,7 +1971,7 @@ int mfm_engine_seek(struct mfm_engine *e, uint64_t outputs_before)
     }
     /* the rotators stand where outputs_before steps of the recurrence leave them (filter/direct_fir.c:166-167); the
      * second-generation kernel folds the count itself, the others read the folded table position from the carried state */
-    std::vector<mfm_chan_state> st(e->ngroups * MFM_CG);
+    std::vector<mfm_chan_state> st(e->plan.ngroups * MFM_CG);
     for (size_t c = 0; c < st.size(); c++) {
         st[c].carry_q = 0;
         st[c].kb = 0;
@@ -2938,18 +2005,10 @@ int mfm_engine_get_stats(struct mfm_engine *e, struct mfm_stats *st)
     st->launches = e->launches;
     st->kernel_ms = e->kernel_ms;
     st->timed_launches = e->launch_ms_n;
-    st->rot_exact_channels = e->rot_exact_channels;
-    st->rot_fast_slices = e->rot_fast_slices;
-    st->k_steps = e->use_mfma ? e->m_ks : 0u;
-    st->tap_hi_mask = e->use_mfma ? e->m_ah_mask : 0u;
-    st->taps_resident = ((e->use_mfma && !e->use_v3 && e->m_resident_taps) || (e->use_v3 && 3u == e->v_layout)) ? 1u : 0u;
-    st->slice_channels = e->use_v3 ? ((3u == e->v_layout) ? 64u * e->v_rb : 64u) : e->use_mfma ? 64u : 0u;
+    plan_form_stats(e->plan, st);
     st->submits = e->submits;
     st->nr_channels = (uint32_t)e->chans.size();
     st->nr_taps = e->nr_taps;
-    st->outputs_per_tile = e->use_v3 ? MFM_V3_OT : e->use_mfma ? e->m_ot : 64u * e->opl;
-    st->lds_bytes = e->use_v3 ? e->v_lds_bytes : e->use_mfma ? e->m_lds_bytes : e->lds_bytes;
-    st->kernel_variant = e->use_v3 ? 2u : e->use_mfma ? 1u : 0u;
     {
         std::lock_guard<std::mutex> guard(e->mu);
         st->pending_blocks = (uint32_t)(e->submit_seq - e->fetch_seq);
@@ -3150,6 +2209,24 @@ void mfm_hosttwin_discriminate_batch(const int32_t *s_re, const int32_t *s_im, s
     for (size_t i = 0; i < n; i++) {
         out[i] = (int16_t)mfm_discriminate(s_re[i], s_im[i], g_atan_lut);
     }
+}
+
+int mfm_hosttwin_kernel_form(struct mfm_engine *e, struct mfm_stats *st)
+{
+    if (!e || !st) {
+        return fail(MFM_E_INVAL, "NULL argument");
+    }
+    if (e->committed) {
+        return fail(MFM_E_STATE, "already committed: mfm_engine_get_stats() reports the form");
+    }
+    KernelPlan p;
+    const int rc = plan_channel_kernel(e->cfg, e->chans, e->nr_taps, p);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    memset(st, 0, sizeof(*st));
+    plan_form_stats(p, st);
+    return MFM_OK;
 }
 
 int16_t mfm_hosttwin_r14(int32_t a)
