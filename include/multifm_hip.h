@@ -499,6 +499,37 @@ int mfm_resampler_process_host(struct mfm_resampler *r, const int16_t *pcm, size
                                int16_t *out, size_t out_stride, size_t *nr_out);
 
 /*
+ * Sign-bit form of the output.  The POCSAG and AIS stages look at one predicate of every resampled sample and at
+ * nothing else (pager/pager_pocsag.c:91,476,516: sample < 0; ais/ais_demod.c:126,172: sample > 0), so a chain
+ * that ends in one of them does not need the resampled PCM in memory: the calls below consume input exactly as
+ * their PCM counterparts do (same phase walk, same carried tail, same `invert`), write NO PCM and leave one packed
+ * bit per output, taken from the Q14-rounded sample in the kernel that computes it.  PCM calls and bits calls may
+ * alternate on one resampler; the stream of outputs continues across them.  A resampler created with dc_block
+ * answers them with MFM_E_INVAL (the DC blocker is a sequential filter over the resampled PCM in memory), as it does
+ * an unknown polarity.
+ */
+#define MFM_BITS_NEG 1u /* bit = (sample < 0)  - POCSAG */
+#define MFM_BITS_POS 2u /* bit = (sample > 0)  - AIS    */
+
+struct mfm_bits_view {          /* valid until the resampler's next process call */
+    const uint32_t *d_bits;     /* device memory, [channel][stride_words]; output j of THIS call is bit j % 32 of word j / 32 */
+    size_t stride_words;
+    size_t nr_bits;             /* outputs per channel of this call (what nr_out would have been); 0 is a valid result */
+    uint32_t polarity;          /* MFM_BITS_NEG or MFM_BITS_POS */
+    uint32_t reserved;          /* 0 */
+};
+
+/* Bits at positions >= nr_bits of a row's last word are 0; words behind it are not defined. */
+int mfm_resampler_process_bits_device(struct mfm_resampler *r, const int16_t *d_pcm, size_t in_stride, size_t nr_in,
+                                      void *stream, uint32_t polarity, struct mfm_bits_view *view);
+/* Host in, device out (what the decoder programs use with -s). */
+int mfm_resampler_process_bits_host_to_device(struct mfm_resampler *r, const int16_t *pcm, size_t in_stride, size_t nr_in,
+                                              void *stream, uint32_t polarity, struct mfm_bits_view *view);
+/* Host convenience (tests): host in, bits out to host memory laid out [channel][bits_stride_words], synchronous. */
+int mfm_resampler_process_bits_host(struct mfm_resampler *r, const int16_t *pcm, size_t in_stride, size_t nr_in,
+                                    uint32_t polarity, uint32_t *bits, size_t bits_stride_words, size_t *nr_bits);
+
+/*
  * ---- Pager stage: POCSAG slicer / sync / batch collection + BCH(31,21) -----
  * Replaces, for ALL channels at once and on PCM that is still in HBM (38 400 Hz, i.e. the resampler's output):
  *
@@ -555,6 +586,10 @@ int mfm_pocsag_process_device(struct mfm_pocsag *p, const int16_t *d_pcm, size_t
                               void *stream);
 /* Host convenience: same from host memory, synchronous. */
 int mfm_pocsag_process_host(struct mfm_pocsag *p, const int16_t *pcm, size_t in_stride, size_t nr_in);
+/* As mfm_pocsag_process_device with nr_in = view->nr_bits, from the resampler's sign bits (polarity MFM_BITS_NEG; any
+ * other is MFM_E_INVAL) instead of PCM: the bits are spliced into the window in the place of the slicer.  PCM calls and
+ * bits calls may alternate on one stage object. */
+int mfm_pocsag_process_bits_device(struct mfm_pocsag *p, const struct mfm_bits_view *view, void *stream);
 /*
  * Wait for the last process call and copy its events: channels ascending, stream order within a channel.
  * MFM_E_NOMEM when `max_events` is too small (nothing copied, *nr_events = needed), MFM_E_STATE when a channel
@@ -696,6 +731,9 @@ void mfm_ais_destroy(struct mfm_ais **pp);
 int mfm_ais_process_device(struct mfm_ais *p, const int16_t *d_pcm, size_t in_stride, size_t nr_in, void *stream);
 /* Host convenience: same from host memory, synchronous. */
 int mfm_ais_process_host(struct mfm_ais *p, const int16_t *pcm, size_t in_stride, size_t nr_in);
+/* As mfm_ais_process_device with nr_in = view->nr_bits, from the resampler's sign bits (polarity MFM_BITS_POS; any
+ * other is MFM_E_INVAL) instead of PCM.  PCM calls and bits calls may alternate on one stage object. */
+int mfm_ais_process_bits_device(struct mfm_ais *p, const struct mfm_bits_view *view, void *stream);
 /*
  * Wait for the last process call and copy its events: channels ascending, stream order within a channel.
  * MFM_E_NOMEM when `max_events` is too small (nothing copied, *nr_events = needed), MFM_E_STATE when a channel
@@ -829,6 +867,10 @@ int mfm_devtest_rcp_table(int device, uint64_t *hash, uint64_t counts[4], uint64
 int mfm_hosttwin_kernel_form(struct mfm_engine *e, struct mfm_stats *st);
 /* the device's table-driven BCH(31,21) decode (syndrome bytes -> 1024-entry flip table), on the host */
 int mfm_hosttwin_bch3121_decode(uint32_t *word);
+/* host twin of the splice that stands in the place of the slicers on the sign-bit path (csrc/mfm_bits.h, the same inline the
+ * kernel runs per word): bits [off0, off0 + nr_bits) of `window` from bits [0, nr_bits) of `src`, bits below off0 kept, the rest
+ * of the last touched word zero, no word behind it touched */
+void mfm_hosttwin_splice_bits(uint32_t *window, uint64_t off0, const uint32_t *src, uint64_t nr_bits);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,11 @@
 """Randomised GPU-vs-oracle runs of the FLEX stage and of the matrix-core resampler (more shapes and chunkings than the
 test-suite has time for).  Exit code 1 on the first difference.
 
-    python tools/fuzz_stages.py [--seconds 120] [--seed 1]
+    python tools/fuzz_stages.py [--seconds 120] [--seed 1] [--mode stages|sign-bits]
+
+--mode sign-bits: one stream of random POCSAG or AIS traffic, cut at random into calls that take the PCM path (resampler ->
+stage) and calls that take the sign-bit path (mfm_resampler_process_bits_device -> mfm_*_process_bits_device) on the SAME
+resampler and stage objects; the events must equal those of the oracle resampler followed by the oracle stage.
 """
 import argparse
 import os
@@ -105,19 +109,91 @@ def resampler_case(pkg, ora, rng):
     return None, got.shape[1]
 
 
+def sign_bits_case(pkg, ora, rng):
+    import torch
+    import ais_ref
+    sy = pkg.synth
+    ais = bool(rng.rand() < 0.5)
+    C = int(rng.randint(1, 7))
+    n_stage = int(rng.randint(60000, 400000))
+    chans = []
+    for c in range(C):
+        if rng.rand() < 0.25:
+            chans.append(rng.normal(0, float(rng.choice([0, 300, 3000])), n_stage).round().astype(np.int16))
+            continue
+        parts, size = [], 0
+        while size < n_stage:
+            seed = int(rng.randint(1 << 30))
+            if ais:
+                pl = [sy.ais_type1(int(rng.randint(1, 1 << 30))), sy.ais_type4(int(rng.randint(1, 1 << 30))), bytes(rng.randint(0, 256, 30).astype(np.uint8))]
+                frames = [sy.ais_frame_bits(pl[int(rng.randint(3))], fcs=None if rng.rand() < 0.7 else int(rng.randint(65536)))
+                          for _ in range(int(rng.randint(1, 8)))]
+                parts.append(sy.ais_pcm(sy.ais_bits(frames, gap_bits=int(rng.randint(0, 40))), noise=float(rng.choice([100, 800, 2500])),
+                                        lead=int(rng.randint(0, 3000)), phase=int(rng.randint(5)), seed=seed))
+            else:
+                msgs = [(int(rng.randint(1 << 18)), int(rng.randint(8)), int(rng.randint(4)), sy.pocsag_alpha_words("fuzz %d" % rng.randint(1 << 30)))
+                        for _ in range(int(rng.randint(1, 5)))]
+                parts.append(sy.pocsag_pcm(sy.pocsag_bits(sy.pocsag_batches(msgs)), int(rng.choice([512, 1200, 2400])),
+                                           noise=float(rng.choice([200, 900, 3000])), lead=int(rng.randint(0, 9000)), trail=int(rng.randint(0, 9000)), seed=seed))
+            size += parts[-1].size
+        chans.append(np.concatenate(parts)[:n_stage])
+    x = np.stack([np.repeat(ch, 5)[::4] for ch in chans])      # 4/5 brings it back to the stage's rate (through the low-pass)
+    n = x.shape[1]
+    invert = bool(rng.rand() < 0.3)
+    if invert:
+        x = (-x.astype(np.int32)).clip(-32768, 32767).astype(np.int16)
+    rtaps = ora.quantize_taps(sy.design_lpf(int(rng.choice([41, 81])), 0.45 / 5, 1.0) * 4)
+    max_in = int(rng.choice([8192, 30000, 100000]))
+    rs = pkg.Resampler(C, rtaps, 4, 5, max_in, device=0, invert=invert, force_dot2=bool(rng.rand() < 0.3))
+    st = (pkg.Ais if ais else pkg.Pocsag)(C, rs.max_out())
+    pol = pkg.binding.MFM_BITS_POS if ais else pkg.binding.MFM_BITS_NEG
+    d = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    parts, pos = [], 0
+    while pos < n:
+        m = min(int(rng.choice([1, 7, 100, 4096, max_in, int(rng.randint(1, max_in + 1))])), n - pos)
+        if rng.rand() < 0.5:
+            st.process_bits_device(rs.process_bits_device(d.data_ptr() + 2 * pos, n, m, pol))
+        else:
+            yptr, ystride, ny = rs.process_device(d.data_ptr() + 2 * pos, n, m)
+            st.process_device(yptr, ystride, ny)
+        parts.append(st.fetch_events())
+        pos += m
+    st.close()
+    rs.close()
+    got = np.concatenate(parts)
+    nev = 0
+    for c in range(C):
+        y = ora.Resampler(rtaps, 4, 5, invert=invert).feed(x[c])
+        g = got[got["channel"] == c]
+        if ais:
+            w = ais_ref.demod(y, channel=c)
+            fields = [f for f in ais_ref.EVENT_DTYPE.names]
+        else:
+            w, _ = ora.Pocsag().feed(y)
+            dup = [i for i in range(len(w) - 1) if w["type"][i] == w["type"][i + 1] == ora.EV_SYNC_FOUND and w["sample"][i] == w["sample"][i + 1]]
+            w = np.delete(w, dup)  # two detectors firing on one sample: the later one wins (pager_pocsag.c:452-457)
+            fields = ["type", "baud", "sample", "aux", "nr_ok", "fail_mask", "raw", "corrected"]
+        if len(g) != len(w) or any(not np.array_equal(g[f], w[f]) for f in fields):
+            return "sign-bits: %s events differ on channel %d (%d vs %d)" % ("ais" if ais else "pocsag", c, len(g), len(w)), 0
+        nev += len(w)
+    return None, nev
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--mode", default="stages", choices=["stages", "sign-bits"])
     args = ap.parse_args()
     from __graft_entry__ import load_package
     import oracle_lib as ora
     pkg = load_package()
     rng = np.random.RandomState(args.seed)
     t0 = time.time()
-    runs = {"flex": [0, 0], "resampler": [0, 0]}
+    cases = (("flex", flex_case), ("resampler", resampler_case)) if args.mode == "stages" else (("sign_bits", sign_bits_case),)
+    runs = {name: [0, 0] for name, _ in cases}
     while time.time() - t0 < args.seconds:
-        for name, fn in (("flex", flex_case), ("resampler", resampler_case)):
+        for name, fn in cases:
             err, units = fn(pkg, ora, rng)
             if err:
                 print("FAIL", err, "after", runs)

@@ -30,6 +30,7 @@ MFM_F_SLICE_64 = 0x1000
 MFM_F_PCM_WRITE_BACK = 0x2000
 MFM_RCP_TABLE_HASH_GFX950 = 0x706D94BC005BCC1A  # include/multifm_hip.h
 MFM_IN_CS16, MFM_IN_CS8, MFM_IN_CU8, MFM_IN_RTLSDR_U8 = 0, 1, 2, 3
+MFM_BITS_NEG, MFM_BITS_POS = 1, 2  # sign-bit views: bit = sample < 0 (POCSAG) / sample > 0 (AIS)
 
 # every symbol include/multifm_hip.h declares (tests check the library exports each one)
 ABI_SYMBOLS = [
@@ -56,6 +57,8 @@ ABI_SYMBOLS = [
     "mfm_flex_create", "mfm_flex_destroy", "mfm_flex_process_device", "mfm_flex_process_host", "mfm_flex_fetch_events",
     "mfm_mm_create", "mfm_mm_destroy", "mfm_mm_max_decisions", "mfm_mm_process_device", "mfm_mm_process_host",
     "mfm_ais_create", "mfm_ais_destroy", "mfm_ais_process_device", "mfm_ais_process_host", "mfm_ais_fetch_events",
+    "mfm_resampler_process_bits_device", "mfm_resampler_process_bits_host_to_device", "mfm_resampler_process_bits_host",
+    "mfm_pocsag_process_bits_device", "mfm_ais_process_bits_device", "mfm_hosttwin_splice_bits",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -172,6 +175,13 @@ class ResamplerConfig(C.Structure):
 
 
 MFM_RS_FORCE_DOT2 = 1
+
+
+class BitsView(C.Structure):
+    """struct mfm_bits_view: one packed predicate bit per resampler output, in device memory, valid until the resampler's
+    next process call.  Output j of the call is bit j % 32 of word j / 32 of its channel's row."""
+    _fields_ = [("d_bits", C.c_void_p), ("stride_words", C.c_size_t), ("nr_bits", C.c_size_t), ("polarity", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class F32Config(C.Structure):
@@ -332,6 +342,15 @@ def load_library():
     lib.mfm_resampler_process_host.argtypes = [vp, i16p, C.c_size_t, C.c_size_t, i16p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.mfm_resampler_process_host_to_device.argtypes = [vp, i16p, C.c_size_t, C.c_size_t, vp, C.POINTER(vp),
                                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    if hasattr(lib, "mfm_resampler_process_bits_device"):   # (an older library under MFM_LIB)
+        lib.mfm_resampler_process_bits_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_uint32, C.POINTER(BitsView)]
+        lib.mfm_resampler_process_bits_host_to_device.argtypes = [vp, i16p, C.c_size_t, C.c_size_t, vp, C.c_uint32, C.POINTER(BitsView)]
+        lib.mfm_resampler_process_bits_host.argtypes = [vp, i16p, C.c_size_t, C.c_size_t, C.c_uint32, u32p, C.c_size_t,
+                                                        C.POINTER(C.c_size_t)]
+        lib.mfm_pocsag_process_bits_device.argtypes = [vp, C.POINTER(BitsView), vp]
+        lib.mfm_ais_process_bits_device.argtypes = [vp, C.POINTER(BitsView), vp]
+        lib.mfm_hosttwin_splice_bits.argtypes = [u32p, C.c_uint64, u32p, C.c_uint64]
+        lib.mfm_hosttwin_splice_bits.restype = None
     f32p = C.POINTER(C.c_float)
     lib.mfm_f32_create.argtypes = [C.POINTER(vp), C.POINTER(F32Config)]
     lib.mfm_f32_add_channel.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.c_size_t, C.c_double]
@@ -765,6 +784,32 @@ class Resampler:
             raise MfmError(rc, "mfm_resampler_process_device", self.lib.mfm_strerror(rc).decode())
         return p.value, st.value, n.value
 
+    def _fail(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+
+    def process_bits_host(self, pcm, polarity):
+        """pcm: int16 [C][n] -> (uint32 [C][ceil(m / 32)], m): bit j % 32 of word j / 32 is the predicate of output j
+        (MFM_BITS_NEG: < 0, MFM_BITS_POS: > 0); no PCM is written.  np.unpackbits(words.view(np.uint8), bitorder="little")
+        gives one byte per output."""
+        a = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.nr_channels, -1)
+        cap = (self.max_out() + 31) // 32
+        out = np.zeros((self.nr_channels, cap), np.uint32)
+        n = C.c_size_t()
+        rc = self.lib.mfm_resampler_process_bits_host(self.h, _i16p(a), a.shape[1], a.shape[1], polarity,
+                                                      out.ctypes.data_as(C.POINTER(C.c_uint32)), cap, C.byref(n))
+        if rc < 0:
+            self._fail(rc, "mfm_resampler_process_bits_host")
+        return out[:, :(n.value + 31) // 32].copy(), n.value
+
+    def process_bits_device(self, d_pcm, in_stride, nr_in, polarity, stream=None):
+        """device PCM in, BitsView out (device memory, valid until this resampler's next process call)"""
+        v = BitsView()
+        rc = self.lib.mfm_resampler_process_bits_device(self.h, C.c_void_p(d_pcm), in_stride, nr_in, C.c_void_p(stream or 0),
+                                                        polarity, C.byref(v))
+        if rc < 0:
+            self._fail(rc, "mfm_resampler_process_bits_device")
+        return v
+
 
 class F32Engine:
     """mfm_f32_*: the channel path on float32 IQ (FIR, derotation, discriminator in fp32)."""
@@ -919,6 +964,12 @@ class Pocsag:
         if rc < 0:
             raise MfmError(rc, "mfm_pocsag_process_device", self.lib.mfm_strerror(rc).decode())
 
+    def process_bits_device(self, view, stream=None):
+        """as process_device with nr_in = view.nr_bits, from a Resampler's MFM_BITS_NEG BitsView instead of PCM"""
+        rc = self.lib.mfm_pocsag_process_bits_device(self.h, C.byref(view), C.c_void_p(stream or 0))
+        if rc < 0:
+            raise MfmError(rc, "mfm_pocsag_process_bits_device", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+
     def fetch_events(self):
         cap = self.nr_channels * self.max_events
         out = np.zeros(cap, POCSAG_EVENT_DTYPE)
@@ -966,6 +1017,12 @@ class Ais:
         rc = self.lib.mfm_ais_process_device(self.h, C.c_void_p(d_pcm), in_stride, nr_in, C.c_void_p(stream or 0))
         if rc < 0:
             raise MfmError(rc, "mfm_ais_process_device", self.lib.mfm_strerror(rc).decode())
+
+    def process_bits_device(self, view, stream=None):
+        """as process_device with nr_in = view.nr_bits, from a Resampler's MFM_BITS_POS BitsView instead of PCM"""
+        rc = self.lib.mfm_ais_process_bits_device(self.h, C.byref(view), C.c_void_p(stream or 0))
+        if rc < 0:
+            raise MfmError(rc, "mfm_ais_process_bits_device", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
 
     def fetch_events(self):
         cap = self.nr_channels * self.max_events
@@ -1036,6 +1093,18 @@ def bch3121_decode(words, device=0):
     if r < 0:
         raise MfmError(r, "mfm_bch3121_decode_host", lib.mfm_strerror(r).decode())
     return w, rc
+
+
+def hosttwin_splice_bits(window, off0, src, nr_bits):
+    """mfm_hosttwin_splice_bits on a copy of `window` (uint32 words): bits [off0, off0 + nr_bits) from `src`"""
+    lib = load_library()
+    w = np.ascontiguousarray(window, dtype=np.uint32).copy()
+    sw = np.ascontiguousarray(src, dtype=np.uint32)
+    if sw.size == 0:
+        sw = np.zeros(1, np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    lib.mfm_hosttwin_splice_bits(w.ctypes.data_as(u32p), int(off0), sw.ctypes.data_as(u32p), int(nr_bits))
+    return w
 
 
 def hosttwin_bch3121_decode(word):

@@ -35,6 +35,8 @@
 
 #include "../../include/multifm_hip.h"
 
+#include "mfm_bits.h"
+
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 
 namespace {
@@ -531,13 +533,13 @@ void mfm_ais_destroy(struct mfm_ais **pp)
     *pp = nullptr;
 }
 
-int mfm_ais_process_device(struct mfm_ais *p, const int16_t *d_pcm, size_t in_stride, size_t nr_in, void *stream)
+} /* extern "C" */
+
+/* the head of a process call, whichever way the bits arrive: order the call behind the last one, make room for n samples
+ * (slide) and say where in the window they go */
+static int ai_begin(mfm_ais *p, uint32_t n, hipStream_t s, uint32_t *poff0)
 {
-    if (!p || (!d_pcm && nr_in) || nr_in > p->cfg.max_in_samples) {
-        return MFM_E_INVAL;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t C = p->cfg.nr_channels, n = (uint32_t)nr_in;
+    const uint32_t C = p->cfg.nr_channels;
     AI_TRY(hipSetDevice(p->cfg.device));
     if (p->have_call && p->last_stream != s) {
         AI_TRY(hipStreamSynchronize(p->last_stream)); /* state lives on the device; keep calls ordered */
@@ -555,12 +557,16 @@ int mfm_ais_process_device(struct mfm_ais *p, const int16_t *d_pcm, size_t in_st
         p->ws = new_ws;
         off0 = (uint32_t)(p->total - p->ws);
     }
+    *poff0 = off0;
+    return MFM_OK;
+}
+
+/* the tail of a process call, once bits [off0, off0 + n) of plane 0 are in place: match, walk, bookkeeping */
+static int ai_finish(mfm_ais *p, uint32_t n, uint32_t off0, hipStream_t s)
+{
+    const uint32_t C = p->cfg.nr_channels;
     const AiBuf buf = p->buf[p->cur];
     if (n) {
-        const uint32_t nsteps = (off0 + n - (off0 & ~511u) + 511) / 512;
-        hipLaunchKernelGGL(ai_slice_kernel, dim3((nsteps + 4 * AI_SLICE_U - 1) / (4 * AI_SLICE_U), C), dim3(256), 0, s, buf, d_pcm,
-                           in_stride, n, off0, nsteps);
-        AI_TRY(hipGetLastError());
         const uint32_t w_first = (off0 & ~(AI_GROUP - 1)) / 32;
         const uint32_t w_end = (off0 + n + 31) / 32;
         hipLaunchKernelGGL(ai_match_kernel, dim3((w_end - w_first + 255) / 256, C), dim3(256), 0, s, buf, w_first);
@@ -573,6 +579,58 @@ int mfm_ais_process_device(struct mfm_ais *p, const int16_t *d_pcm, size_t in_st
     p->last_stream = s;
     p->have_call = true;
     return MFM_OK;
+}
+
+extern "C" {
+
+int mfm_ais_process_device(struct mfm_ais *p, const int16_t *d_pcm, size_t in_stride, size_t nr_in, void *stream)
+{
+    if (!p || (!d_pcm && nr_in) || nr_in > p->cfg.max_in_samples) {
+        return MFM_E_INVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t C = p->cfg.nr_channels, n = (uint32_t)nr_in;
+    uint32_t off0 = 0;
+    const int rc = ai_begin(p, n, s, &off0);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    if (n) {
+        const uint32_t nsteps = (off0 + n - (off0 & ~511u) + 511) / 512;
+        hipLaunchKernelGGL(ai_slice_kernel, dim3((nsteps + 4 * AI_SLICE_U - 1) / (4 * AI_SLICE_U), C), dim3(256), 0, s, p->buf[p->cur],
+                           d_pcm, in_stride, n, off0, nsteps);
+        AI_TRY(hipGetLastError());
+    }
+    return ai_finish(p, n, off0, s);
+}
+
+int mfm_ais_process_bits_device(struct mfm_ais *p, const struct mfm_bits_view *view, void *stream)
+{
+    if (!p || !view || (!view->d_bits && view->nr_bits) || view->nr_bits > p->cfg.max_in_samples) {
+        return MFM_E_INVAL;
+    }
+    if (view->polarity != MFM_BITS_POS) {
+        snprintf(g_ai_error, sizeof(g_ai_error), "the AIS stage slices with sample > 0: it takes MFM_BITS_POS views (got polarity %u)",
+                 view->polarity);
+        mfm_internal_set_error(g_ai_error);
+        return MFM_E_INVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t C = p->cfg.nr_channels, n = (uint32_t)view->nr_bits;
+    uint32_t off0 = 0;
+    const int rc = ai_begin(p, n, s, &off0);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    if (n) {
+        /* the words the slicer writes: from the one that holds off0 to the end of the call's last group of 512 samples */
+        const uint32_t w0 = off0 >> 5, nw = ((off0 + n + 511u) & ~511u) / 32u - w0;
+        const AiBuf buf = p->buf[p->cur];
+        hipLaunchKernelGGL(mfm_splice_kernel, dim3((nw + 255) / 256, C), dim3(256), 0, s, buf.plane(0, 0), buf.BW, view->d_bits,
+                           view->stride_words, n, off0, w0, nw);
+        AI_TRY(hipGetLastError());
+    }
+    return ai_finish(p, n, off0, s);
 }
 
 int mfm_ais_process_host(struct mfm_ais *p, const int16_t *pcm, size_t in_stride, size_t nr_in)

@@ -15,6 +15,9 @@
  *   summ    one bit per 32 samples: some run of two or more matches touches this word (a detector needs more
  *           than eight in a row to fire).  Lets an idle channel be skipped 65536 samples per step.
  *
+ *   (sign-bit path, mfm_pocsag_process_bits_device: the resampler has taken `sample < 0` already; mfm_splice_kernel of
+ *   mfm_bits.h puts its packed words into `bits` in the place of the slicer, everything else is the same code.)
+ *
  * What stays sequential is the walk from event to event (sync found -> 512 strided bits -> 32 sync bits ->
  * ...): one workgroup of four waves per channel does it.  All waves carry the same state; each finds the first
  * "eye closes after more than spb/2 matches" with a segmented wave scan over the m words; in a transmission
@@ -37,6 +40,7 @@
 
 #include "../../include/multifm_hip.h"
 #include "mfm_bch.h"
+#include "mfm_bits.h"
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 
@@ -819,13 +823,13 @@ void mfm_pocsag_destroy(struct mfm_pocsag **pp)
     *pp = nullptr;
 }
 
-int mfm_pocsag_process_device(struct mfm_pocsag *p, const int16_t *d_pcm, size_t in_stride, size_t nr_in, void *stream)
+} /* extern "C" */
+
+/* the head of a process call, whichever way the bits arrive: order the call behind the last one, make room for n samples
+ * (slide) and say where in the window they go */
+static int pg_begin(mfm_pocsag *p, uint32_t n, hipStream_t s, uint32_t *poff0)
 {
-    if (!p || (!d_pcm && nr_in) || nr_in > p->cfg.max_in_samples) {
-        return MFM_E_INVAL;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t C = p->cfg.nr_channels, n = (uint32_t)nr_in;
+    const uint32_t C = p->cfg.nr_channels;
     PG_TRY(hipSetDevice(p->cfg.device));
     if (p->have_call && p->last_stream != s) {
         PG_TRY(hipStreamSynchronize(p->last_stream)); /* state lives on the device; keep calls ordered */
@@ -843,12 +847,16 @@ int mfm_pocsag_process_device(struct mfm_pocsag *p, const int16_t *d_pcm, size_t
         p->ws = new_ws;
         off0 = (uint32_t)(p->total - p->ws);
     }
+    *poff0 = off0;
+    return MFM_OK;
+}
+
+/* the tail of a process call, once bits [off0, off0 + n) of plane 0 are in place: match, walk, bookkeeping */
+static int pg_finish(mfm_pocsag *p, uint32_t n, uint32_t off0, hipStream_t s)
+{
+    const uint32_t C = p->cfg.nr_channels;
     const PgBuf buf = p->buf[p->cur];
     if (n) {
-        const uint32_t nsteps = (off0 + n - (off0 & ~511u) + 511) / 512;
-        hipLaunchKernelGGL(pg_slice_kernel, dim3((nsteps + 4 * PG_SLICE_U - 1) / (4 * PG_SLICE_U), C), dim3(256), 0, s, buf, d_pcm,
-                           in_stride, n, off0, nsteps);
-        PG_TRY(hipGetLastError());
         const uint32_t w_first = (off0 & ~(PG_GROUP - 1)) / 32;
         const uint32_t w_end = (off0 + n + 31) / 32;
         hipLaunchKernelGGL(pg_match_kernel, dim3((w_end - w_first + 255) / 256, C), dim3(256), 0, s, buf, w_first);
@@ -861,6 +869,58 @@ int mfm_pocsag_process_device(struct mfm_pocsag *p, const int16_t *d_pcm, size_t
     p->last_stream = s;
     p->have_call = true;
     return MFM_OK;
+}
+
+extern "C" {
+
+int mfm_pocsag_process_device(struct mfm_pocsag *p, const int16_t *d_pcm, size_t in_stride, size_t nr_in, void *stream)
+{
+    if (!p || (!d_pcm && nr_in) || nr_in > p->cfg.max_in_samples) {
+        return MFM_E_INVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t C = p->cfg.nr_channels, n = (uint32_t)nr_in;
+    uint32_t off0 = 0;
+    const int rc = pg_begin(p, n, s, &off0);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    if (n) {
+        const uint32_t nsteps = (off0 + n - (off0 & ~511u) + 511) / 512;
+        hipLaunchKernelGGL(pg_slice_kernel, dim3((nsteps + 4 * PG_SLICE_U - 1) / (4 * PG_SLICE_U), C), dim3(256), 0, s, p->buf[p->cur],
+                           d_pcm, in_stride, n, off0, nsteps);
+        PG_TRY(hipGetLastError());
+    }
+    return pg_finish(p, n, off0, s);
+}
+
+int mfm_pocsag_process_bits_device(struct mfm_pocsag *p, const struct mfm_bits_view *view, void *stream)
+{
+    if (!p || !view || (!view->d_bits && view->nr_bits) || view->nr_bits > p->cfg.max_in_samples) {
+        return MFM_E_INVAL;
+    }
+    if (view->polarity != MFM_BITS_NEG) {
+        snprintf(g_pg_error, sizeof(g_pg_error), "the POCSAG stage slices with sample < 0: it takes MFM_BITS_NEG views (got polarity %u)",
+                 view->polarity);
+        mfm_internal_set_error(g_pg_error);
+        return MFM_E_INVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t C = p->cfg.nr_channels, n = (uint32_t)view->nr_bits;
+    uint32_t off0 = 0;
+    const int rc = pg_begin(p, n, s, &off0);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    if (n) {
+        /* the words the slicer writes: from the one that holds off0 to the end of the call's last group of 512 samples */
+        const uint32_t w0 = off0 >> 5, nw = ((off0 + n + 511u) & ~511u) / 32u - w0;
+        const PgBuf buf = p->buf[p->cur];
+        hipLaunchKernelGGL(mfm_splice_kernel, dim3((nw + 255) / 256, C), dim3(256), 0, s, buf.plane(0, 0), buf.BW, view->d_bits,
+                           view->stride_words, n, off0, w0, nw);
+        PG_TRY(hipGetLastError());
+    }
+    return pg_finish(p, n, off0, s);
 }
 
 int mfm_pocsag_process_host(struct mfm_pocsag *p, const int16_t *pcm, size_t in_stride, size_t nr_in)
@@ -979,6 +1039,16 @@ int mfm_internal_bch_device_tables(int device, MfmBchTables **out)
 const MfmBchTables *mfm_internal_bch_host_tables(void)
 {
     return &bch_tables();
+}
+
+void mfm_hosttwin_splice_bits(uint32_t *window, uint64_t off0, const uint32_t *src, uint64_t nr_bits)
+{
+    if (!window || !nr_bits || !src) {
+        return;
+    }
+    for (uint64_t w = off0 / 32u; w <= (off0 + nr_bits - 1u) / 32u; w++) {
+        window[w] = mfm_splice_word(src, nr_bits, off0, w, window[w]);
+    }
 }
 
 int mfm_hosttwin_bch3121_decode(uint32_t *word)

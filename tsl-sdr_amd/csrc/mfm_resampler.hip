@@ -26,6 +26,16 @@
  * A lane ends up with four consecutive outputs of one block: one 8-byte store.
  * The DC blocker is a sequential IIR with a truncating shift in the loop (not associative): one thread
  * per channel.
+ *
+ * Sign-bit form of the output (mfm_resampler_process_bits_device).  The POCSAG and AIS stages reduce every resampled sample
+ * to one predicate (< 0, > 0), so both kernels have a second epilogue, chosen at compile time (template argument BITS; 0 is
+ * the PCM epilogue, unchanged), that takes the predicate of the Q14-rounded value in registers and stores packed words
+ * instead of PCM: 1/8 byte per output instead of 2, and nothing for a slicer to read back.
+ *   v_dot2 form: the lanes of a wave hold 64 consecutive outputs per step, so __ballot(predicate) is two finished words.
+ *   matrix form: a lane (kg, n) holds a nibble, outputs 16 n + 4 kg + i of the 256 consecutive outputs of its wave's column
+ *   group g, i.e. bits 16 (n & 1) + 4 kg of word n / 2 of that run.  The four groups' nibbles are merged over kg with a
+ *   reduce-scatter (lane bits 5 and 4: three cross-lane moves for the four groups, after which lane (kg, n) holds group
+ *   g = kg) and over n & 1 with one more; the even lanes then hold the wave's 32 words in order: one 128-byte store per wave.
  */
 #include <hip/hip_runtime.h>
 
@@ -50,7 +60,18 @@ struct RsLaunch {
     size_t in_stride;
     uint32_t tail_len, nr_in, tail_cap, out_cap, n_out, plen, interp, decim, p0, nchan, invert;
     uint32_t pos_end, new_tail;
+    uint32_t *bits;       /* sign-bit form: [C][bits_stride] words, output j = bit j % 32 of word j / 32 */
+    uint32_t bits_stride;
 };
+
+/* the predicate of the sign-bit forms, on the Q14-rounded output as the PCM form stores it: cut to int16 (utils.c:112 - a
+ * sum beyond the int16 range wraps, and the stages see the wrapped sample) */
+template <int BITS>
+__device__ __forceinline__ bool rs_pred(int32_t y)
+{
+    const int16_t s = (int16_t)y;
+    return BITS == (int)MFM_BITS_NEG ? s < 0 : s > 0;
+}
 
 constexpr uint32_t RS_NT = 256, RS_OPT = 4, RS_OPB = RS_NT * RS_OPT; /* threads, outputs per thread / per block */
 constexpr uint32_t RS_PAIRS_MAX = 32;                                /* register-resident phase: up to 64 taps */
@@ -69,7 +90,7 @@ __device__ __forceinline__ int16_t rs_sample(const RsLaunch &L, uint32_t c, uint
 
 /* NP > 0: coefficient pairs of the thread's phase in registers, NP = pairs per phase rounded up to a multiple of 4
  * (the padding pairs are zero); NP = 0: pairs read from LDS, any phase length */
-template <int NP>
+template <int NP, int BITS>
 __global__ __launch_bounds__(RS_NT) void mfm_resample_kernel(const RsLaunch L)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t rs_smem[];
@@ -134,7 +155,16 @@ __global__ __launch_bounds__(RS_NT) void mfm_resample_kernel(const RsLaunch L)
             }
         }
         asm volatile("s_nop 2" : "+v"(acc)); /* a DOT result needs 3 wait states before other VALU code reads it */
-        L.y[(size_t)c * L.out_cap + j] = (int16_t)mfm_r14_wide(acc); /* utils.c:112 */
+        if (BITS) {
+            /* outputs j0 + 256 u + 64 wave + lane: the wave's active lanes (those below n_out; lane 0 is one of them) hold the
+             * bits of two consecutive words, the lanes that left the loop count as 0 */
+            const unsigned long long m = __ballot(rs_pred<BITS>(mfm_r14_wide(acc)));
+            if ((tid & 31u) == 0) {
+                L.bits[(size_t)c * L.bits_stride + (j >> 5)] = (uint32_t)(m >> (tid & 32u));
+            }
+        } else {
+            L.y[(size_t)c * L.out_cap + j] = (int16_t)mfm_r14_wide(acc); /* utils.c:112 */
+        }
         pos_abs += step_pos;
         ph += step_ph;
         if (ph >= L.interp) {
@@ -180,7 +210,7 @@ struct __attribute__((packed, aligned(2))) RsPcm8 {
     int16_t v[8];
 };
 
-template <int KS>
+template <int KS, int BITS>
 __global__ __launch_bounds__(RSM_NT) void mfm_resample_mfma_kernel(const RsMLaunch M)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t rs_smem[];
@@ -241,6 +271,7 @@ __global__ __launch_bounds__(RSM_NT) void mfm_resample_mfma_kernel(const RsMLaun
     for (int i = 0; i < 4; i++) {
         kr[i] = M.krow[4u * kg + (uint32_t)i];
     }
+    uint32_t nibw[4] = { 0, 0, 0, 0 }; /* sign-bit form: my nibble of column group g, at its place in its word */
 #pragma unroll
     for (uint32_t g = 0; g < 4; g++) {
         const uint32_t blk = wave * 64u + g * 16u + n;          /* block within the workgroup */
@@ -263,6 +294,15 @@ __global__ __launch_bounds__(RSM_NT) void mfm_resample_mfma_kernel(const RsMLaun
             const uint32_t acc = (uint32_t)ll[i] + ((uint32_t)md[i] << 8) + ((uint32_t)hh[i] << 16) + (uint32_t)kr[i];
             y[i] = mfm_r14_wide((int32_t)acc); /* utils.c:112 */
         }
+        if (BITS) {
+            uint32_t nib = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                nib |= (rs_pred<BITS>(y[i]) && j + (uint32_t)i < L.n_out ? 1u : 0u) << i;
+            }
+            nibw[g] = nib << (16u * (n & 1u) + 4u * kg);
+            continue;
+        }
         int16_t *dst = L.y + (size_t)c * L.out_cap + j;
         if (j + 4u <= L.n_out) {
             uint2 w;
@@ -276,6 +316,22 @@ __global__ __launch_bounds__(RSM_NT) void mfm_resample_mfma_kernel(const RsMLaun
                     dst[i] = (int16_t)y[i];
                 }
             }
+        }
+    }
+    if (BITS) {
+        /* OR over kg = lane bits 5, 4, handing one half of what is left to the partner at each step: 2 + 1 moves, after
+         * which lane (kg, n) holds the nibbles of all kg for group g = kg; then over n & 1 */
+        const bool b5 = (lane & 32u) != 0u, b4 = (lane & 16u) != 0u;
+        uint32_t k0 = b5 ? nibw[2] : nibw[0], k1 = b5 ? nibw[3] : nibw[1];
+        k0 |= (uint32_t)__shfl_xor((int)(b5 ? nibw[0] : nibw[2]), 32);
+        k1 |= (uint32_t)__shfl_xor((int)(b5 ? nibw[1] : nibw[3]), 32);
+        uint32_t k = b4 ? k1 : k0;
+        k |= (uint32_t)__shfl_xor((int)(b4 ? k0 : k1), 16);
+        k |= (uint32_t)__shfl_xor((int)k, 1);
+        /* word n / 2 of group kg: outputs 16 (b0 + 64 wave + 16 kg) + 32 (n / 2) ..., i.e. the wave's 32 words in lane order */
+        const uint32_t wi = (b0 >> 1) + 32u * wave + 8u * kg + (n >> 1);
+        if ((n & 1u) == 0u && 32u * wi < L.n_out) {
+            L.bits[(size_t)c * L.bits_stride + wi] = k;
         }
     }
 }
@@ -394,6 +450,8 @@ struct mfm_resampler {
     uint32_t tail = 0; /* unconsumed samples in d_x[cur] */
     uint32_t phase_id = 0;
     int16_t *d_stage = nullptr; /* process_host_to_device: [C][max_in_samples] */
+    uint32_t *d_bits = nullptr; /* sign-bit form: [C][bits_stride], allocated by the first bits call */
+    uint32_t bits_stride = 0;
     /* matrix-core form */
     bool use_mfma = false;
     uint32_t m_ks = 0, m_R = 0, m_rp = 0, m_plane = 0, m_lds = 0;
@@ -480,7 +538,11 @@ int mfm_resampler_create(struct mfm_resampler **pr, const struct mfm_resampler_c
     if (r->lds_bytes > 48u * 1024u) {
         /* only extreme decimation ratios get here: they use the LDS-coefficient variant */
         r->reg_coef = false;
-        RS_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfm_resample_kernel<0>),
+        RS_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfm_resample_kernel<0, 0>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
+        RS_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfm_resample_kernel<0, (int)MFM_BITS_NEG>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
+        RS_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfm_resample_kernel<0, (int)MFM_BITS_POS>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
     }
     /* ---- matrix-core form: y[16 m + q] = sum_s G[q][s] x[R m + s], one G per carried phase (see the head of the file) ---- */
@@ -562,6 +624,7 @@ void mfm_resampler_destroy(struct mfm_resampler **pr)
     (void)hipFree(r->d_y);
     (void)hipFree(r->d_dc);
     (void)hipFree(r->d_stage);
+    (void)hipFree(r->d_bits);
     (void)hipFree(r->d_gfrag);
     (void)hipFree(r->d_krow);
     delete r;
@@ -573,18 +636,14 @@ size_t mfm_resampler_max_out(const struct mfm_resampler *r)
     return r ? r->out_cap : 0;
 }
 
-int mfm_resampler_process_device(struct mfm_resampler *r, const int16_t *d_pcm, size_t in_stride, size_t nr_in,
-                                 void *stream, int16_t **d_out, size_t *out_stride, size_t *nr_out)
+} /* extern "C" */
+
+/* one call of either output form: BITS = 0 writes PCM to d_y, MFM_BITS_NEG / MFM_BITS_POS the packed predicate to d_bits.
+ * The walk, the carried tail and the phase are the same, so the two forms may alternate on one stream. */
+template <int BITS>
+static int rs_process(mfm_resampler *r, const int16_t *d_pcm, size_t in_stride, size_t nr_in, hipStream_t s, uint32_t *pn_out)
 {
-    if (!r || !d_pcm || !d_out || !out_stride || !nr_out) {
-        return MFM_E_INVAL;
-    }
-    if (nr_in > r->cfg.max_in_samples) {
-        return MFM_E_INVAL;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const uint32_t C = r->cfg.nr_channels, I = r->cfg.interpolate, D = r->cfg.decimate;
-    RS_TRY(hipSetDevice(r->cfg.device));
     const uint32_t total = r->tail + (uint32_t)nr_in;
     /* outputs m with total - pos_m > plen  <=>  p0 + m*D < (total - plen) * I   (polyphase_fir.c:184) */
     uint32_t n_out = 0;
@@ -600,35 +659,35 @@ int mfm_resampler_process_device(struct mfm_resampler *r, const int16_t *d_pcm, 
      * plen) * I; without, total <= plen */
     const uint32_t new_tail = total - pos_end;
     RsLaunch L{ r->d_x[r->cur], d_pcm, r->d_y, r->d_phase, r->d_x[r->cur ^ 1], in_stride, r->tail, (uint32_t)nr_in, r->tail_cap,
-                r->out_cap, n_out, r->plen, I, D, r->phase_id, C, r->cfg.invert, pos_end, new_tail };
+                r->out_cap, n_out, r->plen, I, D, r->phase_id, C, r->cfg.invert, pos_end, new_tail, r->d_bits, r->bits_stride };
     if (n_out && r->use_mfma) {
         RsMLaunch M{ L, r->d_gfrag + (size_t)r->phase_id * 2u * r->m_ks * 64u, r->d_krow + (size_t)r->phase_id * 16u, r->m_R, r->m_rp,
                      r->m_plane };
         const dim3 grid((n_out + 16u * RSM_NB - 1u) / (16u * RSM_NB), C);
         switch (r->m_ks) {
-        case 1: hipLaunchKernelGGL(mfm_resample_mfma_kernel<1>, grid, dim3(RSM_NT), r->m_lds, s, M); break;
-        case 2: hipLaunchKernelGGL(mfm_resample_mfma_kernel<2>, grid, dim3(RSM_NT), r->m_lds, s, M); break;
-        case 3: hipLaunchKernelGGL(mfm_resample_mfma_kernel<3>, grid, dim3(RSM_NT), r->m_lds, s, M); break;
-        default: hipLaunchKernelGGL(mfm_resample_mfma_kernel<4>, grid, dim3(RSM_NT), r->m_lds, s, M); break;
+        case 1: hipLaunchKernelGGL((mfm_resample_mfma_kernel<1, BITS>), grid, dim3(RSM_NT), r->m_lds, s, M); break;
+        case 2: hipLaunchKernelGGL((mfm_resample_mfma_kernel<2, BITS>), grid, dim3(RSM_NT), r->m_lds, s, M); break;
+        case 3: hipLaunchKernelGGL((mfm_resample_mfma_kernel<3, BITS>), grid, dim3(RSM_NT), r->m_lds, s, M); break;
+        default: hipLaunchKernelGGL((mfm_resample_mfma_kernel<4, BITS>), grid, dim3(RSM_NT), r->m_lds, s, M); break;
         }
         RS_TRY(hipGetLastError());
     } else if (n_out) {
         const dim3 grid((n_out + RS_OPB - 1) / RS_OPB, C);
         const uint32_t np4 = r->reg_coef ? (r->plen / 2u + 3u) / 4u : 0u; /* register variant: pairs rounded up to 4 */
         switch (np4) {
-        case 1: hipLaunchKernelGGL(mfm_resample_kernel<4>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        case 2: hipLaunchKernelGGL(mfm_resample_kernel<8>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        case 3: hipLaunchKernelGGL(mfm_resample_kernel<12>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        case 4: hipLaunchKernelGGL(mfm_resample_kernel<16>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        case 5: hipLaunchKernelGGL(mfm_resample_kernel<20>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        case 6: hipLaunchKernelGGL(mfm_resample_kernel<24>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        case 7: hipLaunchKernelGGL(mfm_resample_kernel<28>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        case 8: hipLaunchKernelGGL(mfm_resample_kernel<32>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
-        default: hipLaunchKernelGGL(mfm_resample_kernel<0>, grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 1: hipLaunchKernelGGL((mfm_resample_kernel<4, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 2: hipLaunchKernelGGL((mfm_resample_kernel<8, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 3: hipLaunchKernelGGL((mfm_resample_kernel<12, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 4: hipLaunchKernelGGL((mfm_resample_kernel<16, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 5: hipLaunchKernelGGL((mfm_resample_kernel<20, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 6: hipLaunchKernelGGL((mfm_resample_kernel<24, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 7: hipLaunchKernelGGL((mfm_resample_kernel<28, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        case 8: hipLaunchKernelGGL((mfm_resample_kernel<32, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
+        default: hipLaunchKernelGGL((mfm_resample_kernel<0, BITS>), grid, dim3(RS_NT), r->lds_bytes, s, L); break;
         }
         RS_TRY(hipGetLastError());
     }
-    if (n_out) {
+    if (n_out && !BITS) {
         if (r->cfg.dc_block) {
             hipLaunchKernelGGL(mfm_dc_block_kernel, dim3((C + 63) / 64), dim3(64), 0, s, r->d_y, r->out_cap, n_out, C,
                                r->dc_p, r->d_dc);
@@ -642,9 +701,77 @@ int mfm_resampler_process_device(struct mfm_resampler *r, const int16_t *d_pcm, 
     r->phase_id = (uint32_t)(t_end % I);
     r->tail = new_tail;
     r->cur ^= 1;
+    *pn_out = n_out;
+    return MFM_OK;
+}
+
+/* what every bits call checks before it touches the stream position; allocates the bit rows on first use */
+static int rs_bits_prepare(mfm_resampler *r, uint32_t polarity)
+{
+    if (polarity != MFM_BITS_NEG && polarity != MFM_BITS_POS) {
+        snprintf(g_rs_error, sizeof(g_rs_error), "unknown sign-bit polarity %u (MFM_BITS_NEG or MFM_BITS_POS)", polarity);
+        mfm_internal_set_error(g_rs_error);
+        return MFM_E_INVAL;
+    }
+    if (r->cfg.dc_block) {
+        snprintf(g_rs_error, sizeof(g_rs_error), "the sign-bit output is not available with the DC blocker: it filters the "
+                                                 "resampled PCM in memory, which this form does not write");
+        mfm_internal_set_error(g_rs_error);
+        return MFM_E_INVAL;
+    }
+    RS_TRY(hipSetDevice(r->cfg.device));
+    if (!r->d_bits) {
+        /* a matrix-form wave stores 32 words at once and checks only its own word against n_out: rows of whole words */
+        r->bits_stride = ((r->out_cap + 31u) / 32u + 7u) & ~7u;
+        RS_TRY(hipMalloc(&r->d_bits, (size_t)r->cfg.nr_channels * r->bits_stride * 4));
+    }
+    return MFM_OK;
+}
+
+extern "C" {
+
+int mfm_resampler_process_device(struct mfm_resampler *r, const int16_t *d_pcm, size_t in_stride, size_t nr_in,
+                                 void *stream, int16_t **d_out, size_t *out_stride, size_t *nr_out)
+{
+    if (!r || !d_pcm || !d_out || !out_stride || !nr_out) {
+        return MFM_E_INVAL;
+    }
+    if (nr_in > r->cfg.max_in_samples) {
+        return MFM_E_INVAL;
+    }
+    RS_TRY(hipSetDevice(r->cfg.device));
+    uint32_t n_out = 0;
+    const int rc = rs_process<0>(r, d_pcm, in_stride, nr_in, static_cast<hipStream_t>(stream), &n_out);
+    if (rc != MFM_OK) {
+        return rc;
+    }
     *d_out = r->d_y;
     *out_stride = r->out_cap;
     *nr_out = n_out;
+    return MFM_OK;
+}
+
+int mfm_resampler_process_bits_device(struct mfm_resampler *r, const int16_t *d_pcm, size_t in_stride, size_t nr_in,
+                                      void *stream, uint32_t polarity, struct mfm_bits_view *view)
+{
+    if (!r || !d_pcm || !view || nr_in > r->cfg.max_in_samples) {
+        return MFM_E_INVAL;
+    }
+    int rc = rs_bits_prepare(r, polarity);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    uint32_t n_out = 0;
+    rc = polarity == MFM_BITS_NEG ? rs_process<(int)MFM_BITS_NEG>(r, d_pcm, in_stride, nr_in, static_cast<hipStream_t>(stream), &n_out)
+                                  : rs_process<(int)MFM_BITS_POS>(r, d_pcm, in_stride, nr_in, static_cast<hipStream_t>(stream), &n_out);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    view->d_bits = r->d_bits;
+    view->stride_words = r->bits_stride;
+    view->nr_bits = n_out;
+    view->polarity = polarity;
+    view->reserved = 0;
     return MFM_OK;
 }
 
@@ -664,6 +791,27 @@ int mfm_resampler_process_host_to_device(struct mfm_resampler *r, const int16_t 
                                 hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
     }
     return mfm_resampler_process_device(r, r->d_stage, r->cfg.max_in_samples, nr_in, stream, d_out, out_stride, nr_out);
+}
+
+int mfm_resampler_process_bits_host_to_device(struct mfm_resampler *r, const int16_t *pcm, size_t in_stride, size_t nr_in,
+                                              void *stream, uint32_t polarity, struct mfm_bits_view *view)
+{
+    if (!r || (!pcm && nr_in) || !view || nr_in > r->cfg.max_in_samples) {
+        return MFM_E_INVAL;
+    }
+    const int rc = rs_bits_prepare(r, polarity); /* refuse before anything is staged */
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    const uint32_t C = r->cfg.nr_channels;
+    if (!r->d_stage) {
+        RS_TRY(hipMalloc(&r->d_stage, (size_t)C * r->cfg.max_in_samples * 2));
+    }
+    if (nr_in) {
+        RS_TRY(hipMemcpy2DAsync(r->d_stage, (size_t)r->cfg.max_in_samples * 2, pcm, in_stride * 2, nr_in * 2, C,
+                                hipMemcpyHostToDevice, static_cast<hipStream_t>(stream)));
+    }
+    return mfm_resampler_process_bits_device(r, r->d_stage, r->cfg.max_in_samples, nr_in, stream, polarity, view);
 }
 
 int mfm_resampler_process_host(struct mfm_resampler *r, const int16_t *pcm, size_t in_stride, size_t nr_in,
@@ -695,6 +843,41 @@ int mfm_resampler_process_host(struct mfm_resampler *r, const int16_t *pcm, size
     (void)hipDeviceSynchronize();
     (void)hipFree(d_in);
     *nr_out = n;
+    return rc;
+}
+
+int mfm_resampler_process_bits_host(struct mfm_resampler *r, const int16_t *pcm, size_t in_stride, size_t nr_in,
+                                    uint32_t polarity, uint32_t *bits, size_t bits_stride_words, size_t *nr_bits)
+{
+    if (!r || !pcm || !bits || !nr_bits) {
+        return MFM_E_INVAL;
+    }
+    int rc = rs_bits_prepare(r, polarity);
+    if (rc != MFM_OK) {
+        return rc;
+    }
+    int16_t *d_in = nullptr;
+    const uint32_t C = r->cfg.nr_channels;
+    RS_TRY(hipMalloc(&d_in, (size_t)C * (nr_in ? nr_in : 1) * 2));
+    if (nr_in) {
+        RS_TRY(hipMemcpy2D(d_in, nr_in * 2, pcm, in_stride * 2, nr_in * 2, C, hipMemcpyHostToDevice));
+    }
+    mfm_bits_view v{};
+    rc = mfm_resampler_process_bits_device(r, d_in, nr_in, nr_in, nullptr, polarity, &v);
+    const size_t nw = (v.nr_bits + 31u) / 32u;
+    if (rc == MFM_OK && nw) {
+        if (nw > bits_stride_words) {
+            rc = MFM_E_INVAL;
+        } else {
+            hipError_t e = hipMemcpy2D(bits, bits_stride_words * 4, v.d_bits, v.stride_words * 4, nw * 4, C, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) {
+                rc = MFM_E_DEVICE;
+            }
+        }
+    }
+    (void)hipDeviceSynchronize();
+    (void)hipFree(d_in);
+    *nr_bits = v.nr_bits;
     return rc;
 }
 

@@ -8,8 +8,8 @@
  *     PCM block (host) -> mfm_resampler (I/D, -b, -i) -> mfm_ais (slicer / preamble / bits / FCS)     on the MI355X
  *     events (host)    -> ais_decode_on_events -> position / base station / static and voyage -> JSON   per channel
  *
- * Same options and loop as decoder_amd (decoder_main.c): -I -D -S -F -f -o -c -b -p -i, plus -B block size and -g
- * device; several inputs are allowed (with more than one, -o NAME writes NAME.0, NAME.1, ...), read in lock step,
+ * Same options and loop as decoder_amd (decoder_main.c): -I -D -S -F -f -o -c -b -p -i, plus -B block size, -g
+ * device and -s (sign bits instead of PCM between resampler and AIS stage, not with -b; same JSON lines); several inputs are allowed (with more than one, -o NAME writes NAME.0, NAME.1, ...), read in lock step,
  * processing stops at the shortest.  The JSON lines are the reference's byte for byte, rawAscii through the same
  * escaper, callsign / ship name / destination unescaped (decoder.c:372).  MFM_DECODER_FIXED_TIME=1 prints the epoch
  * instead of the wall clock, so two runs can be diffed.  There is no CPU path: without a device it refuses.
@@ -146,7 +146,7 @@ static void usage(const char *app)
 {
     DEC_MSG(SEV_INFO, "USAGE",
             "%s -I [interpolate] -D [decimate] -F [filter file] -S [input sample rate] -f [center freq] [-c] "
-            "[-o output JSON file] [-b] [-p pole] [-i] [-B block samples] [-g gpu] in_fifo [in_fifo ...]",
+            "[-o output JSON file] [-b] [-p pole] [-i] [-s] [-B block samples] [-g gpu] in_fifo [in_fifo ...]",
             app);
     exit(EXIT_SUCCESS);
 }
@@ -175,11 +175,11 @@ int main(int argc, char *const argv[])
 {
     unsigned interpolate = 1, decimate = 1, input_sample_rate = 0, center_freq = 0, block = 1u << 18;
     int device = 0, arg;
-    bool dc_blocker = false, invert = false, create_out = false;
+    bool dc_blocker = false, invert = false, create_out = false, sign_bits = false;
     double dc_block_pole = 0.9999;
     const char *filter_file = NULL, *out_file_name = NULL;
 
-    while ((arg = getopt(argc, argv, "co:I:D:S:F:f:p:B:g:bih")) != -1) {
+    while ((arg = getopt(argc, argv, "co:I:D:S:F:f:p:B:g:bish")) != -1) {
         switch (arg) {
         case 'o':
             out_file_name = optarg;
@@ -211,6 +211,9 @@ int main(int argc, char *const argv[])
         case 'i':
             invert = true;
             break;
+        case 's': /* resampler -> AIS stage as one sign bit per sample, no resampled PCM in device memory */
+            sign_bits = true;
+            break;
         case 'B':
             block = (unsigned)strtoll(optarg, NULL, 0);
             break;
@@ -233,6 +236,10 @@ int main(int argc, char *const argv[])
     }
     if (0 == center_freq) {
         DEC_MSG(SEV_FATAL, "BAD-PAGER-FREQ", "Pager frequency must be non-zero");
+        exit(EXIT_FAILURE);
+    }
+    if (sign_bits && dc_blocker) {
+        DEC_MSG(SEV_FATAL, "BAD-SIGN-BIT-PATH", "The sign-bit path (-s) cannot be used with the DC blocker (-b): it filters the resampled PCM.");
         exit(EXIT_FAILURE);
     }
     if (NULL == filter_file) {
@@ -325,8 +332,14 @@ int main(int argc, char *const argv[])
         }
         int16_t *d_out = NULL;
         size_t out_stride = 0, nr_out = 0, nr_events = 0;
-        TSL_BUG_ON(MFM_OK != mfm_resampler_process_host_to_device(rs, pcm, block, n, NULL, &d_out, &out_stride, &nr_out));
-        TSL_BUG_ON(MFM_OK != mfm_ais_process_device(ais, d_out, out_stride, nr_out, NULL));
+        if (sign_bits) {
+            struct mfm_bits_view view;
+            TSL_BUG_ON(MFM_OK != mfm_resampler_process_bits_host_to_device(rs, pcm, block, n, NULL, MFM_BITS_POS, &view));
+            TSL_BUG_ON(MFM_OK != mfm_ais_process_bits_device(ais, &view, NULL));
+        } else {
+            TSL_BUG_ON(MFM_OK != mfm_resampler_process_host_to_device(rs, pcm, block, n, NULL, &d_out, &out_stride, &nr_out));
+            TSL_BUG_ON(MFM_OK != mfm_ais_process_device(ais, d_out, out_stride, nr_out, NULL));
+        }
         TSL_BUG_ON(MFM_OK != mfm_ais_fetch_events(ais, events, max_events, &nr_events));
         /* events come grouped by channel, in stream order inside a channel */
         size_t first = 0;

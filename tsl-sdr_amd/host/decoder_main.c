@@ -11,7 +11,8 @@
  *                      or pager_flex_on_events   -> on_alnum / on_num / on_siv
  *
  * Same options as decoder.c:404 (-I -D -S -F -f -o -c -b -p -i -m -d is not offered), same JSON line layout
- * (decoder.c:173-318); -m FLEX is the default, as in decoder.c:59.  Differences, all forced by batching: several inputs are allowed (with more than one,
+ * (decoder.c:173-318); -s (POCSAG only, not with -b) hands the pager stage one sign bit per resampled sample instead of PCM
+ * (mfm_resampler_process_bits_host_to_device -> mfm_pocsag_process_bits_device), same JSON lines; -m FLEX is the default, as in decoder.c:59.  Differences, all forced by batching: several inputs are allowed (with more than one,
  * -o NAME writes NAME.0, NAME.1, ...); inputs are read in lock step and processing stops at the shortest;
  * -B sets the block size, -g the device.  MFM_DECODER_FIXED_TIME=1 prints the epoch instead of the wall clock,
  * so two runs can be diffed.  AIS is not part of this build.
@@ -170,7 +171,7 @@ static void usage(const char *app)
 {
     DEC_MSG(SEV_INFO, "USAGE",
             "%s -I [interpolate] -D [decimate] -F [filter file] -S [input sample rate] -f [center freq] [-c] "
-            "[-o output JSON file] [-b] [-p pole] [-i] [-m FLEX|POCSAG] [-B block samples] [-g gpu] in_fifo [in_fifo ...]",
+            "[-o output JSON file] [-b] [-p pole] [-i] [-s] [-m FLEX|POCSAG] [-B block samples] [-g gpu] in_fifo [in_fifo ...]",
             app);
     exit(EXIT_SUCCESS);
 }
@@ -199,12 +200,12 @@ int main(int argc, char *const argv[])
 {
     unsigned interpolate = 1, decimate = 1, input_sample_rate = 0, center_freq = 0, block = 1u << 18;
     int device = 0, arg;
-    bool dc_blocker = false, invert = false, create_out = false;
+    bool dc_blocker = false, invert = false, create_out = false, sign_bits = false;
     enum proto proto = PROTO_FLEX;
     double dc_block_pole = 0.9999;
     const char *filter_file = NULL, *out_file_name = NULL;
 
-    while ((arg = getopt(argc, argv, "co:I:D:S:F:f:p:m:B:g:bih")) != -1) {
+    while ((arg = getopt(argc, argv, "co:I:D:S:F:f:p:m:B:g:bish")) != -1) {
         switch (arg) {
         case 'o':
             out_file_name = optarg;
@@ -235,6 +236,9 @@ int main(int argc, char *const argv[])
             break;
         case 'i':
             invert = true;
+            break;
+        case 's': /* resampler -> pager stage as one sign bit per sample, no resampled PCM in device memory */
+            sign_bits = true;
             break;
         case 'm':
             if (!strncasecmp(optarg, "pocsag", 6)) {
@@ -268,6 +272,14 @@ int main(int argc, char *const argv[])
     }
     if (0 == center_freq) {
         DEC_MSG(SEV_FATAL, "BAD-PAGER-FREQ", "Pager frequency must be non-zero");
+        exit(EXIT_FAILURE);
+    }
+    if (sign_bits && PROTO_POCSAG != proto) {
+        DEC_MSG(SEV_FATAL, "BAD-SIGN-BIT-PATH", "The sign-bit path (-s) is for POCSAG: the FLEX stage slices four levels and needs the amplitudes.");
+        exit(EXIT_FAILURE);
+    }
+    if (sign_bits && dc_blocker) {
+        DEC_MSG(SEV_FATAL, "BAD-SIGN-BIT-PATH", "The sign-bit path (-s) cannot be used with the DC blocker (-b): it filters the resampled PCM.");
         exit(EXIT_FAILURE);
     }
     if (NULL == filter_file) {
@@ -384,10 +396,18 @@ int main(int argc, char *const argv[])
         }
         int16_t *d_out = NULL;
         size_t out_stride = 0, nr_out = 0, nr_events = 0;
-        TSL_BUG_ON(MFM_OK != mfm_resampler_process_host_to_device(rs, pcm, block, n, NULL, &d_out, &out_stride, &nr_out));
+        if (sign_bits) {
+            struct mfm_bits_view view;
+            TSL_BUG_ON(MFM_OK != mfm_resampler_process_bits_host_to_device(rs, pcm, block, n, NULL, MFM_BITS_NEG, &view));
+            TSL_BUG_ON(MFM_OK != mfm_pocsag_process_bits_device(pg, &view, NULL));
+        } else {
+            TSL_BUG_ON(MFM_OK != mfm_resampler_process_host_to_device(rs, pcm, block, n, NULL, &d_out, &out_stride, &nr_out));
+        }
         /* events come grouped by channel, in stream order inside a channel */
         if (PROTO_POCSAG == proto) {
-            TSL_BUG_ON(MFM_OK != mfm_pocsag_process_device(pg, d_out, out_stride, nr_out, NULL));
+            if (!sign_bits) {
+                TSL_BUG_ON(MFM_OK != mfm_pocsag_process_device(pg, d_out, out_stride, nr_out, NULL));
+            }
             TSL_BUG_ON(MFM_OK != mfm_pocsag_fetch_events(pg, events, max_events, &nr_events));
             size_t first = 0;
             while (first < nr_events) {
