@@ -742,6 +742,93 @@ int mfm_ais_process_bits_device(struct mfm_ais *p, const struct mfm_bits_view *v
 int mfm_ais_fetch_events(struct mfm_ais *p, struct mfm_ais_event *out, size_t max_events, size_t *nr_events);
 
 /*
+ * ---- Level stage: per-channel signal level and squelch -----------------------------------------------------------
+ * The reference has no counterpart: every channel thread demodulates all the time (multifm/demod.c:48-121) and an empty
+ * channel's discriminator noise runs through every decoder behind it.  This stage answers "which channels carry a signal
+ * right now" for ALL channels at once, on rows that are still in HBM, in one of two forms chosen at create:
+ *
+ *   MFM_LEVEL_PCM   one int16 per sample: the engine's PCM or the resampler's output, rows [channel][in_stride]
+ *   MFM_LEVEL_IQ    two per sample, re, im interleaved: the engine's filtered IQ.  in_stride counts int16 ELEMENTS
+ *                   here as well, so for the engine's IQ rows it is 2 * stride
+ *
+ * Samples are numbered per channel from 0 at create; window k covers samples [k W, (k + 1) W), W = window_samples.  A
+ * window that straddles calls is carried on the device, and a call completes floor((pos + nr_in) / W) - floor(pos / W)
+ * windows, the same number for every channel: records do not depend on how a stream is cut into calls (nr_in = 0 and
+ * nr_in < W included).  All arithmetic is integer and exact.  Per channel and completed window one record:
+ *
+ *   energy       sum of x * x (PCM) or of re * re + im * im (IQ); -32768 squares to 2^30, nothing wraps
+ *   diff_energy  PCM form only, else 0: sum of d * d, d = (int16_t)(x[n] - x[n-1]) - the difference WRAPPED to 16 bits,
+ *                because the discriminator's output is an angle; x[-1] = 0 at stream start, the previous sample is
+ *                carried across windows and calls
+ *   peak         largest |x|, over both components in the IQ form; |-32768| = 32768
+ *   open         squelch state after this window
+ *
+ * Squelch, per channel, stepped once per completed window in stream order on `metric` (the window's energy or
+ * diff_energy, compared with the thresholds as it is, no division).  It starts closed.  Closed: opens when the metric is
+ * on the open side of open_thr (>= for MFM_LEVEL_OPEN_ABOVE: a carrier raises the IQ energy; <= for
+ * MFM_LEVEL_OPEN_BELOW: a captured FM carrier lowers the discriminator's energy).  Open: a window is bad when the metric
+ * is strictly on the closed side of close_thr; hang_windows + 1 bad windows in a row close, a good one resets the count.
+ * The current state of every channel also stands in device memory as one uint32 per channel (d_open of
+ * mfm_level_device_view()): a channel mask for stages that can skip idle channels.
+ */
+#define MFM_LEVEL_PCM 0u
+#define MFM_LEVEL_IQ 1u
+#define MFM_LEVEL_METRIC_ENERGY 0u
+#define MFM_LEVEL_METRIC_DIFF 1u   /* PCM form only */
+#define MFM_LEVEL_OPEN_ABOVE 0u
+#define MFM_LEVEL_OPEN_BELOW 1u
+
+struct mfm_level_record {   /* 40 bytes */
+    uint64_t energy;
+    uint64_t diff_energy;
+    uint64_t window;        /* k */
+    uint32_t peak;
+    uint32_t channel;
+    uint32_t open;          /* 0 / 1 */
+    uint32_t reserved;      /* 0 */
+};
+
+struct mfm_level; /* opaque */
+
+struct mfm_level_config {
+    uint32_t abi_version;    /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_in_samples; /* most samples per channel one process call may carry (<= 2^28) */
+    uint32_t form;           /* MFM_LEVEL_PCM / MFM_LEVEL_IQ */
+    uint32_t window_samples; /* W >= 1 */
+    uint32_t metric;         /* MFM_LEVEL_METRIC_* */
+    uint32_t sense;          /* MFM_LEVEL_OPEN_* */
+    uint64_t open_thr;
+    uint64_t close_thr;      /* MFM_E_INVAL unless close_thr <= open_thr (OPEN_ABOVE) / close_thr >= open_thr (OPEN_BELOW) */
+    uint32_t hang_windows;
+    uint32_t flags;          /* 0 */
+};
+
+int mfm_level_create(struct mfm_level **pp, const struct mfm_level_config *cfg);
+void mfm_level_destroy(struct mfm_level **pp);
+/*
+ * Consume nr_in samples per channel from device memory laid out [channel][in_stride] (int16 elements; for instance
+ * the pointers and stride of mfm_engine_last_output_device(), or the resampler's output).  Work is queued on `stream`;
+ * no host synchronisation; the rows are read until the queued work has run.  The records of THIS call replace those of
+ * the previous one.
+ */
+int mfm_level_process_device(struct mfm_level *p, const int16_t *d_rows, size_t in_stride, size_t nr_in, void *stream);
+/* Host convenience: same from host memory, synchronous. */
+int mfm_level_process_host(struct mfm_level *p, const int16_t *rows, size_t in_stride, size_t nr_in);
+/*
+ * Wait for the last process call and copy its records: channels ascending, windows ascending within a channel,
+ * nr_channels * *nr_windows of them (*nr_windows = windows per channel that call completed; 0 is a valid result).
+ * MFM_E_NOMEM when max_records is smaller than that (nothing copied; *nr_windows says what is needed).
+ */
+int mfm_level_fetch(struct mfm_level *p, struct mfm_level_record *out, size_t max_records, size_t *nr_windows);
+/* For callers that stay on the device: the last call's records at d_records[channel * record_stride + i],
+ * i < *nr_windows, and the squelch state d_open[channel]; both are written by work queued on that call's stream and
+ * stay valid (d_open: current) until the next call.  Any of the four may be NULL. */
+int mfm_level_device_view(struct mfm_level *p, const struct mfm_level_record **d_records, size_t *record_stride, size_t *nr_windows,
+                          const uint32_t **d_open);
+
+/*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
  *   mm_init      pager/mueller_muller.c:10-33
  *   mm_process   pager/mueller_muller.c:41-115
@@ -871,6 +958,13 @@ int mfm_hosttwin_bch3121_decode(uint32_t *word);
  * kernel runs per word): bits [off0, off0 + nr_bits) of `window` from bits [0, nr_bits) of `src`, bits below off0 kept, the rest
  * of the last touched word zero, no word behind it touched */
 void mfm_hosttwin_splice_bits(uint32_t *window, uint64_t off0, const uint32_t *src, uint64_t nr_bits);
+/* host twins of the level stage's arithmetic (csrc/mfm_level.h, the inlines its kernels run): the three sums of one window of
+ * nr_samples samples at x (form MFM_LEVEL_PCM: nr_samples int16; MFM_LEVEL_IQ: 2 * nr_samples, and *diff_energy = 0), prev = the
+ * sample in front of x[0]; and one step of the squelch on *open / *bad (sense MFM_LEVEL_OPEN_*), which returns the new *open */
+void mfm_hosttwin_level_window(const int16_t *x, size_t nr_samples, uint32_t form, int16_t prev, uint64_t *energy, uint64_t *diff_energy,
+                               uint32_t *peak);
+uint32_t mfm_hosttwin_squelch_step(uint32_t sense, uint64_t open_thr, uint64_t close_thr, uint32_t hang_windows, uint64_t metric,
+                                   uint32_t *open, uint32_t *bad);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,211 @@
+#!/usr/bin/env python3
+"""Which channels of a capture carry a signal: channel engine, then the level / squelch stage, both on the device.
+
+    python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
+           [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
+           [--block 1048576] [--summary]
+
+receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
+lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
+
+    {"freq": 929612500, "channel": 0, "window": 3, "energy": ..., "diff_energy": ..., "peak": ..., "open": 1}
+
+--form pcm runs the stage on the discriminator's PCM (a captured carrier LOWERS its energy: default sense below),
+--form iq on the filtered IQ (a carrier RAISES it: default sense above).  --summary adds one line per channel with the
+share of windows it was open.  The thresholds default to 0: read the levels off a first run, then set them.
+
+    python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8]
+
+times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
+against the POCSAG stage's call on the same rows (idle input; its slicer, pg_slice_kernel, reads the same bytes) and
+against the engine launch with and without filtered IQ.  Level pass and comparison alternate in one process, in
+rotating order; mean and standard deviation over --reps repetitions, a difference counts beyond two standard errors
+(the rule of tools/exp/ab.py).  One JSON line."""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_PEAK_BPS = 8.0e12  # MI355X HBM3E, spec
+
+
+def read_config(path):
+    cfg = json.load(open(path))
+    fs, centre, decim = int(cfg["sampleRateHz"]), int(cfg["centerFreqHz"]), int(cfg["decimationFactor"])
+    taps = [float(t) for t in cfg["lpfTaps"]]
+    chans = [(int(ch["chanCenterFreq"]), 10.0 ** (float(ch.get("dBGain", 0.0)) / 10.0)) for ch in cfg["channels"]]
+    return fs, centre, decim, taps, chans
+
+
+def scan(a):
+    import torch  # noqa: F401  (brings the HIP runtime up before the library does)
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    b = pkg.binding
+    fs, centre, decim, taps, chans = read_config(a.config)
+    iq_form = a.form == "iq"
+    sense = a.sense or ("above" if iq_form else "below")
+    eng = pkg.Engine(fs, decim, a.block, device=a.device, flags=b.MFM_F_DEVICE_ONLY)
+    for freq, gain in chans:
+        eng.add_channel(freq - centre, taps, gain, want_iq=iq_form)
+    eng.commit()
+    lv = pkg.Level(len(chans), a.block // decim + 8, a.window, form=b.MFM_LEVEL_IQ if iq_form else b.MFM_LEVEL_PCM,
+                   metric=b.MFM_LEVEL_METRIC_DIFF if a.metric == "diff" else b.MFM_LEVEL_METRIC_ENERGY,
+                   sense=b.MFM_LEVEL_OPEN_ABOVE if sense == "above" else b.MFM_LEVEL_OPEN_BELOW,
+                   open_thr=a.open_thr, close_thr=a.close_thr if a.close_thr is not None else a.open_thr, hang_windows=a.hang,
+                   device=a.device)
+    fmt = {"cs16": b.MFM_IN_CS16, "cs8": b.MFM_IN_CS8, "cu8": b.MFM_IN_CU8}[a.format]
+    bytes_per_sample = 4 if a.format == "cs16" else 2
+    windows = np.zeros(len(chans), np.int64)
+    opened = np.zeros(len(chans), np.int64)
+    out = sys.stdout
+    with open(a.input, "rb") as f:
+        while True:
+            raw = f.read(a.block * bytes_per_sample)
+            n = len(raw) // bytes_per_sample
+            if n == 0:
+                break
+            data = np.frombuffer(raw[:n * bytes_per_sample], np.int16 if a.format == "cs16" else np.uint8)
+            rc = eng.push_bytes(data, fmt)
+            if rc < 0:
+                raise pkg.MfmError(rc, "mfm_engine_push_bytes", eng.lib.mfm_last_error().decode())
+            d_pcm, stride, nout, d_iq = eng.last_output_device()
+            if iq_form:
+                lv.process_device(d_iq, 2 * stride, nout, stream=eng.stream)
+            else:
+                lv.process_device(d_pcm, stride, nout, stream=eng.stream)
+            rec = lv.fetch()
+            for c, (freq, _) in enumerate(chans):
+                for r in rec[c]:
+                    out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
+                                          "diff_energy": int(r["diff_energy"]), "peak": int(r["peak"]), "open": int(r["open"])}) + "\n")
+            windows += rec.shape[1]
+            opened += rec["open"].sum(axis=1).astype(np.int64)
+    if a.summary:
+        for c, (freq, _) in enumerate(chans):
+            out.write(json.dumps({"summary": True, "freq": freq, "channel": c, "windows": int(windows[c]), "open_windows": int(opened[c]),
+                                  "open_share": (float(opened[c]) / float(windows[c])) if windows[c] else 0.0}) + "\n")
+    lv.close()
+    eng.close()
+
+
+def _stats(xs):
+    m = sum(xs) / len(xs)
+    sd = math.sqrt(sum((x - m) ** 2 for x in xs) / (len(xs) - 1)) if len(xs) > 1 else float("nan")
+    return m, sd
+
+
+def bench(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    b = pkg.binding
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench needs the GPU: there is no CPU path to time")
+    rt = C.CDLL("libamdhip64.so")
+    rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    nch, blk = a.bench_channels, 1 << 26
+    fs, decim, taps, offs, gains = pkg.synth.plan("cfg3_1024ch" if nch > 64 else "cfg2_64ch", nr_channels=nch)
+    iq_form = a.form == "iq"
+    src = torch.randint(-20000, 20000, (blk, 2), dtype=torch.int16, device="cuda")
+    engine_ms = {}
+    keep = None
+    for want_iq in (False, True):
+        eng = pkg.Engine(fs, decim, blk, device=0, flags=b.MFM_F_DEVICE_ONLY | b.MFM_F_TIMING)
+        for o, g in zip(offs, gains):
+            eng.add_channel(int(o), taps, float(g), want_iq=want_iq)
+        eng.commit()
+        for _ in range(2 + a.reps):
+            dst, cap = eng.acquire_input()
+            assert cap >= blk
+            assert rt.hipMemcpy(dst, src.data_ptr(), blk * 4, 3) == 0
+            torch.cuda.synchronize()
+            eng.submit(blk)
+            eng.sync()
+        engine_ms["iq" if want_iq else "pcm"] = _stats([float(x) for x in eng.launch_ms()[2:]])
+        if want_iq == iq_form:
+            keep = eng
+        else:
+            eng.close()
+    eng = keep
+    d_pcm, stride, nout, d_iq = eng.last_output_device()
+    lv = pkg.Level(nch, nout, a.window, form=b.MFM_LEVEL_IQ if iq_form else b.MFM_LEVEL_PCM, device=0)
+    pg = pkg.Pocsag(nch, nout, device=0)
+    rows, in_stride = (d_iq, 2 * stride) if iq_form else (d_pcm, stride)
+
+    def run_level():
+        lv.process_device(rows, in_stride, nout)
+
+    def run_pocsag():
+        pg.process_device(d_pcm, stride, nout)
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    variants = [("level", run_level), ("pocsag_call", run_pocsag)]
+    for _, fn in variants:
+        timed(fn, 3)
+    got = {n: [] for n, _ in variants}
+    for rep in range(a.reps):
+        order = variants[rep % 2:] + variants[:rep % 2]
+        for name, fn in order:
+            got[name].append(timed(fn, a.inner))
+    lm, lsd = _stats(got["level"])
+    pm, psd = _stats(got["pocsag_call"])
+    se = math.sqrt(lsd * lsd / a.reps + psd * psd / a.reps)
+    in_bytes = nch * nout * (4 if iq_form else 2)
+    out_bytes = nch * (nout // a.window) * 40
+    res = {"bench": "level_stage", "channels": nch, "form": a.form, "window": a.window, "outputs_per_channel": nout,
+           "reps": a.reps, "calls_per_rep": a.inner,
+           "level_ms": lm, "level_sd": lsd, "pocsag_call_ms": pm, "pocsag_call_sd": psd,
+           "level_minus_pocsag_call_in_se": (lm - pm) / se if se > 0 else None,
+           "bytes_read": in_bytes, "bytes_written": out_bytes, "level_fraction_of_hbm_peak": (in_bytes + out_bytes) / (lm * 1e-3) / HBM_PEAK_BPS,
+           "engine_launch_ms_pcm_only": engine_ms["pcm"][0], "engine_launch_sd_pcm_only": engine_ms["pcm"][1],
+           "engine_launch_ms_with_iq": engine_ms["iq"][0], "engine_launch_sd_with_iq": engine_ms["iq"][1]}
+    print(json.dumps(res))
+    for o in (lv, pg, eng):
+        o.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config")
+    ap.add_argument("--input")
+    ap.add_argument("--format", choices=["cs16", "cs8", "cu8"], default="cs16")
+    ap.add_argument("--form", choices=["pcm", "iq"], default="pcm")
+    ap.add_argument("--window", type=int, default=1000)
+    ap.add_argument("--metric", choices=["energy", "diff"], default="energy")
+    ap.add_argument("--sense", choices=["above", "below"], default=None)
+    ap.add_argument("--open-thr", type=int, default=0)
+    ap.add_argument("--close-thr", type=int, default=None)
+    ap.add_argument("--hang", type=int, default=0)
+    ap.add_argument("--block", type=int, default=1 << 20)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--summary", action="store_true")
+    ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--bench-channels", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=8)
+    ap.add_argument("--inner", type=int, default=10)
+    a = ap.parse_args()
+    if a.bench:
+        return bench(a)
+    if not a.config or not a.input:
+        ap.error("--config and --input are required (or --bench)")
+    scan(a)
+
+
+if __name__ == "__main__":
+    main()

@@ -59,6 +59,8 @@ ABI_SYMBOLS = [
     "mfm_ais_create", "mfm_ais_destroy", "mfm_ais_process_device", "mfm_ais_process_host", "mfm_ais_fetch_events",
     "mfm_resampler_process_bits_device", "mfm_resampler_process_bits_host_to_device", "mfm_resampler_process_bits_host",
     "mfm_pocsag_process_bits_device", "mfm_ais_process_bits_device", "mfm_hosttwin_splice_bits",
+    "mfm_level_create", "mfm_level_destroy", "mfm_level_process_device", "mfm_level_process_host", "mfm_level_fetch",
+    "mfm_level_device_view", "mfm_hosttwin_level_window", "mfm_hosttwin_squelch_step",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -150,6 +152,27 @@ class AisEvent(C.Structure):
 # numpy view of struct mfm_ais_event (192 bytes)
 AIS_EVENT_DTYPE = np.dtype([("channel", "<u4"), ("fcs_valid", "<u4"), ("nr_bytes", "<u4"), ("reserved", "<u4"),
                             ("sample", "<u8"), ("start_sample", "<u8"), ("bytes", "u1", (160,))])
+
+
+class LevelConfig(C.Structure):
+    """struct mfm_level_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32),
+                ("max_in_samples", C.c_uint32), ("form", C.c_uint32), ("window_samples", C.c_uint32),
+                ("metric", C.c_uint32), ("sense", C.c_uint32), ("open_thr", C.c_uint64), ("close_thr", C.c_uint64),
+                ("hang_windows", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LevelRecord(C.Structure):
+    _fields_ = [("energy", C.c_uint64), ("diff_energy", C.c_uint64), ("window", C.c_uint64), ("peak", C.c_uint32),
+                ("channel", C.c_uint32), ("open", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# numpy view of struct mfm_level_record (40 bytes)
+LEVEL_RECORD_DTYPE = np.dtype([("energy", "<u8"), ("diff_energy", "<u8"), ("window", "<u8"), ("peak", "<u4"),
+                               ("channel", "<u4"), ("open", "<u4"), ("reserved", "<u4")])
+MFM_LEVEL_PCM, MFM_LEVEL_IQ = 0, 1
+MFM_LEVEL_METRIC_ENERGY, MFM_LEVEL_METRIC_DIFF = 0, 1
+MFM_LEVEL_OPEN_ABOVE, MFM_LEVEL_OPEN_BELOW = 0, 1
 
 
 class FlexConfig(C.Structure):
@@ -351,6 +374,18 @@ def load_library():
         lib.mfm_ais_process_bits_device.argtypes = [vp, C.POINTER(BitsView), vp]
         lib.mfm_hosttwin_splice_bits.argtypes = [u32p, C.c_uint64, u32p, C.c_uint64]
         lib.mfm_hosttwin_splice_bits.restype = None
+    u64p = C.POINTER(C.c_uint64)
+    lib.mfm_level_create.argtypes = [C.POINTER(vp), C.POINTER(LevelConfig)]
+    lib.mfm_level_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_level_destroy.restype = None
+    lib.mfm_level_process_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.mfm_level_process_host.argtypes = [vp, i16p, C.c_size_t, C.c_size_t]
+    lib.mfm_level_fetch.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.mfm_level_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(vp)]
+    lib.mfm_hosttwin_level_window.argtypes = [i16p, C.c_size_t, C.c_uint32, C.c_int16, u64p, u64p, u32p]
+    lib.mfm_hosttwin_level_window.restype = None
+    lib.mfm_hosttwin_squelch_step.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, u32p, u32p]
+    lib.mfm_hosttwin_squelch_step.restype = C.c_uint32
     f32p = C.POINTER(C.c_float)
     lib.mfm_f32_create.argtypes = [C.POINTER(vp), C.POINTER(F32Config)]
     lib.mfm_f32_add_channel.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.c_size_t, C.c_double]
@@ -1032,6 +1067,95 @@ class Ais:
         if rc < 0:
             raise MfmError(rc, "mfm_ais_fetch_events", self.lib.mfm_strerror(rc).decode())
         return out[:n.value].copy()
+
+
+class Level:
+    """mfm_level: per-channel signal level (energy, wrapped-difference energy, peak) over windows of `window_samples`
+    samples and a squelch stepped once per window, for all channels of a block of PCM (form MFM_LEVEL_PCM) or filtered-IQ
+    (MFM_LEVEL_IQ) rows.  One record per channel and completed window (LEVEL_RECORD_DTYPE)."""
+
+    def __init__(self, nr_channels, max_in_samples, window_samples, form=MFM_LEVEL_PCM, metric=MFM_LEVEL_METRIC_ENERGY,
+                 sense=MFM_LEVEL_OPEN_ABOVE, open_thr=0, close_thr=0, hang_windows=0, device=0, abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        cfg = LevelConfig(abi_version, device, nr_channels, max_in_samples, form, window_samples, metric, sense,
+                          int(open_thr), int(close_thr), hang_windows, 0)
+        rc = self.lib.mfm_level_create(C.byref(self.h), C.byref(cfg))
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_create", (self.lib.mfm_last_error() if rc == MFM_E_INVAL else self.lib.mfm_strerror(rc)).decode())
+        self.nr_channels = nr_channels
+        self.elems = 2 if form == MFM_LEVEL_IQ else 1
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_level_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process_host(self, rows):
+        """rows: int16 [C][n] (PCM form) or [C][n][2] / [C][2 n] (IQ form); returns the records of this call, [C][windows]"""
+        a = np.ascontiguousarray(rows, dtype=np.int16).reshape(self.nr_channels, -1)
+        rc = self.lib.mfm_level_process_host(self.h, _i16p(a), a.shape[1], a.shape[1] // self.elems)
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_process_host", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+        return self.fetch()
+
+    def process_device(self, d_rows, in_stride, nr_in, stream=None):
+        """in_stride counts int16 elements in both forms (the engine's IQ rows: 2 * stride)"""
+        rc = self.lib.mfm_level_process_device(self.h, C.c_void_p(d_rows), in_stride, nr_in, C.c_void_p(stream or 0))
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_process_device", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+
+    def fetch(self, max_records=None):
+        """the last call's records as a structured array [C][windows]; with max_records too small: MfmError(MFM_E_NOMEM)
+        whose `needed` attribute is the record count that would fit"""
+        n = C.c_size_t()
+        if max_records is None:
+            rc = self.lib.mfm_level_fetch(self.h, None, 0, C.byref(n))
+            if rc not in (MFM_OK, MFM_E_NOMEM):
+                raise MfmError(rc, "mfm_level_fetch", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+            max_records = self.nr_channels * n.value
+        out = np.zeros(max(max_records, 1), LEVEL_RECORD_DTYPE)
+        rc = self.lib.mfm_level_fetch(self.h, out.ctypes.data, max_records, C.byref(n))
+        if rc < 0:
+            err = MfmError(rc, "mfm_level_fetch", self.lib.mfm_strerror(rc).decode())
+            err.needed = self.nr_channels * n.value
+            err.buffer = out
+            raise err
+        return out[:self.nr_channels * n.value].reshape(self.nr_channels, n.value).copy()
+
+    def device_view(self):
+        """(d_records, record_stride, nr_windows, d_open): device addresses of the last call's records and of the per-channel
+        squelch state (uint32 each)"""
+        rec, st, n, op = C.c_void_p(), C.c_size_t(), C.c_size_t(), C.c_void_p()
+        rc = self.lib.mfm_level_device_view(self.h, C.byref(rec), C.byref(st), C.byref(n), C.byref(op))
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_device_view", self.lib.mfm_strerror(rc).decode())
+        return rec.value, st.value, n.value, op.value
+
+
+def hosttwin_level_window(x, form=MFM_LEVEL_PCM, prev=0):
+    """mfm_hosttwin_level_window: (energy, diff_energy, peak) of one window; x int16 [n] (PCM) or [n][2] (IQ)"""
+    lib = load_library()
+    a = np.ascontiguousarray(x, dtype=np.int16).reshape(-1)
+    n = a.size // (2 if form == MFM_LEVEL_IQ else 1)
+    e, d, p = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    buf = a if a.size else np.zeros(1, np.int16)
+    lib.mfm_hosttwin_level_window(_i16p(buf), n, form, int(prev), C.byref(e), C.byref(d), C.byref(p))
+    return e.value, d.value, p.value
+
+
+def hosttwin_squelch_step(sense, open_thr, close_thr, hang_windows, metric, open_, bad):
+    """mfm_hosttwin_squelch_step: one window's step; returns the new (open, bad)"""
+    lib = load_library()
+    o, b = C.c_uint32(int(open_)), C.c_uint32(int(bad))
+    lib.mfm_hosttwin_squelch_step(sense, int(open_thr), int(close_thr), hang_windows, int(metric), C.byref(o), C.byref(b))
+    return o.value, b.value
 
 
 class Flex:
