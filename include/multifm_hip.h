@@ -530,6 +530,37 @@ int mfm_resampler_process_bits_host(struct mfm_resampler *r, const int16_t *pcm,
                                     uint32_t polarity, uint32_t *bits, size_t bits_stride_words, size_t *nr_bits);
 
 /*
+ * Which kernel a resampler runs.  mfm_resampler_create() picks between two forms - the matrix-core kernel with 1 to 4 k-steps
+ * and the v_dot2 kernel with a phase's coefficient pairs in registers (instances of 4, 8, ..., 32 pairs) or in LDS - from the
+ * ratio, the number of taps, their range and the flags alone (the rules are at the head of csrc/mfm_resampler.hip); all of them
+ * give the same bits.  The form is decided on the host, so it can be asked of a live object and of a configuration that has
+ * none (mfm_hosttwin_resampler_form, no device needed).
+ */
+#define MFM_RS_FB_NONE 0u      /* the matrix form runs */
+#define MFM_RS_FB_RATIO 1u     /* 16 D / I is not an integer */
+#define MFM_RS_FB_WINDOW 2u    /* the window of a block of 16 outputs is longer than 256 bytes of padded rows */
+#define MFM_RS_FB_BLOCK 3u     /* R = 16 D / I > 240 */
+#define MFM_RS_FB_TAP_RANGE 4u /* a tap beyond +-32639 does not split into two signed bytes */
+#define MFM_RS_FB_FORCED 5u    /* MFM_RS_FORCE_DOT2 */
+
+struct mfm_resampler_form {
+    uint32_t form;          /* 0 v_dot2, 1 matrix */
+    uint32_t fallback;      /* MFM_RS_FB_*: why the matrix form was not taken */
+    uint32_t reg_pairs;     /* v_dot2: the instance's coefficient pairs held in registers (4, 8, ..., 32), 0 = pairs in LDS; matrix: 0 */
+    uint32_t k_steps;       /* matrix: k-steps of 64 window bytes (1 .. 4); v_dot2: 0 */
+    uint32_t block_samples; /* matrix: R = 16 D / I, the samples a block of 16 outputs consumes; v_dot2: 0 */
+    uint32_t row_bytes;     /* matrix: R rounded up to a multiple of 16, a row of the LDS image; v_dot2: 0 */
+    uint32_t window_bytes;  /* matrix: bytes of padded rows the window of one block spans, a multiple of 64; v_dot2: 0 */
+    uint32_t lds_bytes;     /* dynamic LDS of the kernel that will launch */
+    uint32_t phase_len;     /* taps per phase, a multiple of 4 (filter/polyphase_fir.c:70-83) */
+    uint32_t max_out;       /* = mfm_resampler_max_out() */
+    int32_t dc_p;           /* the DC blocker's (1 - pole) in Q14 (filter/dc_blocker.h:56); 0 without dc_block */
+    uint32_t reserved;      /* 0 */
+};
+
+int mfm_resampler_get_form(const struct mfm_resampler *r, struct mfm_resampler_form *form);
+
+/*
  * ---- Pager stage: POCSAG slicer / sync / batch collection + BCH(31,21) -----
  * Replaces, for ALL channels at once and on PCM that is still in HBM (38 400 Hz, i.e. the resampler's output):
  *
@@ -965,6 +996,20 @@ void mfm_hosttwin_level_window(const int16_t *x, size_t nr_samples, uint32_t for
                                uint32_t *peak);
 uint32_t mfm_hosttwin_squelch_step(uint32_t sense, uint64_t open_thr, uint64_t close_thr, uint32_t hang_windows, uint64_t metric,
                                    uint32_t *open, uint32_t *bad);
+/* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
+ * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
+ * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB
+ * of LDS per workgroup. */
+int mfm_hosttwin_resampler_form(const struct mfm_resampler_config *cfg, const int16_t *coeffs, size_t nr_coeffs,
+                                struct mfm_resampler_form *form);
+/* One block of 16 outputs of the matrix form, evaluated on the CPU from the tables its kernel reads and indexed the way its
+ * lanes index them: the A fragments of G for the carried phase `phase` (< I) in the matrix instruction's lane order, the row
+ * constants, the input as two byte planes (x = 256 Xh + Xl + 128) in rows of R samples padded to row_bytes (the padding holds
+ * a non-zero filler: G must be zero over it), the sums ll + (md << 8) + (hh << 16) + krow wrapping in 32 bits, Q14 rounding.
+ * x[0] is the first sample of the block, samples from nr_x on count as 0.  A check of the tables and of the layout arithmetic,
+ * not of the instruction; MFM_E_INVAL where create would not choose the matrix form. */
+int mfm_hosttwin_resampler_matrix_block(const struct mfm_resampler_config *cfg, const int16_t *coeffs, size_t nr_coeffs,
+                                        uint32_t phase, const int16_t *x, size_t nr_x, int16_t y16[16]);
 
 #ifdef __cplusplus
 }

@@ -86,7 +86,9 @@ def test_gpu_resampler_matrix_form_wraps_like_the_reference(pkg, ora, interp, de
     """The matrix-core form (16 D / I integer) splits taps and samples into bytes; full-scale taps up to +-32639 and
     full-scale samples make the int32 sums wrap (filter/utils.c:94-103) - it must wrap identically, block after block,
     and give the same bits as the v_dot2 form (MFM_RS_FORCE_DOT2).  One tap beyond +-32639 (32767): the engine must
-    fall back to v_dot2 by itself."""
+    fall back to v_dot2 by itself - get_form says which form ran and why: matrix for 32639, v_dot2 "tap range" for 32767, v_dot2
+    "forced" with the flag."""
+    b = pkg.binding
     rng = np.random.RandomState(ntaps)
     nch, n = 4, 150000
     x = rng.randint(-32768, 32768, size=(nch, n)).astype(np.int16)
@@ -94,12 +96,16 @@ def test_gpu_resampler_matrix_form_wraps_like_the_reference(pkg, ora, interp, de
     x[2] = -32768
     for big in (32639, 32767):
         taps = rng.randint(-32639, 32640, size=ntaps).astype(np.int16)
-        taps[rng.randint(ntaps)] = big
-        taps[rng.randint(ntaps)] = -32639
+        at_big, at_low = rng.choice(ntaps, size=2, replace=False)   # two places: the second must not overwrite the first
+        taps[at_big] = big
+        taps[at_low] = -32639
         refs = [ora.Resampler(taps, interp, decim) for _ in range(nch)]
         want = np.stack([r.feed(x[c]) for c, r in enumerate(refs)])
         for force in (False, True):
             gpu = pkg.Resampler(nch, taps, interp, decim, 65536, device=0, force_dot2=force)
+            form = gpu.form()
+            want_form = (0, b.MFM_RS_FB_FORCED) if force else (1, b.MFM_RS_FB_NONE) if big == 32639 else (0, b.MFM_RS_FB_TAP_RANGE)
+            assert (form["form"], form["fallback"]) == want_form, f"big={big} force_dot2={force}: {form}"
             got, pos = [], 0
             for m in (65536, 3, 40001, 65536):
                 got.append(gpu.process_host(x[:, pos:pos + m]))

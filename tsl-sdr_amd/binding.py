@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "mfm_pocsag_process_bits_device", "mfm_ais_process_bits_device", "mfm_hosttwin_splice_bits",
     "mfm_level_create", "mfm_level_destroy", "mfm_level_process_device", "mfm_level_process_host", "mfm_level_fetch",
     "mfm_level_device_view", "mfm_hosttwin_level_window", "mfm_hosttwin_squelch_step",
+    "mfm_resampler_get_form", "mfm_hosttwin_resampler_form", "mfm_hosttwin_resampler_matrix_block",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -198,6 +199,18 @@ class ResamplerConfig(C.Structure):
 
 
 MFM_RS_FORCE_DOT2 = 1
+# mfm_resampler_form.fallback: why the matrix form was not taken
+MFM_RS_FB_NONE, MFM_RS_FB_RATIO, MFM_RS_FB_WINDOW, MFM_RS_FB_BLOCK, MFM_RS_FB_TAP_RANGE, MFM_RS_FB_FORCED = 0, 1, 2, 3, 4, 5
+
+
+class ResamplerForm(C.Structure):
+    """struct mfm_resampler_form: the kernel a resampler runs (form 0 v_dot2, 1 matrix) and its geometry"""
+    _fields_ = [("form", C.c_uint32), ("fallback", C.c_uint32), ("reg_pairs", C.c_uint32), ("k_steps", C.c_uint32),
+                ("block_samples", C.c_uint32), ("row_bytes", C.c_uint32), ("window_bytes", C.c_uint32), ("lds_bytes", C.c_uint32),
+                ("phase_len", C.c_uint32), ("max_out", C.c_uint32), ("dc_p", C.c_int32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class BitsView(C.Structure):
@@ -386,6 +399,9 @@ def load_library():
     lib.mfm_hosttwin_level_window.restype = None
     lib.mfm_hosttwin_squelch_step.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, u32p, u32p]
     lib.mfm_hosttwin_squelch_step.restype = C.c_uint32
+    lib.mfm_resampler_get_form.argtypes = [vp, C.POINTER(ResamplerForm)]
+    lib.mfm_hosttwin_resampler_form.argtypes = [C.POINTER(ResamplerConfig), i16p, C.c_size_t, C.POINTER(ResamplerForm)]
+    lib.mfm_hosttwin_resampler_matrix_block.argtypes = [C.POINTER(ResamplerConfig), i16p, C.c_size_t, C.c_uint32, i16p, C.c_size_t, i16p]
     f32p = C.POINTER(C.c_float)
     lib.mfm_f32_create.argtypes = [C.POINTER(vp), C.POINTER(F32Config)]
     lib.mfm_f32_add_channel.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.c_size_t, C.c_double]
@@ -799,6 +815,14 @@ class Resampler:
 
     def max_out(self):
         return self.lib.mfm_resampler_max_out(self.h)
+
+    def form(self):
+        """mfm_resampler_get_form as a dict: the kernel this resampler runs"""
+        f = ResamplerForm()
+        rc = self.lib.mfm_resampler_get_form(self.h, C.byref(f))
+        if rc < 0:
+            raise MfmError(rc, "mfm_resampler_get_form", self.lib.mfm_strerror(rc).decode())
+        return f.as_dict()
 
     def process_host(self, pcm):
         """pcm: int16 [C][n] -> int16 [C][m]"""
@@ -1229,6 +1253,38 @@ def hosttwin_splice_bits(window, off0, src, nr_bits):
     u32p = C.POINTER(C.c_uint32)
     lib.mfm_hosttwin_splice_bits(w.ctypes.data_as(u32p), int(off0), sw.ctypes.data_as(u32p), int(nr_bits))
     return w
+
+
+def _resampler_config(coeffs_q14, interpolate, decimate, max_in_samples, nr_channels, invert, dc_pole, force_dot2):
+    cfg = ResamplerConfig(MFM_ABI_VERSION, 0, nr_channels, interpolate, decimate, max_in_samples, int(invert),
+                          int(dc_pole is not None), float(dc_pole or 0.0), MFM_RS_FORCE_DOT2 if force_dot2 else 0, 0)
+    return cfg, np.ascontiguousarray(coeffs_q14, dtype=np.int16)
+
+
+def hosttwin_resampler_form(coeffs_q14, interpolate, decimate, max_in_samples, nr_channels=1, invert=False, dc_pole=None,
+                            force_dot2=False):
+    """mfm_hosttwin_resampler_form as a dict: the form Resampler(...) would run, planned without a device; MfmError(MFM_E_INVAL)
+    for what create refuses"""
+    lib = load_library()
+    cfg, co = _resampler_config(coeffs_q14, interpolate, decimate, max_in_samples, nr_channels, invert, dc_pole, force_dot2)
+    f = ResamplerForm()
+    rc = lib.mfm_hosttwin_resampler_form(C.byref(cfg), _i16p(co), co.size, C.byref(f))
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_resampler_form", lib.mfm_last_error().decode() or lib.mfm_strerror(rc).decode())
+    return f.as_dict()
+
+
+def hosttwin_resampler_matrix_block(coeffs_q14, interpolate, decimate, phase, x):
+    """mfm_hosttwin_resampler_matrix_block: the 16 outputs of one block of the matrix form at carried phase `phase`, from the
+    tables its kernel reads; x int16, x[0] the block's first sample"""
+    lib = load_library()
+    cfg, co = _resampler_config(coeffs_q14, interpolate, decimate, 1024, 1, False, None, False)
+    xs = np.ascontiguousarray(x, dtype=np.int16)
+    y = np.zeros(16, np.int16)
+    rc = lib.mfm_hosttwin_resampler_matrix_block(C.byref(cfg), _i16p(co), co.size, int(phase), _i16p(xs), xs.size, _i16p(y))
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_resampler_matrix_block", lib.mfm_strerror(rc).decode())
+    return y
 
 
 def hosttwin_bch3121_decode(word):

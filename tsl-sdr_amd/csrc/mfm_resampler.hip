@@ -36,6 +36,30 @@
  *   group g, i.e. bits 16 (n & 1) + 4 kg of word n / 2 of that run.  The four groups' nibbles are merged over kg with a
  *   reduce-scatter (lane bits 5 and 4: three cross-lane moves for the four groups, after which lane (kg, n) holds group
  *   g = kg) and over n & 1 with one more; the even lanes then hold the wave's 32 words in order: one 128-byte store per wave.
+ *
+ * Which kernel runs: decided by rs_plan() (mfm_rs_plan.h) on the host, before the first HIP call, from I, D, the taps and
+ * the flags alone; mfm_resampler_get_form() reports it and tests/test_resampler_forms.py pins it.  The rules, in the order the
+ * planner applies them:
+ *   [plen]   phase length = ceil(taps / I), rounded up to a multiple of 4 (filter/polyphase_fir.c:70-83)
+ *   [walk]   refused (MFM_E_INVAL): ceil(D / I) > plen - an output would consume more samples than a phase holds
+ *   [range]  refused: max_out * D >= 2^32 - the phase walk of a call is 32-bit arithmetic in the kernels
+ *   [lds]    LDS of a v_dot2 workgroup = 2 I plen (coefficient pairs) + 2 (floor(1024 D / I) + plen + 32) (the window of 1024
+ *            outputs) bytes, rounded up to 16; refused above 150 KB, whichever form would run
+ *   [np]     v_dot2 instance: the coefficient pairs in registers when 256 D % I == 0 (a thread's four outputs share a phase),
+ *            plen / 2 <= 32 and that LDS is at most 48 KB - NP = plen / 2 rounded up to 4, one of 4, 8, ..., 32; else NP = 0, pairs
+ *            read from LDS.  Above 48 KB create raises the NP = 0 kernels' dynamic LDS limit
+ *            (hipFuncAttributeMaxDynamicSharedMemorySize)
+ *   [matrix] the matrix form unless, first reason that applies (mfm_resampler_form::fallback):
+ *              forced     MFM_RS_FORCE_DOT2
+ *              ratio      16 D / I is not an integer
+ *              block      R = 16 D / I > 240
+ *              window     K > 256, where K = (last / R) rp + last % R + 1 rounded up to 64 is the length in bytes of a block's
+ *                         window in rows of R samples padded to rp = R rounded up to 16, last = floor((I - 1 + 15 D) / I) + plen - 1
+ *              tap range  a tap beyond +-32639 (does not split into two signed bytes)
+ *            with KS = K / 64 k-steps (1 .. 4) and 2 planes of (256 + ceil(K / rp)) rp bytes of LDS, each rounded up to 64: up to
+ *            123 904 bytes (1/15).  Observed on an MI355X with this runtime (HIP 7.2): launches of this kernel with 66 048, 82 560
+ *            and 123 904 bytes of dynamic LDS are accepted and bit-exact without raising its limit first, so create does not
+ *            raise it
  */
 #include <hip/hip_runtime.h>
 
@@ -48,6 +72,7 @@
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_numerics.h"
+#include "mfm_rs_plan.h"
 
 namespace {
 
@@ -72,9 +97,6 @@ __device__ __forceinline__ bool rs_pred(int32_t y)
     const int16_t s = (int16_t)y;
     return BITS == (int)MFM_BITS_NEG ? s < 0 : s > 0;
 }
-
-constexpr uint32_t RS_NT = 256, RS_OPT = 4, RS_OPB = RS_NT * RS_OPT; /* threads, outputs per thread / per block */
-constexpr uint32_t RS_PAIRS_MAX = 32;                                /* register-resident phase: up to 64 taps */
 
 /* sample v of channel c in the virtual stream "tail, then the new samples"; decoder -i negates on int16 storage */
 __device__ __forceinline__ int16_t rs_sample(const RsLaunch &L, uint32_t c, uint32_t v)
@@ -202,9 +224,6 @@ struct RsMLaunch {
     uint32_t rp;         /* bytes per row in LDS: R rounded up to a multiple of 16 */
     uint32_t plane;      /* bytes per byte plane in LDS */
 };
-
-constexpr uint32_t RSM_NT = 256;  /* threads per workgroup (4 waves) */
-constexpr uint32_t RSM_NB = 256;  /* blocks of 16 outputs per workgroup: each wave does four column groups of 16 blocks */
 
 struct __attribute__((packed, aligned(2))) RsPcm8 {
     int16_t v[8];
@@ -436,6 +455,7 @@ thread_local char g_rs_error[256] = "";
 
 struct mfm_resampler {
     mfm_resampler_config cfg{};
+    RsPlan plan; /* what create() decided (mfm_rs_plan.h); the fields below that repeat it are what the launches read */
     uint32_t plen = 0;
     uint32_t in_cap = 0, out_cap = 0;
     int16_t *d_phase = nullptr;
@@ -478,8 +498,7 @@ int mfm_resampler_create(struct mfm_resampler **pr, const struct mfm_resampler_c
         return MFM_E_INVAL;
     }
     *pr = nullptr;
-    if (cfg->abi_version != MFM_ABI_VERSION || 0 == cfg->interpolate || 0 == cfg->decimate || 0 == cfg->nr_channels ||
-        0 == cfg->max_in_samples) {
+    if (!rs_args_ok(*cfg, nr_coeffs)) {
         return MFM_E_INVAL;
     }
     int ndev = 0;
@@ -491,53 +510,41 @@ int mfm_resampler_create(struct mfm_resampler **pr, const struct mfm_resampler_c
         return MFM_E_NOMEM;
     }
     r->cfg = *cfg;
-    /* filter/polyphase_fir.c:70-83 */
-    uint32_t plen = (uint32_t)((nr_coeffs + cfg->interpolate - 1) / cfg->interpolate);
-    plen = (plen + 3u) & ~3u;
-    r->plen = plen;
-    /* the walk must not step past the samples it has (one output consumes at most ceil(D/I) samples) */
-    if ((cfg->decimate + cfg->interpolate - 1) / cfg->interpolate > plen) {
+    /* everything that is decided is decided here, on the host (mfm_rs_plan.h) ... */
+    RsPlan &p = r->plan;
+    const int rc = rs_plan(*cfg, coeffs, nr_coeffs, p);
+    if (rc != MFM_OK) {
+        if (p.err[0]) {
+            mfm_internal_set_error(p.err);
+        }
         delete r;
-        return MFM_E_INVAL;
+        return rc;
     }
-    std::vector<int16_t> ph((size_t)cfg->interpolate * plen, 0);
-    for (size_t i = 0; i < nr_coeffs; i++) {
-        ph[(i % cfg->interpolate) * plen + (i / cfg->interpolate)] = coeffs[i];
-    }
-    r->in_cap = cfg->max_in_samples + plen + 64;
-    r->out_cap = (uint32_t)(((uint64_t)r->in_cap * cfg->interpolate) / cfg->decimate + 8);
-    r->out_cap = (r->out_cap + 7u) & ~7u; /* rows of the output start 16-byte aligned (the matrix-core form stores four outputs at
-                                           * once, the DC blocker reads and writes eight) */
-    if ((uint64_t)r->out_cap * cfg->decimate >= (1ull << 32)) {
-        delete r;
-        return MFM_E_INVAL;
-    }
-    if (cfg->dc_block) {
-        r->dc_p = (int16_t)((1.0 - cfg->dc_pole) * 16384.0); /* filter/dc_blocker.h:56 */
-    }
+    RsTables t;
+    rs_build_tables(p, coeffs, t);
+    r->plen = p.plen;
+    r->in_cap = p.in_cap;
+    r->out_cap = p.out_cap;
+    r->tail_cap = p.tail_cap;
+    r->dc_p = p.dc_p;
+    r->lds_bytes = p.lds_bytes;
+    r->reg_coef = p.reg_coef;
+    r->use_mfma = p.use_mfma;
+    r->m_ks = p.ks;
+    r->m_R = p.R;
+    r->m_rp = p.rp;
+    r->m_plane = p.m_plane;
+    r->m_lds = p.m_lds;
+    /* ... what follows allocates and uploads */
     *pr = r;
     RS_TRY(hipSetDevice(cfg->device));
-    RS_TRY(hipMalloc(&r->d_phase, ph.size() * 2));
-    RS_TRY(hipMemcpy(r->d_phase, ph.data(), ph.size() * 2, hipMemcpyHostToDevice));
-    r->tail_cap = plen + 8; /* never more than plen samples are left over (see process_device) */
+    RS_TRY(hipMalloc(&r->d_phase, t.phase.size() * 2));
+    RS_TRY(hipMemcpy(r->d_phase, t.phase.data(), t.phase.size() * 2, hipMemcpyHostToDevice));
     for (int i = 0; i < 2; i++) {
         RS_TRY(hipMalloc(&r->d_x[i], (size_t)cfg->nr_channels * r->tail_cap * 2));
         RS_TRY(hipMemset(r->d_x[i], 0, (size_t)cfg->nr_channels * r->tail_cap * 2));
     }
-    /* LDS of a workgroup: coefficient pairs + the input window of RS_OPB outputs */
-    r->lds_bytes = (uint32_t)((size_t)cfg->interpolate * plen * 2 +
-                              (((uint64_t)RS_OPB * cfg->decimate) / cfg->interpolate + plen + 32) * 2);
-    r->lds_bytes = (r->lds_bytes + 15u) & ~15u;
-    if (r->lds_bytes > 150u * 1024u) {
-        snprintf(g_rs_error, sizeof(g_rs_error), "resampling ratio %u/%u with %u taps per phase needs %u bytes of LDS per workgroup",
-                 cfg->interpolate, cfg->decimate, plen, r->lds_bytes);
-        mfm_internal_set_error(g_rs_error);
-        return MFM_E_INVAL;
-    }
-    r->reg_coef = ((uint64_t)RS_NT * cfg->decimate) % cfg->interpolate == 0 && plen / 2 <= RS_PAIRS_MAX;
-    if (r->lds_bytes > 48u * 1024u) {
-        /* only extreme decimation ratios get here: they use the LDS-coefficient variant */
-        r->reg_coef = false;
+    if (!p.use_mfma && p.lds_bytes > RS_LDS_DEFAULT) {
         RS_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfm_resample_kernel<0, 0>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
         RS_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfm_resample_kernel<0, (int)MFM_BITS_NEG>),
@@ -545,63 +552,11 @@ int mfm_resampler_create(struct mfm_resampler **pr, const struct mfm_resampler_c
         RS_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfm_resample_kernel<0, (int)MFM_BITS_POS>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->lds_bytes));
     }
-    /* ---- matrix-core form: y[16 m + q] = sum_s G[q][s] x[R m + s], one G per carried phase (see the head of the file) ---- */
-    {
-        const uint32_t I = cfg->interpolate, D = cfg->decimate;
-        bool ok = (16u * D) % I == 0u && !(cfg->flags & MFM_RS_FORCE_DOT2);
-        const uint32_t R = ok ? 16u * D / I : 0u;
-        const uint32_t rp = (R + 15u) & ~15u;
-        /* output q of a block starts its window floor((phi + q D) / I) samples into the block, phi < I */
-        const uint32_t max_off = (I - 1u + 15u * D) / I;
-        uint32_t K = 0;
-        if (ok) {
-            const uint32_t last = max_off + plen - 1u;                  /* last sample index (from the block's first) with a coefficient */
-            K = (last / R) * rp + last % R + 1u;                        /* its byte position in the padded rows, + 1 */
-            K = (K + 63u) & ~63u;
-            ok = K <= 256u && R <= 240u;
-        }
-        for (size_t i = 0; ok && i < ph.size(); i++) {
-            ok = ph[i] >= -32639 && ph[i] <= 32639;                     /* W = 256 Wh + Wl with both in [-128, 127] */
-        }
-        if (ok) {
-            const uint32_t KS = K / 64u;
-            std::vector<int8_t> frag((size_t)I * 2u * KS * 64u * 16u, 0);
-            std::vector<int32_t> krow((size_t)I * 16u, 0);
-            for (uint32_t phi = 0; phi < I; phi++) {
-                for (uint32_t q = 0; q < 16; q++) {
-                    const uint32_t t = phi + q * D, off = t / I, phq = t % I;
-                    uint32_t sum = 0;
-                    for (uint32_t kk = 0; kk < K; kk++) {
-                        const uint32_t row = kk / rp, col = kk % rp;
-                        int32_t w = 0;
-                        if (col < R) {
-                            const int64_t tap = (int64_t)(row * R + col) - (int64_t)off;
-                            if (tap >= 0 && tap < (int64_t)plen) {
-                                w = ph[(size_t)phq * plen + (size_t)tap];
-                            }
-                        }
-                        sum += (uint32_t)w;
-                        const int32_t wl = (int8_t)(w & 0xff), wh = (w - wl) >> 8;
-                        /* v_mfma_i32_16x16x64_i8 A operand: lane (kg = lane >> 4, i = lane & 15) holds row i, elements 64 ks + 16 kg + j */
-                        const uint32_t ks = kk / 64u, kgq = (kk % 64u) / 16u, j = kk % 16u, ln = kgq * 16u + q;
-                        frag[((((size_t)phi * 2u + 0u) * KS + ks) * 64u + ln) * 16u + j] = (int8_t)wh;
-                        frag[((((size_t)phi * 2u + 1u) * KS + ks) * 64u + ln) * 16u + j] = (int8_t)wl;
-                    }
-                    krow[(size_t)phi * 16u + q] = (int32_t)(128u * sum);
-                }
-            }
-            r->use_mfma = true;
-            r->m_ks = KS;
-            r->m_R = R;
-            r->m_rp = rp;
-            const uint32_t nrows = RSM_NB + (K + rp - 1u) / rp;
-            r->m_plane = (nrows * rp + 63u) & ~63u;
-            r->m_lds = 2u * r->m_plane;
-            RS_TRY(hipMalloc(&r->d_gfrag, frag.size()));
-            RS_TRY(hipMemcpy(r->d_gfrag, frag.data(), frag.size(), hipMemcpyHostToDevice));
-            RS_TRY(hipMalloc(&r->d_krow, krow.size() * 4));
-            RS_TRY(hipMemcpy(r->d_krow, krow.data(), krow.size() * 4, hipMemcpyHostToDevice));
-        }
+    if (p.use_mfma) {
+        RS_TRY(hipMalloc(&r->d_gfrag, t.frag.size()));
+        RS_TRY(hipMemcpy(r->d_gfrag, t.frag.data(), t.frag.size(), hipMemcpyHostToDevice));
+        RS_TRY(hipMalloc(&r->d_krow, t.krow.size() * 4));
+        RS_TRY(hipMemcpy(r->d_krow, t.krow.data(), t.krow.size() * 4, hipMemcpyHostToDevice));
     }
     RS_TRY(hipMalloc(&r->d_y, (size_t)cfg->nr_channels * r->out_cap * 2));
     RS_TRY(hipMalloc(&r->d_dc, (size_t)cfg->nr_channels * sizeof(DcState)));
@@ -634,6 +589,80 @@ void mfm_resampler_destroy(struct mfm_resampler **pr)
 size_t mfm_resampler_max_out(const struct mfm_resampler *r)
 {
     return r ? r->out_cap : 0;
+}
+
+int mfm_resampler_get_form(const struct mfm_resampler *r, struct mfm_resampler_form *form)
+{
+    if (!r || !form) {
+        return MFM_E_INVAL;
+    }
+    rs_plan_form(r->plan, form);
+    return MFM_OK;
+}
+
+int mfm_hosttwin_resampler_form(const struct mfm_resampler_config *cfg, const int16_t *coeffs, size_t nr_coeffs,
+                                struct mfm_resampler_form *form)
+{
+    if (!cfg || !coeffs || !form) {
+        return MFM_E_INVAL;
+    }
+    RsPlan p;
+    const int rc = rs_plan(*cfg, coeffs, nr_coeffs, p);
+    if (rc != MFM_OK) {
+        mfm_internal_set_error(p.err[0] ? p.err : "invalid resampler configuration");
+        return rc;
+    }
+    rs_plan_form(p, form);
+    return MFM_OK;
+}
+
+int mfm_hosttwin_resampler_matrix_block(const struct mfm_resampler_config *cfg, const int16_t *coeffs, size_t nr_coeffs,
+                                        uint32_t phase, const int16_t *x, size_t nr_x, int16_t y16[16])
+{
+    if (!cfg || !coeffs || (!x && nr_x) || !y16) {
+        return MFM_E_INVAL;
+    }
+    RsPlan p;
+    const int rc = rs_plan(*cfg, coeffs, nr_coeffs, p);
+    if (rc != MFM_OK || !p.use_mfma || phase >= p.I) {
+        return MFM_E_INVAL;
+    }
+    RsTables t;
+    rs_build_tables(p, coeffs, t);
+    /* the LDS image of one block's window: K bytes of rows of R samples padded to rp, as the staging loop of
+     * mfm_resample_mfma_kernel leaves them (Xl = (x & 255) - 128, Xh = x >> 8); nothing defined is in the padding */
+    std::vector<int8_t> pl_h(p.K, 0x55), pl_l(p.K, 0x55);
+    for (uint32_t kk = 0; kk < p.K; kk++) {
+        const uint32_t row = kk / p.rp, col = kk % p.rp;
+        if (col < p.R) {
+            const size_t v = (size_t)row * p.R + col;
+            const int32_t s = v < nr_x ? x[v] : 0;
+            pl_l[kk] = (int8_t)((s & 0xff) ^ 0x80);
+            pl_h[kk] = (int8_t)(s >> 8);
+        }
+    }
+    /* lane (kg, n) of the kernel: column n is this block; its A fragment is row i = lane & 15 of G, its results rows 4 kg .. 4 kg + 3.
+     * Row q of the product sums, per k-step, the 16 elements of each of the four lanes (kgq, q) against bytes 64 ks + 16 kgq + j. */
+    const int8_t *a_h = t.frag.data() + ((size_t)phase * 2u + 0u) * p.ks * 64u * 16u;
+    const int8_t *a_l = t.frag.data() + ((size_t)phase * 2u + 1u) * p.ks * 64u * 16u;
+    for (uint32_t q = 0; q < 16; q++) {
+        uint32_t hh = 0, md = 0, ll = 0;
+        for (uint32_t ks = 0; ks < p.ks; ks++) {
+            for (uint32_t kgq = 0; kgq < 4; kgq++) {
+                const size_t fa = ((size_t)ks * 64u + kgq * 16u + q) * 16u;
+                const uint32_t off = 16u * kgq + 64u * ks;
+                for (uint32_t j = 0; j < 16; j++) {
+                    const int32_t ah = a_h[fa + j], al = a_l[fa + j], bh = pl_h[off + j], bl = pl_l[off + j];
+                    hh += (uint32_t)(ah * bh);
+                    md += (uint32_t)(ah * bl) + (uint32_t)(al * bh);
+                    ll += (uint32_t)(al * bl);
+                }
+            }
+        }
+        const uint32_t acc = ll + (md << 8) + (hh << 16) + (uint32_t)t.krow[(size_t)phase * 16u + q];
+        y16[q] = (int16_t)mfm_r14_wide((int32_t)acc); /* utils.c:112 */
+    }
+    return MFM_OK;
 }
 
 } /* extern "C" */
