@@ -860,6 +860,79 @@ int mfm_level_device_view(struct mfm_level *p, const struct mfm_level_record **d
                           const uint32_t **d_open);
 
 /*
+ * ---- Gate stage: only open windows of a channel leave the GPU -------------------------------------------------------
+ * The consumer of the level stage's verdict: of rows that are still in HBM it packs the windows whose record says
+ * `open` into one dense payload, with a run list that says which channel and which samples each piece is.  One short
+ * device-to-host copy (mfm_gate_fetch) or a consumer on the device (mfm_gate_device_view) then carries what is worth
+ * carrying.  The reference has no counterpart.
+ *
+ * Samples are numbered per channel from 0 at create and window k is [k W, (k + 1) W): the level stage's numbers.  A call
+ * with nr_in samples completes floor((pos + nr_in) / W) - floor(pos / W) windows, so the gate is fed the same nr_in
+ * sequence as the level object whose records it reads; the rows may be others than those the level was measured on
+ * (squelch on the IQ energy, gate the PCM) as long as the numbering matches.  The samples of an unfinished window are
+ * carried on the device, at most W - 1 per channel: output does not depend on how a stream is cut into calls (nr_in = 0
+ * and several calls in a row shorter than W included).  Create refuses W * elems_per_sample above 2^20 (the carry buffer
+ * is one window of int16 per channel) with MFM_E_INVAL and a message.
+ *
+ * Window k of channel c goes out exactly when the record of (c, k) has open != 0: the opening window is among them (the
+ * squelch is stepped after it), the tail is what hang_windows gives; no closed window in front of an opening is emitted.
+ * The payload is dense: channels ascending, windows ascending within a channel, each W * elems_per_sample int16, so
+ * consecutive open windows of one channel are contiguous.  Each maximal stretch of consecutive open windows WITHIN ONE
+ * CALL is one mfm_gate_run; a stretch that goes on into the next call begins a new run there (first_window of the one
+ * follows the last window of the other).  Runs stand in payload order.  Order and offsets are deterministic.
+ */
+struct mfm_gate_run {           /* 24 bytes */
+    uint64_t first_window;      /* k of the run's first window; its first sample is k * W */
+    uint64_t payload_offset;    /* in int16 elements, a multiple of W * elems_per_sample */
+    uint32_t channel;
+    uint32_t nr_windows;
+};
+
+struct mfm_gate; /* opaque */
+
+struct mfm_gate_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;       /* 1 .. 65535 */
+    uint32_t max_in_samples;    /* most samples per channel one process call may carry (<= 2^28) */
+    uint32_t window_samples;    /* W, the level stage's W */
+    uint32_t elems_per_sample;  /* 1: PCM rows, 2: filtered-IQ rows (re, im interleaved) */
+    uint32_t max_open_windows;  /* payload capacity per call over all channels, in windows;
+                                   0 = nr_channels * (max_in_samples / W + 1), which cannot overflow */
+    uint32_t flags;             /* 0 */
+};
+
+int mfm_gate_create(struct mfm_gate **pg, const struct mfm_gate_config *cfg);
+void mfm_gate_destroy(struct mfm_gate **pg);
+/*
+ * Consume nr_in samples per channel from device memory laid out [channel][in_stride] (in_stride in int16 ELEMENTS, as in
+ * the level stage; any 2-byte alignment of rows and stride).  d_records, record_stride and nr_windows are what
+ * mfm_level_device_view() returns for the level call on the same block; only .open and .window are read.  nr_windows
+ * other than what this call completes is MFM_E_INVAL (nothing is queued, the position stays).  Work is queued on
+ * `stream`; no host synchronisation; rows and records are read until the queued work has run.  Runs and payload of THIS
+ * call replace those of the previous one.  A record whose .window is not the k the gate expects raises a flag on the
+ * device that mfm_gate_fetch reports.
+ */
+int mfm_gate_process_device(struct mfm_gate *g, const int16_t *d_rows, size_t in_stride, size_t nr_in, const struct mfm_level_record *d_records,
+                            size_t record_stride, size_t nr_windows, void *stream);
+/* Host convenience: the same from host memory (rows [channel][in_stride], records [channel][record_stride]), synchronous. */
+int mfm_gate_process_host(struct mfm_gate *g, const int16_t *rows, size_t in_stride, size_t nr_in, const struct mfm_level_record *records,
+                          size_t record_stride, size_t nr_windows);
+/*
+ * Wait for the last process call, read its two totals into *nr_runs and *nr_elems and copy the used part of both arrays.
+ * MFM_E_NOMEM when max_runs or max_elems is too small (nothing copied, the totals say what is needed); MFM_E_STATE when
+ * the call's open windows exceeded a caller-chosen max_open_windows (nothing copied, nothing was written past the
+ * capacity; the stream position and the carry moved on, so a following call that fits is right again) or when level and
+ * gate were out of step.
+ */
+int mfm_gate_fetch(struct mfm_gate *g, struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                   size_t *nr_elems);
+/* For consumers that stay on the device: the last call's runs, payload and d_totals[4] = { runs, payload elements,
+ * overflow (0 / 1), out of step (0 / 1) }, written by work queued on that call's stream and valid until the next call.
+ * Any of the three may be NULL. */
+int mfm_gate_device_view(struct mfm_gate *g, const struct mfm_gate_run **d_runs, const int16_t **d_payload, const uint64_t **d_totals);
+
+/*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
  *   mm_init      pager/mueller_muller.c:10-33
  *   mm_process   pager/mueller_muller.c:41-115
@@ -996,6 +1069,15 @@ void mfm_hosttwin_level_window(const int16_t *x, size_t nr_samples, uint32_t for
                                uint32_t *peak);
 uint32_t mfm_hosttwin_squelch_step(uint32_t sense, uint64_t open_thr, uint64_t close_thr, uint32_t hang_windows, uint64_t metric,
                                    uint32_t *open, uint32_t *bad);
+/* host twin of one call of the gate stage (csrc/mfm_gate.h, the arithmetic its kernels run: the window cut of a call, run
+ * formation, offsets), on the CPU with no device: pos = samples per channel consumed before the call, rows [channel][in_stride],
+ * carry [channel][W * elems_per_sample] read and then updated, records [channel][record_stride].  0 with runs and payload filled;
+ * MFM_E_INVAL for a wrong nr_windows, MFM_E_STATE for a record with a wrong .window, MFM_E_NOMEM when max_runs or max_elems is
+ * too small (*nr_runs and *nr_elems say what is needed); on any error nothing is written, the carry included. */
+int mfm_hosttwin_gate_call(uint32_t nr_channels, uint32_t window_samples, uint32_t elems_per_sample, uint64_t pos, const int16_t *rows,
+                           size_t in_stride, size_t nr_in, int16_t *carry, const struct mfm_level_record *records, size_t record_stride,
+                           size_t nr_windows, struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                           size_t *nr_elems);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

@@ -3,7 +3,7 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
-           [--block 1048576] [--summary]
+           [--block 1048576] [--summary] [--gate-out DIR]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -14,13 +14,23 @@ lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per
 --form iq on the filtered IQ (a carrier RAISES it: default sense above).  --summary adds one line per channel with the
 share of windows it was open.  The thresholds default to 0: read the levels off a first run, then set them.
 
+--gate-out DIR queues the gate stage behind the level stage on the engine's stream, on the rows the scan runs on (PCM, or
+IQ with --form iq): only the windows the squelch left open leave the device.  Per channel that ever opened DIR/chNNNN.s16
+gets the gated samples, and DIR/index.jsonl one line per run:
+
+    {"channel": 3, "first_sample": 4000, "nr_samples": 2000, "file_offset": 0}
+
+(first_sample and nr_samples in samples of the channel, file_offset in bytes of its file).  What goes to stdout does not change.
+
     python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8]
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
 against the POCSAG stage's call on the same rows (idle input; its slicer, pg_slice_kernel, reads the same bytes) and
 against the engine launch with and without filtered IQ.  Level pass and comparison alternate in one process, in
 rotating order; mean and standard deviation over --reps repetitions, a difference counts beyond two standard errors
-(the rule of tools/exp/ab.py).  One JSON line."""
+(the rule of tools/exp/ab.py).  One JSON line.  A second line times the gate stage on the same rows (whole windows of
+them) with every window closed, every window open and the mask a squelch at the median window energy leaves, each beside a
+device-to-device copy of the bytes that mask lets through and beside the level pass, alternating in the same process."""
 import argparse
 import ctypes as C
 import json
@@ -60,6 +70,12 @@ def scan(a):
                    sense=b.MFM_LEVEL_OPEN_ABOVE if sense == "above" else b.MFM_LEVEL_OPEN_BELOW,
                    open_thr=a.open_thr, close_thr=a.close_thr if a.close_thr is not None else a.open_thr, hang_windows=a.hang,
                    device=a.device)
+    gate, index, started = None, None, set()
+    elems = 2 if iq_form else 1
+    if a.gate_out:
+        os.makedirs(a.gate_out, exist_ok=True)
+        gate = pkg.Gate(len(chans), a.block // decim + 8, a.window, elems_per_sample=elems, device=a.device)
+        index = open(os.path.join(a.gate_out, "index.jsonl"), "w")
     fmt = {"cs16": b.MFM_IN_CS16, "cs8": b.MFM_IN_CS8, "cu8": b.MFM_IN_CU8}[a.format]
     bytes_per_sample = 4 if a.format == "cs16" else 2
     windows = np.zeros(len(chans), np.int64)
@@ -80,7 +96,22 @@ def scan(a):
                 lv.process_device(d_iq, 2 * stride, nout, stream=eng.stream)
             else:
                 lv.process_device(d_pcm, stride, nout, stream=eng.stream)
+            if gate:
+                d_rec, rec_stride, nw, _ = lv.device_view()
+                rows = (d_iq, 2 * stride) if iq_form else (d_pcm, stride)
+                gate.process_device(rows[0], rows[1], nout, d_rec, rec_stride, nw, stream=eng.stream)
             rec = lv.fetch()
+            if gate:
+                runs, payload = gate.fetch()
+                for r in runs:
+                    c, n_el = int(r["channel"]), int(r["nr_windows"]) * a.window * elems
+                    path = os.path.join(a.gate_out, "ch%04d.s16" % c)
+                    with open(path, "ab" if c in started else "wb") as g:
+                        at = g.tell()
+                        payload[int(r["payload_offset"]):int(r["payload_offset"]) + n_el].tofile(g)
+                    started.add(c)
+                    index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * a.window,
+                                            "nr_samples": int(r["nr_windows"]) * a.window, "file_offset": at}) + "\n")
             for c, (freq, _) in enumerate(chans):
                 for r in rec[c]:
                     out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
@@ -91,6 +122,9 @@ def scan(a):
         for c, (freq, _) in enumerate(chans):
             out.write(json.dumps({"summary": True, "freq": freq, "channel": c, "windows": int(windows[c]), "open_windows": int(opened[c]),
                                   "open_share": (float(opened[c]) / float(windows[c])) if windows[c] else 0.0}) + "\n")
+    if gate:
+        index.close()
+        gate.close()
     lv.close()
     eng.close()
 
@@ -176,7 +210,83 @@ def bench(a):
            "engine_launch_ms_pcm_only": engine_ms["pcm"][0], "engine_launch_sd_pcm_only": engine_ms["pcm"][1],
            "engine_launch_ms_with_iq": engine_ms["iq"][0], "engine_launch_sd_with_iq": engine_ms["iq"][1]}
     print(json.dumps(res))
-    for o in (lv, pg, eng):
+    pg.close()
+    bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed)
+    for o in (lv, eng):
+        o.close()
+
+
+def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed):
+    """the gate on whole windows of the rows the level pass was timed on: nb = (nout // W) * W samples per call, so that every
+    call completes the same windows and the carry stays empty.  Its records are those of one level call on these nb samples;
+    later calls find their .window behind the gate's position, which raises the out-of-step flag and changes no work."""
+    b = pkg.binding
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    nch, W, iq_form = a.bench_channels, a.window, a.form == "iq"
+    E = 2 if iq_form else 1
+    nw = nout // W
+    nb = nw * W
+    form = b.MFM_LEVEL_IQ if iq_form else b.MFM_LEVEL_PCM
+    probe = pkg.Level(nch, nout, W, form=form, device=0)
+    probe.process_device(rows, in_stride, nb)
+    energy = probe.fetch()["energy"]
+    probe.close()
+    thr = int(np.median(energy))
+    sq = pkg.Level(nch, nout, W, form=form, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+    sq.process_device(rows, in_stride, nb)
+    scene = sq.fetch()
+    d_scene, scene_stride, scene_nw, _ = sq.device_view()
+    assert scene_nw == nw
+    masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "scene": scene["open"]}
+    keep, recs = [], {}
+    for name in ("all_closed", "all_open"):
+        r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+        r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+        r["open"] = masks[name]
+        t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+        keep.append(t)
+        recs[name] = (t.data_ptr(), nw)
+    recs["scene"] = (d_scene, scene_stride)
+    gate = pkg.Gate(nch, nout, W, elems_per_sample=E, device=0)
+    sink = torch.empty(nch * nb * E, dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+
+    def run_level():
+        lv.process_device(rows, in_stride, nb)
+
+    out = {"bench": "gate_stage", "channels": nch, "form": a.form, "window": W, "samples_per_channel": nb, "windows_per_channel": nw,
+           "reps": a.reps, "calls_per_rep": a.inner, "row_base_mod_16": int(rows % 16), "in_stride_elems_mod_8": int(in_stride % 8),
+           "window_elems_mod_8": int(W * E % 8)}
+    # which alignment path the copy takes: the payload slot of a window is a multiple of W * E elements off a 16-byte base, its
+    # source (window k of a row) lies at row base + k * W * E elements
+    aligned = rows % 16 == 0 and in_stride % 8 == 0 and (W * E) % 8 == 0
+    out["copy_path"] = "16-byte stores fed by aligned 16-byte loads" if aligned else "16-byte stores fed by unaligned 16-byte loads"
+    for name in ("all_closed", "all_open", "scene"):
+        d_rec, rstride = recs[name]
+        nbytes = int(masks[name].astype(bool).sum()) * W * E * 2
+
+        def run_gate():
+            gate.process_device(rows, in_stride, nb, d_rec, rstride, nw)
+
+        def run_copy():
+            if nbytes:
+                assert rt.hipMemcpyAsync(sink.data_ptr(), rows, nbytes, 3, None) == 0
+
+        variants = [("gate", run_gate), ("copy", run_copy), ("level", run_level)]
+        for _, fn in variants:
+            timed(fn, 3)
+        got = {n: [] for n, _ in variants}
+        for rep in range(a.reps):
+            k = rep % len(variants)
+            for vname, fn in variants[k:] + variants[:k]:
+                got[vname].append(timed(fn, a.inner))
+        (gm, gsd), (cm, csd), (lm, lsd) = _stats(got["gate"]), _stats(got["copy"]), _stats(got["level"])
+        out[name] = {"open_windows": nbytes // (W * E * 2), "payload_bytes": nbytes, "gate_ms": gm, "gate_sd": gsd,
+                     "d2d_copy_ms": cm if nbytes else None, "d2d_copy_sd": csd if nbytes else None,
+                     "gate_over_copy": gm / cm if nbytes else None, "level_ms": lm, "level_sd": lsd,
+                     "gate_payload_gbps": nbytes / (gm * 1e-3) / 1e9}
+    print(json.dumps(out))
+    for o in (gate, sq):
         o.close()
 
 
@@ -195,6 +305,7 @@ def main():
     ap.add_argument("--block", type=int, default=1 << 20)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--summary", action="store_true")
+    ap.add_argument("--gate-out", default=None)
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)

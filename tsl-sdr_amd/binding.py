@@ -61,6 +61,8 @@ ABI_SYMBOLS = [
     "mfm_pocsag_process_bits_device", "mfm_ais_process_bits_device", "mfm_hosttwin_splice_bits",
     "mfm_level_create", "mfm_level_destroy", "mfm_level_process_device", "mfm_level_process_host", "mfm_level_fetch",
     "mfm_level_device_view", "mfm_hosttwin_level_window", "mfm_hosttwin_squelch_step",
+    "mfm_gate_create", "mfm_gate_destroy", "mfm_gate_process_device", "mfm_gate_process_host", "mfm_gate_fetch",
+    "mfm_gate_device_view", "mfm_hosttwin_gate_call",
     "mfm_resampler_get_form", "mfm_hosttwin_resampler_form", "mfm_hosttwin_resampler_matrix_block",
 ]
 
@@ -174,6 +176,21 @@ LEVEL_RECORD_DTYPE = np.dtype([("energy", "<u8"), ("diff_energy", "<u8"), ("wind
 MFM_LEVEL_PCM, MFM_LEVEL_IQ = 0, 1
 MFM_LEVEL_METRIC_ENERGY, MFM_LEVEL_METRIC_DIFF = 0, 1
 MFM_LEVEL_OPEN_ABOVE, MFM_LEVEL_OPEN_BELOW = 0, 1
+
+
+class GateConfig(C.Structure):
+    """struct mfm_gate_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32),
+                ("max_in_samples", C.c_uint32), ("window_samples", C.c_uint32), ("elems_per_sample", C.c_uint32),
+                ("max_open_windows", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class GateRun(C.Structure):
+    _fields_ = [("first_window", C.c_uint64), ("payload_offset", C.c_uint64), ("channel", C.c_uint32), ("nr_windows", C.c_uint32)]
+
+
+# numpy view of struct mfm_gate_run (24 bytes)
+GATE_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("payload_offset", "<u8"), ("channel", "<u4"), ("nr_windows", "<u4")])
 
 
 class FlexConfig(C.Structure):
@@ -399,6 +416,16 @@ def load_library():
     lib.mfm_hosttwin_level_window.restype = None
     lib.mfm_hosttwin_squelch_step.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, u32p, u32p]
     lib.mfm_hosttwin_squelch_step.restype = C.c_uint32
+    szp = C.POINTER(C.c_size_t)
+    lib.mfm_gate_create.argtypes = [C.POINTER(vp), C.POINTER(GateConfig)]
+    lib.mfm_gate_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_gate_destroy.restype = None
+    lib.mfm_gate_process_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp]
+    lib.mfm_gate_process_host.argtypes = [vp, i16p, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t]
+    lib.mfm_gate_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_gate_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_hosttwin_gate_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i16p, C.c_size_t, C.c_size_t, i16p, vp,
+                                           C.c_size_t, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_resampler_get_form.argtypes = [vp, C.POINTER(ResamplerForm)]
     lib.mfm_hosttwin_resampler_form.argtypes = [C.POINTER(ResamplerConfig), i16p, C.c_size_t, C.POINTER(ResamplerForm)]
     lib.mfm_hosttwin_resampler_matrix_block.argtypes = [C.POINTER(ResamplerConfig), i16p, C.c_size_t, C.c_uint32, i16p, C.c_size_t, i16p]
@@ -1180,6 +1207,112 @@ def hosttwin_squelch_step(sense, open_thr, close_thr, hang_windows, metric, open
     o, b = C.c_uint32(int(open_)), C.c_uint32(int(bad))
     lib.mfm_hosttwin_squelch_step(sense, int(open_thr), int(close_thr), hang_windows, int(metric), C.byref(o), C.byref(b))
     return o.value, b.value
+
+
+class Gate:
+    """mfm_gate: of a block of PCM (elems_per_sample 1) or filtered-IQ (2) rows, the windows that a Level's records call open,
+    packed into one dense payload with a run list (GATE_RUN_DTYPE).  Fed the same nr_in sequence as that Level."""
+
+    def __init__(self, nr_channels, max_in_samples, window_samples, elems_per_sample=1, max_open_windows=0, device=0,
+                 abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        cfg = GateConfig(abi_version, device, nr_channels, max_in_samples, window_samples, elems_per_sample, max_open_windows, 0)
+        rc = self.lib.mfm_gate_create(C.byref(self.h), C.byref(cfg))
+        if rc < 0:
+            raise MfmError(rc, "mfm_gate_create", (self.lib.mfm_last_error() if rc == MFM_E_INVAL else self.lib.mfm_strerror(rc)).decode())
+        self.nr_channels = nr_channels
+        self.elems = elems_per_sample
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_gate_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE, MFM_E_DEVICE)
+                       else self.lib.mfm_strerror(rc).decode())
+
+    def process_host(self, rows, records):
+        """rows: int16 [C][n] or [C][n][2] / [C][2 n] (two elements per sample); records: LEVEL_RECORD_DTYPE [C][windows] of the
+        same block; returns (runs, payload) of this call"""
+        a = np.ascontiguousarray(rows, dtype=np.int16).reshape(self.nr_channels, -1)
+        r = np.ascontiguousarray(records, dtype=LEVEL_RECORD_DTYPE).reshape(self.nr_channels, -1)
+        rc = self.lib.mfm_gate_process_host(self.h, _i16p(a), a.shape[1], a.shape[1] // self.elems, r.ctypes.data, r.shape[1], r.shape[1])
+        if rc < 0:
+            self._raise(rc, "mfm_gate_process_host")
+        return self.fetch()
+
+    def process_device(self, d_rows, in_stride, nr_in, d_records, record_stride, nr_windows, stream=None):
+        """d_records, record_stride, nr_windows: the first three of Level.device_view() for the same block; in_stride counts
+        int16 elements (the engine's IQ rows: 2 * stride)"""
+        rc = self.lib.mfm_gate_process_device(self.h, C.c_void_p(d_rows), in_stride, nr_in, C.c_void_p(d_records), record_stride,
+                                              nr_windows, C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_gate_process_device")
+
+    def fetch(self, max_runs=None, max_elems=None):
+        """(runs, payload) of the last call: GATE_RUN_DTYPE [nr_runs] and int16 [nr_elems].  With max_runs or max_elems too small:
+        MfmError(MFM_E_NOMEM) whose `needed` attribute is the (runs, elements) that would fit"""
+        nr, ne = C.c_size_t(), C.c_size_t()
+        if max_runs is None or max_elems is None:
+            rc = self.lib.mfm_gate_fetch(self.h, None, 0, C.byref(nr), None, 0, C.byref(ne))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below, with the untouched buffers
+                self._raise(rc, "mfm_gate_fetch")
+            max_runs = nr.value if max_runs is None else max_runs
+            max_elems = ne.value if max_elems is None else max_elems
+        runs = np.zeros(max(max_runs, 1), GATE_RUN_DTYPE)
+        payload = np.zeros(max(max_elems, 1), np.int16)
+        rc = self.lib.mfm_gate_fetch(self.h, runs.ctypes.data, max_runs, C.byref(nr), payload.ctypes.data, max_elems, C.byref(ne))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_gate_fetch")
+            except MfmError as err:
+                err.needed = (nr.value, ne.value)
+                err.buffers = (runs, payload)
+                raise
+        return runs[:nr.value].copy(), payload[:ne.value].copy()
+
+    def device_view(self):
+        """(d_runs, d_payload, d_totals): device addresses of the last call's runs, payload and the four uint64 totals
+        (runs, payload elements, overflow, out of step)"""
+        r, p, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_gate_device_view(self.h, C.byref(r), C.byref(p), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_gate_device_view")
+        return r.value, p.value, t.value
+
+
+def hosttwin_gate_call(window_samples, elems_per_sample, pos, rows, carry, records, max_runs=None, max_elems=None):
+    """mfm_hosttwin_gate_call: one call of the gate on the CPU.  rows int16 [C][n * elems_per_sample], carry int16
+    [C][window_samples * elems_per_sample] (updated in place), records LEVEL_RECORD_DTYPE [C][windows]; returns (runs, payload)"""
+    lib = load_library()
+    carry = np.asarray(carry)
+    assert carry.dtype == np.int16 and carry.flags.c_contiguous
+    nch = carry.shape[0]
+    a = np.ascontiguousarray(rows, dtype=np.int16).reshape(nch, -1)
+    r = np.ascontiguousarray(records, dtype=LEVEL_RECORD_DTYPE).reshape(nch, -1)
+    nw = r.shape[1]
+    max_runs = nch * ((nw + 1) // 2) if max_runs is None else max_runs
+    max_elems = nch * nw * window_samples * elems_per_sample if max_elems is None else max_elems
+    runs = np.zeros(max(max_runs, 1), GATE_RUN_DTYPE)
+    payload = np.zeros(max(max_elems, 1), np.int16)
+    nr, ne = C.c_size_t(), C.c_size_t()
+    abuf = a if a.size else np.zeros((nch, 1), np.int16)
+    rc = lib.mfm_hosttwin_gate_call(nch, window_samples, elems_per_sample, int(pos), _i16p(abuf), a.shape[1], a.shape[1] // elems_per_sample,
+                                    _i16p(carry), r.ctypes.data, nw, nw, runs.ctypes.data, max_runs, C.byref(nr), payload.ctypes.data,
+                                    max_elems, C.byref(ne))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_gate_call", lib.mfm_last_error().decode() if rc == MFM_E_STATE else lib.mfm_strerror(rc).decode())
+        err.needed = (nr.value, ne.value)
+        raise err
+    return runs[:nr.value].copy(), payload[:ne.value].copy()
 
 
 class Flex:
