@@ -880,7 +880,24 @@ int mfm_level_device_view(struct mfm_level *p, const struct mfm_level_record **d
  * consecutive open windows of one channel are contiguous.  Each maximal stretch of consecutive open windows WITHIN ONE
  * CALL is one mfm_gate_run; a stretch that goes on into the next call begins a new run there (first_window of the one
  * follows the last window of the other).  Runs stand in payload order.  Order and offsets are deterministic.
+ *
+ * Pre-roll (mfm_gate_set_preroll; off by default, and with it off everything above holds to the byte).  The squelch is
+ * stepped on a whole window, so a burst that begins late in window k opens only window k + 1 and the rule above drops the
+ * burst's first samples.  With P = preroll_windows (0 .. MFM_GATE_MAX_PREROLL) window k of channel c goes out exactly
+ * when any record (c, j) with k <= j <= k + P has open != 0.  That cannot be known before record k + P exists, so the
+ * gate's output is DELAYED BY P WINDOWS: a process call that brings the total of completed windows from K0 to K1 emits
+ * those of the windows max(K0 - P, 0) .. K1 - P - 1 that satisfy the rule (the first P completed windows of a stream emit
+ * nothing), from a history of the last P windows and the unfinished one that the gate keeps per channel on the device:
+ * (P + 1) * W * elems_per_sample int16 per channel, twice (two buffers used in turn).  nr_windows keeps its meaning (what
+ * this call completes: the records handed over are those of windows K0 .. K1 - 1).  Runs, payload order, first_window
+ * (the true k), payload_offset, "a stretch that goes on into the next call begins a new run there", overflow and
+ * out-of-step are as above, over the range of windows the call emits; output does not depend on how the stream is cut
+ * into calls.  mfm_gate_flush_device ends the stream: it emits, by the same rule with every missing future record taken
+ * as closed, the up to P completed windows not yet decided, as a normal call result; the unfinished window is dropped.
  */
+#define MFM_GATE_MAX_PREROLL 63u
+#define MFM_GATE_MAX_HISTORY_BYTES (1ull << 30) /* one history buffer: nr_channels * (P + 1) * W * elems_per_sample * 2 at most */
+
 struct mfm_gate_run {           /* 24 bytes */
     uint64_t first_window;      /* k of the run's first window; its first sample is k * W */
     uint64_t payload_offset;    /* in int16 elements, a multiple of W * elems_per_sample */
@@ -931,6 +948,21 @@ int mfm_gate_fetch(struct mfm_gate *g, struct mfm_gate_run *runs, size_t max_run
  * overflow (0 / 1), out of step (0 / 1) }, written by work queued on that call's stream and valid until the next call.
  * Any of the three may be NULL. */
 int mfm_gate_device_view(struct mfm_gate *g, const struct mfm_gate_run **d_runs, const int16_t **d_payload, const uint64_t **d_totals);
+/*
+ * Pre-roll of P = preroll_windows windows (see above).  Valid only before the first process call: MFM_E_STATE afterwards.
+ * MFM_E_INVAL with a message that names the bound when P exceeds MFM_GATE_MAX_PREROLL or one history buffer,
+ * nr_channels * (P + 1) * W * elems_per_sample int16 (each channel's part rounded up to 16 bytes), would exceed
+ * MFM_GATE_MAX_HISTORY_BYTES.  Allocates the history, and where the default capacity (max_open_windows == 0) would not
+ * hold a flush of P windows per channel regrows payload and runs to nr_channels * P windows.  P = 0 is the plain gate.
+ */
+int mfm_gate_set_preroll(struct mfm_gate *g, uint32_t preroll_windows);
+/*
+ * End of the stream.  Queues on `stream`, without host synchronisation, the emission of the up to P completed windows
+ * not yet decided (every missing future record taken as closed); the result is read like a process call's, with
+ * mfm_gate_fetch (which waits for it: there is no separate synchronous flush) or mfm_gate_device_view.  With P = 0 that
+ * result is empty.  Afterwards mfm_gate_process_* and a second flush return MFM_E_STATE.
+ */
+int mfm_gate_flush_device(struct mfm_gate *g, void *stream);
 
 /*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
@@ -1078,6 +1110,17 @@ int mfm_hosttwin_gate_call(uint32_t nr_channels, uint32_t window_samples, uint32
                            size_t in_stride, size_t nr_in, int16_t *carry, const struct mfm_level_record *records, size_t record_stride,
                            size_t nr_windows, struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
                            size_t *nr_elems);
+/* host twin of one call (flush == 0) or of the flush (flush != 0: nr_in and nr_windows 0, rows and records unused) of a
+ * gate with pre-roll, with the state the stage carries made explicit: history int16 [nr_channels][(P + 1) * W *
+ * elems_per_sample] (linear, oldest first; the last min(K, P) complete windows and the unfinished one, K = pos / W),
+ * open_bits uint64 [nr_channels] (bit i = the open bit of record K - P + i, 0 where no such record exists), both zero at
+ * pos 0 and updated in place, and pos.  Error rules of mfm_hosttwin_gate_call: on any error nothing is written, history
+ * and bits included.  With preroll_windows = 0 it is mfm_hosttwin_gate_call to the byte (history = carry). */
+int mfm_hosttwin_gate_call_preroll(uint32_t nr_channels, uint32_t window_samples, uint32_t elems_per_sample, uint32_t preroll_windows,
+                                   uint64_t pos, int flush, const int16_t *rows, size_t in_stride, size_t nr_in, int16_t *history,
+                                   uint64_t *open_bits, const struct mfm_level_record *records, size_t record_stride, size_t nr_windows,
+                                   struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                                   size_t *nr_elems);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Register and spill counts of the kernel instances in an object file: tools/kernel_regs.py build/x.o [name filter]"""
+"""Register and spill counts of the kernel instances in an object file: tools/kernel_regs.py build/x.o [name filter]
+
+The gate's kernels are in two objects: build/mfm_gate.o (gt_count, gt_scan, gt_runs, gt_copy, gt_carry) and
+build/mfm_gate_preroll.o (gtp_count, gtp_runs, gtp_copy, gtp_hist)."""
 import re, subprocess, sys, tempfile, os
 LLVM = "/opt/rocm/lib/llvm/bin/"
 obj = sys.argv[1]
@@ -13,7 +16,7 @@ for ent in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
     get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", ent).group(1))
     name = re.search(r"\.name:\s+(\S+)", ent).group(1)
     dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    dem = re.sub(r"^void ", "", dem).split("(")[0]
+    dem = re.sub(r"^void ", "", dem).replace("(anonymous namespace)::", "").split("(")[0]
     if flt in dem:
         print("%-70s vgpr %3d agpr %3s spill %3d | sgpr %3d spill %3d | lds %6d scratch %5d" % (
             dem, get("vgpr_count"), ent.split()[0], get("vgpr_spill_count"), get("sgpr_count"), get("sgpr_spill_count"),

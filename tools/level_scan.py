@@ -3,7 +3,7 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
-           [--block 1048576] [--summary] [--gate-out DIR]
+           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -21,8 +21,11 @@ gets the gated samples, and DIR/index.jsonl one line per run:
     {"channel": 3, "first_sample": 4000, "nr_samples": 2000, "file_offset": 0}
 
 (first_sample and nr_samples in samples of the channel, file_offset in bytes of its file).  What goes to stdout does not change.
+--gate-preroll P (default 0) also lets the P windows in front of every opening through (window k goes out when any of the
+records k .. k + P is open): the gate's output then comes P windows late, and at the end of the input the gate is flushed and
+the runs the flush brings are written like any others.
 
-    python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8]
+    python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8] [--gate-preroll 0,1,4]
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
 against the POCSAG stage's call on the same rows (idle input; its slicer, pg_slice_kernel, reads the same bytes) and
@@ -30,7 +33,11 @@ against the engine launch with and without filtered IQ.  Level pass and comparis
 rotating order; mean and standard deviation over --reps repetitions, a difference counts beyond two standard errors
 (the rule of tools/exp/ab.py).  One JSON line.  A second line times the gate stage on the same rows (whole windows of
 them) with every window closed, every window open and the mask a squelch at the median window energy leaves, each beside a
-device-to-device copy of the bytes that mask lets through and beside the level pass, alternating in the same process."""
+device-to-device copy of the bytes that mask lets through and beside the level pass, alternating in the same process.
+With --gate-preroll (one P, or several with commas) there is one such line per P, each with "preroll" and, for P > 0 behind a
+P = 0 line of the same run, "gate_ms_over_p0" per mask: the cost of the pre-roll.  The payload of a P > 0 line is what the
+dilated mask lets through in the steady state (every call emits the last P windows of the call before it, from the history, and
+all but the last P of its own)."""
 import argparse
 import ctypes as C
 import json
@@ -74,8 +81,21 @@ def scan(a):
     elems = 2 if iq_form else 1
     if a.gate_out:
         os.makedirs(a.gate_out, exist_ok=True)
-        gate = pkg.Gate(len(chans), a.block // decim + 8, a.window, elems_per_sample=elems, device=a.device)
+        gate = pkg.Gate(len(chans), a.block // decim + 8, a.window, elems_per_sample=elems, device=a.device,
+                        preroll_windows=int(a.gate_preroll))
         index = open(os.path.join(a.gate_out, "index.jsonl"), "w")
+
+    def write_runs(runs, payload):
+        for r in runs:
+            c, n_el = int(r["channel"]), int(r["nr_windows"]) * a.window * elems
+            path = os.path.join(a.gate_out, "ch%04d.s16" % c)
+            with open(path, "ab" if c in started else "wb") as g:
+                at = g.tell()
+                payload[int(r["payload_offset"]):int(r["payload_offset"]) + n_el].tofile(g)
+            started.add(c)
+            index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * a.window,
+                                    "nr_samples": int(r["nr_windows"]) * a.window, "file_offset": at}) + "\n")
+
     fmt = {"cs16": b.MFM_IN_CS16, "cs8": b.MFM_IN_CS8, "cu8": b.MFM_IN_CU8}[a.format]
     bytes_per_sample = 4 if a.format == "cs16" else 2
     windows = np.zeros(len(chans), np.int64)
@@ -102,16 +122,7 @@ def scan(a):
                 gate.process_device(rows[0], rows[1], nout, d_rec, rec_stride, nw, stream=eng.stream)
             rec = lv.fetch()
             if gate:
-                runs, payload = gate.fetch()
-                for r in runs:
-                    c, n_el = int(r["channel"]), int(r["nr_windows"]) * a.window * elems
-                    path = os.path.join(a.gate_out, "ch%04d.s16" % c)
-                    with open(path, "ab" if c in started else "wb") as g:
-                        at = g.tell()
-                        payload[int(r["payload_offset"]):int(r["payload_offset"]) + n_el].tofile(g)
-                    started.add(c)
-                    index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * a.window,
-                                            "nr_samples": int(r["nr_windows"]) * a.window, "file_offset": at}) + "\n")
+                write_runs(*gate.fetch())
             for c, (freq, _) in enumerate(chans):
                 for r in rec[c]:
                     out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
@@ -123,6 +134,8 @@ def scan(a):
             out.write(json.dumps({"summary": True, "freq": freq, "channel": c, "windows": int(windows[c]), "open_windows": int(opened[c]),
                                   "open_share": (float(opened[c]) / float(windows[c])) if windows[c] else 0.0}) + "\n")
     if gate:
+        gate.flush_device(stream=eng.stream)  # the windows pre-roll still held back; none with P = 0
+        write_runs(*gate.fetch())
         index.close()
         gate.close()
     lv.close()
@@ -211,15 +224,20 @@ def bench(a):
            "engine_launch_ms_with_iq": engine_ms["iq"][0], "engine_launch_sd_with_iq": engine_ms["iq"][1]}
     print(json.dumps(res))
     pg.close()
-    bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed)
+    p0 = None
+    for P in [int(x) for x in str(a.gate_preroll).split(",")]:
+        line = bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P, p0)
+        p0 = line if P == 0 else p0
     for o in (lv, eng):
         o.close()
 
 
-def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed):
+def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P=0, p0=None):
     """the gate on whole windows of the rows the level pass was timed on: nb = (nout // W) * W samples per call, so that every
     call completes the same windows and the carry stays empty.  Its records are those of one level call on these nb samples;
-    later calls find their .window behind the gate's position, which raises the out-of-step flag and changes no work."""
+    later calls find their .window behind the gate's position, which raises the out-of-step flag and changes no work.
+    With P pre-roll windows every call emits the last P windows of the call before it (the same rows and records) and all but the
+    last P of its own, by the dilated mask; p0 is the P = 0 line of the same run."""
     b = pkg.binding
     rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     nch, W, iq_form = a.bench_channels, a.window, a.form == "iq"
@@ -247,7 +265,7 @@ def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed):
         keep.append(t)
         recs[name] = (t.data_ptr(), nw)
     recs["scene"] = (d_scene, scene_stride)
-    gate = pkg.Gate(nch, nout, W, elems_per_sample=E, device=0)
+    gate = pkg.Gate(nch, nout, W, elems_per_sample=E, device=0, preroll_windows=P)
     sink = torch.empty(nch * nb * E, dtype=torch.int16, device="cuda")
     torch.cuda.synchronize()
 
@@ -256,14 +274,19 @@ def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed):
 
     out = {"bench": "gate_stage", "channels": nch, "form": a.form, "window": W, "samples_per_channel": nb, "windows_per_channel": nw,
            "reps": a.reps, "calls_per_rep": a.inner, "row_base_mod_16": int(rows % 16), "in_stride_elems_mod_8": int(in_stride % 8),
-           "window_elems_mod_8": int(W * E % 8)}
+           "window_elems_mod_8": int(W * E % 8), "preroll": P,
+           "history_bytes": 2 * nch * (((P + 1) * W * E + 7) & ~7) * 2 if P else 0}
     # which alignment path the copy takes: the payload slot of a window is a multiple of W * E elements off a 16-byte base, its
     # source (window k of a row) lies at row base + k * W * E elements
     aligned = rows % 16 == 0 and in_stride % 8 == 0 and (W * E) % 8 == 0
     out["copy_path"] = "16-byte stores fed by aligned 16-byte loads" if aligned else "16-byte stores fed by unaligned 16-byte loads"
     for name in ("all_closed", "all_open", "scene"):
         d_rec, rstride = recs[name]
-        nbytes = int(masks[name].astype(bool).sum()) * W * E * 2
+        m = masks[name].astype(bool)
+        if P:  # the steady state: the records in front of a call are the last P of the same mask
+            ext = np.concatenate([m[:, nw - P:], m], axis=1)
+            m = np.logical_or.reduce([ext[:, t:t + nw] for t in range(P + 1)])
+        nbytes = int(m.sum()) * W * E * 2
 
         def run_gate():
             gate.process_device(rows, in_stride, nb, d_rec, rstride, nw)
@@ -285,9 +308,12 @@ def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed):
                      "d2d_copy_ms": cm if nbytes else None, "d2d_copy_sd": csd if nbytes else None,
                      "gate_over_copy": gm / cm if nbytes else None, "level_ms": lm, "level_sd": lsd,
                      "gate_payload_gbps": nbytes / (gm * 1e-3) / 1e9}
+        if P and p0:
+            out[name]["gate_ms_over_p0"] = gm / p0[name]["gate_ms"]
     print(json.dumps(out))
     for o in (gate, sq):
         o.close()
+    return out
 
 
 def main():
@@ -306,6 +332,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--summary", action="store_true")
     ap.add_argument("--gate-out", default=None)
+    ap.add_argument("--gate-preroll", default="0", help="pre-roll windows of the gate; with --bench one or several, as 0,1,4")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)

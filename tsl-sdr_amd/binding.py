@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "mfm_level_device_view", "mfm_hosttwin_level_window", "mfm_hosttwin_squelch_step",
     "mfm_gate_create", "mfm_gate_destroy", "mfm_gate_process_device", "mfm_gate_process_host", "mfm_gate_fetch",
     "mfm_gate_device_view", "mfm_hosttwin_gate_call",
+    "mfm_gate_set_preroll", "mfm_gate_flush_device", "mfm_hosttwin_gate_call_preroll",
     "mfm_resampler_get_form", "mfm_hosttwin_resampler_form", "mfm_hosttwin_resampler_matrix_block",
 ]
 
@@ -189,6 +190,8 @@ class GateRun(C.Structure):
     _fields_ = [("first_window", C.c_uint64), ("payload_offset", C.c_uint64), ("channel", C.c_uint32), ("nr_windows", C.c_uint32)]
 
 
+MFM_GATE_MAX_PREROLL = 63               # pre-roll windows at most
+MFM_GATE_MAX_HISTORY_BYTES = 1 << 30    # one history buffer of a gate with pre-roll at most
 # numpy view of struct mfm_gate_run (24 bytes)
 GATE_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("payload_offset", "<u8"), ("channel", "<u4"), ("nr_windows", "<u4")])
 
@@ -424,6 +427,10 @@ def load_library():
     lib.mfm_gate_process_host.argtypes = [vp, i16p, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.c_size_t]
     lib.mfm_gate_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_gate_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_gate_set_preroll.argtypes = [vp, C.c_uint32]
+    lib.mfm_gate_flush_device.argtypes = [vp, vp]
+    lib.mfm_hosttwin_gate_call_preroll.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, i16p, C.c_size_t,
+                                                   C.c_size_t, i16p, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_hosttwin_gate_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i16p, C.c_size_t, C.c_size_t, i16p, vp,
                                            C.c_size_t, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_resampler_get_form.argtypes = [vp, C.POINTER(ResamplerForm)]
@@ -1214,7 +1221,7 @@ class Gate:
     packed into one dense payload with a run list (GATE_RUN_DTYPE).  Fed the same nr_in sequence as that Level."""
 
     def __init__(self, nr_channels, max_in_samples, window_samples, elems_per_sample=1, max_open_windows=0, device=0,
-                 abi_version=MFM_ABI_VERSION):
+                 abi_version=MFM_ABI_VERSION, preroll_windows=0):
         self.lib = load_library()
         self.h = C.c_void_p()
         cfg = GateConfig(abi_version, device, nr_channels, max_in_samples, window_samples, elems_per_sample, max_open_windows, 0)
@@ -1223,6 +1230,24 @@ class Gate:
             raise MfmError(rc, "mfm_gate_create", (self.lib.mfm_last_error() if rc == MFM_E_INVAL else self.lib.mfm_strerror(rc)).decode())
         self.nr_channels = nr_channels
         self.elems = elems_per_sample
+        if preroll_windows:
+            try:
+                self.set_preroll(preroll_windows)
+            except MfmError:
+                self.close()
+                raise
+
+    def set_preroll(self, preroll_windows):
+        """mfm_gate_set_preroll: window k goes out when any record k .. k + P is open, P windows late; before the first call only"""
+        rc = self.lib.mfm_gate_set_preroll(self.h, preroll_windows)
+        if rc < 0:
+            self._raise(rc, "mfm_gate_set_preroll")
+
+    def flush_device(self, stream=None):
+        """mfm_gate_flush_device: end of the stream; the windows pre-roll still held back are the result fetch() returns"""
+        rc = self.lib.mfm_gate_flush_device(self.h, C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_gate_flush_device")
 
     def close(self):
         if self.h:
@@ -1310,6 +1335,39 @@ def hosttwin_gate_call(window_samples, elems_per_sample, pos, rows, carry, recor
                                     max_elems, C.byref(ne))
     if rc < 0:
         err = MfmError(rc, "mfm_hosttwin_gate_call", lib.mfm_last_error().decode() if rc == MFM_E_STATE else lib.mfm_strerror(rc).decode())
+        err.needed = (nr.value, ne.value)
+        raise err
+    return runs[:nr.value].copy(), payload[:ne.value].copy()
+
+
+def hosttwin_gate_call_preroll(window_samples, elems_per_sample, preroll_windows, pos, rows, history, open_bits, records, flush=False,
+                               max_runs=None, max_elems=None):
+    """mfm_hosttwin_gate_call_preroll: one call, or with flush the flush (rows and records empty), of a gate with pre-roll on the
+    CPU.  history int16 [C][(P + 1) * window_samples * elems_per_sample] and open_bits uint64 [C] are the stage's state, zero
+    at pos 0 and updated in place; returns (runs, payload)"""
+    lib = load_library()
+    history, open_bits = np.asarray(history), np.asarray(open_bits)
+    assert history.dtype == np.int16 and history.flags.c_contiguous and open_bits.dtype == np.uint64 and open_bits.flags.c_contiguous
+    nch = history.shape[0]
+    we = window_samples * elems_per_sample
+    assert history.shape[1] == (preroll_windows + 1) * we and open_bits.shape == (nch,)
+    a = np.ascontiguousarray(rows, dtype=np.int16).reshape(nch, -1)
+    r = np.ascontiguousarray(records, dtype=LEVEL_RECORD_DTYPE).reshape(nch, -1)
+    nw = r.shape[1]
+    most = preroll_windows if flush else nw
+    max_runs = nch * ((most + 1) // 2) if max_runs is None else max_runs
+    max_elems = nch * most * we if max_elems is None else max_elems
+    runs = np.zeros(max(max_runs, 1), GATE_RUN_DTYPE)
+    payload = np.zeros(max(max_elems, 1), np.int16)
+    nr, ne = C.c_size_t(), C.c_size_t()
+    abuf = a if a.size else np.zeros((nch, 1), np.int16)
+    rc = lib.mfm_hosttwin_gate_call_preroll(nch, window_samples, elems_per_sample, preroll_windows, int(pos), int(bool(flush)), _i16p(abuf),
+                                            a.shape[1], a.shape[1] // elems_per_sample, _i16p(history), open_bits.ctypes.data,
+                                            r.ctypes.data, nw, nw, runs.ctypes.data, max_runs, C.byref(nr), payload.ctypes.data, max_elems,
+                                            C.byref(ne))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_gate_call_preroll",
+                       lib.mfm_last_error().decode() if rc == MFM_E_STATE else lib.mfm_strerror(rc).decode())
         err.needed = (nr.value, ne.value)
         raise err
     return runs[:nr.value].copy(), payload[:ne.value].copy()

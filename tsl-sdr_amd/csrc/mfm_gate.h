@@ -112,4 +112,55 @@ __host__ __device__ inline bool mfm_gate_walk_step(mfm_gate_walk &w, uint64_t ma
     return done;
 }
 
+/*
+ * ---- pre-roll (mfm_gate_set_preroll, P = preroll_windows >= 0) ------------------------------------------------------
+ * Window k goes out when any of the records k .. k + P is open, so a call that brings the records K0 .. K1 - 1 decides the
+ * windows K0 - P .. K1 - P - 1: its CANDIDATES, e = 0 .. nemit - 1 with k = K0 - P + e (a flush brings no record and
+ * decides the P windows left, the missing records taken as closed).  A channel's record bits of the call are one sequence
+ * S: bits 0 .. P - 1 are the P records in front of the call (carried as one 64-bit word per channel, bit i = record
+ * K0 - P + i, zero where no such record exists), bit P + j is record j of the call, everything behind is closed.  The bit
+ * of candidate e is the OR of S[e] .. S[e + P]; for a chunk of 64 candidates that is a shift-and-OR over two words of S.
+ * With that mask in place of the plain one, everything above (walk, starts, slots, runs) is used as it is.
+ *
+ * The samples of the candidates lie in front of the call's rows: the history, a linear buffer per channel that holds the
+ * last min(K, P) complete windows and the r elements of the unfinished one, oldest first.  It stands as a virtual prefix
+ * in front of the rows, so mfm_gate_src with r0 + P * We in place of r0 is the signed source index: the row when >= 0,
+ * otherwise counted back from the history's end.  P is at most MFM_GATE_MAX_PREROLL = 63 (include/multifm_hip.h): S[e] ..
+ * S[e + P] of 64 candidates then lie in two words.
+ */
+
+/* candidates below this one are windows with k < 0: they do not exist and never go out */
+__host__ __device__ inline uint32_t mfm_gate_pre_skip(uint64_t k0, uint32_t P)
+{
+    return k0 < P ? P - (uint32_t)k0 : 0u;
+}
+
+/* what the history holds once K windows are complete and r elements of the next one have come */
+__host__ __device__ inline uint32_t mfm_gate_hist_len(uint64_t K, uint32_t r, uint32_t P, uint32_t We)
+{
+    return (uint32_t)(K < P ? K : P) * We + r;
+}
+
+/* the mask of the 64 candidates whose record bits begin at lo bit 0 (lo = S[e0 .. e0 + 63], hi = S[e0 + 64 .. e0 + 127]);
+ * bits at or above cnt and candidates below skip (counted from candidate 0, the chunk begins at e0) are cleared */
+__host__ __device__ inline uint64_t mfm_gate_dilate(uint64_t lo, uint64_t hi, uint32_t P, uint32_t e0, uint32_t cnt, uint32_t skip)
+{
+    uint64_t d = lo;
+    for (uint32_t t = 1; t <= P; t++) { /* P <= 63: both shifts stay below 64 */
+        d |= (lo >> t) | (hi << (64u - t));
+    }
+    d &= mfm_gate_below(cnt);
+    if (skip > e0) {
+        d &= ~mfm_gate_below(skip - e0);
+    }
+    return d;
+}
+
+/* element i of the history after a call of N elements, as an index into (old history of hlen0 elements ++ the call's row):
+ * the row when >= 0, otherwise counted back from the old history's end */
+__host__ __device__ inline int64_t mfm_gate_hist_src(uint32_t i, uint32_t hlen1, uint32_t N)
+{
+    return (int64_t)N - (int64_t)hlen1 + (int64_t)i;
+}
+
 #endif /* MFM_GATE_H */

@@ -29,6 +29,9 @@
  *   gt_carry_kernel  behind the copy, which read the old carry: the unfinished window's elements replace it, or, when
  *                    the call completed no window, are appended to it.
  *
+ * With pre-roll (mfm_gate_set_preroll, P > 0) a call takes the kernels of mfm_gate_preroll.hip in place of count, runs, copy
+ * and carry; the scan is shared.  With P = 0 the launches are the ones above.
+ *
  * Nothing is floating point, nothing goes through an atomic (order and offsets are a count, a scan and a rank), and the
  * host never waits: how many windows a call completes follows from the stream position alone.
  */
@@ -41,8 +44,7 @@
 #include "../../include/multifm_hip.h"
 
 #include "mfm_gate.h"
-
-extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
+#include "mfm_gate_internal.h"
 
 namespace {
 
@@ -346,25 +348,23 @@ int gt_fail(int code, const char *msg)
         }                                                                                                    \
     } while (0)
 
-struct mfm_gate {
-    mfm_gate_config cfg{};
-    uint32_t W = 0, E = 1, We = 0;
-    uint32_t max_win = 0;      /* windows per channel and call at most */
-    uint64_t cap_windows = 0;  /* payload capacity, windows */
-    uint64_t cap_runs = 0;
-    uint32_t carry_stride = 0;
-    uint32_t log2g = 0, npieces = 1;
-    uint64_t pos = 0;          /* samples per channel consumed so far */
-    int16_t *d_carry = nullptr;
-    uint32_t *d_cnt_open = nullptr, *d_cnt_runs = nullptr, *d_bad = nullptr, *d_base_runs = nullptr, *d_base_open = nullptr, *d_slot = nullptr;
-    uint64_t *d_totals = nullptr;
-    mfm_gate_run *d_runs = nullptr;
-    int16_t *d_payload = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool have_call = false;
-};
+/* struct mfm_gate: mfm_gate_internal.h (shared with the pre-roll mode, mfm_gate_preroll.hip) */
 
 extern "C" {
+
+int mfm_gate_internal_fail(int code, const char *msg)
+{
+    return gt_fail(code, msg);
+}
+
+int mfm_gate_internal_scan(struct mfm_gate *g, hipStream_t s)
+{
+    const uint32_t C = g->cfg.nr_channels;
+    hipLaunchKernelGGL(gt_scan_kernel, dim3(1), dim3(GT_SCAN_THREADS), 0, s, C, (C + GT_SCAN_THREADS - 1) / GT_SCAN_THREADS, g->d_cnt_open,
+                       g->d_cnt_runs, g->d_bad, g->d_base_open, g->d_base_runs, g->d_totals, g->We, g->cap_windows);
+    GT_TRY(hipGetLastError());
+    return MFM_OK;
+}
 
 int mfm_gate_create(struct mfm_gate **pg, const struct mfm_gate_config *cfg)
 {
@@ -446,6 +446,10 @@ void mfm_gate_destroy(struct mfm_gate **pg)
     (void)hipFree(g->d_totals);
     (void)hipFree(g->d_runs);
     (void)hipFree(g->d_payload);
+    for (int i = 0; i < 2; i++) {
+        (void)hipFree(g->d_hist[i]);
+        (void)hipFree(g->d_bits[i]);
+    }
     delete g;
     *pg = nullptr;
 }
@@ -466,10 +470,16 @@ int mfm_gate_process_device(struct mfm_gate *g, const int16_t *d_rows, size_t in
     if (cut.nwin > g->max_win) {
         return gt_fail(MFM_E_INVAL, "internal: window count exceeds the plan");
     }
+    if (g->flushed) {
+        return gt_fail(MFM_E_STATE, "the gate was flushed: the stream has ended");
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     GT_TRY(hipSetDevice(g->cfg.device));
     if (g->have_call && g->last_stream != s) {
         GT_TRY(hipStreamSynchronize(g->last_stream)); /* state lives on the device; keep calls ordered */
+    }
+    if (g->P) { /* the pre-roll mode has kernels of its own; with P = 0 everything below is what it was */
+        return mfm_gate_internal_preroll_call(g, d_rows, in_stride, nr_in, d_records, record_stride, cut.nwin, 0, s);
     }
     const uint32_t C = g->cfg.nr_channels;
     const GtRecs R{ d_records, record_stride, cut.k0, cut.nwin, C };
