@@ -965,6 +965,99 @@ int mfm_gate_set_preroll(struct mfm_gate *g, uint32_t preroll_windows);
 int mfm_gate_flush_device(struct mfm_gate *g, void *stream);
 
 /*
+ * ---- Burst resampler: the gate's runs through the rational resampler, on the device ----------------------------------
+ * The first stage that takes the gate's output rather than full rows: its input is what mfm_gate_device_view returns (the
+ * run list, the dense payload, the totals) and its work is proportional to what the squelch left open.  The arithmetic is
+ * the resampler's above (filter/polyphase_fir.c:162-233), bit for bit: int16 x int16 -> wrapping int32 sum over one phase,
+ * Q14 rounding (a >> 14) + ((a >> 13) & 1) cut to int16, phase walk phase += D; pos += phase / I; phase %= I, an output
+ * only while strictly MORE than plen unconsumed samples exist; `invert` negates the input on int16 storage.
+ *
+ * Stretch.  A stretch of channel c is a maximal sequence of consecutive window numbers k that the gate emitted for c over
+ * the whole stream; it does not depend on how the stream was cut into calls.  The gate begins a new mfm_gate_run at every
+ * call boundary, so a stretch is one or more runs whose first_window values follow on.
+ *
+ * Rule.  The outputs of a stretch are the concatenation of the outputs of its runs, and they are exactly what a fresh
+ * resampler (phase 0, nothing pending) returns when fed the stretch's samples.  The at most plen samples pending at the
+ * end of a stretch produce nothing, as at the end of a stream in the reference; a stretch shorter than plen + 1 samples
+ * produces no output, and its runs still appear, with nr_out = 0.
+ *
+ * State.  Per channel, on the device: the window number expected next, the phase, the outputs so far, the pending count
+ * and plen pending samples.  A run continues its channel's stretch exactly when its first_window equals the expected
+ * number; otherwise it resets the state and begins a new stretch.  Within one call only a channel's first run can continue
+ * (the gate's runs within a call are maximal).  A channel without a run in a call keeps its state.
+ *
+ * Result.  It replaces the previous call's: one mfm_runrs_run per input run, in the gate's order; a dense int16 payload in
+ * that order (out_offset ascending, no gaps); d_totals[4] = { runs, output elements, overflow, gate error }.  Order and
+ * offsets are deterministic.  When the gate's totals carry overflow or out-of-step, or the call does not fit max_windows /
+ * max_runs, the call produces nothing (output elements = 0), raises the flag and leaves the per-channel state untouched:
+ *   overflow    MFM_RUNRS_OVER_OWN: more runs or payload than max_runs / max_windows; MFM_RUNRS_OVER_GATE: the gate's
+ *   gate error  MFM_RUNRS_GATE_OUT_OF_STEP: the gate's; MFM_RUNRS_GATE_BAD_RUNS: a run names a channel or payload range that
+ *               does not exist (not a gate's run list)
+ *
+ * Refusals at create (MFM_E_INVAL with a message, never a fallback): the stage takes PCM payloads only (a gate with
+ * elems_per_sample == 1); it has no DC blocker and no sign-bit output, so `flags` must be 0; a ratio whose walk steps past
+ * a phase (mfm_rs_plan.h's rule, as mfm_resampler_create); a coefficient image I * plen int16 that, with the input window of
+ * one workgroup, exceeds MFM_RUNRS_MAX_LDS_BYTES.
+ */
+#define MFM_RUNRS_MAX_LDS_BYTES 49152u /* coefficient image + one workgroup's input window */
+#define MFM_RUNRS_BEGINS 1u            /* mfm_runrs_run.flags bit 0: the run begins a stretch */
+#define MFM_RUNRS_OVER_OWN 1u
+#define MFM_RUNRS_OVER_GATE 2u
+#define MFM_RUNRS_GATE_OUT_OF_STEP 1u
+#define MFM_RUNRS_GATE_BAD_RUNS 2u
+
+struct mfm_runrs_run {          /* 40 bytes */
+    uint64_t first_window;      /* the gate run's */
+    uint64_t out_offset;        /* in int16 elements of the output payload */
+    uint64_t first_out;         /* index of the run's first output within its stretch */
+    uint32_t channel;
+    uint32_t nr_out;
+    uint32_t flags;             /* MFM_RUNRS_BEGINS */
+    uint32_t reserved;          /* 0 */
+};
+
+struct mfm_runrs; /* opaque */
+
+struct mfm_runrs_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;       /* 1 .. 65535 */
+    uint32_t interpolate;       /* I */
+    uint32_t decimate;          /* D */
+    uint32_t window_samples;    /* W, the gate's */
+    uint32_t max_windows;       /* the gate's payload capacity per call, in windows (its max_open_windows); 0 = the gate's own
+                                   default, nr_channels * max(max_in_samples / W + 1, preroll_windows), which cannot overflow */
+    uint32_t max_runs;          /* 0 = a bound that cannot overflow: two runs of a channel have a closed window between them */
+    uint32_t invert;            /* decoder -i */
+    uint32_t flags;             /* 0 */
+    uint32_t max_in_samples;    /* the gate's; read only where max_windows or max_runs is 0 */
+    uint32_t preroll_windows;   /* the gate's P (its flush emits up to P windows per channel); likewise */
+};
+
+/* coeffs are the Q14 int16 taps, as in mfm_resampler_create */
+int mfm_runrs_create(struct mfm_runrs **prr, const struct mfm_runrs_config *cfg, const int16_t *coeffs, size_t nr_coeffs);
+void mfm_runrs_destroy(struct mfm_runrs **prr);
+/*
+ * Resample the runs of one gate call: d_runs, d_payload and d_totals are what mfm_gate_device_view returned after
+ * mfm_gate_process_device or mfm_gate_flush_device.  Work is queued on `stream` (the gate call's, or one ordered behind it);
+ * no host synchronisation: run count and payload length are read on the device, launches are sized from the capacities
+ * fixed at create.  The three arrays are read until the queued work has run.
+ */
+int mfm_runrs_process_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                             void *stream);
+/*
+ * Wait for the last call, read its totals into *nr_runs and *nr_elems and copy the used part of both arrays.  MFM_E_NOMEM
+ * when max_runs or max_elems is too small (nothing copied, the totals say what is needed); MFM_E_STATE with a message when
+ * the call raised overflow or gate error (nothing copied, nothing was written past the capacity, the state did not move:
+ * the same input in calls that fit is right again).
+ */
+int mfm_runrs_fetch(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                    size_t *nr_elems);
+/* For consumers that stay on the device: the last call's runs, payload and d_totals[4], written by work queued on that
+ * call's stream and valid until the next call.  Any of the three may be NULL. */
+int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_runs, const int16_t **d_payload, const uint64_t **d_totals);
+
+/*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
  *   mm_init      pager/mueller_muller.c:10-33
  *   mm_process   pager/mueller_muller.c:41-115
@@ -1121,6 +1214,30 @@ int mfm_hosttwin_gate_call_preroll(uint32_t nr_channels, uint32_t window_samples
                                    uint64_t *open_bits, const struct mfm_level_record *records, size_t record_stride, size_t nr_windows,
                                    struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
                                    size_t *nr_elems);
+/* host twin of the burst resampler's closed form (csrc/mfm_runrs.h, what its plan and state kernels run), n cases at once:
+ * a run of nr_samples[i] samples met with phase[i] (< interpolate) and pending[i] (<= plen) unconsumed samples produces
+ * nr_out[i] outputs and leaves phase_out[i] and pending_out[i].  MFM_E_INVAL for a ratio the stage refuses or a case out of
+ * range. */
+int mfm_hosttwin_runrs_plan(uint32_t interpolate, uint32_t decimate, uint32_t plen, const uint32_t *phase, const uint32_t *pending,
+                            const uint64_t *nr_samples, size_t n, uint64_t *nr_out, uint32_t *phase_out, uint32_t *pending_out);
+/* the per-channel state of the burst resampler as the host twin carries it: zero-filled except expected = ~0 (no stretch)
+ * at the start of a stream */
+struct mfm_runrs_state {        /* 24 bytes */
+    uint64_t expected;          /* window number that continues the channel's stretch */
+    uint64_t outs;              /* outputs of the stretch so far */
+    uint32_t phase;
+    uint32_t pending;           /* samples in the channel's part of `pending` */
+};
+/* host twin of one mfm_runrs_process_device call, no device needed: gate_runs / gate_payload are one gate call's result
+ * (nr_gate_runs, nr_gate_elems: its totals), state [nr_channels] and pending [nr_channels][plen] are updated in place, plen =
+ * ((nr_coeffs + interpolate - 1) / interpolate + 3) & ~3.  MFM_E_INVAL for what create refuses and for a run list that is not a
+ * gate's, MFM_E_NOMEM when max_runs or max_elems is too small (*nr_runs / *nr_elems say what is needed); on any error nothing
+ * is written, the state included. */
+int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert,
+                            const int16_t *coeffs, size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending,
+                            const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload, size_t nr_gate_elems,
+                            struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                            size_t *nr_elems);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

@@ -3,7 +3,7 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
-           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P]]
+           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -25,6 +25,16 @@ gets the gated samples, and DIR/index.jsonl one line per run:
 records k .. k + P is open): the gate's output then comes P windows late, and at the end of the input the gate is flushed and
 the runs the flush brings are written like any others.
 
+--gate-resample I/D --resample-taps FILE (with --gate-out and --form pcm) queues the burst resampler behind the gate on the same
+stream: every stretch of consecutive gated windows of a channel goes through a fresh rational resampler I/D whose taps are FILE's
+"lpfCoeffs" (quantised to Q14 as the decoder does).  Beside the gated files DIR/chNNNN.rs.s16 gets the channel's resampled
+samples and DIR/resampled.jsonl one line per run:
+
+    {"channel": 3, "first_sample": 4000, "first_out": 0, "nr_out": 1597, "begins": 1, "file_offset": 0}
+
+(first_sample in samples of the channel at the input rate, first_out the index of the run's first output within its stretch,
+begins 1 on a stretch's first run, file_offset in bytes of the .rs.s16 file).
+
     python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8] [--gate-preroll 0,1,4]
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
@@ -37,7 +47,9 @@ device-to-device copy of the bytes that mask lets through and beside the level p
 With --gate-preroll (one P, or several with commas) there is one such line per P, each with "preroll" and, for P > 0 behind a
 P = 0 line of the same run, "gate_ms_over_p0" per mask: the cost of the pre-roll.  The payload of a P > 0 line is what the
 dilated mask lets through in the steady state (every call emits the last P windows of the call before it, from the history, and
-all but the last P of its own)."""
+all but the last P of its own).  With --form pcm a last line ("runrs_stage") times the burst resampler (4/5, 81 taps) behind the
+gate for the three masks, alternating in the same process with mfm_resampler_process_device (MFM_RS_FORCE_DOT2) on the full rows:
+all-open over that plain resampler as a ratio with its standard error, all-closed as an absolute time."""
 import argparse
 import ctypes as C
 import json
@@ -84,6 +96,28 @@ def scan(a):
         gate = pkg.Gate(len(chans), a.block // decim + 8, a.window, elems_per_sample=elems, device=a.device,
                         preroll_windows=int(a.gate_preroll))
         index = open(os.path.join(a.gate_out, "index.jsonl"), "w")
+    rr, rs_index, rs_started = None, None, set()
+    if a.gate_resample:
+        if not gate or iq_form:
+            raise SystemExit("--gate-resample needs --gate-out and --form pcm: the burst resampler takes PCM payloads only")
+        if not a.resample_taps:
+            raise SystemExit("--gate-resample needs --resample-taps FILE")
+        interp, decim_rs = [int(x) for x in a.gate_resample.split("/")]
+        co = np.array([int(float(t) * 16384.0) for t in json.load(open(a.resample_taps))["lpfCoeffs"]], np.int16)  # decoder.c:530-533
+        rr = pkg.RunResampler(len(chans), co, interp, decim_rs, a.window, max_in_samples=a.block // decim + 8,
+                              preroll_windows=int(a.gate_preroll), device=a.device)
+        rs_index = open(os.path.join(a.gate_out, "resampled.jsonl"), "w")
+
+    def write_resampled(runs, payload):
+        for r in runs:
+            c = int(r["channel"])
+            path = os.path.join(a.gate_out, "ch%04d.rs.s16" % c)
+            with open(path, "ab" if c in rs_started else "wb") as g:
+                at = g.tell()
+                payload[int(r["out_offset"]):int(r["out_offset"]) + int(r["nr_out"])].tofile(g)
+            rs_started.add(c)
+            rs_index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * a.window, "first_out": int(r["first_out"]),
+                                       "nr_out": int(r["nr_out"]), "begins": int(r["flags"]) & 1, "file_offset": at}) + "\n")
 
     def write_runs(runs, payload):
         for r in runs:
@@ -120,9 +154,13 @@ def scan(a):
                 d_rec, rec_stride, nw, _ = lv.device_view()
                 rows = (d_iq, 2 * stride) if iq_form else (d_pcm, stride)
                 gate.process_device(rows[0], rows[1], nout, d_rec, rec_stride, nw, stream=eng.stream)
+                if rr:
+                    rr.process_device(*gate.device_view(), stream=eng.stream)
             rec = lv.fetch()
             if gate:
                 write_runs(*gate.fetch())
+            if rr:
+                write_resampled(*rr.fetch())
             for c, (freq, _) in enumerate(chans):
                 for r in rec[c]:
                     out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
@@ -135,7 +173,13 @@ def scan(a):
                                   "open_share": (float(opened[c]) / float(windows[c])) if windows[c] else 0.0}) + "\n")
     if gate:
         gate.flush_device(stream=eng.stream)  # the windows pre-roll still held back; none with P = 0
+        if rr:
+            rr.process_device(*gate.device_view(), stream=eng.stream)
         write_runs(*gate.fetch())
+        if rr:
+            write_resampled(*rr.fetch())
+            rs_index.close()
+            rr.close()
         index.close()
         gate.close()
     lv.close()
@@ -228,6 +272,8 @@ def bench(a):
     for P in [int(x) for x in str(a.gate_preroll).split(",")]:
         line = bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P, p0)
         p0 = line if P == 0 else p0
+    if not iq_form:
+        bench_runrs(a, pkg, torch, rows, in_stride, nout, timed)
     for o in (lv, eng):
         o.close()
 
@@ -316,6 +362,77 @@ def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P=0, p0=None
     return out
 
 
+def bench_runrs(a, pkg, torch, rows, in_stride, nout, timed):
+    """the burst resampler behind the gate, 4/5 with 81 taps, on whole windows of the PCM rows.  Per mask one gate call leaves its
+    runs and payload in place and the stage is timed on that device view over and over: from the second call on a run's
+    first_window is behind what its channel expects, so every call begins every stretch anew and does the same work.  The plain
+    resampler (v_dot2 form forced) on the full rows alternates with it in the same process, in rotating order."""
+    b = pkg.binding
+    nch, W, I, D = a.bench_channels, a.window, 4, 5
+    nw = nout // W
+    nb = nw * W
+    taps = (np.hanning(81) * 0.2 * 16384.0).astype(np.int16)
+    probe = pkg.Level(nch, nout, W, device=0)
+    probe.process_device(rows, in_stride, nb)
+    energy = probe.fetch()["energy"]
+    probe.close()
+    thr = int(np.median(energy))
+    sq = pkg.Level(nch, nout, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+    sq.process_device(rows, in_stride, nb)
+    scene = sq.fetch()
+    d_scene, scene_stride, _, _ = sq.device_view()
+    masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "scene": scene["open"]}
+    keep, recs = [], {"scene": (d_scene, scene_stride)}
+    for name in ("all_closed", "all_open"):
+        r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+        r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+        r["open"] = masks[name]
+        t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+        keep.append(t)
+        recs[name] = (t.data_ptr(), nw)
+    plain = pkg.Resampler(nch, taps, I, D, nb, device=0, force_dot2=True)
+    rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=nout, device=0)
+
+    def run_plain():
+        plain.process_device(rows, in_stride, nb)
+
+    out = {"bench": "runrs_stage", "channels": nch, "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I,
+           "decimate": D, "taps": int(taps.size), "reps": a.reps, "calls_per_rep": a.inner}
+    for name in ("all_closed", "all_open", "scene"):
+        gate = pkg.Gate(nch, nout, W, device=0)
+        gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+        view = gate.device_view()
+
+        def run_rr():
+            rr.process_device(*view)
+
+        variants = [("runrs", run_rr), ("plain", run_plain)]
+        for _, fn in variants:
+            timed(fn, 3)
+        try:  # the totals alone: the payload stays on the device
+            rr.fetch(max_runs=0, max_elems=0)
+            nr_runs, nr_out = 0, 0
+        except pkg.MfmError as err:
+            if err.code != b.MFM_E_NOMEM:
+                raise
+            nr_runs, nr_out = err.needed
+        got = {n: [] for n, _ in variants}
+        for rep in range(a.reps):
+            k = rep % len(variants)
+            for vname, fn in variants[k:] + variants[:k]:
+                got[vname].append(timed(fn, a.inner))
+        (rm, rsd), (pm, psd) = _stats(got["runrs"]), _stats(got["plain"])
+        ratio = rm / pm
+        ratio_se = ratio * math.sqrt(rsd * rsd / a.reps / (rm * rm) + psd * psd / a.reps / (pm * pm))
+        out[name] = {"open_share": float(masks[name].astype(bool).mean()), "runs": int(nr_runs),
+                     "input_samples": int(masks[name].astype(bool).sum()) * W, "output_samples": int(nr_out), "runrs_ms": rm, "runrs_sd": rsd, "plain_dot2_ms": pm, "plain_dot2_sd": psd,
+                     "runrs_over_plain": ratio, "runrs_over_plain_se": ratio_se}
+        gate.close()
+    print(json.dumps(out))
+    for o in (rr, plain, sq):
+        o.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config")
@@ -333,6 +450,8 @@ def main():
     ap.add_argument("--summary", action="store_true")
     ap.add_argument("--gate-out", default=None)
     ap.add_argument("--gate-preroll", default="0", help="pre-roll windows of the gate; with --bench one or several, as 0,1,4")
+    ap.add_argument("--gate-resample", default=None, help="I/D: resample the gate's runs on the device (with --gate-out, --form pcm)")
+    ap.add_argument("--resample-taps", default=None, help="JSON file whose lpfCoeffs are the resampler's taps")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)

@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "mfm_gate_device_view", "mfm_hosttwin_gate_call",
     "mfm_gate_set_preroll", "mfm_gate_flush_device", "mfm_hosttwin_gate_call_preroll",
     "mfm_resampler_get_form", "mfm_hosttwin_resampler_form", "mfm_hosttwin_resampler_matrix_block",
+    "mfm_runrs_create", "mfm_runrs_destroy", "mfm_runrs_process_device", "mfm_runrs_fetch", "mfm_runrs_device_view",
+    "mfm_hosttwin_runrs_plan", "mfm_hosttwin_runrs_call",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -194,6 +196,29 @@ MFM_GATE_MAX_PREROLL = 63               # pre-roll windows at most
 MFM_GATE_MAX_HISTORY_BYTES = 1 << 30    # one history buffer of a gate with pre-roll at most
 # numpy view of struct mfm_gate_run (24 bytes)
 GATE_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("payload_offset", "<u8"), ("channel", "<u4"), ("nr_windows", "<u4")])
+
+
+class RunrsConfig(C.Structure):
+    """struct mfm_runrs_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("interpolate", C.c_uint32),
+                ("decimate", C.c_uint32), ("window_samples", C.c_uint32), ("max_windows", C.c_uint32), ("max_runs", C.c_uint32),
+                ("invert", C.c_uint32), ("flags", C.c_uint32), ("max_in_samples", C.c_uint32), ("preroll_windows", C.c_uint32)]
+
+
+class RunrsRun(C.Structure):
+    _fields_ = [("first_window", C.c_uint64), ("out_offset", C.c_uint64), ("first_out", C.c_uint64), ("channel", C.c_uint32),
+                ("nr_out", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+MFM_RUNRS_MAX_LDS_BYTES = 49152
+MFM_RUNRS_BEGINS = 1                                    # mfm_runrs_run.flags bit 0: the run begins a stretch
+MFM_RUNRS_OVER_OWN, MFM_RUNRS_OVER_GATE = 1, 2          # d_totals[2]
+MFM_RUNRS_GATE_OUT_OF_STEP, MFM_RUNRS_GATE_BAD_RUNS = 1, 2  # d_totals[3]
+MFM_RUNRS_NO_WINDOW = (1 << 64) - 1                     # mfm_runrs_state.expected of a channel without a stretch
+# numpy views of struct mfm_runrs_run (40 bytes) and struct mfm_runrs_state (24 bytes, the host twin's per-channel state)
+RUNRS_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("out_offset", "<u8"), ("first_out", "<u8"), ("channel", "<u4"),
+                            ("nr_out", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+RUNRS_STATE_DTYPE = np.dtype([("expected", "<u8"), ("outs", "<u8"), ("phase", "<u4"), ("pending", "<u4")])
 
 
 class FlexConfig(C.Structure):
@@ -433,6 +458,15 @@ def load_library():
                                                    C.c_size_t, i16p, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_hosttwin_gate_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, i16p, C.c_size_t, C.c_size_t, i16p, vp,
                                            C.c_size_t, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_runrs_create.argtypes = [C.POINTER(vp), C.POINTER(RunrsConfig), i16p, C.c_size_t]
+    lib.mfm_runrs_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runrs_destroy.restype = None
+    lib.mfm_runrs_process_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mfm_runrs_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_runrs_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_hosttwin_runrs_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    lib.mfm_hosttwin_runrs_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i16p, C.c_size_t, vp, i16p,
+                                            vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_resampler_get_form.argtypes = [vp, C.POINTER(ResamplerForm)]
     lib.mfm_hosttwin_resampler_form.argtypes = [C.POINTER(ResamplerConfig), i16p, C.c_size_t, C.POINTER(ResamplerForm)]
     lib.mfm_hosttwin_resampler_matrix_block.argtypes = [C.POINTER(ResamplerConfig), i16p, C.c_size_t, C.c_uint32, i16p, C.c_size_t, i16p]
@@ -1368,6 +1402,134 @@ def hosttwin_gate_call_preroll(window_samples, elems_per_sample, preroll_windows
     if rc < 0:
         err = MfmError(rc, "mfm_hosttwin_gate_call_preroll",
                        lib.mfm_last_error().decode() if rc == MFM_E_STATE else lib.mfm_strerror(rc).decode())
+        err.needed = (nr.value, ne.value)
+        raise err
+    return runs[:nr.value].copy(), payload[:ne.value].copy()
+
+
+def runrs_phase_len(nr_coeffs, interpolate):
+    """taps per phase (csrc/mfm_rs_plan.h): ceil(nr_coeffs / interpolate) rounded up to a multiple of 4"""
+    return ((nr_coeffs + interpolate - 1) // interpolate + 3) & ~3
+
+
+class RunResampler:
+    """mfm_runrs: the runs of a Gate's device view through the rational resampler, one fresh resampler per stretch of
+    consecutive windows of a channel; one RUNRS_RUN_DTYPE per gate run and a dense int16 payload.  max_windows / max_runs 0
+    take the defaults of a Gate made from the same nr_channels, max_in_samples, window_samples and preroll_windows."""
+
+    def __init__(self, nr_channels, coeffs_q14, interpolate, decimate, window_samples, max_in_samples=0, preroll_windows=0,
+                 max_windows=0, max_runs=0, invert=False, device=0, flags=0, abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        cfg = RunrsConfig(abi_version, device, nr_channels, interpolate, decimate, window_samples, max_windows, max_runs, int(invert),
+                          flags, max_in_samples, preroll_windows)
+        co = np.ascontiguousarray(coeffs_q14, dtype=np.int16)
+        rc = self.lib.mfm_runrs_create(C.byref(self.h), C.byref(cfg), _i16p(co) if co.size else None, co.size)
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_create")
+        self.nr_channels = nr_channels
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runrs_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_payload, d_totals, stream=None):
+        """the three addresses of Gate.device_view(), after the gate's process_device or flush_device on the same stream"""
+        rc = self.lib.mfm_runrs_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_process_device")
+
+    def fetch(self, max_runs=None, max_elems=None):
+        """(runs, payload) of the last call: RUNRS_RUN_DTYPE [nr_runs] and int16 [nr_elems].  With max_runs or max_elems too
+        small: MfmError(MFM_E_NOMEM) whose `needed` attribute is the (runs, elements) that would fit"""
+        nr, ne = C.c_size_t(), C.c_size_t()
+        if max_runs is None or max_elems is None:
+            rc = self.lib.mfm_runrs_fetch(self.h, None, 0, C.byref(nr), None, 0, C.byref(ne))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below, with the untouched buffers
+                self._raise(rc, "mfm_runrs_fetch")
+            max_runs = nr.value if max_runs is None else max_runs
+            max_elems = ne.value if max_elems is None else max_elems
+        runs = np.zeros(max(max_runs, 1), RUNRS_RUN_DTYPE)
+        payload = np.zeros(max(max_elems, 1), np.int16)
+        rc = self.lib.mfm_runrs_fetch(self.h, runs.ctypes.data, max_runs, C.byref(nr), payload.ctypes.data, max_elems, C.byref(ne))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runrs_fetch")
+            except MfmError as err:
+                err.needed = (nr.value, ne.value)
+                err.buffers = (runs, payload)
+                raise
+        return runs[:nr.value].copy(), payload[:ne.value].copy()
+
+    def device_view(self):
+        """(d_runs, d_payload, d_totals): device addresses of the last call's runs, payload and the four uint64 totals
+        (runs, output elements, overflow, gate error)"""
+        r, p, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runrs_device_view(self.h, C.byref(r), C.byref(p), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_device_view")
+        return r.value, p.value, t.value
+
+
+def hosttwin_runrs_state(nr_channels, nr_coeffs, interpolate):
+    """(state, pending) of the host twin at the start of a stream: RUNRS_STATE_DTYPE [C] and int16 [C][plen]"""
+    state = np.zeros(nr_channels, RUNRS_STATE_DTYPE)
+    state["expected"] = MFM_RUNRS_NO_WINDOW
+    return state, np.zeros((nr_channels, runrs_phase_len(nr_coeffs, interpolate)), np.int16)
+
+
+def hosttwin_runrs_plan(interpolate, decimate, plen, phase, pending, nr_samples):
+    """mfm_hosttwin_runrs_plan: the closed form for arrays of cases; returns (nr_out uint64, phase uint32, pending uint32)"""
+    lib = load_library()
+    ph = np.ascontiguousarray(phase, dtype=np.uint32)
+    pe = np.ascontiguousarray(pending, dtype=np.uint32)
+    ns = np.ascontiguousarray(nr_samples, dtype=np.uint64)
+    assert ph.shape == pe.shape == ns.shape and ph.ndim == 1
+    n = ph.size
+    out, pho, peo = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+    rc = lib.mfm_hosttwin_runrs_plan(interpolate, decimate, plen, ph.ctypes.data, pe.ctypes.data, ns.ctypes.data, n, out.ctypes.data,
+                                     pho.ctypes.data, peo.ctypes.data)
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runrs_plan", lib.mfm_strerror(rc).decode())
+    return out[:n], pho[:n], peo[:n]
+
+
+def hosttwin_runrs_call(window_samples, coeffs_q14, interpolate, decimate, state, pending, gate_runs, gate_payload, invert=False,
+                        max_runs=None, max_elems=None):
+    """mfm_hosttwin_runrs_call: one call of the burst resampler on the CPU.  state RUNRS_STATE_DTYPE [C] and pending int16
+    [C][plen] (hosttwin_runrs_state) are updated in place; gate_runs GATE_RUN_DTYPE and gate_payload int16 are one gate call's
+    result; returns (runs, payload)"""
+    lib = load_library()
+    state, pending = np.asarray(state), np.asarray(pending)
+    co = np.ascontiguousarray(coeffs_q14, dtype=np.int16)
+    assert state.dtype == RUNRS_STATE_DTYPE and state.flags.c_contiguous and pending.dtype == np.int16 and pending.flags.c_contiguous
+    nch = state.shape[0]
+    assert pending.shape == (nch, runrs_phase_len(max(co.size, 1), max(interpolate, 1)))
+    gr = np.ascontiguousarray(gate_runs, dtype=GATE_RUN_DTYPE).reshape(-1)
+    gp = np.ascontiguousarray(gate_payload, dtype=np.int16).reshape(-1)
+    if max_runs is None:
+        max_runs = gr.size
+    if max_elems is None:  # a run of n samples that meets p <= plen pending ones produces at most (n + p) I / D + 1 outputs
+        max_elems = (gp.size + gr.size * pending.shape[1]) * max(interpolate, 1) // max(decimate, 1) + gr.size
+    runs = np.zeros(max(max_runs, 1), RUNRS_RUN_DTYPE)
+    payload = np.zeros(max(max_elems, 1), np.int16)
+    nr, ne = C.c_size_t(), C.c_size_t()
+    rc = lib.mfm_hosttwin_runrs_call(nch, window_samples, interpolate, decimate, int(invert), _i16p(co) if co.size else None, co.size,
+                                     state.ctypes.data, _i16p(pending), gr.ctypes.data if gr.size else None, gr.size,
+                                     gp.ctypes.data if gp.size else None, gp.size, runs.ctypes.data, max_runs, C.byref(nr),
+                                     payload.ctypes.data, max_elems, C.byref(ne))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runrs_call", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
         err.needed = (nr.value, ne.value)
         raise err
     return runs[:nr.value].copy(), payload[:ne.value].copy()

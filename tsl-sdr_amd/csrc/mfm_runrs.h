@@ -1,0 +1,88 @@
+/*
+ * mfm_runrs.h - the arithmetic of the burst resampler (mfm_runrs_*, include/multifm_hip.h), stated once for the kernels
+ * and for the host twin (mfm_hosttwin_runrs_call) the CPU tests run: whether a run of the gate continues its channel's
+ * stretch, how many outputs it produces and what it leaves behind, and where a sample of the run lies.
+ *
+ * A run's input is the virtual stream "the channel's pending samples, then the run's payload samples": `pending` of the
+ * first and nsamp = nr_windows * W of the second.  Output j of the run reads plen samples from position
+ * floor((p0 + j D) / I) of that stream with the taps of phase (p0 + j D) % I, where p0 < I is the phase the stretch had
+ * reached (filter/polyphase_fir.c:206-211 unrolled), and exists only while strictly more than plen samples are unconsumed
+ * (polyphase_fir.c:184).
+ */
+#ifndef MFM_RUNRS_H
+#define MFM_RUNRS_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/multifm_hip.h"
+
+#define MFM_RUNRS_NO_WINDOW (~0ull) /* `expected` of a channel that has no stretch to continue */
+
+/* per-channel state between calls: struct mfm_runrs_state (include/multifm_hip.h); the pending samples stand beside it,
+ * plen per channel, stored as received (inversion is applied on use) */
+
+/* what a run starts from */
+struct mfm_runrs_start {
+    uint64_t first_out;
+    uint32_t phase, pending;
+    uint32_t begins; /* 1: a new stretch (fresh resampler) */
+};
+
+/* first_in_channel: the run is the channel's first of this call.  Only that one can continue: the gate's runs within a call
+ * are maximal, so a later run of the channel has a closed window in front of it */
+__host__ __device__ inline mfm_runrs_start mfm_runrs_start_of(const mfm_runrs_state &st, bool first_in_channel, uint64_t first_window)
+{
+    mfm_runrs_start s;
+    const bool cont = first_in_channel && st.expected != MFM_RUNRS_NO_WINDOW && st.expected == first_window;
+    s.first_out = cont ? st.outs : 0ull;
+    s.phase = cont ? st.phase : 0u;
+    s.pending = cont ? st.pending : 0u;
+    s.begins = cont ? 0u : 1u;
+    return s;
+}
+
+struct mfm_runrs_step {
+    uint64_t nr_out;  /* outputs of the run */
+    uint64_t pos_end; /* samples of the virtual stream consumed */
+    uint32_t phase;   /* left behind */
+    uint32_t pending; /* left behind: tot - pos_end, never more than plen */
+};
+
+/* The number of j >= 0 with floor((p0 + j D) / I) <= tot - plen - 1, in closed form: with M = tot - plen - 1 >= 0 that is
+ * p0 + j D <= M I + I - 1, so j <= ((M + 1) I - 1 - p0) / D; p0 < I keeps the numerator non-negative.  The walk then stands
+ * at t = p0 + nr_out D: position t / I >= M + 1, so at most plen samples stay pending; a ratio that mfm_rs_plan.h accepts
+ * (ceil(D / I) <= plen) keeps the position at or below tot. */
+__host__ __device__ inline mfm_runrs_step mfm_runrs_plan_run(uint32_t I, uint32_t D, uint32_t plen, uint32_t p0, uint32_t pending, uint64_t nsamp)
+{
+    mfm_runrs_step r;
+    const uint64_t tot = (uint64_t)pending + nsamp;
+    if (tot <= plen) {
+        r.nr_out = 0;
+        r.pos_end = 0;
+        r.phase = p0;
+        r.pending = (uint32_t)tot;
+        return r;
+    }
+    r.nr_out = ((tot - plen) * I - 1u - p0) / D + 1u;
+    const uint64_t t = p0 + r.nr_out * D;
+    r.pos_end = t / I;
+    r.phase = (uint32_t)(t - r.pos_end * I);
+    r.pending = (uint32_t)(tot - r.pos_end);
+    return r;
+}
+
+/* sample v of the run's virtual stream; outside it (the zero-padded taps of a phase read there) 0.  `invert` negates on
+ * int16 storage (decoder/decoder.c:624) */
+__host__ __device__ inline int16_t mfm_runrs_sample(const int16_t *pend, uint32_t pending, const int16_t *run, uint64_t nsamp, int64_t v, bool invert)
+{
+    int16_t s = 0;
+    if (v >= 0 && v < (int64_t)pending) {
+        s = pend[v];
+    } else if (v >= (int64_t)pending && (uint64_t)(v - pending) < nsamp) {
+        s = run[v - pending];
+    }
+    return invert ? (int16_t)(-s) : s;
+}
+
+#endif /* MFM_RUNRS_H */

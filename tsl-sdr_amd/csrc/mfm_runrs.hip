@@ -1,0 +1,813 @@
+/*
+ * mfm_runrs.hip - the burst resampler: the runs the squelch gate left in its dense payload go through the rational resampler
+ * (filter/polyphase_fir.c:162-233) on the device, one fresh resampler per stretch of consecutive windows of a channel.  See
+ * include/multifm_hip.h for the boundary, mfm_runrs.h for the arithmetic, mfm_rs_plan.h for the phase length and the ratios
+ * that are refused.
+ *
+ * The input is what mfm_gate_device_view returns; how many runs and samples a call carries is read on the device, so the
+ * host never waits and every launch is sized from the capacities fixed at create.
+ *
+ *   rr_plan_kernel   one lane per run.  A run that is its channel's first of the call and whose first_window is the number
+ *                    the channel expects continues the stretch (phase, pending samples, outputs so far from the channel's
+ *                    state); every other run begins one.  nr_out in closed form (mfm_runrs_plan_run), the descriptor, the
+ *                    run's count of workgroups for the FIR kernel; a channel's last run leaves its index for the state kernel.
+ *   rr_scan_kernel   one block: exclusive scan of nr_out (out_offset) and of the workgroup counts over all runs (a thread
+ *                    sums a stretch of runs, the waves scan by lane shifts, the 16 wave sums go through LDS), the totals and
+ *                    the flags.  No atomics.
+ *   rr_fir_kernel    the hot path.  A workgroup takes 1024 consecutive outputs of one run, which it finds from its index by
+ *                    binary search in the scanned workgroup counts.  It stages the coefficient pairs and its input window -
+ *                    the channel's pending samples, then the run's payload samples - into LDS: the window is laid out so
+ *                    that every group of eight samples is 16 bytes in the payload too, and a group that lies wholly in the
+ *                    run is one 16-byte load, the others (the pending samples, the run's ends) go one by one.  A thread
+ *                    computes four outputs 256 apart as v_dot2_i32_i16 over sample pairs with wrapping int32; where
+ *                    256 D is a multiple of I they share a phase and its pairs sit in registers (NP = 4 .. 32, as the NP
+ *                    instances of mfm_resampler.hip), otherwise the pairs are read from LDS (NP = 0).
+ *   rr_state_kernel  one block per channel: the state the channel's last run leaves (expected window, phase, outputs,
+ *                    pending samples) goes into the OTHER of two state buffers; a channel without a run, and every channel
+ *                    when the call raised a flag, copies its state over.  The buffers are used in turn, so the FIR kernel
+ *                    and this one read the old state while the new one is written.
+ *
+ * Nothing is floating point and nothing goes through an atomic.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/multifm_hip.h"
+
+extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
+#include "mfm_numerics.h"
+#include "mfm_rs_plan.h"
+#include "mfm_runrs.h"
+
+namespace {
+
+constexpr uint32_t RR_NT = 256, RR_OPT = 4, RR_OPB = RR_NT * RR_OPT; /* FIR kernel: threads, outputs per thread / per workgroup */
+constexpr uint32_t RR_SCAN_THREADS = 1024;
+constexpr uint32_t RR_NONE = 0xffffffffu;                            /* d_chan_last: the channel has no run in this call */
+constexpr uint32_t RR_T_RUNS = 0, RR_T_ELEMS = 1, RR_T_OVERFLOW = 2, RR_T_GATE = 3; /* d_totals[], ours and the gate's */
+constexpr uint32_t RR_MAX_RATIO_TERM = 1u << 20;                     /* I and D at most: 1024 D + I stays far below 2^32 */
+constexpr uint64_t RR_MAX_OUT = 1ull << 31;                          /* output elements per call at most */
+
+struct RrPlan { /* what the plan pass found for a run and the FIR and state kernels need again */
+    uint32_t p0, pending;
+};
+
+/* everything create derives from the configuration and the taps, without a device */
+struct RrGeom {
+    uint32_t C = 0, W = 0, I = 0, D = 0, plen = 0, np = 0;
+    uint32_t coef_bytes = 0, x_cap = 0, lds_bytes = 0;
+    uint64_t cap_windows = 0, cap_runs = 0, cap_elems = 0, out_cap = 0, max_blocks = 0;
+    RsPlan rs;
+    char err[224] = "";
+};
+
+int rr_geometry(const mfm_runrs_config &cfg, const int16_t *coeffs, size_t nr_coeffs, bool with_caps, RrGeom &g)
+{
+    if (cfg.abi_version != MFM_ABI_VERSION || 0 == cfg.nr_channels || cfg.nr_channels > 65535u) {
+        snprintf(g.err, sizeof(g.err), "abi_version or nr_channels (1 .. 65535) out of range");
+        return MFM_E_INVAL;
+    }
+    if (cfg.flags != 0) {
+        snprintf(g.err, sizeof(g.err), "flags must be 0: the burst resampler has no DC blocker and no sign-bit output");
+        return MFM_E_INVAL;
+    }
+    if (0 == cfg.interpolate || 0 == cfg.decimate || cfg.interpolate > RR_MAX_RATIO_TERM || cfg.decimate > RR_MAX_RATIO_TERM) {
+        snprintf(g.err, sizeof(g.err), "interpolate and decimate must be 1 .. %u", RR_MAX_RATIO_TERM);
+        return MFM_E_INVAL;
+    }
+    if (0 == cfg.window_samples || cfg.window_samples > (1u << 20)) {
+        snprintf(g.err, sizeof(g.err), "window_samples must be 1 .. 2^20, the window of a gate with elems_per_sample == 1 (PCM payloads only)");
+        return MFM_E_INVAL;
+    }
+    if (!coeffs || !nr_coeffs) {
+        snprintf(g.err, sizeof(g.err), "no taps");
+        return MFM_E_INVAL;
+    }
+    /* [plen] and [walk]: mfm_rs_plan.h's rules, through its planner (the v_dot2 form, one sample per call: only these two
+     * of its checks can fail) */
+    mfm_resampler_config rc{};
+    rc.abi_version = MFM_ABI_VERSION;
+    rc.nr_channels = cfg.nr_channels;
+    rc.interpolate = cfg.interpolate;
+    rc.decimate = cfg.decimate;
+    rc.max_in_samples = 1;
+    rc.flags = MFM_RS_FORCE_DOT2;
+    const int planned = rs_plan(rc, coeffs, nr_coeffs, g.rs);
+    g.C = cfg.nr_channels;
+    g.W = cfg.window_samples;
+    g.I = cfg.interpolate;
+    g.D = cfg.decimate;
+    g.plen = g.rs.plen;
+    /* LDS of a FIR workgroup: the coefficient image, then the input window of RR_OPB outputs.  The window begins up to 7
+     * samples early (16-byte groups), its last output starts at most 1023 D / I + 1 samples in, reads plen samples and the
+     * zero pairs that round NP up, and the whole is rounded up to eight: at most 1023 D / I + plen + 31 samples */
+    const uint64_t coef = ((uint64_t)g.I * g.plen * 2u + 15u) & ~15ull;
+    const uint64_t x_cap = (((uint64_t)RR_OPB * g.D) / g.I + g.plen + 40u) & ~7ull;
+    if (g.plen && coef + x_cap * 2u > MFM_RUNRS_MAX_LDS_BYTES) {
+        snprintf(g.err, sizeof(g.err),
+                 "the coefficient image (%u phases of %u taps: %llu bytes) and the input window of a workgroup (%llu bytes) exceed "
+                 "MFM_RUNRS_MAX_LDS_BYTES = %u bytes of LDS",
+                 g.I, g.plen, (unsigned long long)coef, (unsigned long long)(x_cap * 2u), MFM_RUNRS_MAX_LDS_BYTES);
+        return MFM_E_INVAL;
+    }
+    if (planned != MFM_OK) {
+        snprintf(g.err, sizeof(g.err), "%s", g.rs.err[0] ? g.rs.err : "the resampler's planner refuses this ratio and these taps");
+        return MFM_E_INVAL;
+    }
+    g.coef_bytes = (uint32_t)coef;
+    g.x_cap = (uint32_t)x_cap;
+    g.lds_bytes = (uint32_t)(coef + x_cap * 2u);
+    const bool reg_coef = ((uint64_t)RR_NT * g.D) % g.I == 0 && g.plen / 2u <= RS_PAIRS_MAX;
+    g.np = reg_coef ? ((g.plen / 2u + 3u) / 4u) * 4u : 0u;
+    if (!with_caps) {
+        return MFM_OK;
+    }
+    /* capacities: what one gate call can hand over */
+    const uint64_t max_win = cfg.max_in_samples ? (uint64_t)cfg.max_in_samples / g.W + 1u : 0u;
+    const uint64_t per_chan = max_win > cfg.preroll_windows ? max_win : cfg.preroll_windows; /* a flush emits up to P windows */
+    if ((0 == cfg.max_windows || 0 == cfg.max_runs) && 0 == cfg.max_in_samples) {
+        snprintf(g.err, sizeof(g.err), "max_windows or max_runs is 0 (the gate's default) and max_in_samples is 0: give the gate's max_in_samples");
+        return MFM_E_INVAL;
+    }
+    g.cap_windows = cfg.max_windows ? cfg.max_windows : (uint64_t)g.C * per_chan;
+    if (cfg.max_runs) {
+        g.cap_runs = cfg.max_runs;
+    } else {
+        const uint64_t most = (uint64_t)g.C * ((per_chan + 1u) / 2u); /* two runs of a channel have a closed window between them */
+        g.cap_runs = g.cap_windows < most ? g.cap_windows : most;
+    }
+    g.cap_elems = g.cap_windows * g.W;
+    /* a run of n samples that meets p <= plen pending ones produces at most (n + p) I / D + 1 outputs */
+    g.out_cap = ((g.cap_elems + g.cap_runs * g.plen) * g.I) / g.D + g.cap_runs;
+    g.max_blocks = g.out_cap / RR_OPB + g.cap_runs; /* a run of n outputs takes n / RR_OPB + 1 workgroups at most */
+    if (g.cap_runs >= RR_MAX_OUT || g.cap_elems >= (1ull << 40) || g.out_cap >= RR_MAX_OUT || g.max_blocks >= RR_MAX_OUT) {
+        snprintf(g.err, sizeof(g.err), "max_windows * window_samples * interpolate / decimate must stay below 2^31 output samples per call (%llu)",
+                 (unsigned long long)g.out_cap);
+        return MFM_E_INVAL;
+    }
+    return MFM_OK;
+}
+
+struct RrCall {
+    const mfm_gate_run *gruns;
+    const int16_t *gpayload;
+    const uint64_t *gtotals;
+    const mfm_runrs_state *chan_old;
+    mfm_runrs_state *chan_new;
+    const int16_t *pend_old; /* [C][pend_stride] */
+    int16_t *pend_new;
+    const int16_t *phase;    /* [I][plen] */
+    mfm_runrs_run *runs;
+    RrPlan *plan;
+    uint32_t *nblk;          /* [cap_runs] workgroups per run */
+    uint32_t *blk_base;      /* [cap_runs + 1] their exclusive scan */
+    uint32_t *bad;           /* [cap_runs] */
+    uint32_t *chan_last;     /* [C] */
+    uint32_t *ctl;           /* [0] workgroups of the FIR kernel, [1] runs */
+    uint64_t *totals;
+    int16_t *y;
+    uint64_t cap_runs, cap_elems, out_cap;
+    uint32_t C, W, I, D, plen, pend_stride, invert, coef_bytes;
+};
+
+/* 1 / 2 when the gate's totals say that nothing may be read: its own flags, or more than this object was made for */
+__device__ __forceinline__ bool rr_refused(const RrCall &A, uint64_t &over, uint64_t &gate)
+{
+    over = A.gtotals[RR_T_OVERFLOW] ? MFM_RUNRS_OVER_GATE : 0u;
+    gate = A.gtotals[RR_T_GATE] ? MFM_RUNRS_GATE_OUT_OF_STEP : 0u;
+    if (!over && !gate && (A.gtotals[RR_T_RUNS] > A.cap_runs || A.gtotals[RR_T_ELEMS] > A.cap_elems)) {
+        over = MFM_RUNRS_OVER_OWN;
+    }
+    return over || gate;
+}
+
+__global__ __launch_bounds__(256) void rr_plan_kernel(const RrCall A)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t over, gate;
+    if (rr_refused(A, over, gate) || r >= A.gtotals[RR_T_RUNS]) { /* surplus lanes, and every lane of a refused call */
+        return;
+    }
+    const uint64_t n = A.gtotals[RR_T_RUNS];
+    const mfm_gate_run g = A.gruns[r];
+    const uint64_t nsamp = (uint64_t)g.nr_windows * A.W;
+    if (g.channel >= A.C || g.payload_offset > A.gtotals[RR_T_ELEMS] || nsamp > A.gtotals[RR_T_ELEMS] - g.payload_offset) {
+        A.bad[r] = 1; /* not a gate's run: the scan raises the flag and nothing goes out */
+        A.nblk[r] = 0;
+        A.runs[r].nr_out = 0;
+        return;
+    }
+    const bool first = r == 0 || A.gruns[r - 1].channel != g.channel;
+    const bool last = r + 1 == n || A.gruns[r + 1].channel != g.channel;
+    const mfm_runrs_start s = mfm_runrs_start_of(A.chan_old[g.channel], first, g.first_window);
+    const mfm_runrs_step st = mfm_runrs_plan_run(A.I, A.D, A.plen, s.phase, s.pending, nsamp);
+    mfm_runrs_run o;
+    o.first_window = g.first_window;
+    o.out_offset = 0; /* the scan */
+    o.first_out = s.first_out;
+    o.channel = g.channel;
+    o.nr_out = (uint32_t)st.nr_out; /* below 2^31: nsamp is within the capacity */
+    o.flags = s.begins ? MFM_RUNRS_BEGINS : 0u;
+    o.reserved = 0;
+    A.runs[r] = o;
+    A.plan[r] = RrPlan{ s.phase, s.pending };
+    A.nblk[r] = (uint32_t)((st.nr_out + RR_OPB - 1u) / RR_OPB);
+    A.bad[r] = 0;
+    if (last) {
+        A.chan_last[g.channel] = (uint32_t)r;
+    }
+}
+
+/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
+__device__ __forceinline__ uint64_t rr_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
+        if (lane >= (uint32_t)o) {
+            inc += ((uint64_t)hi << 32) | lo;
+        }
+    }
+    if (lane == 63) {
+        lds[wave] = inc;
+    }
+    __syncthreads();
+    uint64_t base = 0, all = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < RR_SCAN_THREADS / 64; i++) {
+        const uint64_t t = lds[i];
+        base += i < wave ? t : 0u;
+        all += t;
+    }
+    __syncthreads();
+    *total = all;
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_kernel(const RrCall A)
+{
+    __shared__ uint64_t lds[RR_SCAN_THREADS / 64];
+    uint64_t over, gate;
+    if (rr_refused(A, over, gate)) {
+        if (threadIdx.x == 0) {
+            A.totals[RR_T_RUNS] = 0;
+            A.totals[RR_T_ELEMS] = 0;
+            A.totals[RR_T_OVERFLOW] = over;
+            A.totals[RR_T_GATE] = gate;
+            A.ctl[0] = 0;
+            A.ctl[1] = 0;
+        }
+        return;
+    }
+    const uint64_t n = A.gtotals[RR_T_RUNS]; /* <= cap_runs < 2^32 */
+    const uint64_t per = (n + RR_SCAN_THREADS - 1) / RR_SCAN_THREADS;
+    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
+    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    uint64_t so = 0, sb = 0;
+    uint32_t sw = 0;
+#pragma unroll 1
+    for (uint64_t r = r0; r < r1; r++) {
+        so += A.runs[r].nr_out;
+        sb += A.nblk[r];
+        sw |= A.bad[r];
+    }
+    /* the workgroup counts ride in the scan of the outputs: a run has at most nr_out / 1024 + 1 of them, so their sum over
+     * fewer than 2^31 runs of fewer than 2^31 outputs stays below 2^32, and the outputs' sum below 2^62 */
+    uint64_t to, tb;
+    uint64_t bo = rr_block_scan(so, lds, &to);
+    uint64_t bb = rr_block_scan(sb, lds, &tb);
+    /* run lists that are not a gate's (overlapping payload ranges) could ask for more than the output holds */
+    const bool wrong = __syncthreads_or(sw != 0) != 0 || to > A.out_cap;
+#pragma unroll 1
+    for (uint64_t r = r0; r < r1; r++) {
+        A.runs[r].out_offset = bo;
+        A.blk_base[r] = (uint32_t)bb;
+        bo += A.runs[r].nr_out;
+        bb += A.nblk[r];
+    }
+    if (threadIdx.x == 0) {
+        A.blk_base[n] = (uint32_t)tb;
+        A.totals[RR_T_RUNS] = wrong ? 0u : n;
+        A.totals[RR_T_ELEMS] = wrong ? 0u : to;
+        A.totals[RR_T_OVERFLOW] = 0;
+        A.totals[RR_T_GATE] = wrong ? MFM_RUNRS_GATE_BAD_RUNS : 0u;
+        A.ctl[0] = wrong ? 0u : (uint32_t)tb;
+        A.ctl[1] = wrong ? 0u : (uint32_t)n;
+    }
+}
+
+/* eight samples as one 16-byte access */
+struct __attribute__((aligned(16))) rr_x8 {
+    uint32_t d[4];
+};
+
+__device__ __forceinline__ uint32_t rr_neg2(uint32_t w) /* both int16 halves negated on int16 storage */
+{
+    return ((0u - (w & 0xffffu)) & 0xffffu) | ((0u - (w >> 16)) << 16);
+}
+
+/* NP > 0: coefficient pairs of the thread's phase in registers, NP = pairs per phase rounded up to a multiple of 4 (the
+ * padding pairs are zero); NP = 0: pairs read from LDS, any phase length */
+template <int NP>
+__global__ __launch_bounds__(RR_NT) void rr_fir_kernel(const RrCall A)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t rr_smem[];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    if (b >= A.ctl[0]) { /* surplus workgroups: the launch is sized from the capacity */
+        return;
+    }
+    /* the run of workgroup b: the last r with blk_base[r] <= b (runs without output have no workgroup) */
+    uint32_t lo = 0, hi = A.ctl[1];
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (A.blk_base[mid] <= b) {
+            lo = mid;
+        } else {
+            hi = mid;
+        }
+    }
+    const uint32_t r = lo;
+    const mfm_gate_run g = A.gruns[r];
+    const RrPlan P = A.plan[r];
+    const uint32_t n_out = A.runs[r].nr_out, c = A.runs[r].channel;
+    const uint64_t y0 = A.runs[r].out_offset;
+    const uint32_t j0 = (b - A.blk_base[r]) * RR_OPB;
+    const uint32_t cnt = n_out - j0 < RR_OPB ? n_out - j0 : RR_OPB;
+    const uint64_t nsamp = (uint64_t)g.nr_windows * A.W;
+    const int16_t *run = A.gpayload + g.payload_offset;
+    const int16_t *pend = A.pend_old + (size_t)c * A.pend_stride;
+    const bool invert = A.invert != 0;
+
+    uint32_t *ph_s = reinterpret_cast<uint32_t *>(rr_smem); /* [I][plen / 2] coefficient pairs */
+    const uint32_t npairs = A.plen / 2u;                    /* plen is a multiple of 4 */
+    int16_t *x_s = reinterpret_cast<int16_t *>(rr_smem + A.coef_bytes);
+    /* filter/polyphase_fir.c:206-211 unrolled to output j of the run: position (p0 + j D) / I, phase (p0 + j D) % I.  One
+     * 64-bit division per workgroup; within it everything is relative and fits 32 bits (1024 D + I < 2^31) */
+    const uint64_t t0 = P.p0 + (uint64_t)j0 * A.D;
+    const uint64_t pos0 = t0 / A.I;
+    const uint32_t ph0 = (uint32_t)(t0 - pos0 * A.I);
+    /* x_s[0] is the sample `adj` in front of position pos0, where the payload is 16-byte aligned */
+    const int64_t e0 = (int64_t)pos0 - (int64_t)P.pending; /* position pos0 as an index into the run's samples */
+    const uint32_t adj = (uint32_t)((reinterpret_cast<uintptr_t>(run) / 2u + (uint64_t)e0) & 7u);
+    const uint32_t last_rel = (ph0 + (cnt - 1u) * A.D) / A.I;
+    const uint32_t nwin = (adj + last_rel + A.plen + 16u + 7u) & ~7u; /* <= x_cap (rr_geometry) */
+    for (uint32_t i = tid; i < A.I * npairs; i += RR_NT) {
+        ph_s[i] = reinterpret_cast<const uint32_t *>(A.phase)[i];
+    }
+    for (uint32_t k = tid; k < nwin / 8u; k += RR_NT) {
+        const int64_t e = e0 - (int64_t)adj + 8 * (int64_t)k;
+        if (e >= 0 && (uint64_t)e + 8u <= nsamp) {
+            rr_x8 w = *reinterpret_cast<const rr_x8 *>(run + e);
+            if (invert) {
+                w.d[0] = rr_neg2(w.d[0]);
+                w.d[1] = rr_neg2(w.d[1]);
+                w.d[2] = rr_neg2(w.d[2]);
+                w.d[3] = rr_neg2(w.d[3]);
+            }
+            *reinterpret_cast<rr_x8 *>(x_s + 8u * k) = w;
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 8; i++) {
+                x_s[8u * k + i] = mfm_runrs_sample(pend, P.pending, run, nsamp, e + (int64_t)P.pending + i, invert);
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t *x32 = reinterpret_cast<const uint32_t *>(x_s);
+
+    /* one division per thread: its outputs are RR_NT apart, so position and phase advance by constants */
+    const uint32_t t_first = ph0 + tid * A.D;
+    uint32_t pos = adj + t_first / A.I, ph = t_first % A.I;
+    const uint32_t step_pos = (RR_NT * A.D) / A.I, step_ph = (RR_NT * A.D) % A.I;
+    constexpr bool REGCOEF = NP > 0;
+    uint32_t cw[REGCOEF ? NP : 1];
+    if (REGCOEF) {
+        /* 256 D is a multiple of I: outputs tid, tid + 256, ... of this workgroup have the same phase */
+#pragma unroll
+        for (uint32_t i = 0; i < (uint32_t)NP; i++) {
+            cw[i] = i < npairs ? ph_s[ph * npairs + i] : 0u;
+        }
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < RR_OPT; u++) {
+        const uint32_t j = tid + u * RR_NT;
+        if (j >= cnt) {
+            break;
+        }
+        const uint32_t *xw = x32 + (pos >> 1);
+        const uint32_t sh = (pos & 1u) * 16u;
+        int32_t acc = 0; /* filter/utils.c:94-103, int32 wrap-around */
+        uint32_t lo2 = xw[0];
+        if (REGCOEF) {
+#pragma unroll
+            for (uint32_t i = 0; i < (uint32_t)NP; i++) {
+                const uint32_t hi2 = xw[i + 1];
+                const uint32_t pr = __builtin_amdgcn_alignbit(hi2, lo2, sh); /* samples pos + 2i, pos + 2i + 1 */
+                asm("v_dot2_i32_i16 %0, %1, %2, %0" : "+v"(acc) : "v"(pr), "v"(cw[i]));
+                lo2 = hi2;
+            }
+        } else {
+            const uint32_t *cp = ph_s + ph * npairs;
+            for (uint32_t i = 0; i < npairs; i++) {
+                const uint32_t hi2 = xw[i + 1];
+                const uint32_t pr = __builtin_amdgcn_alignbit(hi2, lo2, sh);
+                asm("v_dot2_i32_i16 %0, %1, %2, %0" : "+v"(acc) : "v"(pr), "v"(cp[i]));
+                lo2 = hi2;
+            }
+        }
+        asm volatile("s_nop 2" : "+v"(acc)); /* a DOT result needs 3 wait states before other VALU code reads it */
+        A.y[y0 + j0 + j] = (int16_t)mfm_r14_wide(acc); /* utils.c:112 */
+        pos += step_pos;
+        ph += step_ph;
+        if (ph >= A.I) {
+            ph -= A.I;
+            pos += 1u;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void rr_state_kernel(const RrCall A)
+{
+    __shared__ uint32_t s_last;
+    const uint32_t c = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        s_last = A.chan_last[c];
+        A.chan_last[c] = RR_NONE; /* for the next call */
+    }
+    __syncthreads();
+    const uint32_t last = s_last;
+    const bool refused = A.totals[RR_T_OVERFLOW] != 0 || A.totals[RR_T_GATE] != 0;
+    const mfm_runrs_state old = A.chan_old[c];
+    const int16_t *po = A.pend_old + (size_t)c * A.pend_stride;
+    int16_t *pn = A.pend_new + (size_t)c * A.pend_stride;
+    if (last == RR_NONE || refused) { /* the state stays */
+        if (tid == 0) {
+            A.chan_new[c] = old;
+        }
+        for (uint32_t i = tid; i < old.pending; i += blockDim.x) {
+            pn[i] = po[i];
+        }
+        return;
+    }
+    const mfm_gate_run g = A.gruns[last];
+    const RrPlan P = A.plan[last];
+    const uint64_t nsamp = (uint64_t)g.nr_windows * A.W;
+    const mfm_runrs_step st = mfm_runrs_plan_run(A.I, A.D, A.plen, P.p0, P.pending, nsamp);
+    if (tid == 0) {
+        mfm_runrs_state nw;
+        nw.expected = g.first_window + g.nr_windows;
+        nw.outs = A.runs[last].first_out + st.nr_out;
+        nw.phase = st.phase;
+        nw.pending = st.pending;
+        A.chan_new[c] = nw;
+    }
+    const int16_t *run = A.gpayload + g.payload_offset;
+    for (uint32_t i = tid; i < st.pending; i += blockDim.x) { /* stored as received: inversion is applied on use */
+        pn[i] = mfm_runrs_sample(po, P.pending, run, nsamp, (int64_t)(st.pos_end + i), false);
+    }
+}
+
+thread_local char g_rr_error[256] = "";
+
+int rr_fail(int code, const char *msg)
+{
+    snprintf(g_rr_error, sizeof(g_rr_error), "%s", msg);
+    mfm_internal_set_error(g_rr_error);
+    return code;
+}
+
+} /* namespace */
+
+#define RR_TRY(expr)                                                                                         \
+    do {                                                                                                     \
+        hipError_t err_ = (expr);                                                                            \
+        if (err_ != hipSuccess) {                                                                            \
+            snprintf(g_rr_error, sizeof(g_rr_error), "%s failed: %s", #expr, hipGetErrorString(err_));       \
+            mfm_internal_set_error(g_rr_error);                                                              \
+            return err_ == hipErrorOutOfMemory ? MFM_E_NOMEM : MFM_E_DEVICE;                                 \
+        }                                                                                                    \
+    } while (0)
+
+struct mfm_runrs {
+    mfm_runrs_config cfg{};
+    RrGeom g;
+    uint32_t pend_stride = 0;
+    int16_t *d_phase = nullptr;
+    mfm_runrs_state *d_chan[2] = { nullptr, nullptr }; /* used in turn: a call reads [cur] and writes [cur ^ 1] */
+    int16_t *d_pend[2] = { nullptr, nullptr };
+    uint32_t cur = 0;
+    RrPlan *d_plan = nullptr;
+    uint32_t *d_nblk = nullptr, *d_blk_base = nullptr, *d_bad = nullptr, *d_chan_last = nullptr, *d_ctl = nullptr;
+    uint64_t *d_totals = nullptr;
+    mfm_runrs_run *d_runs = nullptr;
+    int16_t *d_out = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool have_call = false;
+};
+
+extern "C" {
+
+int mfm_runrs_create(struct mfm_runrs **prr, const struct mfm_runrs_config *cfg, const int16_t *coeffs, size_t nr_coeffs)
+{
+    if (!prr || !cfg) {
+        return MFM_E_INVAL;
+    }
+    *prr = nullptr;
+    mfm_runrs *rr = new (std::nothrow) mfm_runrs();
+    if (!rr) {
+        return MFM_E_NOMEM;
+    }
+    if (rr_geometry(*cfg, coeffs, nr_coeffs, true, rr->g) != MFM_OK) {
+        const int rc = rr_fail(MFM_E_INVAL, rr->g.err);
+        delete rr;
+        return rc;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device < 0 || cfg->device >= ndev) {
+        delete rr;
+        return MFM_E_DEVICE; /* no CPU path */
+    }
+    rr->cfg = *cfg;
+    const RrGeom &g = rr->g;
+    RsTables tab;
+    rs_build_tables(g.rs, coeffs, tab);
+    std::vector<mfm_runrs_state> fresh(g.C);
+    for (auto &st : fresh) {
+        st = mfm_runrs_state{ MFM_RUNRS_NO_WINDOW, 0, 0, 0 };
+    }
+    rr->pend_stride = (g.plen + 7u) & ~7u;
+    const size_t nruns = (size_t)(g.cap_runs ? g.cap_runs : 1), nout = (size_t)(g.out_cap ? g.out_cap : 1);
+    *prr = rr; /* from here on the caller's destroy frees what was allocated */
+    RR_TRY(hipSetDevice(cfg->device));
+    RR_TRY(hipMalloc(&rr->d_phase, tab.phase.size() * 2));
+    RR_TRY(hipMemcpy(rr->d_phase, tab.phase.data(), tab.phase.size() * 2, hipMemcpyHostToDevice));
+    for (int i = 0; i < 2; i++) {
+        RR_TRY(hipMalloc(&rr->d_chan[i], (size_t)g.C * sizeof(mfm_runrs_state)));
+        RR_TRY(hipMemcpy(rr->d_chan[i], fresh.data(), (size_t)g.C * sizeof(mfm_runrs_state), hipMemcpyHostToDevice));
+        RR_TRY(hipMalloc(&rr->d_pend[i], (size_t)g.C * rr->pend_stride * 2));
+        RR_TRY(hipMemset(rr->d_pend[i], 0, (size_t)g.C * rr->pend_stride * 2));
+    }
+    RR_TRY(hipMalloc(&rr->d_plan, nruns * sizeof(RrPlan)));
+    RR_TRY(hipMalloc(&rr->d_nblk, nruns * 4));
+    RR_TRY(hipMalloc(&rr->d_blk_base, (nruns + 1) * 4));
+    RR_TRY(hipMalloc(&rr->d_bad, nruns * 4));
+    RR_TRY(hipMalloc(&rr->d_chan_last, (size_t)g.C * 4));
+    RR_TRY(hipMemset(rr->d_chan_last, 0xff, (size_t)g.C * 4));
+    RR_TRY(hipMalloc(&rr->d_ctl, 2 * 4));
+    RR_TRY(hipMemset(rr->d_ctl, 0, 2 * 4));
+    RR_TRY(hipMalloc(&rr->d_totals, 4 * 8));
+    RR_TRY(hipMemset(rr->d_totals, 0, 4 * 8));
+    RR_TRY(hipMalloc(&rr->d_runs, nruns * sizeof(mfm_runrs_run)));
+    RR_TRY(hipMalloc(&rr->d_out, nout * 2));
+    RR_TRY(hipDeviceSynchronize());
+    return MFM_OK;
+}
+
+void mfm_runrs_destroy(struct mfm_runrs **prr)
+{
+    if (!prr || !*prr) {
+        return;
+    }
+    mfm_runrs *rr = *prr;
+    (void)hipSetDevice(rr->cfg.device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(rr->d_phase);
+    for (int i = 0; i < 2; i++) {
+        (void)hipFree(rr->d_chan[i]);
+        (void)hipFree(rr->d_pend[i]);
+    }
+    (void)hipFree(rr->d_plan);
+    (void)hipFree(rr->d_nblk);
+    (void)hipFree(rr->d_blk_base);
+    (void)hipFree(rr->d_bad);
+    (void)hipFree(rr->d_chan_last);
+    (void)hipFree(rr->d_ctl);
+    (void)hipFree(rr->d_totals);
+    (void)hipFree(rr->d_runs);
+    (void)hipFree(rr->d_out);
+    delete rr;
+    *prr = nullptr;
+}
+
+int mfm_runrs_process_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                             void *stream)
+{
+    if (!rr || !d_runs || !d_payload || !d_totals) {
+        return MFM_E_INVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RR_TRY(hipSetDevice(rr->cfg.device));
+    if (rr->have_call && rr->last_stream != s) {
+        RR_TRY(hipStreamSynchronize(rr->last_stream)); /* state lives on the device; keep calls ordered */
+    }
+    const RrGeom &g = rr->g;
+    const uint32_t cur = rr->cur;
+    const RrCall A{ d_runs,      d_payload,       d_totals,  rr->d_chan[cur], rr->d_chan[cur ^ 1u], rr->d_pend[cur], rr->d_pend[cur ^ 1u],
+                    rr->d_phase, rr->d_runs,      rr->d_plan, rr->d_nblk,     rr->d_blk_base,       rr->d_bad,       rr->d_chan_last,
+                    rr->d_ctl,   rr->d_totals,    rr->d_out, g.cap_runs,      g.cap_elems,          g.out_cap,       g.C,
+                    g.W,         g.I,             g.D,       g.plen,          rr->pend_stride,      rr->cfg.invert,  g.coef_bytes };
+    if (g.cap_runs) {
+        hipLaunchKernelGGL(rr_plan_kernel, dim3((uint32_t)((g.cap_runs + 255u) / 256u)), dim3(256), 0, s, A);
+        RR_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(rr_scan_kernel, dim3(1), dim3(RR_SCAN_THREADS), 0, s, A);
+    RR_TRY(hipGetLastError());
+    if (g.max_blocks) {
+        const dim3 grid((uint32_t)g.max_blocks);
+        switch (g.np / 4u) {
+        case 1: hipLaunchKernelGGL((rr_fir_kernel<4>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        case 2: hipLaunchKernelGGL((rr_fir_kernel<8>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        case 3: hipLaunchKernelGGL((rr_fir_kernel<12>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        case 4: hipLaunchKernelGGL((rr_fir_kernel<16>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        case 5: hipLaunchKernelGGL((rr_fir_kernel<20>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        case 6: hipLaunchKernelGGL((rr_fir_kernel<24>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        case 7: hipLaunchKernelGGL((rr_fir_kernel<28>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        case 8: hipLaunchKernelGGL((rr_fir_kernel<32>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        default: hipLaunchKernelGGL((rr_fir_kernel<0>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+        }
+        RR_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(rr_state_kernel, dim3(g.C), dim3(64), 0, s, A);
+    RR_TRY(hipGetLastError());
+    rr->cur ^= 1u;
+    rr->last_stream = s;
+    rr->have_call = true;
+    return MFM_OK;
+}
+
+int mfm_runrs_fetch(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                    size_t *nr_elems)
+{
+    if (!rr || !nr_runs || !nr_elems || (!runs && max_runs) || (!payload && max_elems)) {
+        return MFM_E_INVAL;
+    }
+    *nr_runs = 0;
+    *nr_elems = 0;
+    if (!rr->have_call) {
+        return MFM_OK;
+    }
+    RR_TRY(hipSetDevice(rr->cfg.device));
+    RR_TRY(hipStreamSynchronize(rr->last_stream));
+    uint64_t t[4];
+    RR_TRY(hipMemcpy(t, rr->d_totals, sizeof(t), hipMemcpyDeviceToHost));
+    *nr_runs = (size_t)t[RR_T_RUNS];
+    *nr_elems = (size_t)t[RR_T_ELEMS];
+    if (t[RR_T_GATE] & MFM_RUNRS_GATE_OUT_OF_STEP) {
+        return rr_fail(MFM_E_STATE, "the gate's call was out of step with its level stage");
+    }
+    if (t[RR_T_GATE]) {
+        return rr_fail(MFM_E_STATE, "the run list is not a gate's: a run names a channel or a payload range that does not exist");
+    }
+    if (t[RR_T_OVERFLOW] & MFM_RUNRS_OVER_GATE) {
+        return rr_fail(MFM_E_STATE, "the gate's call overflowed its max_open_windows");
+    }
+    if (t[RR_T_OVERFLOW]) {
+        return rr_fail(MFM_E_STATE, "the gate's call exceeds max_windows or max_runs");
+    }
+    if (t[RR_T_RUNS] > max_runs || t[RR_T_ELEMS] > max_elems) {
+        return MFM_E_NOMEM;
+    }
+    if (t[RR_T_RUNS]) {
+        RR_TRY(hipMemcpy(runs, rr->d_runs, (size_t)t[RR_T_RUNS] * sizeof(mfm_runrs_run), hipMemcpyDeviceToHost));
+    }
+    if (t[RR_T_ELEMS]) {
+        RR_TRY(hipMemcpy(payload, rr->d_out, (size_t)t[RR_T_ELEMS] * 2, hipMemcpyDeviceToHost));
+    }
+    return MFM_OK;
+}
+
+int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_runs, const int16_t **d_payload, const uint64_t **d_totals)
+{
+    if (!rr) {
+        return MFM_E_INVAL;
+    }
+    if (d_runs) {
+        *d_runs = rr->d_runs;
+    }
+    if (d_payload) {
+        *d_payload = rr->d_out;
+    }
+    if (d_totals) {
+        *d_totals = rr->d_totals;
+    }
+    return MFM_OK;
+}
+
+int mfm_hosttwin_runrs_plan(uint32_t interpolate, uint32_t decimate, uint32_t plen, const uint32_t *phase, const uint32_t *pending,
+                            const uint64_t *nr_samples, size_t n, uint64_t *nr_out, uint32_t *phase_out, uint32_t *pending_out)
+{
+    if (!interpolate || !decimate || !plen || interpolate > RR_MAX_RATIO_TERM || decimate > RR_MAX_RATIO_TERM ||
+        (decimate + interpolate - 1) / interpolate > plen || (n && (!phase || !pending || !nr_samples || !nr_out || !phase_out || !pending_out))) {
+        return MFM_E_INVAL;
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (phase[i] >= interpolate || pending[i] > plen || nr_samples[i] >= (1ull << 40)) {
+            return MFM_E_INVAL;
+        }
+    }
+    for (size_t i = 0; i < n; i++) {
+        const mfm_runrs_step st = mfm_runrs_plan_run(interpolate, decimate, plen, phase[i], pending[i], nr_samples[i]);
+        nr_out[i] = st.nr_out;
+        phase_out[i] = st.phase;
+        pending_out[i] = st.pending;
+    }
+    return MFM_OK;
+}
+
+int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert,
+                            const int16_t *coeffs, size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending,
+                            const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload, size_t nr_gate_elems,
+                            struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                            size_t *nr_elems)
+{
+    if (!state || !pending || !nr_runs || !nr_elems || (!gate_runs && nr_gate_runs) || (!gate_payload && nr_gate_elems) || (!runs && max_runs) ||
+        (!payload && max_elems)) {
+        return MFM_E_INVAL;
+    }
+    mfm_runrs_config cfg{};
+    cfg.abi_version = MFM_ABI_VERSION;
+    cfg.nr_channels = nr_channels;
+    cfg.interpolate = interpolate;
+    cfg.decimate = decimate;
+    cfg.window_samples = window_samples;
+    RrGeom g;
+    if (rr_geometry(cfg, coeffs, nr_coeffs, false, g) != MFM_OK) {
+        return rr_fail(MFM_E_INVAL, g.err);
+    }
+    RsTables tab;
+    rs_build_tables(g.rs, coeffs, tab);
+    const uint32_t I = g.I, D = g.D, plen = g.plen, W = g.W;
+    /* the plan pass and the scan */
+    std::vector<mfm_runrs_start> start(nr_gate_runs);
+    std::vector<mfm_runrs_step> step(nr_gate_runs);
+    uint64_t total = 0;
+    for (size_t r = 0; r < nr_gate_runs; r++) {
+        const mfm_gate_run &gr = gate_runs[r];
+        const uint64_t nsamp = (uint64_t)gr.nr_windows * W;
+        if (gr.channel >= nr_channels || gr.payload_offset > nr_gate_elems || nsamp > nr_gate_elems - gr.payload_offset) {
+            return rr_fail(MFM_E_INVAL, "the run list is not a gate's: a run names a channel or a payload range that does not exist");
+        }
+        const bool first = r == 0 || gate_runs[r - 1].channel != gr.channel;
+        start[r] = mfm_runrs_start_of(state[gr.channel], first, gr.first_window);
+        step[r] = mfm_runrs_plan_run(I, D, plen, start[r].phase, start[r].pending, nsamp);
+        total += step[r].nr_out;
+    }
+    *nr_runs = nr_gate_runs;
+    *nr_elems = (size_t)total;
+    if (nr_gate_runs > max_runs || total > max_elems) {
+        return MFM_E_NOMEM; /* nothing written, the state included: the caller may call again */
+    }
+    /* the outputs, then the state each channel's last run leaves (which reads the old pending samples, as the outputs do) */
+    uint64_t at = 0;
+    for (size_t r = 0; r < nr_gate_runs; r++) {
+        const mfm_gate_run &gr = gate_runs[r];
+        const uint64_t nsamp = (uint64_t)gr.nr_windows * W;
+        const int16_t *run = gate_payload + gr.payload_offset;
+        const int16_t *pend = pending + (size_t)gr.channel * plen;
+        mfm_runrs_run &o = runs[r];
+        o.first_window = gr.first_window;
+        o.out_offset = at;
+        o.first_out = start[r].first_out;
+        o.channel = gr.channel;
+        o.nr_out = (uint32_t)step[r].nr_out;
+        o.flags = start[r].begins ? MFM_RUNRS_BEGINS : 0u;
+        o.reserved = 0;
+        for (uint64_t j = 0; j < step[r].nr_out; j++) {
+            const uint64_t t = start[r].phase + j * D, pos = t / I, ph = t - pos * I;
+            uint32_t acc = 0; /* filter/utils.c:94-103, int32 wrap-around */
+            for (uint32_t k = 0; k < plen; k++) {
+                const int32_t x = mfm_runrs_sample(pend, start[r].pending, run, nsamp, (int64_t)(pos + k), invert != 0);
+                acc += (uint32_t)(x * (int32_t)tab.phase[(size_t)ph * plen + k]);
+            }
+            payload[at + j] = (int16_t)mfm_r14_wide((int32_t)acc); /* utils.c:112 */
+        }
+        at += step[r].nr_out;
+    }
+    std::vector<int16_t> keep(plen);
+    for (size_t r = 0; r < nr_gate_runs; r++) {
+        const mfm_gate_run &gr = gate_runs[r];
+        if (r + 1 != nr_gate_runs && gate_runs[r + 1].channel == gr.channel) {
+            continue;
+        }
+        const uint64_t nsamp = (uint64_t)gr.nr_windows * W;
+        int16_t *pend = pending + (size_t)gr.channel * plen;
+        for (uint32_t i = 0; i < step[r].pending; i++) {
+            keep[i] = mfm_runrs_sample(pend, start[r].pending, gate_payload + gr.payload_offset, nsamp, (int64_t)(step[r].pos_end + i), false);
+        }
+        memcpy(pend, keep.data(), (size_t)step[r].pending * 2);
+        mfm_runrs_state &st = state[gr.channel];
+        st.expected = gr.first_window + gr.nr_windows;
+        st.outs = start[r].first_out + step[r].nr_out;
+        st.phase = step[r].phase;
+        st.pending = step[r].pending;
+    }
+    return MFM_OK;
+}
+
+} /* extern "C" */
