@@ -871,8 +871,8 @@ int mfm_level_device_view(struct mfm_level *p, const struct mfm_level_record **d
  * sequence as the level object whose records it reads; the rows may be others than those the level was measured on
  * (squelch on the IQ energy, gate the PCM) as long as the numbering matches.  The samples of an unfinished window are
  * carried on the device, at most W - 1 per channel: output does not depend on how a stream is cut into calls (nr_in = 0
- * and several calls in a row shorter than W included).  Create refuses W * elems_per_sample above 2^20 (the carry buffer
- * is one window of int16 per channel) with MFM_E_INVAL and a message.
+ * and several calls in a row shorter than W included).  Create refuses W * elems_per_sample above 2^20 (the carry is
+ * one window of int16 per channel, kept twice: it is the history below with P = 0) with MFM_E_INVAL and a message.
  *
  * Window k of channel c goes out exactly when the record of (c, k) has open != 0: the opening window is among them (the
  * squelch is stepped after it), the tail is what hang_windows gives; no closed window in front of an opening is emitted.

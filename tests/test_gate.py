@@ -234,9 +234,58 @@ def test_hosttwin_refuses_what_the_stage_refuses(pkg):
     _check_crossing(pkg, stream, mask, first, second)
 
 
+def test_hosttwin_refusals_on_a_later_call_leave_a_filled_carry(pkg):
+    """the refusals above at the second call, where the carry holds the two samples the first call left: MFM_E_STATE "out of
+    step", MFM_E_NOMEM with the needed sizes, and the carry unchanged after each"""
+    b = pkg.binding
+    W, E, nch, stream, mask = _crossing_case(pkg)
+    carry = np.zeros((nch, W), np.int16)
+    first = b.hosttwin_gate_call(W, E, 0, stream[:, :12], carry, records_of(pkg, mask, 0, 2))
+    assert np.array_equal(carry[:, :2], stream[:, 10:12]) and carry.any()
+    kept = carry.copy()
+    with pytest.raises(pkg.MfmError) as ei:  # 13 samples from 12 complete three windows, not two
+        b.hosttwin_gate_call(W, E, 12, stream[:, 12:], carry, records_of(pkg, mask, 2, 4))
+    assert ei.value.code == b.MFM_E_INVAL and np.array_equal(carry, kept)
+    rec = records_of(pkg, mask, 2, 5)
+    rec["window"][0, 2] -= 1
+    with pytest.raises(pkg.MfmError) as ei:
+        b.hosttwin_gate_call(W, E, 12, stream[:, 12:], carry, rec)
+    assert ei.value.code == b.MFM_E_STATE and "out of step" in str(ei.value) and np.array_equal(carry, kept)
+    for kw in (dict(max_runs=1), dict(max_elems=2 * W - 1)):
+        with pytest.raises(pkg.MfmError) as ei:
+            b.hosttwin_gate_call(W, E, 12, stream[:, 12:], carry, records_of(pkg, mask, 2, 5), **kw)
+        assert ei.value.code == b.MFM_E_NOMEM and ei.value.needed == (2, 2 * W) and np.array_equal(carry, kept)
+    second = b.hosttwin_gate_call(W, E, 12, stream[:, 12:], carry, records_of(pkg, mask, 2, 5))
+    _check_crossing(pkg, stream, mask, first, second)
+
+
+def _history_case(pkg):
+    """W = 5000, E = 2: a window is 10 000 elements, two pieces of the copy kernel.  The first call completes no window and
+    leaves 9200 elements of window 0 on the device, so in the second call that window's piece 0 (8192 elements) lies wholly
+    in the history and its piece 1 across the seam; the third call begins 9214 elements into window 2"""
+    W, E, nch = 5000, 2, 3
+    n = 4 * W + 13
+    cuts = [4600, 2 * W + 7, n - 4600 - 2 * W - 7]
+    assert 4600 * E >= 8192 and all(m > 0 for m in cuts)
+    rng = np.random.RandomState(61)
+    stream = rng.randint(-32768, 32768, size=(nch, n * E)).astype(np.int16)
+    masks = {"open": np.ones((nch, 4), bool), "bernoulli": rng.rand(nch, 4) < 0.5}
+    first = masks["bernoulli"][:, [0, 2]]
+    assert first.any() and not first.all()  # of the windows that begin in the history some go out and some do not
+    return W, E, nch, stream, cuts, masks
+
+
+def test_hosttwin_piece_wholly_in_the_carry(pkg):
+    W, E, nch, stream, cuts, masks = _history_case(pkg)
+    for kind, mask in masks.items():
+        carry = np.zeros((nch, W * E), np.int16)
+        drive(pkg, stream, mask, W, E, cuts, lambda pos, rows, rec: pkg.binding.hosttwin_gate_call(W, E, pos, rows, carry, rec),
+              f"history case, mask {kind}")
+
+
 def test_create_refuses_bad_configurations(pkg):
-    """argument checks come before the device is touched: MFM_E_INVAL with or without a GPU.  The carry buffer bounds
-    window_samples * elems_per_sample at 2^20"""
+    """argument checks come before the device is touched: MFM_E_INVAL with or without a GPU.  The carry (the history's
+    unfinished window) bounds window_samples * elems_per_sample at 2^20"""
     b = pkg.binding
     good = dict(nr_channels=2, max_in_samples=4096, window_samples=64)
 
@@ -425,6 +474,17 @@ def test_gpu_wide_copy_path(pkg):
         lead = 3 if We_odd else 0
         _device_calls(pkg, torch, stream, mask, W, E, [3 * 4096 + 17, n - 3 * 4096 - 17], n * E + (1 if We_odd else 8), lead,
                       f"wide E {E} lead {lead}", 3 * 4096 + 17)
+
+
+@pytest.mark.gpu
+def test_gpu_piece_wholly_in_the_history_without_preroll(pkg):
+    """_history_case on the device: a piece that lies wholly in the history takes the 16-byte loop from the history's pointer, the
+    next one the loop across the seam; rows 16-byte aligned with a stride that is a multiple of 8, and off by 3 with an odd one"""
+    import torch
+    W, E, nch, stream, cuts, masks = _history_case(pkg)
+    for lead, pad in ((0, 8), (3, 1)):
+        for kind, mask in masks.items():
+            _device_calls(pkg, torch, stream, mask, W, E, cuts, stream.shape[1] + pad, lead, f"history case lead {lead} mask {kind}", max(cuts))
 
 
 @pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""Pre-roll of the squelch gate (mfm_gate_set_preroll, mfm_gate_flush_device, csrc/mfm_gate_preroll.hip): with P pre-roll
+"""Pre-roll of the squelch gate (mfm_gate_set_preroll, mfm_gate_flush_device, csrc/mfm_gate.hip): with P pre-roll
 windows, window k of a channel goes out exactly when any of its records k .. k + P is open, P windows late, and a flush ends
 the stream with the P windows still held back.
 
@@ -240,15 +240,16 @@ def test_hosttwin_preroll_refuses_and_leaves_its_state(pkg):
 
 
 def test_preroll_kernels_use_no_scratch_and_do_not_spill():
-    """the code object's notes of build/mfm_gate_preroll.o (tools/kernel_regs.py): four kernels, no private segment, no spilled
-    register"""
-    obj = os.path.join(ROOT, "tsl-sdr_amd", "build", "mfm_gate_preroll.o")
-    assert os.path.exists(obj), "the build leaves tsl-sdr_amd/build/mfm_gate_preroll.o"
+    """the code object's notes of build/mfm_gate.o (tools/kernel_regs.py), which holds the gate's one set of kernels, pre-roll
+    or not: exactly these five, no private segment, no spilled register"""
+    obj = os.path.join(ROOT, "tsl-sdr_amd", "build", "mfm_gate.o")
+    assert os.path.exists(obj), "the build leaves tsl-sdr_amd/build/mfm_gate.o"
     if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
         pytest.skip("no llvm tools here")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), obj], capture_output=True, text=True, check=True).stdout
     lines = [ln for ln in out.splitlines() if "vgpr" in ln]
-    assert sorted(ln.split()[0] for ln in lines) == ["gtp_copy_kernel", "gtp_count_kernel", "gtp_hist_kernel", "gtp_runs_kernel"], out
+    assert sorted(ln.split()[0] for ln in lines) == ["gt_copy_kernel", "gt_count_kernel", "gt_hist_kernel", "gt_runs_kernel",
+                                                     "gt_scan_kernel"], out
     for ln in lines:
         m = re.search(r"vgpr\s+(\d+) agpr\s+\d+ spill\s+(\d+) \| sgpr\s+\d+ spill\s+(\d+) \| lds\s+(\d+) scratch\s+(\d+)", ln)
         assert m and int(m.group(1)) <= 128 and (int(m.group(2)), int(m.group(3)), int(m.group(5))) == (0, 0, 0), ln
@@ -466,6 +467,33 @@ def test_gpu_preroll_zero_and_a_flush_are_the_plain_gate(pkg):
             again()
         assert ei.value.code == b.MFM_E_STATE
     gate.close()
+
+
+@pytest.mark.gpu
+def test_gpu_setter_back_to_zero_is_the_plain_gate(pkg):
+    """set_preroll(2), then set_preroll(0): the history is sized for P = 0 again.  The crossing case, then windows of two pieces
+    with calls that begin deep in the unfinished window (tg._history_case); each ends in a flush that returns nothing"""
+    W, E, nch, stream, mask = tg._crossing_case(pkg)
+    gate = pkg.Gate(nch, 16, W)
+    gate.set_preroll(2)
+    gate.set_preroll(0)
+    first = gate.process_host(stream[:, :12], tg.records_of(pkg, mask, 0, 2))
+    second = gate.process_host(stream[:, 12:], tg.records_of(pkg, mask, 2, 5))
+    tg._check_crossing(pkg, stream, mask, first, second)
+    gate.flush_device()
+    runs, payload = gate.fetch()
+    assert runs.size == 0 and payload.size == 0
+    gate.close()
+    W, E, nch, stream, cuts, masks = tg._history_case(pkg)
+    for kind, mask in masks.items():
+        gate = pkg.Gate(nch, max(cuts), W, elems_per_sample=E)
+        gate.set_preroll(2)
+        gate.set_preroll(0)
+        tg.drive(pkg, stream, mask, W, E, cuts, lambda pos, rows, rec: gate.process_host(rows, rec), f"back to zero, mask {kind}")
+        gate.flush_device()
+        runs, payload = gate.fetch()
+        assert runs.size == 0 and payload.size == 0
+        gate.close()
 
 
 @pytest.mark.gpu

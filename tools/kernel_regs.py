@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Register and spill counts of the kernel instances in an object file: tools/kernel_regs.py build/x.o [name filter]
 
-The gate's kernels are in two objects: build/mfm_gate.o (gt_count, gt_scan, gt_runs, gt_copy, gt_carry) and
-build/mfm_gate_preroll.o (gtp_count, gtp_runs, gtp_copy, gtp_hist)."""
+The gate's kernels are in one object, build/mfm_gate.o: gt_count, gt_scan, gt_runs, gt_copy, gt_hist."""
 import re, subprocess, sys, tempfile, os
 LLVM = "/opt/rocm/lib/llvm/bin/"
 obj = sys.argv[1]

@@ -321,7 +321,7 @@ def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P=0, p0=None
     out = {"bench": "gate_stage", "channels": nch, "form": a.form, "window": W, "samples_per_channel": nb, "windows_per_channel": nw,
            "reps": a.reps, "calls_per_rep": a.inner, "row_base_mod_16": int(rows % 16), "in_stride_elems_mod_8": int(in_stride % 8),
            "window_elems_mod_8": int(W * E % 8), "preroll": P,
-           "history_bytes": 2 * nch * (((P + 1) * W * E + 7) & ~7) * 2 if P else 0}
+           "history_bytes": 2 * nch * (((P + 1) * W * E + 7) & ~7) * 2}
     # which alignment path the copy takes: the payload slot of a window is a multiple of W * E elements off a 16-byte base, its
     # source (window k of a row) lies at row base + k * W * E elements
     aligned = rows % 16 == 0 and in_stride % 8 == 0 and (W * E) % 8 == 0

@@ -1,10 +1,10 @@
 /*
  * mfm_gate.h - the arithmetic of the squelch gate stage (mfm_gate_*, include/multifm_hip.h), stated once for the kernels
- * and for the host twin (mfm_hosttwin_gate_call) the CPU tests run: how a call is cut into windows, how a channel's open
- * windows form runs, and where each window lies in the payload and in the call's rows.
+ * and for the host twin (mfm_hosttwin_gate_call_preroll) the CPU tests run: how a call is cut into windows, which windows go
+ * out, how they form runs, and where each window lies in the payload, in the call's rows and in the history.
  *
  * A row is a run of int16 ELEMENTS (E per sample); a window is We = W * E of them.  A channel's records of one call are
- * walked 64 at a time: `mask` has bit i set when window i of the chunk is open (on the device one ballot), and everything
+ * walked 64 at a time: `mask` has bit i set when window i of the chunk goes out (mfm_gate_dilate of the record bits), and everything
  * below is popcounts and trailing-zero counts on that mask plus four numbers carried from chunk to chunk.
  */
 #ifndef MFM_GATE_H
@@ -13,14 +13,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MFM_GATE_MAX_WINDOW_ELEMS (1u << 20) /* W * elems_per_sample at most: the carry buffer is this per channel */
+#define MFM_GATE_MAX_WINDOW_ELEMS (1u << 20) /* W * elems_per_sample at most: the history is up to 64 of these per channel */
 #define MFM_GATE_CLOSED 0xffffffffu          /* payload slot of a window that does not go out */
 
 /* what a call of nr_in samples at stream position pos (samples) covers */
 struct mfm_gate_cut {
     uint64_t k0;   /* window the call's first sample lies in */
     uint32_t nwin; /* windows the call completes: k0 .. k0 + nwin - 1 */
-    uint32_t r0;   /* ELEMENTS of window k0 that earlier calls left in the carry */
+    uint32_t r0;   /* ELEMENTS of window k0 that earlier calls left: the carry, the history's last part */
     uint32_t r1;   /* elements of the unfinished window k0 + nwin that this call leaves there */
 };
 
@@ -35,10 +35,11 @@ __host__ __device__ inline mfm_gate_cut mfm_gate_cut_of(uint64_t pos, uint64_t n
     return c;
 }
 
-/* element j of window m of the call (m counted from k0): its index in the call's row when >= 0, else carry[r0 + index] */
-__host__ __device__ inline int64_t mfm_gate_src(uint32_t m, uint32_t j, uint32_t We, uint32_t r0)
+/* element j of candidate m of the call, whose first element lies `back` = P * We + r0 elements in front of the row's: its
+ * index in the call's row when >= 0, else counted back from the history's end */
+__host__ __device__ inline int64_t mfm_gate_src(uint32_t m, uint32_t j, uint32_t We, uint32_t back)
 {
-    return (int64_t)((uint64_t)m * We + j) - (int64_t)r0;
+    return (int64_t)((uint64_t)m * We + j) - (int64_t)back;
 }
 
 __host__ __device__ inline uint64_t mfm_gate_below(uint32_t i) /* bits 0 .. i - 1 */
@@ -113,18 +114,19 @@ __host__ __device__ inline bool mfm_gate_walk_step(mfm_gate_walk &w, uint64_t ma
 }
 
 /*
- * ---- pre-roll (mfm_gate_set_preroll, P = preroll_windows >= 0) ------------------------------------------------------
+ * ---- which windows go out, and where their samples are (P = preroll_windows >= 0, mfm_gate_set_preroll) ----------------
  * Window k goes out when any of the records k .. k + P is open, so a call that brings the records K0 .. K1 - 1 decides the
  * windows K0 - P .. K1 - P - 1: its CANDIDATES, e = 0 .. nemit - 1 with k = K0 - P + e (a flush brings no record and
  * decides the P windows left, the missing records taken as closed).  A channel's record bits of the call are one sequence
  * S: bits 0 .. P - 1 are the P records in front of the call (carried as one 64-bit word per channel, bit i = record
  * K0 - P + i, zero where no such record exists), bit P + j is record j of the call, everything behind is closed.  The bit
  * of candidate e is the OR of S[e] .. S[e + P]; for a chunk of 64 candidates that is a shift-and-OR over two words of S.
- * With that mask in place of the plain one, everything above (walk, starts, slots, runs) is used as it is.
+ * That mask is what the walk above takes.  With P = 0 it is the record bits themselves, no candidate is skipped, and the
+ * history below is the carry alone.
  *
  * The samples of the candidates lie in front of the call's rows: the history, a linear buffer per channel that holds the
  * last min(K, P) complete windows and the r elements of the unfinished one, oldest first.  It stands as a virtual prefix
- * in front of the rows, so mfm_gate_src with r0 + P * We in place of r0 is the signed source index: the row when >= 0,
+ * in front of the rows, so mfm_gate_src with back = r0 + P * We is the signed source index: the row when >= 0,
  * otherwise counted back from the history's end.  P is at most MFM_GATE_MAX_PREROLL = 63 (include/multifm_hip.h): S[e] ..
  * S[e + P] of 64 candidates then lie in two words.
  */

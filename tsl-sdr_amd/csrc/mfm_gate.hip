@@ -1,50 +1,87 @@
 /*
  * mfm_gate.hip - the squelch gate: of rows that are still in HBM (the engine's PCM or filtered IQ, the resampler's output)
- * only the windows the level stage left OPEN go into one dense payload, with a run list that says which channel and which
- * samples each piece is.  See include/multifm_hip.h for the boundary, mfm_gate.h for the arithmetic.
+ * only the windows the level stage left OPEN, and the P pre-roll windows in front of every opening, go into one dense
+ * payload, with a run list that says which channel and which samples each piece is.  See include/multifm_hip.h for the
+ * boundary, mfm_gate.h for the arithmetic.
  *
  * The reference has no such stage (nor a squelch).  What the stage computes is an exact copy, so a numpy restatement is the
- * yardstick (tests/test_gate.py).
+ * yardstick (tests/test_gate.py, tests/test_gate_preroll.py).
  *
- * Layout of the work.  A row is a run of int16 ELEMENTS (E per sample), a window is We = W * E of them; a call completes
- * nwin windows per channel (mfm_gate_cut_of), the first of which may begin in the carry: the at most We - 1 elements of an
- * unfinished window that earlier calls left on the device.
+ * Layout of the work.  A row is a run of int16 ELEMENTS (E per sample), a window is We = W * E of them.  Window k of a
+ * channel goes out when any of its records k .. k + P is open (P = preroll_windows, 0 unless mfm_gate_set_preroll said
+ * otherwise), so a call that brings the records K0 .. K1 - 1 decides the windows K0 - P .. K1 - P - 1, its candidates, whose
+ * samples may lie in earlier calls.  The device therefore keeps per channel
  *
- *   gt_count_kernel  one WAVE per channel walks the channel's records 64 at a time: one ballot of `open` per chunk, the
- *                    open windows and the run starts are popcounts of it.  A record whose .window is not the expected k
+ *   the history   a LINEAR buffer of at most (P + 1) * We elements: the last min(K, P) complete windows and the unfinished
+ *                 one, oldest first.  It stands as a virtual prefix in front of the call's rows; mfm_gate_src gives a signed
+ *                 index, the row when >= 0, otherwise counted back from the history's end.  There are two buffers used in
+ *                 turn: a call reads one and gt_hist_kernel, behind the copy, writes the other from (old history ++ rows),
+ *                 so a call shorter than the history is a move between buffers and nothing is read after it was written.
+ *                 (A ring would save that move; it would also put a second seam into the copy's source.  The move is
+ *                 (P + 1) * We elements per channel and call at most.)
+ *   the bits      one 64-bit word: the open bits of the P records in front of the next call.  Two words used in turn as
+ *                 well: the count pass writes the next one, the runs pass still reads the current one.
+ *
+ * With P = 0 the history is the unfinished window alone and the word stays 0; nothing in this file asks whether P is 0.
+ *
+ *   gt_count_kernel  one WAVE per channel walks the channel's candidates 64 at a time: one ballot of the record bits per
+ *                    chunk (the word behind it is the next chunk's), dilated by shift-and-OR (mfm_gate_dilate); the open
+ *                    windows and the run starts are popcounts of that mask.  A record whose .window is not the expected k
  *                    marks the channel.
  *   gt_scan_kernel   one block: exclusive scan of both counts over all channels (a thread sums a stretch of channels, the
  *                    waves scan by lane shifts, the 16 wave sums go through LDS), the totals, the overflow and
  *                    out-of-step flags.
- *   gt_runs_kernel   one wave per channel again: with the channel's base from the scan every window gets its slot in the
- *                    payload (or MFM_GATE_CLOSED) and every run start writes its descriptor; on overflow nothing does.
+ *   gt_runs_kernel   one wave per channel again: with the channel's base from the scan every candidate gets its slot in the
+ *                    payload (or MFM_GATE_CLOSED) and every run start writes its descriptor (first_window is the true k);
+ *                    on overflow nothing does.
  *   gt_copy_kernel   the hot path.  A group of G lanes (G = 1 .. 256, a power of two chosen from We) copies one piece of
  *                    at most 8192 elements of one open window; the group of a closed window returns after reading its
  *                    slot.  The piece is cut where the DESTINATION reaches 16-byte alignment: up to 7 elements one by
  *                    one, then 16-byte stores, each fed by one 16-byte load from wherever the source lies (aligned when
  *                    source and destination agree modulo 16 bytes, otherwise an unaligned load, which the memory path
- *                    splits), up to four of them in flight per lane, then up to 7 elements again.  A call's first window,
- *                    when it begins in the carry, takes a plainer loop; its one chunk of eight that straddles the carry
- *                    and the call's rows is put together element by element.
- *   gt_carry_kernel  behind the copy, which read the old carry: the unfinished window's elements replace it, or, when
- *                    the call completed no window, are appended to it.
+ *                    splits), up to four of them in flight per lane, then up to 7 elements again.  The body of a piece lies
+ *                    wholly in the rows, wholly in the history or across the seam; the first two take that loop from their
+ *                    base pointer, the third a plainer loop whose one chunk of eight on the seam is put together singly.
+ *   gt_hist_kernel   the history's update, behind the copy, which read the old one.
  *
- * With pre-roll (mfm_gate_set_preroll, P > 0) a call takes the kernels of mfm_gate_preroll.hip in place of count, runs, copy
- * and carry; the scan is shared.  With P = 0 the launches are the ones above.
- *
- * Nothing is floating point, nothing goes through an atomic (order and offsets are a count, a scan and a rank), and the
- * host never waits: how many windows a call completes follows from the stream position alone.
+ * A flush is a call with no rows and no records that decides the P windows left.  Nothing is floating point, nothing goes
+ * through an atomic (order and offsets are a count, a scan and a rank), and the host never waits: how many windows a call
+ * completes follows from the stream position alone.
  */
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "../../include/multifm_hip.h"
 
 #include "mfm_gate.h"
-#include "mfm_gate_internal.h"
+
+extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
+
+struct mfm_gate {
+    mfm_gate_config cfg{};
+    uint32_t W = 0, E = 1, We = 0;
+    uint32_t max_win = 0;      /* windows per channel a process call completes at most */
+    uint64_t cap_windows = 0;  /* payload capacity, windows */
+    uint64_t cap_runs = 0;
+    uint32_t log2g = 0, npieces = 1;
+    uint64_t pos = 0;          /* samples per channel consumed so far */
+    uint32_t *d_cnt_open = nullptr, *d_cnt_runs = nullptr, *d_bad = nullptr, *d_base_runs = nullptr, *d_base_open = nullptr, *d_slot = nullptr;
+    uint64_t *d_totals = nullptr;
+    mfm_gate_run *d_runs = nullptr;
+    int16_t *d_payload = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool have_call = false, flushed = false;
+    uint32_t P = 0;
+    uint32_t slot_stride = 0;  /* of d_slot: candidates per channel and call at most, max(max_win, largest P set) */
+    uint32_t hist_stride = 0;  /* elements per channel of either history buffer */
+    int16_t *d_hist[2] = { nullptr, nullptr };  /* used in turn: a call reads [cur] and writes [cur ^ 1] */
+    uint64_t *d_bits[2] = { nullptr, nullptr }; /* the open bits of the P records in front of the next call, likewise */
+    uint32_t cur = 0;
+};
 
 namespace {
 
@@ -63,25 +100,31 @@ struct __attribute__((aligned(16))) gt_x8 {
 struct GtRecs {
     const mfm_level_record *rec;
     size_t rec_stride;
-    uint64_t k0;
-    uint32_t nwin;
+    uint64_t k0;    /* the call's first record */
+    uint32_t nrec;  /* records the call brings */
+    uint32_t nemit; /* candidates: nrec, at a flush P */
+    uint32_t P;
     uint32_t nr_channels;
 };
 
-/* the ballot of one chunk of the channel's records: bit i = window m0 + i is open.  `wrong` collects out-of-step records. */
-__device__ __forceinline__ uint64_t gt_chunk_mask(const GtRecs &R, const mfm_level_record *rc, uint32_t m0, uint32_t lane, uint32_t &wrong)
+/* 64 bits of the channel's sequence S from bit i0 on (mfm_gate.h): prev below P, then the call's records, then closed.
+ * `wrong` collects out-of-step records. */
+__device__ __forceinline__ uint64_t gt_word(const GtRecs &R, const mfm_level_record *rc, uint64_t prev, uint32_t i0, uint32_t lane, uint32_t &wrong)
 {
-    const uint32_t m = m0 + lane;
+    const uint32_t i = i0 + lane;
     bool open = false;
-    if (m < R.nwin) {
-        open = rc[m].open != 0;
-        wrong |= rc[m].window != R.k0 + m ? 1u : 0u;
+    if (i < R.P) {
+        open = (prev >> i) & 1ull;
+    } else if (i - R.P < R.nrec) {
+        const uint32_t j = i - R.P;
+        open = rc[j].open != 0;
+        wrong |= rc[j].window != R.k0 + j ? 1u : 0u;
     }
     return __ballot(open);
 }
 
-__global__ __launch_bounds__(256) void gt_count_kernel(const GtRecs R, uint32_t *__restrict__ cnt_open, uint32_t *__restrict__ cnt_runs,
-                                                      uint32_t *__restrict__ bad)
+__global__ __launch_bounds__(256) void gt_count_kernel(const GtRecs R, const uint64_t *__restrict__ bits_in, uint64_t *__restrict__ bits_out,
+                                                      uint32_t *__restrict__ cnt_open, uint32_t *__restrict__ cnt_runs, uint32_t *__restrict__ bad)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t c = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
@@ -89,19 +132,28 @@ __global__ __launch_bounds__(256) void gt_count_kernel(const GtRecs R, uint32_t 
         return;
     }
     const mfm_level_record *rc = R.rec + (size_t)c * R.rec_stride;
+    const uint64_t prev = bits_in[c];
+    const uint32_t skip = mfm_gate_pre_skip(R.k0, R.P);
     mfm_gate_walk w{};
     uint32_t wrong = 0;
-    for (uint32_t m0 = 0; m0 < R.nwin; m0 += 64) {
-        const uint32_t cnt = R.nwin - m0 < 64u ? R.nwin - m0 : 64u;
-        const uint64_t mask = gt_chunk_mask(R, rc, m0, lane, wrong);
+    uint64_t lo = gt_word(R, rc, prev, 0, lane, wrong);
+    for (uint32_t e0 = 0; e0 < R.nemit; e0 += 64) {
+        const uint32_t cnt = R.nemit - e0 < 64u ? R.nemit - e0 : 64u;
+        const uint64_t hi = gt_word(R, rc, prev, e0 + 64, lane, wrong);
+        const uint64_t mask = mfm_gate_dilate(lo, hi, R.P, e0, cnt, skip);
         uint32_t dr, dl;
-        (void)mfm_gate_walk_step(w, mask, cnt, m0 + 64 >= R.nwin, dr, dl);
+        (void)mfm_gate_walk_step(w, mask, cnt, e0 + 64 >= R.nemit, dr, dl);
+        lo = hi;
     }
+    /* the P records in front of the next call: S[nrec .. nrec + P - 1] */
+    uint32_t unused = 0;
+    const uint64_t next = gt_word(R, rc, prev, R.nrec, lane, unused) & mfm_gate_below(R.P);
     const bool any_wrong = __ballot(wrong != 0) != 0;
     if (lane == 0) {
         cnt_open[c] = w.opens;
         cnt_runs[c] = w.runs;
         bad[c] = any_wrong ? 1u : 0u;
+        bits_out[c] = next;
     }
 }
 
@@ -168,9 +220,9 @@ __global__ __launch_bounds__(GT_SCAN_THREADS) void gt_scan_kernel(uint32_t nr_ch
     }
 }
 
-__global__ __launch_bounds__(256) void gt_runs_kernel(const GtRecs R, const uint32_t *__restrict__ base_open, const uint32_t *__restrict__ base_runs,
-                                                     const uint64_t *__restrict__ totals, mfm_gate_run *__restrict__ runs,
-                                                     uint32_t *__restrict__ slot, uint32_t slot_stride, uint32_t We)
+__global__ __launch_bounds__(256) void gt_runs_kernel(const GtRecs R, const uint64_t *__restrict__ bits_in, const uint32_t *__restrict__ base_open,
+                                                     const uint32_t *__restrict__ base_runs, const uint64_t *__restrict__ totals,
+                                                     mfm_gate_run *__restrict__ runs, uint32_t *__restrict__ slot, uint32_t slot_stride, uint32_t We)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t c = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
@@ -180,29 +232,33 @@ __global__ __launch_bounds__(256) void gt_runs_kernel(const GtRecs R, const uint
     const mfm_level_record *rc = R.rec + (size_t)c * R.rec_stride;
     uint32_t *sc = slot + (size_t)c * slot_stride;
     if (totals[GT_T_OVERFLOW]) { /* the payload cannot take the call: nothing goes out */
-        for (uint32_t m = lane; m < R.nwin; m += 64) {
+        for (uint32_t m = lane; m < R.nemit; m += 64) {
             sc[m] = MFM_GATE_CLOSED;
         }
         return;
     }
+    const uint64_t prev = bits_in[c];
+    const uint32_t skip = mfm_gate_pre_skip(R.k0, R.P);
     const uint32_t bo = base_open[c];
     mfm_gate_run *rr = runs + base_runs[c];
     mfm_gate_walk w{};
     uint32_t wrong = 0;
-    for (uint32_t m0 = 0; m0 < R.nwin; m0 += 64) {
-        const uint32_t cnt = R.nwin - m0 < 64u ? R.nwin - m0 : 64u;
-        const bool last = m0 + 64 >= R.nwin;
-        const uint64_t mask = gt_chunk_mask(R, rc, m0, lane, wrong);
+    uint64_t lo = gt_word(R, rc, prev, 0, lane, wrong);
+    for (uint32_t e0 = 0; e0 < R.nemit; e0 += 64) {
+        const uint32_t cnt = R.nemit - e0 < 64u ? R.nemit - e0 : 64u;
+        const bool last = e0 + 64 >= R.nemit;
+        const uint64_t hi = gt_word(R, rc, prev, e0 + 64, lane, wrong);
+        const uint64_t mask = mfm_gate_dilate(lo, hi, R.P, e0, cnt, skip);
         const uint64_t starts = mfm_gate_starts(w, mask);
         if (lane < cnt) {
             const bool open = (mask >> lane) & 1ull;
             const uint32_t at = bo + mfm_gate_slot(w, mask, lane); /* < cap_windows <= 2^32 - 2 */
-            sc[m0 + lane] = open ? at : MFM_GATE_CLOSED;
+            sc[e0 + lane] = open ? at : MFM_GATE_CLOSED;
             if ((starts >> lane) & 1ull) {
                 uint32_t rank, len;
                 bool whole;
                 mfm_gate_run_at(w, mask, starts, lane, cnt, last, rank, len, whole);
-                rr[rank].first_window = R.k0 + m0 + lane;
+                rr[rank].first_window = R.k0 + e0 + lane - R.P; /* an open candidate lies at or above skip: k >= 0 */
                 rr[rank].payload_offset = (uint64_t)at * We;
                 rr[rank].channel = c;
                 if (whole) {
@@ -214,27 +270,30 @@ __global__ __launch_bounds__(256) void gt_runs_kernel(const GtRecs R, const uint
         if (mfm_gate_walk_step(w, mask, cnt, last, done_run, done_len) && lane == 0) {
             rr[done_run].nr_windows = done_len;
         }
+        lo = hi;
     }
 }
 
 struct GtCopy {
-    size_t stride;         /* of rows, elements */
-    uint32_t carry_stride; /* elements */
+    size_t stride;        /* of rows, elements */
+    uint32_t hist_stride; /* elements */
     uint32_t slot_stride;
-    uint32_t We, r0, nwin;
-    uint32_t log2g;        /* lanes per piece = 1 << log2g */
-    uint32_t npieces;      /* pieces per window */
+    uint32_t We, nemit;
+    uint32_t back;        /* P * We + r0: elements of the virtual stream between candidate 0's first and the row's first */
+    uint32_t hlen;        /* elements the history holds */
+    uint32_t log2g;       /* lanes per piece = 1 << log2g */
+    uint32_t npieces;     /* pieces per window */
 };
 
-__global__ __launch_bounds__(256) void gt_copy_kernel(const GtCopy K, const int16_t *__restrict__ rows, const int16_t *__restrict__ carry,
+__global__ __launch_bounds__(256) void gt_copy_kernel(const GtCopy K, const int16_t *__restrict__ rows, const int16_t *__restrict__ hist,
                                                      const uint32_t *__restrict__ slot, int16_t *__restrict__ payload)
 {
     const uint32_t G = 1u << K.log2g;
     const uint32_t lane = threadIdx.x & (G - 1u);
     const uint32_t u = blockIdx.x * (256u >> K.log2g) + (threadIdx.x >> K.log2g); /* piece of the channel */
     const uint32_t c = blockIdx.y;
-    const uint32_t m = K.npieces == 1 ? u : u / K.npieces;
-    if (m >= K.nwin) {
+    const uint32_t m = K.npieces == 1 ? u : u / K.npieces; /* the candidate */
+    if (m >= K.nemit) {
         return;
     }
     const uint32_t at = slot[(size_t)c * K.slot_stride + m];
@@ -244,12 +303,11 @@ __global__ __launch_bounds__(256) void gt_copy_kernel(const GtCopy K, const int1
     const uint32_t p0 = (u - m * K.npieces) * GT_PIECE; /* the piece: elements [p0, p0 + len) of the window */
     const uint32_t len = K.We - p0 < GT_PIECE ? K.We - p0 : GT_PIECE;
     const int16_t *xr = rows + (size_t)c * K.stride;
-    const int16_t *xc = carry + (size_t)c * K.carry_stride;
+    /* xlow[g] for g < 0: the history, counted back from its end (an open candidate is a window that exists, g >= -hlen) */
+    const int16_t *xlow = hist + (size_t)c * K.hist_stride + K.hlen;
     const uint64_t d0 = (uint64_t)at * K.We + p0;
     int16_t *dst = payload + d0;
-    /* element j of the piece: in the row at g0 + j when that is >= 0, else in the carry at g0 + j + r0 (window 0 only) */
-    const int64_t g0 = mfm_gate_src(m, p0, K.We, K.r0);
-    const int16_t *xlow = xc + (int64_t)K.r0; /* xlow[g] for g < 0 */
+    const int64_t g0 = mfm_gate_src(m, p0, K.We, K.back);
     auto one = [&](uint32_t j) {
         const int64_t g = g0 + j;
         dst[j] = g >= 0 ? xr[g] : xlow[g];
@@ -259,8 +317,8 @@ __global__ __launch_bounds__(256) void gt_copy_kernel(const GtCopy K, const int1
     head = head < len ? head : len;
     const uint32_t nbody = (len - head) >> 3;
     const int64_t gb = g0 + head;
-    if (gb >= 0) { /* all of the body lies in the row: every window but a call's first, and that one when the carry is empty */
-        const int16_t *src = xr + gb;
+    if (gb >= 0 || gb + (int64_t)(8u * nbody) <= 0) { /* all of the body in the row, or all of it in the history */
+        const int16_t *src = (gb >= 0 ? xr : xlow) + gb;
         int16_t *out = dst + head;
         auto ld = [&](uint32_t t) { return *reinterpret_cast<const gt_x8u *>(src + 8u * t); };
         auto st = [&](uint32_t t, const gt_x8u &v) {
@@ -288,8 +346,8 @@ __global__ __launch_bounds__(256) void gt_copy_kernel(const GtCopy K, const int1
             st(t, ld(t));
         }
     } else {
-        /* a call's first window, begun in the carry.  The one chunk whose eight elements begin in the carry and end in the
-         * row, if any, is put together singly */
+        /* the body begins in the history and ends in the row.  The one chunk whose eight elements lie on both sides, if
+         * any, is put together singly */
         const uint32_t ts = (-gb & 7) ? (uint32_t)(-gb >> 3) : ~0u;
         for (uint32_t t = lane; t < nbody; t += G) {
             const int64_t g = gb + 8u * t;
@@ -316,14 +374,16 @@ __global__ __launch_bounds__(256) void gt_copy_kernel(const GtCopy K, const int1
     }
 }
 
-/* elements [s0, s0 + n) of every channel's row go to carry[d0 ...] */
-__global__ __launch_bounds__(256) void gt_carry_kernel(const int16_t *__restrict__ rows, size_t stride, int16_t *__restrict__ carry,
-                                                      uint32_t carry_stride, uint32_t s0, uint32_t d0, uint32_t n)
+/* the history after the call: its hlen1 elements are the last hlen1 of (old history of hlen0 ++ the row's N) */
+__global__ __launch_bounds__(256) void gt_hist_kernel(const int16_t *__restrict__ rows, size_t stride, const int16_t *__restrict__ hist_in,
+                                                     int16_t *__restrict__ hist_out, uint32_t hist_stride, uint32_t hlen0, uint32_t hlen1,
+                                                     uint32_t N)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t c = blockIdx.y;
-    if (i < n) {
-        carry[(size_t)c * carry_stride + d0 + i] = rows[(size_t)c * stride + s0 + i];
+    if (i < hlen1) {
+        const int64_t g = mfm_gate_hist_src(i, hlen1, N);
+        hist_out[(size_t)c * hist_stride + i] = g >= 0 ? rows[(size_t)c * stride + g] : hist_in[(size_t)c * hist_stride + hlen0 + g];
     }
 }
 
@@ -336,8 +396,6 @@ int gt_fail(int code, const char *msg)
     return code;
 }
 
-} /* namespace */
-
 #define GT_TRY(expr)                                                                                         \
     do {                                                                                                     \
         hipError_t err_ = (expr);                                                                            \
@@ -348,23 +406,114 @@ int gt_fail(int code, const char *msg)
         }                                                                                                    \
     } while (0)
 
-/* struct mfm_gate: mfm_gate_internal.h (shared with the pre-roll mode, mfm_gate_preroll.hip) */
-
-extern "C" {
-
-int mfm_gate_internal_fail(int code, const char *msg)
-{
-    return gt_fail(code, msg);
-}
-
-int mfm_gate_internal_scan(struct mfm_gate *g, hipStream_t s)
+/* what depends on P: d_slot, d_runs and d_payload grow where a flush of P windows per channel needs more than they hold
+ * (they never shrink), history and bits are made anew, zeroed.  The object changes only where a step succeeded, and P
+ * with the last one; the caller has checked P and set the device. */
+int gt_size_for(mfm_gate *g, uint32_t P)
 {
     const uint32_t C = g->cfg.nr_channels;
-    hipLaunchKernelGGL(gt_scan_kernel, dim3(1), dim3(GT_SCAN_THREADS), 0, s, C, (C + GT_SCAN_THREADS - 1) / GT_SCAN_THREADS, g->d_cnt_open,
-                       g->d_cnt_runs, g->d_bad, g->d_base_open, g->d_base_runs, g->d_totals, g->We, g->cap_windows);
-    GT_TRY(hipGetLastError());
+    const uint32_t per_ch = g->max_win > P ? g->max_win : P; /* candidates per channel and call at most: a flush has P */
+    const uint64_t all = (uint64_t)C * per_ch;
+    if (per_ch > g->slot_stride) {
+        uint32_t *slot = nullptr;
+        GT_TRY(hipMalloc(&slot, (size_t)all * 4));
+        (void)hipFree(g->d_slot);
+        g->d_slot = slot;
+        g->slot_stride = per_ch;
+    }
+    /* the default capacity holds any call, and a flush is one; a caller-chosen capacity stays, but the run list must hold
+     * what fits it: a flush has up to (P + 1) / 2 runs per channel */
+    const uint64_t cap_windows = 0 == g->cfg.max_open_windows && all > g->cap_windows ? all : g->cap_windows;
+    const uint64_t most_runs = (uint64_t)C * ((per_ch + 1) / 2); /* two runs of a channel have a closed window between them */
+    const uint64_t cap_runs = cap_windows < most_runs ? cap_windows : most_runs;
+    if (cap_runs > g->cap_runs) {
+        mfm_gate_run *runs = nullptr;
+        GT_TRY(hipMalloc(&runs, (size_t)cap_runs * sizeof(mfm_gate_run)));
+        (void)hipFree(g->d_runs);
+        g->d_runs = runs;
+        g->cap_runs = cap_runs;
+    }
+    if (cap_windows > g->cap_windows) {
+        int16_t *payload = nullptr;
+        GT_TRY(hipMalloc(&payload, (size_t)cap_windows * g->We * 2));
+        (void)hipFree(g->d_payload);
+        g->d_payload = payload;
+        g->cap_windows = cap_windows;
+    }
+    const uint32_t hist_stride = ((P + 1u) * g->We + 7u) & ~7u; /* <= 64 * 2^20 + 7 */
+    const size_t bytes[4] = { (size_t)C * hist_stride * 2, (size_t)C * hist_stride * 2, (size_t)C * 8, (size_t)C * 8 };
+    void *fresh[4] = { nullptr, nullptr, nullptr, nullptr };
+    hipError_t history_alloc = hipSuccess;
+    for (int i = 0; i < 4 && history_alloc == hipSuccess; i++) {
+        history_alloc = hipMalloc(&fresh[i], bytes[i]);
+        history_alloc = history_alloc == hipSuccess ? hipMemset(fresh[i], 0, bytes[i]) : history_alloc;
+    }
+    history_alloc = history_alloc == hipSuccess ? hipDeviceSynchronize() : history_alloc;
+    if (history_alloc != hipSuccess) {
+        for (void *p : fresh) {
+            (void)hipFree(p);
+        }
+        GT_TRY(history_alloc);
+    }
+    for (int i = 0; i < 2; i++) {
+        (void)hipFree(g->d_hist[i]);
+        (void)hipFree(g->d_bits[i]);
+        g->d_hist[i] = static_cast<int16_t *>(fresh[i]);
+        g->d_bits[i] = static_cast<uint64_t *>(fresh[2 + i]);
+    }
+    g->hist_stride = hist_stride;
+    g->cur = 0;
+    g->P = P;
     return MFM_OK;
 }
+
+/* one process call (flush == 0) or the flush: count, scan, runs and copy where the call has candidates, the history.
+ * Arguments checked by the caller */
+int gt_call(mfm_gate *g, const int16_t *d_rows, size_t in_stride, size_t nr_in, const mfm_level_record *d_records, size_t record_stride,
+            const mfm_gate_cut &cut, int flush, hipStream_t s)
+{
+    const uint32_t C = g->cfg.nr_channels, P = g->P, We = g->We;
+    const uint32_t nemit = flush ? P : cut.nwin;
+    const uint32_t hlen0 = mfm_gate_hist_len(cut.k0, cut.r0, P, We);
+    const GtRecs R{ d_records, record_stride, cut.k0, cut.nwin, nemit, P, C };
+    const int16_t *hin = g->d_hist[g->cur];
+    hipLaunchKernelGGL(gt_count_kernel, dim3((C + 3) / 4), dim3(256), 0, s, R, g->d_bits[g->cur], g->d_bits[g->cur ^ 1u], g->d_cnt_open,
+                       g->d_cnt_runs, g->d_bad);
+    GT_TRY(hipGetLastError());
+    hipLaunchKernelGGL(gt_scan_kernel, dim3(1), dim3(GT_SCAN_THREADS), 0, s, C, (C + GT_SCAN_THREADS - 1) / GT_SCAN_THREADS, g->d_cnt_open,
+                       g->d_cnt_runs, g->d_bad, g->d_base_open, g->d_base_runs, g->d_totals, We, g->cap_windows);
+    GT_TRY(hipGetLastError());
+    if (nemit) {
+        hipLaunchKernelGGL(gt_runs_kernel, dim3((C + 3) / 4), dim3(256), 0, s, R, g->d_bits[g->cur], g->d_base_open, g->d_base_runs, g->d_totals,
+                           g->d_runs, g->d_slot, g->slot_stride, We);
+        GT_TRY(hipGetLastError());
+        const GtCopy K{ in_stride, g->hist_stride, g->slot_stride, We, nemit, P * We + cut.r0, hlen0, g->log2g, g->npieces };
+        const uint64_t pieces = (uint64_t)nemit * g->npieces;
+        const uint32_t per_block = 256u >> g->log2g;
+        hipLaunchKernelGGL(gt_copy_kernel, dim3((uint32_t)((pieces + per_block - 1) / per_block), C), dim3(256), 0, s, K, d_rows, hin, g->d_slot,
+                           g->d_payload);
+        GT_TRY(hipGetLastError());
+    }
+    if (flush) {
+        g->flushed = true; /* the history is of no more use; the unfinished window is dropped */
+    } else if (nr_in) {    /* nr_in == 0 leaves the history as it is, and the bits: S[0 .. P - 1] is prev */
+        const uint32_t hlen1 = mfm_gate_hist_len(cut.k0 + cut.nwin, cut.r1, P, We);
+        if (hlen1) {
+            hipLaunchKernelGGL(gt_hist_kernel, dim3((hlen1 + 255) / 256, C), dim3(256), 0, s, d_rows, in_stride, hin, g->d_hist[g->cur ^ 1u],
+                               g->hist_stride, hlen0, hlen1, (uint32_t)nr_in * g->E);
+            GT_TRY(hipGetLastError());
+        }
+        g->cur ^= 1u; /* both the bits (written by the count pass) and the history */
+    }
+    g->pos += nr_in;
+    g->last_stream = s;
+    g->have_call = true;
+    return MFM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
 
 int mfm_gate_create(struct mfm_gate **pg, const struct mfm_gate_config *cfg)
 {
@@ -402,18 +551,16 @@ int mfm_gate_create(struct mfm_gate **pg, const struct mfm_gate_config *cfg)
     g->E = cfg->elems_per_sample;
     g->We = g->W * g->E;
     g->max_win = max_win;
+    g->slot_stride = max_win;
     g->cap_windows = cfg->max_open_windows && cfg->max_open_windows < all ? cfg->max_open_windows : all;
     const uint64_t most_runs = (uint64_t)C * ((max_win + 1) / 2); /* two runs of a channel have a closed window between them */
     g->cap_runs = g->cap_windows < most_runs ? g->cap_windows : most_runs;
-    g->carry_stride = (g->We + 7u) & ~7u;
     const uint32_t chunks = (g->We + 7u) / 8u;
     while ((1u << g->log2g) < chunks && g->log2g < 8) {
         g->log2g++;
     }
     g->npieces = (g->We + GT_PIECE - 1) / GT_PIECE;
     *pg = g;
-    GT_TRY(hipMalloc(&g->d_carry, (size_t)C * g->carry_stride * 2));
-    GT_TRY(hipMemset(g->d_carry, 0, (size_t)C * g->carry_stride * 2));
     GT_TRY(hipMalloc(&g->d_cnt_open, (size_t)C * 4));
     GT_TRY(hipMalloc(&g->d_cnt_runs, (size_t)C * 4));
     GT_TRY(hipMalloc(&g->d_bad, (size_t)C * 4));
@@ -424,8 +571,7 @@ int mfm_gate_create(struct mfm_gate **pg, const struct mfm_gate_config *cfg)
     GT_TRY(hipMemset(g->d_totals, 0, 4 * 8));
     GT_TRY(hipMalloc(&g->d_runs, (size_t)g->cap_runs * sizeof(mfm_gate_run)));
     GT_TRY(hipMalloc(&g->d_payload, (size_t)g->cap_windows * g->We * 2));
-    GT_TRY(hipDeviceSynchronize());
-    return MFM_OK;
+    return gt_size_for(g, 0); /* the history of P = 0 is the carry: one window per channel (twice) */
 }
 
 void mfm_gate_destroy(struct mfm_gate **pg)
@@ -436,7 +582,6 @@ void mfm_gate_destroy(struct mfm_gate **pg)
     mfm_gate *g = *pg;
     (void)hipSetDevice(g->cfg.device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(g->d_carry);
     (void)hipFree(g->d_cnt_open);
     (void)hipFree(g->d_cnt_runs);
     (void)hipFree(g->d_bad);
@@ -452,6 +597,37 @@ void mfm_gate_destroy(struct mfm_gate **pg)
     }
     delete g;
     *pg = nullptr;
+}
+
+int mfm_gate_set_preroll(struct mfm_gate *g, uint32_t preroll_windows)
+{
+    if (!g) {
+        return MFM_E_INVAL;
+    }
+    if (g->have_call || g->flushed) {
+        return gt_fail(MFM_E_STATE, "mfm_gate_set_preroll comes before the first process call");
+    }
+    const uint32_t P = preroll_windows, C = g->cfg.nr_channels;
+    char msg[200];
+    if (P > MFM_GATE_MAX_PREROLL) {
+        snprintf(msg, sizeof(msg), "preroll_windows above MFM_GATE_MAX_PREROLL = %u", MFM_GATE_MAX_PREROLL);
+        return gt_fail(MFM_E_INVAL, msg);
+    }
+    const uint64_t hist_bytes = (uint64_t)C * (((P + 1u) * g->We + 7u) & ~7u) * 2u;
+    if (P && hist_bytes > MFM_GATE_MAX_HISTORY_BYTES) { /* P = 0 is what create made: one window, bounded there */
+        snprintf(msg, sizeof(msg), "the history, (P + 1) windows of int16 per channel = %llu bytes, exceeds MFM_GATE_MAX_HISTORY_BYTES = %llu",
+                 (unsigned long long)hist_bytes, (unsigned long long)MFM_GATE_MAX_HISTORY_BYTES);
+        return gt_fail(MFM_E_INVAL, msg);
+    }
+    if ((uint64_t)C * P > 0xfffffffeull) {
+        return gt_fail(MFM_E_INVAL, "nr_channels * preroll_windows must stay below 2^32 - 1");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || g->cfg.device >= ndev) {
+        return MFM_E_DEVICE;
+    }
+    GT_TRY(hipSetDevice(g->cfg.device));
+    return gt_size_for(g, P);
 }
 
 int mfm_gate_process_device(struct mfm_gate *g, const int16_t *d_rows, size_t in_stride, size_t nr_in, const struct mfm_level_record *d_records,
@@ -478,39 +654,23 @@ int mfm_gate_process_device(struct mfm_gate *g, const int16_t *d_rows, size_t in
     if (g->have_call && g->last_stream != s) {
         GT_TRY(hipStreamSynchronize(g->last_stream)); /* state lives on the device; keep calls ordered */
     }
-    if (g->P) { /* the pre-roll mode has kernels of its own; with P = 0 everything below is what it was */
-        return mfm_gate_internal_preroll_call(g, d_rows, in_stride, nr_in, d_records, record_stride, cut.nwin, 0, s);
+    return gt_call(g, d_rows, in_stride, nr_in, d_records, record_stride, cut, 0, s);
+}
+
+int mfm_gate_flush_device(struct mfm_gate *g, void *stream)
+{
+    if (!g) {
+        return MFM_E_INVAL;
     }
-    const uint32_t C = g->cfg.nr_channels;
-    const GtRecs R{ d_records, record_stride, cut.k0, cut.nwin, C };
-    hipLaunchKernelGGL(gt_count_kernel, dim3((C + 3) / 4), dim3(256), 0, s, R, g->d_cnt_open, g->d_cnt_runs, g->d_bad);
-    GT_TRY(hipGetLastError());
-    hipLaunchKernelGGL(gt_scan_kernel, dim3(1), dim3(GT_SCAN_THREADS), 0, s, C, (C + GT_SCAN_THREADS - 1) / GT_SCAN_THREADS, g->d_cnt_open,
-                       g->d_cnt_runs, g->d_bad, g->d_base_open, g->d_base_runs, g->d_totals, g->We, g->cap_windows);
-    GT_TRY(hipGetLastError());
-    if (cut.nwin) {
-        hipLaunchKernelGGL(gt_runs_kernel, dim3((C + 3) / 4), dim3(256), 0, s, R, g->d_base_open, g->d_base_runs, g->d_totals, g->d_runs,
-                           g->d_slot, g->max_win, g->We);
-        GT_TRY(hipGetLastError());
-        const GtCopy K{ in_stride, g->carry_stride, g->max_win, g->We, cut.r0, cut.nwin, g->log2g, g->npieces };
-        const uint64_t pieces = (uint64_t)cut.nwin * g->npieces;
-        const uint32_t per_block = 256u >> g->log2g;
-        hipLaunchKernelGGL(gt_copy_kernel, dim3((uint32_t)((pieces + per_block - 1) / per_block), C), dim3(256), 0, s, K, d_rows, g->d_carry,
-                           g->d_slot, g->d_payload);
-        GT_TRY(hipGetLastError());
+    if (g->flushed) {
+        return gt_fail(MFM_E_STATE, "the gate was flushed: the stream has ended");
     }
-    /* the unfinished window: what the call leaves of it replaces the carry, or joins it when no window was completed */
-    const uint32_t N = (uint32_t)nr_in * g->E;
-    const uint32_t n = cut.nwin ? cut.r1 : N;
-    if (n) {
-        hipLaunchKernelGGL(gt_carry_kernel, dim3((n + 255) / 256, C), dim3(256), 0, s, d_rows, in_stride, g->d_carry, g->carry_stride,
-                           cut.nwin ? N - cut.r1 : 0u, cut.nwin ? 0u : cut.r0, n);
-        GT_TRY(hipGetLastError());
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GT_TRY(hipSetDevice(g->cfg.device));
+    if (g->have_call && g->last_stream != s) {
+        GT_TRY(hipStreamSynchronize(g->last_stream));
     }
-    g->pos += nr_in;
-    g->last_stream = s;
-    g->have_call = true;
-    return MFM_OK;
+    return gt_call(g, nullptr, 0, 0, nullptr, 0, mfm_gate_cut_of(g->pos, 0, g->W, g->E), 1, s);
 }
 
 int mfm_gate_process_host(struct mfm_gate *g, const int16_t *rows, size_t in_stride, size_t nr_in, const struct mfm_level_record *records,
@@ -597,59 +757,78 @@ int mfm_gate_device_view(struct mfm_gate *g, const struct mfm_gate_run **d_runs,
     return MFM_OK;
 }
 
-int mfm_hosttwin_gate_call(uint32_t nr_channels, uint32_t window_samples, uint32_t elems_per_sample, uint64_t pos, const int16_t *rows,
-                           size_t in_stride, size_t nr_in, int16_t *carry, const struct mfm_level_record *records, size_t record_stride,
-                           size_t nr_windows, struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
-                           size_t *nr_elems)
+int mfm_hosttwin_gate_call_preroll(uint32_t nr_channels, uint32_t window_samples, uint32_t elems_per_sample, uint32_t preroll_windows,
+                                   uint64_t pos, int flush, const int16_t *rows, size_t in_stride, size_t nr_in, int16_t *history,
+                                   uint64_t *open_bits, const struct mfm_level_record *records, size_t record_stride, size_t nr_windows,
+                                   struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                                   size_t *nr_elems)
 {
-    if (!nr_channels || !window_samples || (elems_per_sample != 1 && elems_per_sample != 2) || !carry || !nr_runs || !nr_elems ||
-        (!rows && nr_in) || (!runs && max_runs) || (!payload && max_elems)) {
+    if (!nr_channels || !window_samples || (elems_per_sample != 1 && elems_per_sample != 2) || preroll_windows > MFM_GATE_MAX_PREROLL ||
+        !history || !open_bits || !nr_runs || !nr_elems || (!rows && nr_in) || (!runs && max_runs) || (!payload && max_elems) ||
+        (flush && (nr_in || nr_windows))) {
         return MFM_E_INVAL;
     }
-    const uint32_t We = window_samples * elems_per_sample;
+    const uint32_t P = preroll_windows, We = window_samples * elems_per_sample;
+    const size_t hstride = (size_t)(P + 1u) * We;
     const mfm_gate_cut cut = mfm_gate_cut_of(pos, nr_in, window_samples, elems_per_sample);
     if (nr_windows != cut.nwin || (cut.nwin && (!records || record_stride < cut.nwin))) {
         return MFM_E_INVAL;
     }
+    const uint32_t nrec = cut.nwin, nemit = flush ? P : nrec;
+    const uint32_t skip = mfm_gate_pre_skip(cut.k0, P);
+    const uint32_t hlen0 = mfm_gate_hist_len(cut.k0, cut.r0, P, We);
+    bool wrong = false;
+    auto word = [&](uint32_t c, uint32_t i0) { /* gt_word */
+        const mfm_level_record *rc = records + c * record_stride;
+        uint64_t v = 0;
+        for (uint32_t l = 0; l < 64; l++) {
+            const uint32_t i = i0 + l;
+            bool open = false;
+            if (i < P) {
+                open = (open_bits[c] >> i) & 1ull;
+            } else if (i - P < nrec) {
+                open = rc[i - P].open != 0;
+                wrong |= rc[i - P].window != cut.k0 + (i - P);
+            }
+            v |= open ? 1ull << l : 0ull;
+        }
+        return v;
+    };
     /* the count pass and the scan */
     uint64_t open_total = 0, run_total = 0;
-    bool wrong = false;
-    auto chunk_mask = [&](const mfm_level_record *rc, uint32_t m0, uint32_t cnt) {
-        uint64_t mask = 0;
-        for (uint32_t i = 0; i < cnt; i++) {
-            mask |= rc[m0 + i].open ? 1ull << i : 0ull;
-            wrong |= rc[m0 + i].window != cut.k0 + m0 + i;
-        }
-        return mask;
-    };
     for (uint32_t c = 0; c < nr_channels; c++) {
         mfm_gate_walk w{};
-        for (uint32_t m0 = 0; m0 < cut.nwin; m0 += 64) {
-            const uint32_t cnt = cut.nwin - m0 < 64u ? cut.nwin - m0 : 64u;
+        uint64_t lo = word(c, 0);
+        for (uint32_t e0 = 0; e0 < nemit; e0 += 64) {
+            const uint32_t cnt = nemit - e0 < 64u ? nemit - e0 : 64u;
+            const uint64_t hi = word(c, e0 + 64);
             uint32_t dr, dl;
-            (void)mfm_gate_walk_step(w, chunk_mask(records + c * record_stride, m0, cnt), cnt, m0 + 64 >= cut.nwin, dr, dl);
+            (void)mfm_gate_walk_step(w, mfm_gate_dilate(lo, hi, P, e0, cnt, skip), cnt, e0 + 64 >= nemit, dr, dl);
+            lo = hi;
         }
         open_total += w.opens;
         run_total += w.runs;
     }
     *nr_runs = (size_t)run_total;
     *nr_elems = (size_t)(open_total * We);
-    int rc = MFM_OK;
     if (wrong) {
-        rc = gt_fail(MFM_E_STATE, "level and gate out of step");
-    } else if (run_total > max_runs || open_total * We > max_elems) {
-        rc = MFM_E_NOMEM;
+        return gt_fail(MFM_E_STATE, "level and gate out of step");
+    }
+    if (run_total > max_runs || open_total * We > max_elems) {
+        return MFM_E_NOMEM; /* nothing written, history and bits included: the caller may call again */
     }
     /* runs and payload */
     uint64_t bo = 0, br = 0;
-    for (uint32_t c = 0; c < nr_channels && rc == MFM_OK; c++) {
+    for (uint32_t c = 0; c < nr_channels; c++) {
         const int16_t *xr = rows + c * in_stride;
-        const int16_t *xc = carry + (size_t)c * We;
+        const int16_t *xlow = history + c * hstride + hlen0;
         mfm_gate_walk w{};
-        for (uint32_t m0 = 0; m0 < cut.nwin; m0 += 64) {
-            const uint32_t cnt = cut.nwin - m0 < 64u ? cut.nwin - m0 : 64u;
-            const bool last = m0 + 64 >= cut.nwin;
-            const uint64_t mask = chunk_mask(records + c * record_stride, m0, cnt);
+        uint64_t lo = word(c, 0);
+        for (uint32_t e0 = 0; e0 < nemit; e0 += 64) {
+            const uint32_t cnt = nemit - e0 < 64u ? nemit - e0 : 64u;
+            const bool last = e0 + 64 >= nemit;
+            const uint64_t hi = word(c, e0 + 64);
+            const uint64_t mask = mfm_gate_dilate(lo, hi, P, e0, cnt, skip);
             const uint64_t starts = mfm_gate_starts(w, mask);
             for (uint32_t i = 0; i < cnt; i++) {
                 if (!((mask >> i) & 1ull)) {
@@ -657,15 +836,15 @@ int mfm_hosttwin_gate_call(uint32_t nr_channels, uint32_t window_samples, uint32
                 }
                 const uint64_t at = bo + mfm_gate_slot(w, mask, i);
                 for (uint32_t j = 0; j < We; j++) {
-                    const int64_t g = mfm_gate_src(m0 + i, j, We, cut.r0);
-                    payload[at * We + j] = g >= 0 ? xr[g] : xc[g + cut.r0];
+                    const int64_t g = mfm_gate_src(e0 + i, j, We, P * We + cut.r0);
+                    payload[at * We + j] = g >= 0 ? xr[g] : xlow[g];
                 }
                 if ((starts >> i) & 1ull) {
                     uint32_t rank, len;
                     bool whole;
                     mfm_gate_run_at(w, mask, starts, i, cnt, last, rank, len, whole);
                     mfm_gate_run &r = runs[br + rank];
-                    r.first_window = cut.k0 + m0 + i;
+                    r.first_window = cut.k0 + e0 + i - P;
                     r.payload_offset = at * We;
                     r.channel = c;
                     if (whole) {
@@ -677,29 +856,44 @@ int mfm_hosttwin_gate_call(uint32_t nr_channels, uint32_t window_samples, uint32
             if (mfm_gate_walk_step(w, mask, cnt, last, done_run, done_len)) {
                 runs[br + done_run].nr_windows = done_len;
             }
+            lo = hi;
         }
         bo += w.opens;
         br += w.runs;
     }
-    if (rc != MFM_OK) {
-        return rc; /* nothing written, the carry included: the caller may call again */
+    if (flush) {
+        return MFM_OK;
     }
-    /* the carry, behind the copy that read it */
+    /* the bits and the history, behind the copy that read them */
     const uint32_t N = (uint32_t)nr_in * elems_per_sample;
+    const uint32_t hlen1 = mfm_gate_hist_len(cut.k0 + nrec, cut.r1, P, We);
+    std::vector<int16_t> next(hlen1 ? hlen1 : 1);
     for (uint32_t c = 0; c < nr_channels; c++) {
-        int16_t *xc = carry + (size_t)c * We;
+        open_bits[c] = word(c, nrec) & mfm_gate_below(P);
+        int16_t *h = history + c * hstride;
         const int16_t *xr = rows + c * in_stride;
-        if (cut.nwin) {
-            for (uint32_t i = 0; i < cut.r1; i++) {
-                xc[i] = xr[N - cut.r1 + i];
-            }
-        } else {
-            for (uint32_t i = 0; i < N; i++) {
-                xc[cut.r0 + i] = xr[i];
-            }
+        for (uint32_t i = 0; i < hlen1; i++) {
+            const int64_t g = mfm_gate_hist_src(i, hlen1, N);
+            next[i] = g >= 0 ? xr[g] : h[hlen0 + g];
         }
+        memcpy(h, next.data(), (size_t)hlen1 * 2);
     }
-    return rc;
+    return MFM_OK;
+}
+
+/* the twin without pre-roll: P = 0, where the history is the carry, [channel][We], and the bits stay 0.  Every argument
+ * check and return code is the one above */
+int mfm_hosttwin_gate_call(uint32_t nr_channels, uint32_t window_samples, uint32_t elems_per_sample, uint64_t pos, const int16_t *rows,
+                           size_t in_stride, size_t nr_in, int16_t *carry, const struct mfm_level_record *records, size_t record_stride,
+                           size_t nr_windows, struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                           size_t *nr_elems)
+{
+    if (!nr_channels) {
+        return MFM_E_INVAL;
+    }
+    std::vector<uint64_t> bits(nr_channels, 0);
+    return mfm_hosttwin_gate_call_preroll(nr_channels, window_samples, elems_per_sample, 0, pos, 0, rows, in_stride, nr_in, carry, bits.data(),
+                                          records, record_stride, nr_windows, runs, max_runs, nr_runs, payload, max_elems, nr_elems);
 }
 
 } /* extern "C" */
