@@ -1056,6 +1056,99 @@ int mfm_runrs_fetch(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max
 /* For consumers that stay on the device: the last call's runs, payload and d_totals[4], written by work queued on that
  * call's stream and valid until the next call.  Any of the three may be NULL. */
 int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_runs, const int16_t **d_payload, const uint64_t **d_totals);
+/* The capacities fixed at create, which a stage behind sizes itself from: the most runs and the most output elements one call
+ * can produce (max_runs as given or its default; ((max_windows * W + max_runs * plen) * I) / D + max_runs). */
+int mfm_runrs_get_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *max_out_elems);
+
+/*
+ * ---- Burst AIS stage: the burst resampler's runs through the AIS demodulator, on the device -----------------------------
+ * The AIS stage above (mfm_ais_*) on ragged runs instead of full rows: its input is what mfm_runrs_device_view returns (the
+ * run list, the dense resampled payload, the totals), all read on the device, and its output is AIS packet events.
+ *
+ * Stretch means what it means for the burst resampler; this stage does not track windows.  Run r continues its channel's
+ * stretch exactly when MFM_RUNRS_BEGINS is clear in runs[r].flags, otherwise it begins a new one.  Sample numbers are
+ * stretch-relative: sample first_out + j is output j of the run.
+ *
+ * Rule.  The events of a stretch are exactly what a fresh reference demodulator (ais_demod_on_pcm, ais/ais_demod.c:215-258,
+ * SEARCH_SYNC, all registers and prior samples zero) returns when fed the stretch's resampled PCM, with the conventions of
+ * mfm_ais: bit = (sample > 0); the first packet bit is read four samples after the matching sample, then one every five; an
+ * event at each packet end with current_bit / 8 >= 4; the FCS as there.  A packet still being received when its stretch ends
+ * is dropped without an event.  A run with nr_out == 0 produces no event and still begins or continues its stretch.  Events
+ * do not depend on how the stream was cut into calls.
+ *
+ * State.  Per channel, on the device (struct mfm_runais_state below, which the host twin carries too): the walker's state of
+ * the stretch in progress (mode, positions, NRZI and flag history, the packet so far), the outputs seen, the stretch's first
+ * window, and the last 256 sample bits of the stretch: (160 + 5) samples of register history, rounded to words.  Two state
+ * buffers are used in turn: a channel's first run reads the old state, its last run leaves the new one.  A channel without a
+ * run in a call keeps its state.
+ *
+ * Result.  It replaces the previous call's: one dense list of mfm_runais_event in run order, stream order within a run;
+ * d_totals[4] = { events, runs, overflow, input error }.  Order and content are deterministic: the walk of a run writes into a
+ * slot range given by a scan, and the ranges are packed afterwards.
+ *
+ * Event bound.  The first packet bit is read 4 samples after the preamble match, one more every 5, and an event needs 32
+ * kept bits, so a packet ends at least 4 + 5 * 31 = 159 samples after its match, which lies behind the previous packet end:
+ * two packet ends of a stretch are at least 160 samples apart.  A run of nr_out samples therefore ends at most
+ * nr_out / 160 + 1 packets (the + 1: a packet carried in ends anywhere), and a call at most the sum of that over its runs.
+ *
+ * Refused calls produce nothing, leave the per-channel state untouched and raise a flag that mfm_runais_fetch reports as
+ * MFM_E_STATE with a message:
+ *   overflow     MFM_RUNAIS_OVER_RUNS: more runs than max_runs; MFM_RUNAIS_OVER_EVENTS: the call's event bound exceeds
+ *                max_events (by the bound, not by the count, so "does it fit" does not depend on the signal)
+ *   input error  MFM_RUNAIS_IN_RUNRS: the resampler's totals carry overflow or gate error; MFM_RUNAIS_IN_OUT_OF_STEP: a
+ *                continuing run's first_out is not the channel's output count, the channel has no stretch, or the run is not
+ *                its channel's first of the call; MFM_RUNAIS_IN_BAD_RUNS: a run names a channel >= nr_channels, channels do
+ *                not ascend, a beginning run's first_out is not 0, an output range lies beyond the resampler's totals or the
+ *                totals beyond max_out_samples.  These are checked before anything of the payload is read.
+ */
+#define MFM_RUNAIS_OVER_RUNS 1u
+#define MFM_RUNAIS_OVER_EVENTS 2u
+#define MFM_RUNAIS_IN_RUNRS 1u
+#define MFM_RUNAIS_IN_OUT_OF_STEP 2u
+#define MFM_RUNAIS_IN_BAD_RUNS 4u
+
+struct mfm_runais_event {       /* 200 bytes */
+    uint32_t channel;
+    uint32_t fcs_valid;
+    uint32_t nr_bytes;          /* 4 .. 160, FCS bytes included */
+    uint32_t run;               /* index, in this call's run list, of the run in which the packet ended */
+    uint64_t stretch_window;    /* first window of the stretch: its first input sample is stretch_window * W */
+    uint64_t sample;            /* stretch-relative index of the resampled sample that ended the packet */
+    uint64_t start_sample;      /* stretch-relative index of the sample where the preamble matched */
+    uint8_t bytes[160];         /* as mfm_ais_event.bytes */
+};
+
+struct mfm_runais; /* opaque */
+
+struct mfm_runais_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_runs;          /* the burst resampler's capacities (mfm_runrs_get_capacity) */
+    uint32_t max_out_samples;
+    uint32_t max_events;        /* per call, all channels; 0 = max_out_samples / 160 + max_runs, cannot overflow */
+    uint32_t flags;             /* 0 */
+};
+
+int mfm_runais_create(struct mfm_runais **pa, const struct mfm_runais_config *cfg);
+void mfm_runais_destroy(struct mfm_runais **pa);
+/*
+ * Demodulate the runs of one burst resampler call: d_runs, d_payload and d_totals are what mfm_runrs_device_view returned.
+ * Work is queued on `stream` (the resampler call's, or one ordered behind it); no host synchronisation and no count read on
+ * the host: launches are sized from the capacities fixed at create, surplus workgroups return after reading the totals.  The
+ * three arrays are read until the queued work has run.
+ */
+int mfm_runais_process_device(struct mfm_runais *a, const struct mfm_runrs_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                              void *stream);
+/*
+ * Wait for the last call and copy its events (the copy is sized by the call's events).  MFM_E_NOMEM when max_events is too
+ * small (nothing copied, *nr_events = needed); MFM_E_STATE with a message when the call was refused (nothing copied, the
+ * state did not move: the same input in a call that is right is right again).
+ */
+int mfm_runais_fetch(struct mfm_runais *a, struct mfm_runais_event *events, size_t max_events, size_t *nr_events);
+/* For consumers that stay on the device: the last call's events and d_totals[4], valid until the next call.  Either may be
+ * NULL. */
+int mfm_runais_device_view(struct mfm_runais *a, const struct mfm_runais_event **d_events, const uint64_t **d_totals);
 
 /*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
@@ -1238,6 +1331,32 @@ int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint3
                             const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload, size_t nr_gate_elems,
                             struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
                             size_t *nr_elems);
+/* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream */
+struct mfm_runais_state {       /* 264 bytes */
+    uint64_t outs;              /* outputs of the stretch so far */
+    uint64_t stretch_window;    /* first window of the stretch */
+    uint64_t pos;               /* SEARCH: next sample to look at (all positions stretch-relative) */
+    uint64_t r;                 /* SEARCH: first sample after the last detector reset */
+    uint64_t rd;                /* RECEIVE: next sample to read a bit from */
+    uint64_t start;             /* RECEIVE: sample where the preamble matched */
+    uint32_t mode;              /* 0 SEARCH, 1 RECEIVE */
+    uint32_t last_sample;       /* RECEIVE: the bit read last (NRZI) */
+    uint32_t hist8;             /* RECEIVE: the eight decoded bits read last, newest in bit 7 */
+    uint32_t cur_bit;           /* RECEIVE: bits kept so far */
+    uint32_t has_stretch;       /* 0: nothing to continue */
+    uint32_t reserved;          /* 0 */
+    uint32_t packet[40];        /* the packet so far, LSB first */
+    uint32_t tail[8];           /* the last 256 sample bits of the stretch, the newest in bit 31 of tail[7]; zeros in front of
+                                   a stretch shorter than that */
+};
+/* host twin of one mfm_runais_process_device call and its fetch, no device needed: runs / payload / totals are one burst
+ * resampler call's result (totals[4] as its d_totals), state [nr_channels] is read and updated in place, max_runs,
+ * max_out_samples and max_events are the configuration's (max_events 0 = its default).  Same refusals: MFM_E_STATE with the
+ * message mfm_runais_fetch gives and *flags = overflow | input error << 8; MFM_E_NOMEM when max_out is too small (*nr_events
+ * = needed); on any error nothing is written, the state included. */
+int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                             struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                             const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

@@ -3,7 +3,7 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
-           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE]]
+           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-ais]]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -35,6 +35,15 @@ samples and DIR/resampled.jsonl one line per run:
 (first_sample in samples of the channel at the input rate, first_out the index of the run's first output within its stretch,
 begins 1 on a stretch's first run, file_offset in bytes of the .rs.s16 file).
 
+--gate-ais (with --gate-resample) queues the burst AIS stage behind the burst resampler on the same stream, the flush call
+included: every stretch goes through a fresh AIS demodulator, and DIR/ais.jsonl gets one line per candidate packet:
+
+    {"channel": 3, "first_sample": 4000, "sample": 2549, "start_sample": 1575, "nr_bytes": 23, "fcs_valid": 1, "bytes": "0465..."}
+
+(first_sample: where the packet's stretch begins, in samples of the channel at the input rate; sample and start_sample: the
+resampled samples, counted from the stretch's first, where the packet ended and where its preamble matched; bytes: nr_bytes
+bytes as hex, the FCS included).
+
     python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8] [--gate-preroll 0,1,4]
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
@@ -49,7 +58,10 @@ P = 0 line of the same run, "gate_ms_over_p0" per mask: the cost of the pre-roll
 dilated mask lets through in the steady state (every call emits the last P windows of the call before it, from the history, and
 all but the last P of its own).  With --form pcm a last line ("runrs_stage") times the burst resampler (4/5, 81 taps) behind the
 gate for the three masks, alternating in the same process with mfm_resampler_process_device (MFM_RS_FORCE_DOT2) on the full rows:
-all-open over that plain resampler as a ratio with its standard error, all-closed as an absolute time."""
+all-open over that plain resampler as a ratio with its standard error, all-closed as an absolute time.  A line behind it
+("runais_stage"; --bench-runais prints that line alone, without the engine) times the burst chain burst resampler -> burst AIS
+stage on a gate's device view against the plain chain mfm_resampler -> mfm_ais on the full rows, 4/5 with 41 taps, for the same
+three masks and for two row sets of its own: idle (noise) and busy (synthesized AIS frames on every channel)."""
 import argparse
 import ctypes as C
 import json
@@ -107,6 +119,18 @@ def scan(a):
         rr = pkg.RunResampler(len(chans), co, interp, decim_rs, a.window, max_in_samples=a.block // decim + 8,
                               preroll_windows=int(a.gate_preroll), device=a.device)
         rs_index = open(os.path.join(a.gate_out, "resampled.jsonl"), "w")
+    ra, ais_index = None, None
+    if a.gate_ais:
+        if not rr:
+            raise SystemExit("--gate-ais needs --gate-resample: the burst AIS stage takes the burst resampler's runs")
+        ra = pkg.RunAis.behind(rr, device=a.device)
+        ais_index = open(os.path.join(a.gate_out, "ais.jsonl"), "w")
+
+    def write_ais(events):
+        for e in events:
+            ais_index.write(json.dumps({"channel": int(e["channel"]), "first_sample": int(e["stretch_window"]) * a.window,
+                                        "sample": int(e["sample"]), "start_sample": int(e["start_sample"]), "nr_bytes": int(e["nr_bytes"]),
+                                        "fcs_valid": int(e["fcs_valid"]), "bytes": bytes(e["bytes"][:int(e["nr_bytes"])]).hex()}) + "\n")
 
     def write_resampled(runs, payload):
         for r in runs:
@@ -156,11 +180,15 @@ def scan(a):
                 gate.process_device(rows[0], rows[1], nout, d_rec, rec_stride, nw, stream=eng.stream)
                 if rr:
                     rr.process_device(*gate.device_view(), stream=eng.stream)
+                if ra:
+                    ra.process_device(*rr.device_view(), stream=eng.stream)
             rec = lv.fetch()
             if gate:
                 write_runs(*gate.fetch())
             if rr:
                 write_resampled(*rr.fetch())
+            if ra:
+                write_ais(ra.fetch())
             for c, (freq, _) in enumerate(chans):
                 for r in rec[c]:
                     out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
@@ -175,10 +203,17 @@ def scan(a):
         gate.flush_device(stream=eng.stream)  # the windows pre-roll still held back; none with P = 0
         if rr:
             rr.process_device(*gate.device_view(), stream=eng.stream)
+        if ra:
+            ra.process_device(*rr.device_view(), stream=eng.stream)
         write_runs(*gate.fetch())
         if rr:
             write_resampled(*rr.fetch())
             rs_index.close()
+        if ra:
+            write_ais(ra.fetch())
+            ais_index.close()
+            ra.close()
+        if rr:
             rr.close()
         index.close()
         gate.close()
@@ -274,6 +309,7 @@ def bench(a):
         p0 = line if P == 0 else p0
     if not iq_form:
         bench_runrs(a, pkg, torch, rows, in_stride, nout, timed)
+        bench_runais(a, pkg, torch)
     for o in (lv, eng):
         o.close()
 
@@ -433,6 +469,125 @@ def bench_runrs(a, pkg, torch, rows, in_stride, nout, timed):
         o.close()
 
 
+def _busy_rows(pkg, nch, n):
+    """[nch][n] int16 at 60 kHz: AIS frames of three types, CRC rejects and stretches without transitions on every channel (eight
+    different streams, rotated from channel to channel)"""
+    sy = pkg.synth
+    rng = np.random.RandomState(5)
+    pl = [sy.ais_type1(mmsi=123456789, sog=123), sy.ais_type4(mmsi=111222333), sy.ais_type5(mmsi=987654321, ship_name="BENCH")]
+    n48 = n * 4 // 5 + 8
+    base = []
+    for k in range(8):
+        frames = []
+        while sum(len(f) for f in frames) * 5 < n48:
+            j = int(rng.randint(0, 5))
+            if j < 3:
+                frames.append(sy.ais_frame_bits(pl[j]))
+            elif j == 3:
+                frames.append(sy.ais_frame_bits(pl[int(rng.randint(0, 3))], fcs=int(rng.randint(0, 65536))))
+            else:
+                frames.append(np.ones(int(rng.randint(1, 400)), np.uint8))
+        x = sy.ais_pcm(sy.ais_bits(frames, gap_bits=2), noise=400.0, phase=k % 5, seed=k)
+        base.append(np.repeat(x, 5)[::4][:n])
+    return np.stack([np.roll(base[c % 8], 977 * (c // 8)) for c in range(nch)])
+
+
+def bench_runais(a, pkg, torch):
+    """burst resampler -> burst AIS stage on the device view one gate call left (every call begins every stretch anew, as in
+    bench_runrs, so every call does the same work) against mfm_resampler (v_dot2 form) -> mfm_ais on the full rows; the two chains
+    alternate in one process in rotating order"""
+    b = pkg.binding
+    nch, W, I, D = a.bench_channels, a.window, 4, 5
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    taps = np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16)
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "runais_stage", "channels": nch, "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I,
+           "decimate": D, "taps": int(taps.size), "reps": a.reps, "calls_per_rep": a.inner, "search": "M words computed in the walker"}
+    rng = np.random.RandomState(1)
+    for rows_name in ("idle", "busy"):
+        host = rng.randint(-3000, 3001, size=(nch, n)).astype(np.int16) if rows_name == "idle" else _busy_rows(pkg, nch, n)
+        d_rows = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "scene": scene["open"]}
+        keep, recs = [], {"scene": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        plain = pkg.Resampler(nch, taps, I, D, nb, device=0, force_dot2=True)
+        ais = pkg.Ais(nch, plain.max_out(), device=0)
+        rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        ra = pkg.RunAis.behind(rr)
+
+        def run_plain():
+            yptr, ystride, ny = plain.process_device(rows, in_stride, nb)
+            ais.process_device(yptr, ystride, ny)
+
+        res = {}
+        for name in ("all_closed", "scene", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_burst():
+                rr.process_device(*view)
+                ra.process_device(*rr.device_view())
+
+            variants = [("burst", run_burst), ("plain", run_plain)]
+            for _, fn in variants:
+                timed(fn, 3)
+            nr_events, plain_events = len(ra.fetch()), len(ais.fetch_events())
+            got = {v: [] for v, _ in variants}
+            for rep in range(a.reps):
+                k = rep % len(variants)
+                for vname, fn in variants[k:] + variants[:k]:
+                    got[vname].append(timed(fn, a.inner))
+            (bm, bsd), (pm, psd) = _stats(got["burst"]), _stats(got["plain"])
+            ratio = bm / pm
+            ratio_se = ratio * math.sqrt(bsd * bsd / a.reps / (bm * bm) + psd * psd / a.reps / (pm * pm))
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "burst_events_per_call": nr_events,
+                         "plain_events_last_call": plain_events, "burst_ms": bm, "burst_sd": bsd, "plain_ms": pm, "plain_sd": psd,
+                         "burst_over_plain": ratio, "burst_over_plain_se": ratio_se}
+            gate.close()
+        out[rows_name] = res
+        for o in (ra, rr, ais, plain, sq):
+            o.close()
+        del d_rows, keep
+    print(json.dumps(out))
+
+
+def bench_runais_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runais needs the GPU: there is no CPU path to time")
+    bench_runais(a, pkg, torch)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config")
@@ -452,11 +607,15 @@ def main():
     ap.add_argument("--gate-preroll", default="0", help="pre-roll windows of the gate; with --bench one or several, as 0,1,4")
     ap.add_argument("--gate-resample", default=None, help="I/D: resample the gate's runs on the device (with --gate-out, --form pcm)")
     ap.add_argument("--resample-taps", default=None, help="JSON file whose lpfCoeffs are the resampler's taps")
+    ap.add_argument("--gate-ais", action="store_true", help="demodulate AIS on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--bench-runais", action="store_true", help="the runais_stage line of --bench alone")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
     a = ap.parse_args()
+    if a.bench_runais:
+        return bench_runais_alone(a)
     if a.bench:
         return bench(a)
     if not a.config or not a.input:

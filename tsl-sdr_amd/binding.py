@@ -67,6 +67,8 @@ ABI_SYMBOLS = [
     "mfm_resampler_get_form", "mfm_hosttwin_resampler_form", "mfm_hosttwin_resampler_matrix_block",
     "mfm_runrs_create", "mfm_runrs_destroy", "mfm_runrs_process_device", "mfm_runrs_fetch", "mfm_runrs_device_view",
     "mfm_hosttwin_runrs_plan", "mfm_hosttwin_runrs_call",
+    "mfm_runrs_get_capacity", "mfm_runais_create", "mfm_runais_destroy", "mfm_runais_process_device", "mfm_runais_fetch",
+    "mfm_runais_device_view", "mfm_hosttwin_runais_call",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -219,6 +221,27 @@ MFM_RUNRS_NO_WINDOW = (1 << 64) - 1                     # mfm_runrs_state.expect
 RUNRS_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("out_offset", "<u8"), ("first_out", "<u8"), ("channel", "<u4"),
                             ("nr_out", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 RUNRS_STATE_DTYPE = np.dtype([("expected", "<u8"), ("outs", "<u8"), ("phase", "<u4"), ("pending", "<u4")])
+
+
+class RunaisConfig(C.Structure):
+    """struct mfm_runais_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("max_runs", C.c_uint32),
+                ("max_out_samples", C.c_uint32), ("max_events", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RunaisEvent(C.Structure):
+    _fields_ = [("channel", C.c_uint32), ("fcs_valid", C.c_uint32), ("nr_bytes", C.c_uint32), ("run", C.c_uint32),
+                ("stretch_window", C.c_uint64), ("sample", C.c_uint64), ("start_sample", C.c_uint64), ("bytes", C.c_uint8 * 160)]
+
+
+MFM_RUNAIS_OVER_RUNS, MFM_RUNAIS_OVER_EVENTS = 1, 2                                # d_totals[2]
+MFM_RUNAIS_IN_RUNRS, MFM_RUNAIS_IN_OUT_OF_STEP, MFM_RUNAIS_IN_BAD_RUNS = 1, 2, 4   # d_totals[3]
+# numpy views of struct mfm_runais_event (200 bytes) and struct mfm_runais_state (264 bytes, per channel)
+RUNAIS_EVENT_DTYPE = np.dtype([("channel", "<u4"), ("fcs_valid", "<u4"), ("nr_bytes", "<u4"), ("run", "<u4"),
+                               ("stretch_window", "<u8"), ("sample", "<u8"), ("start_sample", "<u8"), ("bytes", "u1", (160,))])
+RUNAIS_STATE_DTYPE = np.dtype([("outs", "<u8"), ("stretch_window", "<u8"), ("pos", "<u8"), ("r", "<u8"), ("rd", "<u8"),
+                               ("start", "<u8"), ("mode", "<u4"), ("last_sample", "<u4"), ("hist8", "<u4"), ("cur_bit", "<u4"),
+                               ("has_stretch", "<u4"), ("reserved", "<u4"), ("packet", "<u4", (40,)), ("tail", "<u4", (8,))])
 
 
 class FlexConfig(C.Structure):
@@ -464,6 +487,15 @@ def load_library():
     lib.mfm_runrs_process_device.argtypes = [vp, vp, vp, vp, vp]
     lib.mfm_runrs_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_runrs_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runrs_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.mfm_runais_create.argtypes = [C.POINTER(vp), C.POINTER(RunaisConfig)]
+    lib.mfm_runais_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runais_destroy.restype = None
+    lib.mfm_runais_process_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mfm_runais_fetch.argtypes = [vp, vp, C.c_size_t, szp]
+    lib.mfm_runais_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_hosttwin_runais_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
+                                             C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runrs_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, vp, vp, vp]
     lib.mfm_hosttwin_runrs_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i16p, C.c_size_t, vp, i16p,
                                             vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
@@ -1479,6 +1511,135 @@ class RunResampler:
         if rc < 0:
             self._raise(rc, "mfm_runrs_device_view")
         return r.value, p.value, t.value
+
+
+    def capacity(self):
+        """(max_runs, max_out_elems): the most runs and output elements one call can produce, which a stage behind sizes
+        itself from"""
+        nr, ne = C.c_uint32(), C.c_uint64()
+        rc = self.lib.mfm_runrs_get_capacity(self.h, C.byref(nr), C.byref(ne))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_get_capacity")
+        return nr.value, ne.value
+
+
+class RunAis:
+    """mfm_runais: the runs of a RunResampler's device view through the AIS demodulator, one fresh demodulator per stretch;
+    one RUNAIS_EVENT_DTYPE per candidate packet.  max_runs and max_out_samples are the burst resampler's capacities
+    (RunAis.behind reads them); max_events 0 is a bound that cannot overflow."""
+
+    def __init__(self, nr_channels, max_runs, max_out_samples, max_events=0, device=0, flags=0, abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        cfg = RunaisConfig(abi_version, device, nr_channels, max_runs, max_out_samples, max_events, flags)
+        rc = self.lib.mfm_runais_create(C.byref(self.h), C.byref(cfg))
+        if rc < 0:
+            self._raise(rc, "mfm_runais_create")
+        self.nr_channels = nr_channels
+
+    @classmethod
+    def behind(cls, run_resampler, max_events=0, device=0):
+        """a stage sized for everything one call of `run_resampler` can produce"""
+        max_runs, max_out = run_resampler.capacity()
+        return cls(run_resampler.nr_channels, max_runs, max_out, max_events=max_events, device=device)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runais_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_payload, d_totals, stream=None):
+        """the three addresses of RunResampler.device_view(), after its process_device on the same stream"""
+        rc = self.lib.mfm_runais_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runais_process_device")
+
+    def fetch(self, max_events=None):
+        """the events of the last call (RUNAIS_EVENT_DTYPE).  With max_events too small: MfmError(MFM_E_NOMEM) whose `needed`
+        attribute is the number that would fit and whose `buffer` is untouched"""
+        nr = C.c_size_t()
+        if max_events is None:
+            rc = self.lib.mfm_runais_fetch(self.h, None, 0, C.byref(nr))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below, with the untouched buffer
+                self._raise(rc, "mfm_runais_fetch")
+            max_events = nr.value
+        out = np.zeros(max(max_events, 1), RUNAIS_EVENT_DTYPE)
+        rc = self.lib.mfm_runais_fetch(self.h, out.ctypes.data, max_events, C.byref(nr))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runais_fetch")
+            except MfmError as err:
+                err.needed = nr.value
+                err.buffer = out
+                raise
+        return out[:nr.value].copy()
+
+    def device_view(self):
+        """(d_events, d_totals): device addresses of the last call's events and the four uint64 totals (events, runs, overflow,
+        input error)"""
+        e, t = C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runais_device_view(self.h, C.byref(e), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runais_device_view")
+        return e.value, t.value
+
+
+def hosttwin_runais_state(nr_channels):
+    """the host twin's per-channel state at the start of a stream: RUNAIS_STATE_DTYPE [C], all zero (no stretch)"""
+    return np.zeros(nr_channels, RUNAIS_STATE_DTYPE)
+
+
+def hosttwin_runais_call(state, runs, payload, totals=None, max_runs=None, max_out_samples=None, max_events=0, max_out=None):
+    """mfm_hosttwin_runais_call: one call of the burst AIS stage on the CPU.  state (hosttwin_runais_state) is updated in
+    place; runs RUNRS_RUN_DTYPE and payload int16 are one burst resampler call's result, totals its four totals (default: the
+    lengths, no flags); max_runs / max_out_samples / max_events are the configuration's (default: what the call needs);
+    returns the events.  A refused call raises MfmError(MFM_E_STATE) with a `flags` attribute (overflow | input error << 8)"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNAIS_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    pl = np.ascontiguousarray(payload, dtype=np.int16).reshape(-1)
+    t = np.array([rr.size, pl.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_out_samples = max(pl.size, 1) if max_out_samples is None else max_out_samples
+    if max_out is None:
+        max_out = pl.size // 160 + rr.size
+    out = np.zeros(max(max_out, 1), RUNAIS_EVENT_DTYPE)
+    nr, fl = C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runais_call(state.shape[0], max_runs, max_out_samples, max_events, state.ctypes.data,
+                                      rr.ctypes.data if rr.size else None, pl.ctypes.data if pl.size else None, t.ctypes.data,
+                                      out.ctypes.data, max_out, C.byref(nr), C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runais_call", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.flags = nr.value, fl.value
+        raise err
+    return out[:nr.value].copy()
+
+
+def runais_to_ais_events(events, interpolate, decimate, window_samples):
+    """mfm_ais_event records (AIS_EVENT_DTYPE, what host/mfm_ais.c's ais_decode_on_events takes) from the burst stage's: the
+    stretch-relative sample numbers become positions of the channel's stream at the output rate, sample = stretch_window * W *
+    I // D + sample and start_sample likewise.  That is the position to within one sample: a fresh resampler's first output
+    stands for the stretch's first input sample, and the floor drops less than one output period"""
+    ev = np.asarray(events)
+    assert ev.dtype == RUNAIS_EVENT_DTYPE
+    out = np.zeros(ev.shape, AIS_EVENT_DTYPE)
+    base = np.array([int(w) * window_samples * interpolate // decimate for w in ev["stretch_window"]], np.uint64).reshape(ev.shape)
+    for f in ("channel", "fcs_valid", "nr_bytes", "bytes"):
+        out[f] = ev[f]
+    out["sample"] = base + ev["sample"]
+    out["start_sample"] = base + ev["start_sample"]
+    return out
 
 
 def hosttwin_runrs_state(nr_channels, nr_coeffs, interpolate):

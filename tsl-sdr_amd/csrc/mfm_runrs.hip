@@ -699,6 +699,20 @@ int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_r
     return MFM_OK;
 }
 
+int mfm_runrs_get_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *max_out_elems)
+{
+    if (!rr) {
+        return MFM_E_INVAL;
+    }
+    if (max_runs) {
+        *max_runs = (uint32_t)rr->g.cap_runs;
+    }
+    if (max_out_elems) {
+        *max_out_elems = rr->g.out_cap;
+    }
+    return MFM_OK;
+}
+
 int mfm_hosttwin_runrs_plan(uint32_t interpolate, uint32_t decimate, uint32_t plen, const uint32_t *phase, const uint32_t *pending,
                             const uint64_t *nr_samples, size_t n, uint64_t *nr_out, uint32_t *phase_out, uint32_t *pending_out)
 {
