@@ -1151,6 +1151,113 @@ int mfm_runais_fetch(struct mfm_runais *a, struct mfm_runais_event *events, size
 int mfm_runais_device_view(struct mfm_runais *a, const struct mfm_runais_event **d_events, const uint64_t **d_totals);
 
 /*
+ * ---- Burst POCSAG stage: the burst resampler's runs through the POCSAG demodulator, on the device -----------------------
+ * The pager stage above (mfm_pocsag_*) on ragged runs instead of full rows: its input is what mfm_runrs_device_view returns
+ * (the run list, the dense resampled payload, the totals), all read on the device, and its output is POCSAG events.  The
+ * stage assumes 38 400 Hz, as mfm_pocsag does.
+ *
+ * Stretch means what it means for the burst resampler; this stage does not track windows.  Run r continues its channel's
+ * stretch exactly when MFM_RUNRS_BEGINS is clear in runs[r].flags, otherwise it begins a new one.  Sample numbers are
+ * stretch-relative: sample first_out + j is output j of the run.
+ *
+ * Rule.  The events of a stretch are exactly what a fresh reference decoder (pager_pocsag_on_pcm, pager/pager_pocsag.c:434-543,
+ * with the three detectors of :81-117; state SEARCH, all eye registers, counters and batch words zero) returns when fed the
+ * stretch's resampled PCM, with the conventions of mfm_pocsag: bit = (sample < 0); sync = popcount(word ^ 0x7cd215d8) <= 4;
+ * the eye fires when a run of more than samples_per_bit / 2 matches ends, with offset matches / 2; batch words are filled LSB
+ * first and masked with 0x7fffffff before BCH, nr_ok / fail_mask / raw / corrected as there; when two detectors fire on one
+ * sample the later one (2400 after 1200 after 512) wins and only the winner is reported.  A batch or sync word still being
+ * collected when its stretch ends is dropped without an event, as the reference drops it at the end of a stream.  A run with
+ * nr_out == 0 produces no event and still begins or continues its stretch.  Events do not depend on how the stream was cut
+ * into calls.
+ *
+ * No lag.  An event is reported by the call and run whose [first_out, first_out + nr_out) holds its `sample`: the partly
+ * collected batch travels in the per-channel state, as it does in the reference's struct pager_pocsag_batch.
+ *
+ * State.  Per channel, on the device (struct mfm_runpocsag_state below, which the host twin carries too): the walker's mode,
+ * baud and samples per bit, the sample-skip counter, the batch so far, the sync word so far, the three nr_eye_matches, the
+ * outputs seen, the stretch's first window, the distance back to the last detector reset (saturating) and the last 2400
+ * sample bits of the stretch: the slowest detector keeps 32 bits 75 samples apart.  Two state buffers are used in turn: a
+ * channel's first run reads the old state, its last run leaves the new one.  A channel without a run in a call keeps its
+ * state.  Only a channel's first run of a call can continue a stretch, so every run of a call is walked independently.
+ *
+ * Result.  It replaces the previous call's: one dense list of mfm_runpocsag_event in run order, stream order within a run;
+ * d_totals[4] = { events, runs, overflow, input error }.  Order and content are deterministic: the walk of a run writes into a
+ * slot range given by a scan, and the ranges are packed afterwards.
+ *
+ * Event bound.  Within a stretch the events follow (FOUND BATCH (KEPT BATCH)* LOST)*.  A BATCH event needs 512 bits after the
+ * previous sync slot's 32, so two BATCH events are at least 544 bit periods = 544 * 16 = 8704 samples apart: a run of nr_out
+ * samples holds at most nr_out / 8704 + 1 of them.  Between two consecutive BATCH events lie at most two others (KEPT, or LOST
+ * FOUND), in front of a run's first at most two (a transmission carried in: LOST FOUND) and behind its last at most two, so a
+ * run holds at most 3 * (nr_out / 8704 + 1) + 2 events and a call at most the sum of that over its runs.
+ *
+ * Refused calls produce nothing, leave the per-channel state untouched and raise a flag that mfm_runpocsag_fetch reports as
+ * MFM_E_STATE with a message:
+ *   overflow     MFM_RUNPOCSAG_OVER_RUNS: more runs than max_runs; MFM_RUNPOCSAG_OVER_EVENTS: the call's event bound exceeds
+ *                max_events (by the bound, not by the count, so "does it fit" does not depend on the signal)
+ *   input error  MFM_RUNPOCSAG_IN_RUNRS: the resampler's totals carry overflow or gate error; MFM_RUNPOCSAG_IN_OUT_OF_STEP: a
+ *                continuing run's first_out is not the channel's output count, the channel has no stretch, or the run is not
+ *                its channel's first of the call; MFM_RUNPOCSAG_IN_BAD_RUNS: a run names a channel >= nr_channels, channels
+ *                do not ascend, a beginning run's first_out is not 0, an output range lies beyond the resampler's totals or
+ *                the totals beyond max_out_samples.  These are checked before anything of the payload is read.
+ */
+#define MFM_RUNPOCSAG_OVER_RUNS 1u
+#define MFM_RUNPOCSAG_OVER_EVENTS 2u
+#define MFM_RUNPOCSAG_IN_RUNRS 1u
+#define MFM_RUNPOCSAG_IN_OUT_OF_STEP 2u
+#define MFM_RUNPOCSAG_IN_BAD_RUNS 4u
+
+struct mfm_runpocsag_event {    /* 176 bytes */
+    uint32_t type;              /* MFM_POCSAG_EV_* */
+    uint32_t baud;              /* 512 / 1200 / 2400 */
+    uint32_t channel;
+    uint32_t aux;               /* as mfm_pocsag_event.aux */
+    uint32_t run;               /* index, in this call's run list, of the run that holds `sample` */
+    uint32_t nr_ok;             /* BATCH: as mfm_pocsag_event */
+    uint32_t fail_mask;
+    uint32_t reserved;          /* 0 */
+    uint64_t stretch_window;    /* first window of the stretch: its first input sample is stretch_window * W */
+    uint64_t sample;            /* stretch-relative index of the resampled sample that completed the event */
+    uint32_t raw[16];
+    uint32_t corrected[16];
+};
+
+struct mfm_runpocsag; /* opaque */
+
+struct mfm_runpocsag_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_runs;          /* the burst resampler's capacities (mfm_runrs_get_capacity) */
+    uint32_t max_out_samples;
+    uint32_t max_events;        /* per call, all channels; 0 = 3 * (max_out_samples / 8704) + 5 * max_runs, cannot overflow */
+    uint32_t flags;             /* 0 */
+};
+
+int mfm_runpocsag_create(struct mfm_runpocsag **pp, const struct mfm_runpocsag_config *cfg);
+void mfm_runpocsag_destroy(struct mfm_runpocsag **pp);
+/*
+ * Decode the runs of one burst resampler call: d_runs, d_payload and d_totals are what mfm_runrs_device_view returned.
+ * Work is queued on `stream` (the resampler call's, or one ordered behind it); no host synchronisation and no count read on
+ * the host: launches are sized from the capacities fixed at create, surplus workgroups return after reading the totals.  The
+ * three arrays are read until the queued work has run.
+ */
+int mfm_runpocsag_process_device(struct mfm_runpocsag *p, const struct mfm_runrs_run *d_runs, const int16_t *d_payload,
+                                 const uint64_t *d_totals, void *stream);
+/*
+ * Wait for the last call and copy its events (the copy is sized by the call's events).  MFM_E_NOMEM when max_events is too
+ * small (nothing copied, *nr_events = needed); MFM_E_STATE with a message when the call was refused (nothing copied, the
+ * state did not move: the same input in a call that is right is right again).
+ */
+int mfm_runpocsag_fetch(struct mfm_runpocsag *p, struct mfm_runpocsag_event *events, size_t max_events, size_t *nr_events);
+/* For consumers that stay on the device: the last call's events and d_totals[4], valid until the next call.  Either may be
+ * NULL. */
+int mfm_runpocsag_device_view(struct mfm_runpocsag *p, const struct mfm_runpocsag_event **d_events, const uint64_t **d_totals);
+struct mfm_runpocsag_state;
+/* Wait for the last call and copy the per-channel state it left, state[nr_channels] (for tests and for moving a stream
+ * between objects: it is what the host twin carries). */
+int mfm_runpocsag_fetch_state(struct mfm_runpocsag *p, struct mfm_runpocsag_state *state, size_t nr_channels);
+
+/*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
  *   mm_init      pager/mueller_muller.c:10-33
  *   mm_process   pager/mueller_muller.c:41-115
@@ -1357,6 +1464,35 @@ struct mfm_runais_state {       /* 264 bytes */
 int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
                              struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
                              const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags);
+/* the per-channel state of the burst POCSAG stage, on the device and in the host twin: all zero at the start of a stream.
+ * Fields a mode does not use are zero. */
+struct mfm_runpocsag_state {    /* 432 bytes */
+    uint64_t outs;              /* outputs of the stretch so far */
+    uint64_t stretch_window;    /* first window of the stretch */
+    uint32_t mode;              /* 0 SEARCH, 2 BATCH, 3 SYNCWORD */
+    uint32_t baud;              /* BATCH / SYNCWORD: 512 / 1200 / 2400 */
+    uint32_t spb;               /* BATCH / SYNCWORD: samples per bit (the reference's sample_skip) */
+    uint32_t skip;              /* BATCH / SYNCWORD: the reference's 16-bit cur_sample_skip after the last output */
+    uint32_t batch_word;        /* BATCH: words complete */
+    uint32_t batch_bit;         /* BATCH: bits of the word in progress */
+    uint32_t sync_word;         /* SYNCWORD: the bits of the sync slot so far, the newest in bit 0 */
+    uint32_t nr_sync_bits;
+    uint32_t nr_eye[3];         /* SEARCH: nr_eye_matches of the 512 / 1200 / 2400 detector after the last output */
+    uint32_t since_reset;       /* SEARCH: outputs since the last detector reset (stretch start or SYNC_LOST), at most 2400 */
+    uint32_t has_stretch;       /* 0: nothing to continue */
+    uint32_t batch[16];         /* BATCH: the batch so far, LSB first */
+    uint32_t tail[75];          /* the last 2400 sample bits of the stretch, the newest in bit 31 of tail[74]; zeros in front
+                                   of a stretch shorter than that */
+};
+/* host twin of one mfm_runpocsag_process_device call and its fetch, no device needed: runs / payload / totals are one burst
+ * resampler call's result (totals[4] as its d_totals), state [nr_channels] is read and updated in place, max_runs,
+ * max_out_samples and max_events are the configuration's (max_events 0 = its default).  Same refusals: MFM_E_STATE with the
+ * message mfm_runpocsag_fetch gives and *flags = overflow | input error << 8; MFM_E_NOMEM when max_out is too small
+ * (*nr_events = needed); on any error nothing is written, the state included. */
+int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                                const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events,
+                                uint32_t *flags);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

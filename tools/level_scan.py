@@ -3,7 +3,7 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
-           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-ais]]]
+           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-ais | --gate-pocsag]]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -44,6 +44,21 @@ included: every stretch goes through a fresh AIS demodulator, and DIR/ais.jsonl 
 resampled samples, counted from the stretch's first, where the packet ended and where its preamble matched; bytes: nr_bytes
 bytes as hex, the FCS included).
 
+--gate-pocsag (with --gate-resample whose output rate is 38 400 Hz; not together with --gate-ais) queues the burst POCSAG stage
+behind the burst resampler on the same stream, the flush call included: every stretch goes through a fresh POCSAG demodulator.
+DIR/pocsag.jsonl gets one line per event:
+
+    {"channel": 3, "first_sample": 4000, "type": 2, "baud": 1200, "sample": 26999, "aux": 0, "nr_ok": 16, "fail_mask": 0,
+     "corrected": ["7a89c197", ...]}
+
+(first_sample: where the event's stretch begins, in samples of the channel at the input rate; type: MFM_POCSAG_EV_*; sample: the
+resampled sample, counted from the stretch's first, that completed the event; corrected: the 16 words of a BATCH as hex, empty
+otherwise).  DIR/pages.jsonl gets the pages a fresh host pager per stretch (host/mfm_pager_pocsag.c, through libmfm_host.so)
+assembles from the events, in the shape decoder_amd prints them, with the channel and the stretch in the place of the time:
+
+    {"proto": "pocsag", "type": "alphanumeric", "channel": 3, "first_sample": 4000, "baud": 1200, "capCode": 596523, "function": 2,
+     "message": "HELLO"}
+
     python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8] [--gate-preroll 0,1,4]
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
@@ -61,7 +76,10 @@ gate for the three masks, alternating in the same process with mfm_resampler_pro
 all-open over that plain resampler as a ratio with its standard error, all-closed as an absolute time.  A line behind it
 ("runais_stage"; --bench-runais prints that line alone, without the engine) times the burst chain burst resampler -> burst AIS
 stage on a gate's device view against the plain chain mfm_resampler -> mfm_ais on the full rows, 4/5 with 41 taps, for the same
-three masks and for two row sets of its own: idle (noise) and busy (synthesized AIS frames on every channel)."""
+three masks and for two row sets of its own: idle (noise) and busy (synthesized AIS frames on every channel).  A last line
+("runpocsag_stage"; --bench-runpocsag prints that line alone) does the same for the burst chain burst resampler -> burst POCSAG
+stage against mfm_resampler -> mfm_pocsag, busy being synthesized POCSAG transmissions on every channel, and says whether a
+sample of the burst events (the first runs of a call) equalled the host twin's."""
 import argparse
 import ctypes as C
 import json
@@ -126,6 +144,30 @@ def scan(a):
         ra = pkg.RunAis.behind(rr, device=a.device)
         ais_index = open(os.path.join(a.gate_out, "ais.jsonl"), "w")
 
+    rp, pocsag_index, pages_index, pagers = None, None, None, {}
+    if a.gate_pocsag:
+        if not rr:
+            raise SystemExit("--gate-pocsag needs --gate-resample: the burst POCSAG stage takes the burst resampler's runs")
+        if ra:
+            raise SystemExit("--gate-pocsag and --gate-ais exclude each other: one stage reads the burst resampler's runs")
+        rp = pkg.RunPocsag.behind(rr, device=a.device)
+        pocsag_index = open(os.path.join(a.gate_out, "pocsag.jsonl"), "w")
+        pages_index = open(os.path.join(a.gate_out, "pages.jsonl"), "w")
+
+    def write_pocsag(events):
+        """the events, and the pages of a fresh host pager per (channel, stretch)"""
+        for e in events:
+            c, first = int(e["channel"]), int(e["stretch_window"]) * a.window
+            pocsag_index.write(json.dumps({"channel": c, "first_sample": first, "type": int(e["type"]), "baud": int(e["baud"]),
+                                           "sample": int(e["sample"]), "aux": int(e["aux"]), "nr_ok": int(e["nr_ok"]),
+                                           "fail_mask": int(e["fail_mask"]),
+                                           "corrected": ["%08x" % int(w) for w in e["corrected"]] if int(e["type"]) == 2 else []}) + "\n")
+            if c not in pagers or pagers[c].first != first:
+                if c in pagers:
+                    pagers[c].close()
+                pagers[c] = HostPager(c, first, pages_index)
+            pagers[c].on_events(b.runpocsag_to_pocsag_events(np.array([e], b.RUNPOCSAG_EVENT_DTYPE)))
+
     def write_ais(events):
         for e in events:
             ais_index.write(json.dumps({"channel": int(e["channel"]), "first_sample": int(e["stretch_window"]) * a.window,
@@ -182,6 +224,8 @@ def scan(a):
                     rr.process_device(*gate.device_view(), stream=eng.stream)
                 if ra:
                     ra.process_device(*rr.device_view(), stream=eng.stream)
+                if rp:
+                    rp.process_device(*rr.device_view(), stream=eng.stream)
             rec = lv.fetch()
             if gate:
                 write_runs(*gate.fetch())
@@ -189,6 +233,8 @@ def scan(a):
                 write_resampled(*rr.fetch())
             if ra:
                 write_ais(ra.fetch())
+            if rp:
+                write_pocsag(rp.fetch())
             for c, (freq, _) in enumerate(chans):
                 for r in rec[c]:
                     out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
@@ -205,6 +251,8 @@ def scan(a):
             rr.process_device(*gate.device_view(), stream=eng.stream)
         if ra:
             ra.process_device(*rr.device_view(), stream=eng.stream)
+        if rp:
+            rp.process_device(*rr.device_view(), stream=eng.stream)
         write_runs(*gate.fetch())
         if rr:
             write_resampled(*rr.fetch())
@@ -213,12 +261,54 @@ def scan(a):
             write_ais(ra.fetch())
             ais_index.close()
             ra.close()
+        if rp:
+            write_pocsag(rp.fetch())
+            for hp in pagers.values():
+                hp.close()
+            pocsag_index.close()
+            pages_index.close()
+            rp.close()
         if rr:
             rr.close()
         index.close()
         gate.close()
     lv.close()
     eng.close()
+
+
+class HostPager:
+    """host/mfm_pager_pocsag.c through libmfm_host.so: one pager for one stretch of one channel; every page goes to `out` as a
+    JSON line in the shape decoder_amd prints (decoder_main.c on_page), the channel and the stretch in the place of the time"""
+    CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint16, C.c_uint32, C.POINTER(C.c_char), C.c_size_t, C.c_uint8)
+
+    def __init__(self, channel, first, out):
+        so = os.path.join(ROOT, "tsl-sdr_amd", "host", "libmfm_host.so")
+        if not os.path.exists(so):
+            raise SystemExit(f"{so} missing: run make -C tsl-sdr_amd")
+        self.h = C.CDLL(so)
+        self.channel, self.first, self.out = channel, first, out
+        self._num = self.CB(lambda p, baud, cap, data, n, fn: self._page("numeric", baud, cap, data, n, fn))
+        self._alpha = self.CB(lambda p, baud, cap, data, n, fn: self._page("alphanumeric", baud, cap, data, n, fn))
+        self.p = C.c_void_p()
+        self.h.pager_pocsag_new.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, self.CB, self.CB, C.c_bool]
+        self.h.pager_pocsag_on_events.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        self.h.pager_pocsag_delete.argtypes = [C.POINTER(C.c_void_p)]
+        if self.h.pager_pocsag_new(C.byref(self.p), 0, self._num, self._alpha, False) != 0:
+            raise SystemExit("pager_pocsag_new failed")
+
+    def _page(self, kind, baud, cap, data, n, fn):
+        text = "".join({3: " ", 4: " ", 0x17: " ", 8: "<BKSP>", 12: "<FF>"}.get(ch, chr(ch)) for ch in C.string_at(data, n))
+        self.out.write(json.dumps({"proto": "pocsag", "type": kind, "channel": self.channel, "first_sample": self.first, "baud": int(baud),
+                                   "capCode": int(cap), "function": int(fn), "message": text}) + "\n")
+        return 0
+
+    def on_events(self, ev):
+        ev = np.ascontiguousarray(ev)
+        if self.h.pager_pocsag_on_events(self.p, ev.ctypes.data, ev.size) != 0:
+            raise SystemExit("pager_pocsag_on_events failed")
+
+    def close(self):
+        self.h.pager_pocsag_delete(C.byref(self.p))
 
 
 def _stats(xs):
@@ -310,6 +400,7 @@ def bench(a):
     if not iq_form:
         bench_runrs(a, pkg, torch, rows, in_stride, nout, timed)
         bench_runais(a, pkg, torch)
+        bench_runpocsag(a, pkg, torch)
     for o in (lv, eng):
         o.close()
 
@@ -579,6 +670,139 @@ def bench_runais(a, pkg, torch):
     print(json.dumps(out))
 
 
+def _busy_pocsag_rows(pkg, nch, n):
+    """[nch][n] int16 at 48 kHz (38 400 Hz behind the 4/5 resampler): POCSAG transmissions at 512, 1200 and 2400 baud back to
+    back with short noise gaps on every channel (six different streams, rotated from channel to channel)"""
+    sy = pkg.synth
+    rng = np.random.RandomState(6)
+    msgs = [(0x12345, 3, 2, sy.pocsag_alpha_words("HELLO MI355X\x04")), (0x00777, 5, 0, sy.pocsag_numeric_words("0123-456 [9]")),
+            (0x3FFFF, 0, 3, sy.pocsag_alpha_words("The quick brown fox jumps over the lazy dog 0123456789\x03"))]
+    n38 = n * 4 // 5 + 8
+    base = []
+    for k in range(6):
+        parts, have = [], 0
+        while have < n38:
+            baud = (2400, 1200, 2400, 512, 2400, 1200)[(k + len(parts)) % 6]
+            pick = [msgs[int(j)] for j in rng.randint(0, 3, 1 + int(rng.randint(0, 3)))]
+            parts.append(sy.pocsag_pcm(sy.pocsag_bits(sy.pocsag_batches(pick)), baud, noise=600.0, lead=int(rng.randint(200, 3000)),
+                                       trail=2600, seed=10 * k + len(parts)))
+            have += parts[-1].size
+        base.append(np.repeat(np.concatenate(parts)[:n38], 5)[::4][:n])
+    return np.stack([np.roll(base[c % 6], 1013 * (c // 6)) for c in range(nch)])
+
+
+def bench_runpocsag(a, pkg, torch):
+    """burst resampler -> burst POCSAG stage on the device view one gate call left (every call begins every stretch anew, as in
+    bench_runrs, so every call does the same work) against mfm_resampler (v_dot2 form) -> mfm_pocsag on the full rows; the two
+    chains alternate in one process in rotating order.  The events of a call's first runs are compared with the host twin's"""
+    b = pkg.binding
+    nch, W, I, D = a.bench_channels, a.window, 4, 5
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    taps = np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16)
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "runpocsag_stage", "channels": nch, "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I,
+           "decimate": D, "taps": int(taps.size), "reps": a.reps, "calls_per_rep": a.inner,
+           "search": "match planes and summary (rp_match_kernel), EXACT words in the walker"}
+    rng = np.random.RandomState(1)
+    sample_ok, sample_events = True, 0
+    for rows_name in ("idle", "busy"):
+        host = rng.randint(-3000, 3001, size=(nch, n)).astype(np.int16) if rows_name == "idle" else _busy_pocsag_rows(pkg, nch, n)
+        d_rows = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "scene": scene["open"]}
+        keep, recs = [], {"scene": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        plain = pkg.Resampler(nch, taps, I, D, nb, device=0, force_dot2=True)
+        pg = pkg.Pocsag(nch, plain.max_out(), device=0)
+        rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        rp = pkg.RunPocsag.behind(rr)
+
+        def run_plain():
+            yptr, ystride, ny = plain.process_device(rows, in_stride, nb)
+            pg.process_device(yptr, ystride, ny)
+
+        res = {}
+        for name in ("all_closed", "scene", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_burst():
+                rr.process_device(*view)
+                rp.process_device(*rr.device_view())
+
+            variants = [("burst", run_burst), ("plain", run_plain)]
+            for _, fn in variants:
+                timed(fn, 3)
+            ev = rp.fetch()
+            plain_events = len(pg.fetch_events())
+            # a sample against the twin: the call's first runs (each begins its stretch, so each stands alone)
+            runs, payload = rr.fetch()
+            k = 0
+            while k < min(len(runs), 6) and int(runs["out_offset"][k]) + int(runs["nr_out"][k]) <= 1 << 20:
+                k += 1
+            if k:
+                assert (runs["flags"][:k] & 1).all()
+                want = b.hosttwin_runpocsag_call(b.hosttwin_runpocsag_state(nch), runs[:k], payload[:int(runs["out_offset"][k - 1]) + int(runs["nr_out"][k - 1])])
+                got = ev[ev["run"] < k]
+                sample_ok = sample_ok and got.tobytes() == want.tobytes()
+                sample_events += len(want)
+            got_t = {v: [] for v, _ in variants}
+            for rep in range(a.reps):
+                j = rep % len(variants)
+                for vname, fn in variants[j:] + variants[:j]:
+                    got_t[vname].append(timed(fn, a.inner))
+            (bm, bsd), (pm, psd) = _stats(got_t["burst"]), _stats(got_t["plain"])
+            ratio = bm / pm
+            ratio_se = ratio * math.sqrt(bsd * bsd / a.reps / (bm * bm) + psd * psd / a.reps / (pm * pm))
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "runs": int(len(runs)), "burst_events_per_call": int(len(ev)),
+                         "plain_events_last_call": plain_events, "burst_ms": bm, "burst_sd": bsd, "plain_ms": pm, "plain_sd": psd,
+                         "burst_over_plain": ratio, "burst_over_plain_se": ratio_se}
+            gate.close()
+        out[rows_name] = res
+        for o in (rp, rr, pg, plain, sq):
+            o.close()
+        del d_rows, keep
+    out["sample_equals_twin"] = bool(sample_ok)
+    out["sample_events"] = int(sample_events)
+    print(json.dumps(out))
+
+
+def bench_runpocsag_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runpocsag needs the GPU: there is no CPU path to time")
+    bench_runpocsag(a, pkg, torch)
+
+
 def bench_runais_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -608,14 +832,18 @@ def main():
     ap.add_argument("--gate-resample", default=None, help="I/D: resample the gate's runs on the device (with --gate-out, --form pcm)")
     ap.add_argument("--resample-taps", default=None, help="JSON file whose lpfCoeffs are the resampler's taps")
     ap.add_argument("--gate-ais", action="store_true", help="demodulate AIS on the resampled runs on the device (with --gate-resample)")
+    ap.add_argument("--gate-pocsag", action="store_true", help="demodulate POCSAG on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-runais", action="store_true", help="the runais_stage line of --bench alone")
+    ap.add_argument("--bench-runpocsag", action="store_true", help="the runpocsag_stage line of --bench alone")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
     a = ap.parse_args()
     if a.bench_runais:
         return bench_runais_alone(a)
+    if a.bench_runpocsag:
+        return bench_runpocsag_alone(a)
     if a.bench:
         return bench(a)
     if not a.config or not a.input:

@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     "mfm_hosttwin_runrs_plan", "mfm_hosttwin_runrs_call",
     "mfm_runrs_get_capacity", "mfm_runais_create", "mfm_runais_destroy", "mfm_runais_process_device", "mfm_runais_fetch",
     "mfm_runais_device_view", "mfm_hosttwin_runais_call",
+    "mfm_runpocsag_create", "mfm_runpocsag_destroy", "mfm_runpocsag_process_device", "mfm_runpocsag_fetch", "mfm_runpocsag_device_view",
+    "mfm_runpocsag_fetch_state", "mfm_hosttwin_runpocsag_call",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -242,6 +244,36 @@ RUNAIS_EVENT_DTYPE = np.dtype([("channel", "<u4"), ("fcs_valid", "<u4"), ("nr_by
 RUNAIS_STATE_DTYPE = np.dtype([("outs", "<u8"), ("stretch_window", "<u8"), ("pos", "<u8"), ("r", "<u8"), ("rd", "<u8"),
                                ("start", "<u8"), ("mode", "<u4"), ("last_sample", "<u4"), ("hist8", "<u4"), ("cur_bit", "<u4"),
                                ("has_stretch", "<u4"), ("reserved", "<u4"), ("packet", "<u4", (40,)), ("tail", "<u4", (8,))])
+
+
+class RunPocsagConfig(C.Structure):
+    """struct mfm_runpocsag_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("max_runs", C.c_uint32),
+                ("max_out_samples", C.c_uint32), ("max_events", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RunPocsagEvent(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("baud", C.c_uint32), ("channel", C.c_uint32), ("aux", C.c_uint32), ("run", C.c_uint32),
+                ("nr_ok", C.c_uint32), ("fail_mask", C.c_uint32), ("reserved", C.c_uint32), ("stretch_window", C.c_uint64),
+                ("sample", C.c_uint64), ("raw", C.c_uint32 * 16), ("corrected", C.c_uint32 * 16)]
+
+
+MFM_RUNPOCSAG_OVER_RUNS, MFM_RUNPOCSAG_OVER_EVENTS = 1, 2                                   # d_totals[2]
+MFM_RUNPOCSAG_IN_RUNRS, MFM_RUNPOCSAG_IN_OUT_OF_STEP, MFM_RUNPOCSAG_IN_BAD_RUNS = 1, 2, 4   # d_totals[3]
+RUNPOCSAG_MIN_SPACING = 544 * 16   # samples between two BATCH events of a stretch at least (csrc/mfm_runpocsag.h)
+# numpy views of struct mfm_runpocsag_event (176 bytes) and struct mfm_runpocsag_state (432 bytes, per channel)
+RUNPOCSAG_EVENT_DTYPE = np.dtype([("type", "<u4"), ("baud", "<u4"), ("channel", "<u4"), ("aux", "<u4"), ("run", "<u4"),
+                                  ("nr_ok", "<u4"), ("fail_mask", "<u4"), ("reserved", "<u4"), ("stretch_window", "<u8"),
+                                  ("sample", "<u8"), ("raw", "<u4", (16,)), ("corrected", "<u4", (16,))])
+RUNPOCSAG_STATE_DTYPE = np.dtype([("outs", "<u8"), ("stretch_window", "<u8"), ("mode", "<u4"), ("baud", "<u4"), ("spb", "<u4"),
+                                  ("skip", "<u4"), ("batch_word", "<u4"), ("batch_bit", "<u4"), ("sync_word", "<u4"),
+                                  ("nr_sync_bits", "<u4"), ("nr_eye", "<u4", (3,)), ("since_reset", "<u4"), ("has_stretch", "<u4"),
+                                  ("batch", "<u4", (16,)), ("tail", "<u4", (75,))])
+
+
+def runpocsag_slots(nr_out):
+    """the event bound of a run of nr_out samples (mfm_runpocsag_slots)"""
+    return 3 * (int(nr_out) // RUNPOCSAG_MIN_SPACING + 1) + 2
 
 
 class FlexConfig(C.Structure):
@@ -494,6 +526,15 @@ def load_library():
     lib.mfm_runais_process_device.argtypes = [vp, vp, vp, vp, vp]
     lib.mfm_runais_fetch.argtypes = [vp, vp, C.c_size_t, szp]
     lib.mfm_runais_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runpocsag_create.argtypes = [C.POINTER(vp), C.POINTER(RunPocsagConfig)]
+    lib.mfm_runpocsag_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runpocsag_destroy.restype = None
+    lib.mfm_runpocsag_process_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mfm_runpocsag_fetch.argtypes = [vp, vp, C.c_size_t, szp]
+    lib.mfm_runpocsag_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runpocsag_fetch_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
+                                                C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runais_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
                                              C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runrs_plan.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, vp, vp, vp]
@@ -1639,6 +1680,129 @@ def runais_to_ais_events(events, interpolate, decimate, window_samples):
         out[f] = ev[f]
     out["sample"] = base + ev["sample"]
     out["start_sample"] = base + ev["start_sample"]
+    return out
+
+
+class RunPocsag:
+    """mfm_runpocsag: the runs of a RunResampler's device view (38 400 Hz) through the POCSAG demodulator, one fresh demodulator
+    per stretch; RUNPOCSAG_EVENT_DTYPE records.  max_runs and max_out_samples are the burst resampler's capacities
+    (RunPocsag.behind reads them); max_events 0 is a bound that cannot overflow."""
+
+    def __init__(self, nr_channels, max_runs, max_out_samples, max_events=0, device=0, flags=0, abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        cfg = RunPocsagConfig(abi_version, device, nr_channels, max_runs, max_out_samples, max_events, flags)
+        rc = self.lib.mfm_runpocsag_create(C.byref(self.h), C.byref(cfg))
+        if rc < 0:
+            self._raise(rc, "mfm_runpocsag_create")
+        self.nr_channels = nr_channels
+
+    @classmethod
+    def behind(cls, run_resampler, max_events=0, device=0):
+        """a stage sized for everything one call of `run_resampler` can produce"""
+        max_runs, max_out = run_resampler.capacity()
+        return cls(run_resampler.nr_channels, max_runs, max_out, max_events=max_events, device=device)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runpocsag_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_payload, d_totals, stream=None):
+        """the three addresses of RunResampler.device_view(), after its process_device on the same stream"""
+        rc = self.lib.mfm_runpocsag_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runpocsag_process_device")
+
+    def fetch(self, max_events=None):
+        """the events of the last call (RUNPOCSAG_EVENT_DTYPE).  With max_events too small: MfmError(MFM_E_NOMEM) whose `needed`
+        attribute is the number that would fit and whose `buffer` is untouched"""
+        nr = C.c_size_t()
+        if max_events is None:
+            rc = self.lib.mfm_runpocsag_fetch(self.h, None, 0, C.byref(nr))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below, with the untouched buffer
+                self._raise(rc, "mfm_runpocsag_fetch")
+            max_events = nr.value
+        out = np.zeros(max(max_events, 1), RUNPOCSAG_EVENT_DTYPE)
+        rc = self.lib.mfm_runpocsag_fetch(self.h, out.ctypes.data, max_events, C.byref(nr))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runpocsag_fetch")
+            except MfmError as err:
+                err.needed = nr.value
+                err.buffer = out
+                raise
+        return out[:nr.value].copy()
+
+    def device_view(self):
+        """(d_events, d_totals): device addresses of the last call's events and the four uint64 totals (events, runs, overflow,
+        input error)"""
+        e, t = C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runpocsag_device_view(self.h, C.byref(e), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runpocsag_device_view")
+        return e.value, t.value
+
+    def fetch_state(self):
+        """the per-channel state the last call left (RUNPOCSAG_STATE_DTYPE [C]): what the host twin carries"""
+        out = np.zeros(self.nr_channels, RUNPOCSAG_STATE_DTYPE)
+        rc = self.lib.mfm_runpocsag_fetch_state(self.h, out.ctypes.data, self.nr_channels)
+        if rc < 0:
+            self._raise(rc, "mfm_runpocsag_fetch_state")
+        return out
+
+
+def hosttwin_runpocsag_state(nr_channels):
+    """the host twin's per-channel state at the start of a stream: RUNPOCSAG_STATE_DTYPE [C], all zero (no stretch)"""
+    return np.zeros(nr_channels, RUNPOCSAG_STATE_DTYPE)
+
+
+def hosttwin_runpocsag_call(state, runs, payload, totals=None, max_runs=None, max_out_samples=None, max_events=0, max_out=None):
+    """mfm_hosttwin_runpocsag_call: one call of the burst POCSAG stage on the CPU.  state (hosttwin_runpocsag_state) is updated
+    in place; runs RUNRS_RUN_DTYPE and payload int16 are one burst resampler call's result, totals its four totals (default:
+    the lengths, no flags); max_runs / max_out_samples / max_events are the configuration's (default: what the call needs);
+    returns the events.  A refused call raises MfmError(MFM_E_STATE) with a `flags` attribute (overflow | input error << 8)"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNPOCSAG_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    pl = np.ascontiguousarray(payload, dtype=np.int16).reshape(-1)
+    t = np.array([rr.size, pl.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_out_samples = max(pl.size, 1) if max_out_samples is None else max_out_samples
+    if max_out is None:
+        max_out = 3 * (pl.size // RUNPOCSAG_MIN_SPACING) + 5 * rr.size
+    out = np.zeros(max(max_out, 1), RUNPOCSAG_EVENT_DTYPE)
+    nr, fl = C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runpocsag_call(state.shape[0], max_runs, max_out_samples, max_events, state.ctypes.data,
+                                         rr.ctypes.data if rr.size else None, pl.ctypes.data if pl.size else None, t.ctypes.data,
+                                         out.ctypes.data, max_out, C.byref(nr), C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runpocsag_call", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.flags = nr.value, fl.value
+        raise err
+    return out[:nr.value].copy()
+
+
+def runpocsag_to_pocsag_events(events):
+    """mfm_pocsag_event records (POCSAG_EVENT_DTYPE, what host/mfm_pager_pocsag.c's pager_pocsag_on_events takes) from the burst
+    stage's, field for field, the stretch-relative `sample` kept: one pager object per (channel, stretch), a fresh one at
+    every new stretch_window, as the stage has a fresh demodulator there"""
+    ev = np.asarray(events)
+    assert ev.dtype == RUNPOCSAG_EVENT_DTYPE
+    out = np.zeros(ev.shape, POCSAG_EVENT_DTYPE)
+    for f in ("type", "baud", "channel", "aux", "sample", "nr_ok", "fail_mask", "raw", "corrected"):
+        out[f] = ev[f]
     return out
 
 

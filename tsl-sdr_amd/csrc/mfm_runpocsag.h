@@ -1,0 +1,78 @@
+/*
+ * mfm_runpocsag.h - what the kernels of the burst POCSAG stage (mfm_runpocsag_*, include/multifm_hip.h) and its host twin
+ * (mfm_hosttwin_runpocsag_call) must state once: the layout of a run's bit segment, its share of the event slots, the
+ * checks a run has to pass before anything of the payload is read, and the bits a stretch leaves behind.
+ *
+ * A run's segment is MFM_RUNPOCSAG_HIST_WORDS words of history, then its nr_out sample bits (bit = sample < 0), then one
+ * word of padding: segment bit 2400 + j is output j of the run, i.e. stretch sample first_out + j.  The history is the
+ * channel's carried tail when the run continues a stretch and zeros when it begins one: exactly the reference's zero-filled
+ * eye registers (pager/pager_pocsag.c:119-126), with the detector reset at stretch sample 0.
+ *
+ * The tail.  A detector of samples_per_bit S visits one of its S registers per sample, each register every S samples, and a
+ * register holds the 32 bits shifted in last: what the detectors do at sample n depends on the sample bits n - j * S, j = 0 ..
+ * 31, on their nr_eye_matches (carried in the state) and on nothing older.  The slowest detector has S = 75, so at most
+ * 32 * 75 = 2400 samples before the current one matter (31 * 75 = 2325 are read): 75 whole words.
+ *
+ * The EXACT span.  A reset (stretch start or SYNC_LOST) zero-fills the registers, so a register's bit j is zero, whatever the
+ * bit stream holds, while n - j * S lies before the reset: for n < reset + 31 * 75 the walker masks those bits off, from
+ * there on the registers equal the free-running shifted views.  The span is the row stage's 31 bit periods of the slowest
+ * rate; it is measured from the carried since_reset when a run continues a stretch.
+ */
+#ifndef MFM_RUNPOCSAG_H
+#define MFM_RUNPOCSAG_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/multifm_hip.h"
+
+#define MFM_RUNPOCSAG_HIST_WORDS 75u /* 32 bits * 75 samples per bit of register history = 2400 samples, whole words */
+#define MFM_RUNPOCSAG_HIST_BITS (32u * MFM_RUNPOCSAG_HIST_WORDS)
+#define MFM_RUNPOCSAG_SLOW_SPAN (31u * 75u)    /* samples after a reset during which some register bit is zero-filled */
+#define MFM_RUNPOCSAG_MIN_SPACING (544u * 16u) /* samples between two BATCH events of a stretch at least (see the header) */
+#define MFM_RUNPOCSAG_SYNC 0x7cd215d8u         /* pager_pocsag_priv.h:40 */
+
+enum { MFM_RUNPOCSAG_SEARCH = 0, MFM_RUNPOCSAG_BATCH = 2, MFM_RUNPOCSAG_SYNCWORD = 3 };
+
+/* words of a run's segment: history, bits, one word of padding (the tail is cut out with a funnel shift over two words) */
+__host__ __device__ inline uint32_t mfm_runpocsag_seg_words(uint32_t nr_out)
+{
+    return MFM_RUNPOCSAG_HIST_WORDS + (nr_out + 31u) / 32u + 1u;
+}
+
+/* event slots of a run: at most nr_out / 8704 + 1 BATCH events, at most two other events between two of them, in front of
+ * the first and behind the last (the derivation is in the header) */
+__host__ __device__ inline uint32_t mfm_runpocsag_slots(uint32_t nr_out)
+{
+    return 3u * (nr_out / MFM_RUNPOCSAG_MIN_SPACING + 1u) + 2u;
+}
+
+/*
+ * The input-error flags of run `run` (0: it may be read).  prev: the run in front of it in the list (NULL for the first),
+ * nr_elems: the resampler's total of output elements, state: the per-channel state the call started from.
+ */
+__host__ __device__ inline uint32_t mfm_runpocsag_check_run(const mfm_runrs_run &run, const mfm_runrs_run *prev, uint32_t nr_channels,
+                                                            uint64_t nr_elems, const mfm_runpocsag_state *state)
+{
+    if (run.channel >= nr_channels || (prev && prev->channel > run.channel) || run.out_offset > nr_elems ||
+        run.nr_out > nr_elems - run.out_offset) {
+        return MFM_RUNPOCSAG_IN_BAD_RUNS;
+    }
+    if (run.flags & MFM_RUNRS_BEGINS) {
+        return run.first_out != 0 ? MFM_RUNPOCSAG_IN_BAD_RUNS : 0u;
+    }
+    /* only a channel's first run of a call can continue: a later one has a closed window in front of it */
+    const bool first = !prev || prev->channel != run.channel;
+    const mfm_runpocsag_state &st = state[run.channel];
+    return first && st.has_stretch && st.outs == run.first_out ? 0u : MFM_RUNPOCSAG_IN_OUT_OF_STEP;
+}
+
+/* word k (0 .. 74) of the tail a run leaves: segment bits [nr_out + 32 k, nr_out + 32 k + 32), which end with the run's last
+ * sample and begin in the carried history when the run is shorter than 2400 samples */
+__host__ __device__ inline uint32_t mfm_runpocsag_tail_word(const uint32_t *seg, uint32_t nr_out, uint32_t k)
+{
+    const uint32_t q = (nr_out >> 5) + k, s = nr_out & 31u;
+    return s ? (seg[q] >> s) | (seg[q + 1] << (32u - s)) : seg[q];
+}
+
+#endif /* MFM_RUNPOCSAG_H */
