@@ -1258,6 +1258,124 @@ struct mfm_runpocsag_state;
 int mfm_runpocsag_fetch_state(struct mfm_runpocsag *p, struct mfm_runpocsag_state *state, size_t nr_channels);
 
 /*
+ * ---- Burst FLEX stage: the burst resampler's runs through the FLEX front half, on the device ------------------------------
+ * The pager stage above (mfm_flex_*) on ragged runs instead of full rows: its input is what mfm_runrs_device_view returns
+ * (the run list, the dense resampled payload, the totals), all read on the device, and its output is FLEX events and the
+ * words of the frames collected.  The stage assumes 16 000 Hz, as mfm_flex does.
+ *
+ * Stretch means what it means for the burst resampler; this stage does not track windows.  Run r continues its channel's
+ * stretch exactly when MFM_RUNRS_BEGINS is clear in runs[r].flags, otherwise it begins a new one.  Only a channel's first run
+ * of a call can continue.  Sample numbers are stretch-relative: sample first_out + j is output j of the run.
+ *
+ * Rule.  The events and frame words of a stretch are exactly what a fresh reference decoder (pager_flex_on_pcm in state
+ * SYNC_1, registers, counters and phase words zero) returns when fed the stretch's resampled PCM, with every convention the
+ * mfm_flex_* comment lists: bit = (sample >= 0); ten BS1 registers; the eye is a run of three or more matching samples,
+ * counted modulo 256; only the upper half of A is compared, with fewer than 4 differing bits; the swing in int16 arithmetic;
+ * registers zero-filled after every reset, so nothing matches for 310 samples, and the stretch start is such a reset; a sync
+ * run without swing is MFM_FLEX_EV_BAD_FIW with fiw_rc 3.  A sync, FIW or block still being collected when its stretch ends
+ * is dropped without an event.  A run with nr_out == 0 produces nothing and still begins or continues its stretch.  Events
+ * do not depend on how the stream was cut into calls.
+ *
+ * No lag.  An event is reported by the call and run whose [first_out, first_out + nr_out) holds its `sample`: BAD_BAUD at
+ * s0 + 790 (s0 the first sync bit), BAD_FIW at f = s0 + 1110, FRAME at the last block symbol.
+ *
+ * State.  Per channel, on the device (struct mfm_runflex_state below, which the host twin carries too): the walker's mode and
+ * what it has of the frame so far, positions stretch-relative, the outputs seen and the stretch's first window; and a ring
+ * of the last 32 768 PCM samples of the stretch, indexed by stretch sample & 32767: the sync words are read again when the
+ * FIW arrives and a block's symbols when its last one does, up to 28 155 samples later.  Two state buffers are used in turn;
+ * the ring is written in place and last, from the channel's last run of a call, and not at all by a refused call.  A run that
+ * begins a stretch never reads the ring.  A channel without a run in a call keeps its state.
+ *
+ * Result.  It replaces the previous call's: one dense list of mfm_runflex_event in run order, stream order within a run, and
+ * one dense list of mfm_flex_frame_words, indexed by the FRAME events' frame_index, in event order;
+ * d_totals[4] = { events, frames, overflow, input error }.  Order and content are deterministic: the walk of a run writes into
+ * slot ranges given by a scan, and the ranges are packed afterwards.
+ *
+ * Bounds.  Every event is followed by a reset, and after a reset the next event needs 311 dead samples, a run of 3 matches,
+ * the sample that ends it, 1 sample or more to the first sync bit and 790 more: two events of a stretch are at least 1105
+ * samples apart, so a run holds at most nr_out / 1105 + 1 events.  A FRAME's last symbol lies at least 28 560 samples behind
+ * its last FIW bit, which lies 1110 behind the first sync bit: two FRAME events are at least 315 + 1110 + 28 560 = 29 985
+ * samples apart, so a run holds at most nr_out / 29985 + 1 frames.  A call holds at most the sums over its runs.
+ *
+ * Refused calls produce nothing, leave the per-channel state and the ring untouched and raise a flag that mfm_runflex_fetch
+ * reports as MFM_E_STATE with a message:
+ *   overflow     MFM_RUNFLEX_OVER_RUNS: more runs than max_runs; MFM_RUNFLEX_OVER_EVENTS: the call's event bound exceeds
+ *                max_events or its frame bound max_frames (by the bound, not by the count)
+ *   input error  MFM_RUNFLEX_IN_RUNRS, MFM_RUNFLEX_IN_OUT_OF_STEP, MFM_RUNFLEX_IN_BAD_RUNS: as the burst POCSAG stage's,
+ *                checked before anything of the payload is read.
+ */
+#define MFM_RUNFLEX_OVER_RUNS 1u
+#define MFM_RUNFLEX_OVER_EVENTS 2u
+#define MFM_RUNFLEX_IN_RUNRS 1u
+#define MFM_RUNFLEX_IN_OUT_OF_STEP 2u
+#define MFM_RUNFLEX_IN_BAD_RUNS 4u
+
+struct mfm_runflex_event {      /* 104 bytes: struct mfm_flex_event, then the run and the stretch */
+    uint32_t type;              /* MFM_FLEX_EV_* */
+    uint32_t channel;
+    uint64_t sample;            /* stretch-relative index of the resampled sample that completed the event */
+    uint64_t sync_sample;       /* FRAME: stretch-relative sample of the last FIW bit */
+    uint32_t coding;            /* as mfm_flex_event, field for field */
+    uint32_t baud;
+    uint32_t eye;
+    uint32_t a;
+    uint32_t b;
+    uint32_t inv_a;
+    uint32_t fiw_raw;
+    uint32_t fiw;
+    uint32_t fiw_rc;
+    int32_t sample_range;
+    int32_t sample_delta;
+    uint32_t cycle;
+    uint32_t frame;
+    uint32_t frame_index;       /* FRAME: index of this frame's words in the call's list of frames */
+    uint32_t nr_phases;
+    uint32_t reserved;          /* 0 */
+    uint32_t run;               /* index, in this call's run list, of the run that holds `sample` */
+    uint32_t reserved2;         /* 0 */
+    uint64_t stretch_window;    /* first window of the stretch: its first input sample is stretch_window * W */
+};
+
+struct mfm_runflex; /* opaque */
+
+struct mfm_runflex_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_runs;          /* the burst resampler's capacities (mfm_runrs_get_capacity) */
+    uint32_t max_out_samples;
+    uint32_t max_events;        /* per call, all channels; 0 = max_out_samples / 1105 + max_runs, cannot overflow */
+    uint32_t max_frames;        /* per call, all channels; 0 = max_out_samples / 29985 + max_runs, cannot overflow */
+    uint32_t flags;             /* 0 */
+};
+
+int mfm_runflex_create(struct mfm_runflex **pf, const struct mfm_runflex_config *cfg);
+void mfm_runflex_destroy(struct mfm_runflex **pf);
+/*
+ * Decode the runs of one burst resampler call: d_runs, d_payload and d_totals are what mfm_runrs_device_view returned.
+ * Work is queued on `stream` (the resampler call's, or one ordered behind it); no host synchronisation and no count read on
+ * the host: launches are sized from the capacities fixed at create, surplus workgroups return after reading the totals.  The
+ * three arrays are read until the queued work has run.
+ */
+int mfm_runflex_process_device(struct mfm_runflex *f, const struct mfm_runrs_run *d_runs, const int16_t *d_payload,
+                               const uint64_t *d_totals, void *stream);
+/*
+ * Wait for the last call and copy its events and the words of its frames (the copies are sized by the call's counts).
+ * MFM_E_NOMEM when either array is too small (nothing copied, *nr_events / *nr_frames = needed); MFM_E_STATE with a message
+ * when the call was refused (nothing copied, the state did not move: the same input in a call that is right is right again).
+ */
+int mfm_runflex_fetch(struct mfm_runflex *f, struct mfm_runflex_event *events, size_t max_events, size_t *nr_events,
+                      struct mfm_flex_frame_words *frames, size_t max_frames, size_t *nr_frames);
+/* For consumers that stay on the device: the last call's events, frames and d_totals[4], valid until the next call.  Each may
+ * be NULL. */
+int mfm_runflex_device_view(struct mfm_runflex *f, const struct mfm_runflex_event **d_events,
+                            const struct mfm_flex_frame_words **d_frames, const uint64_t **d_totals);
+struct mfm_runflex_state;
+/* Wait for the last call and copy the per-channel state it left, state[nr_channels], and, unless ring is NULL, the rings,
+ * ring[nr_channels][32768] (for tests and for moving a stream between objects: it is what the host twin carries). */
+int mfm_runflex_fetch_state(struct mfm_runflex *f, struct mfm_runflex_state *state, int16_t *ring, size_t nr_channels);
+
+/*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
  *   mm_init      pager/mueller_muller.c:10-33
  *   mm_process   pager/mueller_muller.c:41-115
@@ -1493,6 +1611,38 @@ int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_
                                 struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
                                 const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events,
                                 uint32_t *flags);
+/* the per-channel state of the burst FLEX stage, on the device and in the host twin, beside the channel's ring of 32 768 PCM
+ * samples: all zero at the start of a stream.  Positions are stretch-relative.  Fields a mode does not use are zero. */
+struct mfm_runflex_state {      /* 88 bytes */
+    uint64_t outs;              /* outputs of the stretch so far */
+    uint64_t stretch_window;    /* first window of the stretch */
+    uint64_t p;                 /* SEARCH: next sample to look at (behind a reset: 311 samples behind it, maybe beyond outs) */
+    uint64_t j;                 /* SYNC1: the sample that ended the BS1 run; FRAME: the sample of the last FIW bit */
+    uint32_t mode;              /* 0 SEARCH, 1 SYNC1 (waiting for the sync words or the FIW), 2 FRAME (waiting for the block) */
+    uint32_t run;               /* SEARCH: matches counted in the run that is open at p */
+    uint32_t eye;               /* SYNC1 / FRAME: the run length modulo 256 that opened the eye */
+    uint32_t coding;            /* FRAME: what the FRAME event will carry, as mfm_flex_event */
+    uint32_t a;
+    uint32_t b;
+    uint32_t inv_a;
+    uint32_t fiw_raw;
+    uint32_t fiw;
+    int32_t sample_range;
+    int32_t sample_delta;
+    uint32_t cycle;
+    uint32_t frame;
+    uint32_t has_stretch;       /* 0: nothing to continue */
+};
+/* host twin of one mfm_runflex_process_device call and its fetch, no device needed: runs / payload / totals are one burst
+ * resampler call's result (totals[4] as its d_totals), state [nr_channels] and ring [nr_channels][32768] are read and updated
+ * in place, max_runs, max_out_samples, max_events and max_frames are the configuration's (0 = the default).  Same refusals:
+ * MFM_E_STATE with the message mfm_runflex_fetch gives and *flags = overflow | input error << 8; MFM_E_NOMEM when max_out or
+ * max_out_frames is too small (*nr_events, *nr_frames = needed); on any error nothing is written, state and ring included. */
+int mfm_hosttwin_runflex_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                              uint32_t max_frames, struct mfm_runflex_state *state, int16_t *ring, const struct mfm_runrs_run *runs,
+                              const int16_t *payload, const uint64_t *totals, struct mfm_runflex_event *events, size_t max_out,
+                              size_t *nr_events, struct mfm_flex_frame_words *frames, size_t max_out_frames, size_t *nr_frames,
+                              uint32_t *flags);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

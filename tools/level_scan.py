@@ -3,7 +3,7 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
-           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-ais | --gate-pocsag]]]
+           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-ais | --gate-pocsag | --gate-flex]]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -59,6 +59,22 @@ assembles from the events, in the shape decoder_amd prints them, with the channe
     {"proto": "pocsag", "type": "alphanumeric", "channel": 3, "first_sample": 4000, "baud": 1200, "capCode": 596523, "function": 2,
      "message": "HELLO"}
 
+--gate-flex (with --gate-resample whose output rate is 16 000 Hz; not together with --gate-ais or --gate-pocsag) queues the burst
+FLEX stage behind the burst resampler on the same stream, the flush call included: every stretch goes through a fresh FLEX
+decoder.  DIR/flex.jsonl gets one line per event:
+
+    {"channel": 3, "first_sample": 4000, "type": 1, "sample": 31204, "sync_sample": 2642, "coding": 2, "baud": 3200, "eye": 10,
+     "a": 1335318841, "b": 21845, "inv_a": 2959648454, "fiw_raw": 2820680286, "fiw": 673196638, "fiw_rc": 0, "sample_range": 18001,
+     "sample_delta": 1, "cycle": 5, "frame": 42, "nr_phases": 2}
+
+(first_sample as above; type: MFM_FLEX_EV_*; sample and sync_sample: resampled samples counted from the stretch's first; the rest
+are the fields of mfm_flex_event).  DIR/pages.jsonl gets the messages a fresh host FLEX pager per stretch (host/mfm_pager_flex.c,
+through libmfm_host.so) assembles from the frames' words, in the shape decoder_amd prints them, with the channel and the stretch in
+the place of the time:
+
+    {"proto": "flex", "type": "alphanumeric", "channel": 3, "first_sample": 4000, "baud": 3200, "frameNo": 42, "cycleNo": 5,
+     "phaseNo": "A", "capCode": 123456, "fragment": false, "maildrop": false, "fragSeq": 3, "message": "HELLO"}
+
     python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8] [--gate-preroll 0,1,4]
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
@@ -79,7 +95,10 @@ stage on a gate's device view against the plain chain mfm_resampler -> mfm_ais o
 three masks and for two row sets of its own: idle (noise) and busy (synthesized AIS frames on every channel).  A last line
 ("runpocsag_stage"; --bench-runpocsag prints that line alone) does the same for the burst chain burst resampler -> burst POCSAG
 stage against mfm_resampler -> mfm_pocsag, busy being synthesized POCSAG transmissions on every channel, and says whether a
-sample of the burst events (the first runs of a call) equalled the host twin's."""
+sample of the burst events (the first runs of a call) equalled the host twin's.  --bench-runflex prints a line of the same build
+("runflex_stage") for the burst chain burst resampler (16/25, 101 taps) -> burst FLEX stage against mfm_resampler -> mfm_flex, busy
+being synthesized FLEX frames of the four codings on every channel, the three masks all-closed, half-open (a squelch at the median
+window energy) and all-open."""
 import argparse
 import ctypes as C
 import json
@@ -154,6 +173,25 @@ def scan(a):
         pocsag_index = open(os.path.join(a.gate_out, "pocsag.jsonl"), "w")
         pages_index = open(os.path.join(a.gate_out, "pages.jsonl"), "w")
 
+    rf, flex_index, flex_pagers = None, None, {}
+    if a.gate_flex:   # main() has refused it without --gate-resample or beside another stage
+        rf = pkg.RunFlex.behind(rr, device=a.device)
+        flex_index = open(os.path.join(a.gate_out, "flex.jsonl"), "w")
+        pages_index = open(os.path.join(a.gate_out, "pages.jsonl"), "w")
+
+    def write_flex(events, frames):
+        """the events, and the messages of a fresh host FLEX pager per (channel, stretch)"""
+        for e in events:
+            c, first = int(e["channel"]), int(e["stretch_window"]) * a.window
+            line = {"channel": c, "first_sample": first}
+            line.update({f: int(e[f]) for f in FLEX_LINE_FIELDS})
+            flex_index.write(json.dumps(line) + "\n")
+            if c not in flex_pagers or flex_pagers[c].first != first:
+                if c in flex_pagers:
+                    flex_pagers[c].close()
+                flex_pagers[c] = HostFlexPager(c, first, pages_index)
+            flex_pagers[c].on_events(b.runflex_to_flex_events(np.array([e], b.RUNFLEX_EVENT_DTYPE)), frames)
+
     def write_pocsag(events):
         """the events, and the pages of a fresh host pager per (channel, stretch)"""
         for e in events:
@@ -226,6 +264,8 @@ def scan(a):
                     ra.process_device(*rr.device_view(), stream=eng.stream)
                 if rp:
                     rp.process_device(*rr.device_view(), stream=eng.stream)
+                if rf:
+                    rf.process_device(*rr.device_view(), stream=eng.stream)
             rec = lv.fetch()
             if gate:
                 write_runs(*gate.fetch())
@@ -235,6 +275,8 @@ def scan(a):
                 write_ais(ra.fetch())
             if rp:
                 write_pocsag(rp.fetch())
+            if rf:
+                write_flex(*rf.fetch())
             for c, (freq, _) in enumerate(chans):
                 for r in rec[c]:
                     out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
@@ -253,6 +295,8 @@ def scan(a):
             ra.process_device(*rr.device_view(), stream=eng.stream)
         if rp:
             rp.process_device(*rr.device_view(), stream=eng.stream)
+        if rf:
+            rf.process_device(*rr.device_view(), stream=eng.stream)
         write_runs(*gate.fetch())
         if rr:
             write_resampled(*rr.fetch())
@@ -268,6 +312,13 @@ def scan(a):
             pocsag_index.close()
             pages_index.close()
             rp.close()
+        if rf:
+            write_flex(*rf.fetch())
+            for hp in flex_pagers.values():
+                hp.close()
+            flex_index.close()
+            pages_index.close()
+            rf.close()
         if rr:
             rr.close()
         index.close()
@@ -309,6 +360,56 @@ class HostPager:
 
     def close(self):
         self.h.pager_pocsag_delete(C.byref(self.p))
+
+
+FLEX_LINE_FIELDS = ("type", "sample", "sync_sample", "coding", "baud", "eye", "a", "b", "inv_a", "fiw_raw", "fiw", "fiw_rc", "sample_range",
+                    "sample_delta", "cycle", "frame", "nr_phases")
+
+
+class HostFlexPager:
+    """host/mfm_pager_flex.c through libmfm_host.so: one pager for one stretch of one channel; every message goes to `out` as a
+    JSON line in the shape decoder_amd prints (decoder_main.c), the channel and the stretch in the place of the time"""
+    ALN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint16, C.c_uint8, C.c_uint8, C.c_uint8, C.c_uint64, C.c_bool, C.c_bool, C.c_uint8,
+                      C.POINTER(C.c_char), C.c_size_t)
+    NUM = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint16, C.c_uint8, C.c_uint8, C.c_uint8, C.c_uint64, C.POINTER(C.c_char), C.c_size_t)
+    SIV = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint16, C.c_uint8, C.c_uint8, C.c_uint8, C.c_uint64, C.c_uint8, C.c_uint32)
+
+    def __init__(self, channel, first, out):
+        so = os.path.join(ROOT, "tsl-sdr_amd", "host", "libmfm_host.so")
+        if not os.path.exists(so):
+            raise SystemExit(f"{so} missing: run make -C tsl-sdr_amd")
+        self.h = C.CDLL(so)
+        self.channel, self.first, self.out = channel, first, out
+        self._aln = self.ALN(lambda f, baud, ph, cy, fr, cap, frag, md, seq, data, n: self._line(
+            "alphanumeric", baud, ph, cy, fr, cap, fragment=bool(frag), maildrop=bool(md), fragSeq=int(seq), message=self._text(data, n)))
+        self._num = self.NUM(lambda f, baud, ph, cy, fr, cap, data, n: self._line("numeric", baud, ph, cy, fr, cap, message=self._text(data, n)))
+        self._siv = self.SIV(lambda f, baud, ph, cy, fr, cap, t, d: self._line(
+            "tempAddrActivation", baud, ph, cy, fr, cap, startFrameNo=int(d) & 0x7F, tempAddressId=(int(d) >> 7) & 0xF) if t == 0 else 0)
+        self.p = C.c_void_p()
+        self.h.pager_flex_new.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, self.ALN, self.NUM, self.SIV]
+        self.h.pager_flex_on_events.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        self.h.pager_flex_delete.argtypes = [C.POINTER(C.c_void_p)]
+        if self.h.pager_flex_new(C.byref(self.p), 0, self._aln, self._num, self._siv) != 0:
+            raise SystemExit("pager_flex_new failed")
+
+    @staticmethod
+    def _text(data, n):
+        return "".join({3: " ", 4: " ", 0x17: " ", 8: "<BKSP>", 12: "<FF>"}.get(ch, chr(ch)) for ch in C.string_at(data, n))
+
+    def _line(self, kind, baud, phase, cycle, frame, cap, **rest):
+        line = {"proto": "flex", "type": kind, "channel": self.channel, "first_sample": self.first, "baud": int(baud), "frameNo": int(frame),
+                "cycleNo": int(cycle), "phaseNo": "ABCD"[int(phase)], "capCode": int(cap)}
+        line.update(rest)
+        self.out.write(json.dumps(line) + "\n")
+        return 0
+
+    def on_events(self, ev, frames):
+        ev, frames = np.ascontiguousarray(ev), np.ascontiguousarray(frames)
+        if self.h.pager_flex_on_events(self.p, ev.ctypes.data, ev.size, frames.ctypes.data) != 0:
+            raise SystemExit("pager_flex_on_events failed")
+
+    def close(self):
+        self.h.pager_flex_delete(C.byref(self.p))
 
 
 def _stats(xs):
@@ -794,6 +895,132 @@ def bench_runpocsag(a, pkg, torch):
     print(json.dumps(out))
 
 
+def _busy_flex_rows(pkg, nch, n):
+    """[nch][n] int16 at 25 kHz (16 000 Hz behind the 16/25 resampler): FLEX frames of the four codings back to back on every
+    channel (four different streams, rotated from channel to channel)"""
+    sy = pkg.synth
+    recs = [dict(kind="alnum", capcode=1000 + i, text="THE QUICK BROWN FOX JUMPS OVER THE LAZY DOG %d" % i) for i in range(4)]
+    frames = []
+    for k in range(4):
+        ph = {p: sy.flex_phase_words(recs) for p in sy.FLEX_CODINGS[k]["phases"]}
+        frames.append(sy.flex_pcm([sy.flex_frame_levels(k, 1, k, ph)], noise=300, seed=k, rate=25000))
+    base = [np.concatenate([frames[(k + i) % 4] for i in range(n // frames[0].size + 2)])[:n] for k in range(4)]
+    return np.stack([np.roll(base[c % 4], 1013 * (c // 4)) for c in range(nch)])
+
+
+def bench_runflex(a, pkg, torch):
+    """burst resampler -> burst FLEX stage on the device view one gate call left (every call begins every stretch anew, as in
+    bench_runrs, so every call does the same work) against mfm_resampler (v_dot2 form) -> mfm_flex on the full rows; the two
+    chains alternate in one process in rotating order.  The events and words of a call's first runs are compared with the host
+    twin's"""
+    b = pkg.binding
+    nch, W, I, D = a.bench_channels, a.window, 16, 25
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    taps = np.round(pkg.synth.design_lpf(101, 0.45 / 25, 1.0) * 16 * 16384.0).astype(np.int16)
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "runflex_stage", "channels": nch, "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I,
+           "decimate": D, "taps": int(taps.size), "reps": a.reps, "calls_per_rep": a.inner,
+           "search": "match plane and summary (rf_match_kernel)"}
+    rng = np.random.RandomState(1)
+    sample_ok, sample_events = True, 0
+    for rows_name in ("idle", "busy"):
+        host = rng.randint(-3000, 3001, size=(nch, n)).astype(np.int16) if rows_name == "idle" else _busy_flex_rows(pkg, nch, n)
+        d_rows = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "half_open": scene["open"]}
+        keep, recs = [], {"half_open": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        plain = pkg.Resampler(nch, taps, I, D, nb, device=0, force_dot2=True)
+        fx = pkg.Flex(nch, plain.max_out(), device=0)
+        rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        rf = pkg.RunFlex.behind(rr)
+
+        def run_plain():
+            yptr, ystride, ny = plain.process_device(rows, in_stride, nb)
+            fx.process_device(yptr, ystride, ny)
+
+        res = {}
+        for name in ("all_closed", "half_open", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_burst():
+                rr.process_device(*view)
+                rf.process_device(*rr.device_view())
+
+            variants = [("burst", run_burst), ("plain", run_plain)]
+            for _, fn in variants:
+                timed(fn, 3)
+            ev, fw = rf.fetch()
+            plain_events = len(fx.fetch_events()[0])
+            # a sample against the twin: the call's first runs (each begins its stretch, so each stands alone)
+            runs, payload = rr.fetch()
+            k = 0
+            while k < min(len(runs), 6) and int(runs["out_offset"][k]) + int(runs["nr_out"][k]) <= 1 << 20:
+                k += 1
+            if k:
+                assert (runs["flags"][:k] & 1).all()
+                want = b.hosttwin_runflex_call(b.hosttwin_runflex_state(nch), runs[:k], payload[:int(runs["out_offset"][k - 1]) + int(runs["nr_out"][k - 1])])
+                got = ev[ev["run"] < k]
+                sample_ok = sample_ok and got.tobytes() == want[0].tobytes() and fw[:len(want[1])].tobytes() == want[1].tobytes()
+                sample_events += len(want[0])
+            got_t = {v: [] for v, _ in variants}
+            for rep in range(a.reps):
+                j = rep % len(variants)
+                for vname, fn in variants[j:] + variants[:j]:
+                    got_t[vname].append(timed(fn, a.inner))
+            (bm, bsd), (pm, psd) = _stats(got_t["burst"]), _stats(got_t["plain"])
+            ratio = bm / pm
+            ratio_se = ratio * math.sqrt(bsd * bsd / a.reps / (bm * bm) + psd * psd / a.reps / (pm * pm))
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "runs": int(len(runs)), "burst_events_per_call": int(len(ev)),
+                         "burst_frames_per_call": int(len(fw)), "plain_events_last_call": plain_events, "burst_ms": bm, "burst_sd": bsd,
+                         "plain_ms": pm, "plain_sd": psd, "burst_over_plain": ratio, "burst_over_plain_se": ratio_se}
+            gate.close()
+        out[rows_name] = res
+        for o in (rf, rr, fx, plain, sq):
+            o.close()
+        del d_rows, keep
+    out["sample_equals_twin"] = bool(sample_ok)
+    out["sample_events"] = int(sample_events)
+    print(json.dumps(out))
+
+
+def bench_runflex_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runflex needs the GPU: there is no CPU path to time")
+    bench_runflex(a, pkg, torch)
+
+
 def bench_runpocsag_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -833,9 +1060,11 @@ def main():
     ap.add_argument("--resample-taps", default=None, help="JSON file whose lpfCoeffs are the resampler's taps")
     ap.add_argument("--gate-ais", action="store_true", help="demodulate AIS on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--gate-pocsag", action="store_true", help="demodulate POCSAG on the resampled runs on the device (with --gate-resample)")
+    ap.add_argument("--gate-flex", action="store_true", help="decode FLEX on the resampled runs on the device (with --gate-resample to 16 000 Hz)")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-runais", action="store_true", help="the runais_stage line of --bench alone")
     ap.add_argument("--bench-runpocsag", action="store_true", help="the runpocsag_stage line of --bench alone")
+    ap.add_argument("--bench-runflex", action="store_true", help="the runflex_stage line alone")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
@@ -844,10 +1073,16 @@ def main():
         return bench_runais_alone(a)
     if a.bench_runpocsag:
         return bench_runpocsag_alone(a)
+    if a.bench_runflex:
+        return bench_runflex_alone(a)
     if a.bench:
         return bench(a)
     if not a.config or not a.input:
         ap.error("--config and --input are required (or --bench)")
+    if a.gate_flex and not a.gate_resample:
+        raise SystemExit("--gate-flex needs --gate-resample: the burst FLEX stage takes the burst resampler's runs")
+    if a.gate_flex and (a.gate_ais or a.gate_pocsag):
+        raise SystemExit("--gate-flex, --gate-pocsag and --gate-ais exclude each other: one stage reads the burst resampler's runs")
     scan(a)
 
 

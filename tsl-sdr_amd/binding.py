@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "mfm_runais_device_view", "mfm_hosttwin_runais_call",
     "mfm_runpocsag_create", "mfm_runpocsag_destroy", "mfm_runpocsag_process_device", "mfm_runpocsag_fetch", "mfm_runpocsag_device_view",
     "mfm_runpocsag_fetch_state", "mfm_hosttwin_runpocsag_call",
+    "mfm_runflex_create", "mfm_runflex_destroy", "mfm_runflex_process_device", "mfm_runflex_fetch", "mfm_runflex_device_view",
+    "mfm_runflex_fetch_state", "mfm_hosttwin_runflex_call",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -289,6 +291,36 @@ FLEX_EVENT_DTYPE = np.dtype([("type", "<u4"), ("channel", "<u4"), ("sample", "<u
                              ("frame_index", "<u4"), ("nr_phases", "<u4"), ("reserved", "<u4")])
 FLEX_FRAME_DTYPE = np.dtype([("words", "<u4", (4, 88))])
 MFM_FLEX_EV_FRAME, MFM_FLEX_EV_BAD_BAUD, MFM_FLEX_EV_BAD_FIW = 1, 2, 3
+
+
+class RunFlexConfig(C.Structure):
+    """struct mfm_runflex_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("max_runs", C.c_uint32),
+                ("max_out_samples", C.c_uint32), ("max_events", C.c_uint32), ("max_frames", C.c_uint32), ("flags", C.c_uint32)]
+
+
+MFM_RUNFLEX_OVER_RUNS, MFM_RUNFLEX_OVER_EVENTS = 1, 2                                 # d_totals[2]
+MFM_RUNFLEX_IN_RUNRS, MFM_RUNFLEX_IN_OUT_OF_STEP, MFM_RUNFLEX_IN_BAD_RUNS = 1, 2, 4   # d_totals[3]
+RUNFLEX_EVENT_SPACING = 1105    # samples between two events of a stretch at least (csrc/mfm_runflex.h)
+RUNFLEX_FRAME_SPACING = 29985   # samples between two FRAME events of a stretch at least
+RUNFLEX_RING = 32768            # PCM samples per channel the stage keeps
+# numpy views of struct mfm_runflex_event (104 bytes: mfm_flex_event, then run and stretch) and struct mfm_runflex_state (88
+# bytes, per channel)
+RUNFLEX_EVENT_DTYPE = np.dtype(FLEX_EVENT_DTYPE.descr + [("run", "<u4"), ("reserved2", "<u4"), ("stretch_window", "<u8")])
+RUNFLEX_STATE_DTYPE = np.dtype([("outs", "<u8"), ("stretch_window", "<u8"), ("p", "<u8"), ("j", "<u8"), ("mode", "<u4"),
+                                ("run", "<u4"), ("eye", "<u4"), ("coding", "<u4"), ("a", "<u4"), ("b", "<u4"), ("inv_a", "<u4"),
+                                ("fiw_raw", "<u4"), ("fiw", "<u4"), ("sample_range", "<i4"), ("sample_delta", "<i4"),
+                                ("cycle", "<u4"), ("frame", "<u4"), ("has_stretch", "<u4")])
+
+
+def runflex_event_bound(nr_out):
+    """the event bound of a run of nr_out samples (mfm_runflex_event_slots)"""
+    return int(nr_out) // RUNFLEX_EVENT_SPACING + 1
+
+
+def runflex_frame_bound(nr_out):
+    """the frame bound of a run of nr_out samples (mfm_runflex_frame_slots)"""
+    return int(nr_out) // RUNFLEX_FRAME_SPACING + 1
 
 
 class ResamplerConfig(C.Structure):
@@ -533,6 +565,15 @@ def load_library():
     lib.mfm_runpocsag_fetch.argtypes = [vp, vp, C.c_size_t, szp]
     lib.mfm_runpocsag_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     lib.mfm_runpocsag_fetch_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_runflex_create.argtypes = [C.POINTER(vp), C.POINTER(RunFlexConfig)]
+    lib.mfm_runflex_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runflex_destroy.restype = None
+    lib.mfm_runflex_process_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mfm_runflex_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_runflex_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runflex_fetch_state.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                              C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
                                                 C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runais_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -1802,6 +1843,141 @@ def runpocsag_to_pocsag_events(events):
     assert ev.dtype == RUNPOCSAG_EVENT_DTYPE
     out = np.zeros(ev.shape, POCSAG_EVENT_DTYPE)
     for f in ("type", "baud", "channel", "aux", "sample", "nr_ok", "fail_mask", "raw", "corrected"):
+        out[f] = ev[f]
+    return out
+
+
+class RunFlex:
+    """mfm_runflex: the runs of a RunResampler's device view (16 000 Hz) through the FLEX front half, one fresh decoder per
+    stretch; RUNFLEX_EVENT_DTYPE records and FLEX_FRAME_DTYPE words.  max_runs and max_out_samples are the burst resampler's
+    capacities (RunFlex.behind reads them); max_events 0 and max_frames 0 are bounds that cannot overflow."""
+
+    def __init__(self, nr_channels, max_runs, max_out_samples, max_events=0, max_frames=0, device=0, flags=0,
+                 abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        cfg = RunFlexConfig(abi_version, device, nr_channels, max_runs, max_out_samples, max_events, max_frames, flags)
+        rc = self.lib.mfm_runflex_create(C.byref(self.h), C.byref(cfg))
+        if rc < 0:
+            self._raise(rc, "mfm_runflex_create")
+        self.nr_channels = nr_channels
+
+    @classmethod
+    def behind(cls, run_resampler, max_events=0, max_frames=0, device=0):
+        """a stage sized for everything one call of `run_resampler` can produce"""
+        max_runs, max_out = run_resampler.capacity()
+        return cls(run_resampler.nr_channels, max_runs, max_out, max_events=max_events, max_frames=max_frames, device=device)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runflex_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_payload, d_totals, stream=None):
+        """the three addresses of RunResampler.device_view(), after its process_device on the same stream"""
+        rc = self.lib.mfm_runflex_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runflex_process_device")
+
+    def fetch(self, max_events=None, max_frames=None):
+        """(events, frames) of the last call (RUNFLEX_EVENT_DTYPE, FLEX_FRAME_DTYPE).  With max_events or max_frames too small:
+        MfmError(MFM_E_NOMEM) whose `needed` / `needed_frames` attributes are the numbers that would fit and whose `buffer` /
+        `frame_buffer` are untouched"""
+        ne, nf = C.c_size_t(), C.c_size_t()
+        if max_events is None or max_frames is None:
+            rc = self.lib.mfm_runflex_fetch(self.h, None, 0, C.byref(ne), None, 0, C.byref(nf))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below, with the untouched buffers
+                self._raise(rc, "mfm_runflex_fetch")
+            max_events = ne.value if max_events is None else max_events
+            max_frames = nf.value if max_frames is None else max_frames
+        ev = np.zeros(max(max_events, 1), RUNFLEX_EVENT_DTYPE)
+        fw = np.zeros(max(max_frames, 1), FLEX_FRAME_DTYPE)
+        rc = self.lib.mfm_runflex_fetch(self.h, ev.ctypes.data, max_events, C.byref(ne), fw.ctypes.data, max_frames, C.byref(nf))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runflex_fetch")
+            except MfmError as err:
+                err.needed, err.needed_frames = ne.value, nf.value
+                err.buffer, err.frame_buffer = ev, fw
+                raise
+        return ev[:ne.value].copy(), fw[:nf.value].copy()
+
+    def device_view(self):
+        """(d_events, d_frames, d_totals): device addresses of the last call's events, frame words and the four uint64 totals
+        (events, frames, overflow, input error)"""
+        e, f, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runflex_device_view(self.h, C.byref(e), C.byref(f), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runflex_device_view")
+        return e.value, f.value, t.value
+
+    def fetch_state(self, with_ring=True):
+        """the per-channel state the last call left (RUNFLEX_STATE_DTYPE [C]) and, with_ring, the rings (int16 [C][32768]): what
+        the host twin carries"""
+        out = np.zeros(self.nr_channels, RUNFLEX_STATE_DTYPE)
+        ring = np.zeros((self.nr_channels, RUNFLEX_RING), np.int16) if with_ring else None
+        rc = self.lib.mfm_runflex_fetch_state(self.h, out.ctypes.data, ring.ctypes.data if with_ring else None, self.nr_channels)
+        if rc < 0:
+            self._raise(rc, "mfm_runflex_fetch_state")
+        return (out, ring) if with_ring else out
+
+
+def hosttwin_runflex_state(nr_channels):
+    """the host twin's (state, ring) at the start of a stream: RUNFLEX_STATE_DTYPE [C] and int16 [C][32768], all zero"""
+    return np.zeros(nr_channels, RUNFLEX_STATE_DTYPE), np.zeros((nr_channels, RUNFLEX_RING), np.int16)
+
+
+def hosttwin_runflex_call(state, runs, payload, totals=None, max_runs=None, max_out_samples=None, max_events=0, max_frames=0,
+                          max_out=None, max_out_frames=None):
+    """mfm_hosttwin_runflex_call: one call of the burst FLEX stage on the CPU.  state = (state, ring) of hosttwin_runflex_state,
+    both updated in place; runs RUNRS_RUN_DTYPE and payload int16 are one burst resampler call's result, totals its four totals
+    (default: the lengths, no flags); max_runs / max_out_samples / max_events / max_frames are the configuration's (default:
+    what the call needs); returns (events, frames).  A refused call raises MfmError(MFM_E_STATE) with a `flags` attribute
+    (overflow | input error << 8)"""
+    lib = load_library()
+    st, ring = state
+    assert st.dtype == RUNFLEX_STATE_DTYPE and st.flags.c_contiguous and st.ndim == 1
+    assert ring.dtype == np.int16 and ring.flags.c_contiguous and ring.shape == (st.shape[0], RUNFLEX_RING)
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    pl = np.ascontiguousarray(payload, dtype=np.int16).reshape(-1)
+    t = np.array([rr.size, pl.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_out_samples = max(pl.size, 1) if max_out_samples is None else max_out_samples
+    if max_out is None:
+        max_out = pl.size // RUNFLEX_EVENT_SPACING + rr.size
+    if max_out_frames is None:
+        max_out_frames = pl.size // RUNFLEX_FRAME_SPACING + rr.size
+    ev = np.zeros(max(max_out, 1), RUNFLEX_EVENT_DTYPE)
+    fw = np.zeros(max(max_out_frames, 1), FLEX_FRAME_DTYPE)
+    ne, nf, fl = C.c_size_t(), C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runflex_call(st.shape[0], max_runs, max_out_samples, max_events, max_frames, st.ctypes.data, ring.ctypes.data,
+                                       rr.ctypes.data if rr.size else None, pl.ctypes.data if pl.size else None, t.ctypes.data,
+                                       ev.ctypes.data, max_out, C.byref(ne), fw.ctypes.data, max_out_frames, C.byref(nf), C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runflex_call", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.needed_frames, err.flags = ne.value, nf.value, fl.value
+        raise err
+    return ev[:ne.value].copy(), fw[:nf.value].copy()
+
+
+def runflex_to_flex_events(events):
+    """mfm_flex_event records (FLEX_EVENT_DTYPE, what host/mfm_pager_flex.c's pager_flex_on_events takes beside the frames) from
+    the burst stage's, field for field, the stretch-relative `sample` and `sync_sample` kept: one pager object per (channel,
+    stretch), a fresh one at every new stretch_window, as the stage has a fresh decoder there"""
+    ev = np.asarray(events)
+    assert ev.dtype == RUNFLEX_EVENT_DTYPE
+    out = np.zeros(ev.shape, FLEX_EVENT_DTYPE)
+    for f in FLEX_EVENT_DTYPE.names:
         out[f] = ev[f]
     return out
 
