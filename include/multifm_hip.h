@@ -995,9 +995,9 @@ int mfm_gate_flush_device(struct mfm_gate *g, void *stream);
  *               does not exist (not a gate's run list)
  *
  * Refusals at create (MFM_E_INVAL with a message, never a fallback): the stage takes PCM payloads only (a gate with
- * elems_per_sample == 1); it has no DC blocker and no sign-bit output, so `flags` must be 0; a ratio whose walk steps past
- * a phase (mfm_rs_plan.h's rule, as mfm_resampler_create); a coefficient image I * plen int16 that, with the input window of
- * one workgroup, exceeds MFM_RUNRS_MAX_LDS_BYTES.
+ * elems_per_sample == 1); it has no DC blocker, and its sign-bit output is an entry of its own (below), so `flags` must be
+ * 0; a ratio whose walk steps past a phase (mfm_rs_plan.h's rule, as mfm_resampler_create); a coefficient image I * plen int16
+ * that, with the input window of one workgroup, exceeds MFM_RUNRS_MAX_LDS_BYTES.
  */
 #define MFM_RUNRS_MAX_LDS_BYTES 49152u /* coefficient image + one workgroup's input window */
 #define MFM_RUNRS_BEGINS 1u            /* mfm_runrs_run.flags bit 0: the run begins a stretch */
@@ -1059,6 +1059,44 @@ int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_r
 /* The capacities fixed at create, which a stage behind sizes itself from: the most runs and the most output elements one call
  * can produce (max_runs as given or its default; ((max_windows * W + max_runs * plen) * I) / D + max_runs). */
 int mfm_runrs_get_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *max_out_elems);
+
+/*
+ * The bits form: the sign-bit path of the burst chain.  The burst AIS stage looks only at sample > 0 and the burst POCSAG
+ * stage only at sample < 0, so for them the resampler can write one predicate bit per output in the place of the int16.
+ *
+ * Input.  The call consumes its input exactly as mfm_runrs_process_device does: the same plan, stretch rule, refusals and
+ * per-channel state.  PCM calls and bits calls may alternate on one object, and a stretch continues across them.  `polarity`
+ * is MFM_BITS_NEG or MFM_BITS_POS (anything else: MFM_E_INVAL with a message).  `invert` applies to the input as in the PCM
+ * form; the predicate is taken from the Q14-rounded int16 output, so the bits are exactly the predicate of what the PCM form
+ * writes.
+ *
+ * Result.  It replaces the previous call's, of either form.  The run list is as in the PCM form except that out_offset counts
+ * 32-bit WORDS of the bits payload: a run owns (nr_out + 31) / 32 words, ascending, no gaps (a run with nr_out == 0 owns
+ * none); output j of a run is bit j % 32 of word out_offset + j / 32; bits at and above nr_out in a run's last word are 0.
+ * d_totals[4] = { runs, payload words, overflow, gate error }.  Every run's bits start on a word, which is what lets the
+ * stages behind copy words instead of slicing samples.  A refused call writes nothing and leaves the state where it was.
+ *
+ * Which accessor.  After a bits call mfm_runrs_fetch and mfm_runrs_device_view answer MFM_E_STATE with a message (no PCM was
+ * written); after a PCM call, and before the first call of either form (mfm_runrs_bits_view), the bits accessors do.
+ *
+ * Capacity.  The bits payload is allocated at create: max_out_elems / 32 + max_runs words (mfm_runrs_get_bits_capacity).
+ */
+int mfm_runrs_process_bits_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload,
+                                  const uint64_t *d_totals, uint32_t polarity, void *stream);
+struct mfm_runrs_bits_view {    /* valid until the resampler's next process call of either form */
+    const struct mfm_runrs_run *d_runs;
+    const uint32_t *d_bits;
+    const uint64_t *d_totals;
+    uint32_t polarity;          /* MFM_BITS_NEG or MFM_BITS_POS */
+    uint32_t reserved;          /* 0 */
+};
+/* For consumers that stay on the device: the last (bits) call's runs, bit payload, d_totals[4] and polarity. */
+int mfm_runrs_bits_view(struct mfm_runrs *rr, struct mfm_runrs_bits_view *view);
+/* As mfm_runrs_fetch for a bits call: the runs and the used words of the bit payload; *nr_words = the call's total. */
+int mfm_runrs_fetch_bits(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, uint32_t *bits, size_t max_words,
+                         size_t *nr_words);
+/* The capacities of the bits form: max_runs as mfm_runrs_get_capacity gives it, and max_out_elems / 32 + max_runs words. */
+int mfm_runrs_get_bits_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *max_words);
 
 /*
  * ---- Burst AIS stage: the burst resampler's runs through the AIS demodulator, on the device -----------------------------
@@ -1140,6 +1178,15 @@ void mfm_runais_destroy(struct mfm_runais **pa);
  */
 int mfm_runais_process_device(struct mfm_runais *a, const struct mfm_runrs_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
                               void *stream);
+/*
+ * The same call on the burst resampler's bits form (mfm_runrs_bits_view after mfm_runrs_process_bits_device with
+ * MFM_BITS_POS; any other polarity: MFM_E_INVAL with a message at the call).  Events, state, bounds and refusals are exactly
+ * those of the PCM entry on the same stretches; PCM and bits calls may alternate on one object (the carried tail is bits in
+ * both).  Only the slicer differs: word k of a run's sample bits is payload word out_offset + k, a 4-byte copy per 32
+ * samples.  The range check reads out_offset + (nr_out + 31) / 32 <= totals[1] (totals[1] itself at most max_out_samples / 32
+ * + max_runs), runs before anything of the payload is read, and the sum of nr_out is still bounded by max_out_samples.
+ */
+int mfm_runais_process_bits_device(struct mfm_runais *a, const struct mfm_runrs_bits_view *view, void *stream);
 /*
  * Wait for the last call and copy its events (the copy is sized by the call's events).  MFM_E_NOMEM when max_events is too
  * small (nothing copied, *nr_events = needed); MFM_E_STATE with a message when the call was refused (nothing copied, the
@@ -1243,6 +1290,15 @@ void mfm_runpocsag_destroy(struct mfm_runpocsag **pp);
  */
 int mfm_runpocsag_process_device(struct mfm_runpocsag *p, const struct mfm_runrs_run *d_runs, const int16_t *d_payload,
                                  const uint64_t *d_totals, void *stream);
+/*
+ * The same call on the burst resampler's bits form (mfm_runrs_bits_view after mfm_runrs_process_bits_device with
+ * MFM_BITS_NEG; any other polarity: MFM_E_INVAL with a message at the call).  Events, state, bounds and refusals are exactly
+ * those of the PCM entry on the same stretches; PCM and bits calls may alternate on one object (the carried tail is bits in
+ * both).  Only the slicer differs: word k of a run's sample bits is payload word out_offset + k, a 4-byte copy per 32
+ * samples.  The range check reads out_offset + (nr_out + 31) / 32 <= totals[1] (totals[1] itself at most max_out_samples / 32
+ * + max_runs), runs before anything of the payload is read, and the sum of nr_out is still bounded by max_out_samples.
+ */
+int mfm_runpocsag_process_bits_device(struct mfm_runpocsag *p, const struct mfm_runrs_bits_view *view, void *stream);
 /*
  * Wait for the last call and copy its events (the copy is sized by the call's events).  MFM_E_NOMEM when max_events is too
  * small (nothing copied, *nr_events = needed); MFM_E_STATE with a message when the call was refused (nothing copied, the
@@ -1556,6 +1612,14 @@ int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint3
                             const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload, size_t nr_gate_elems,
                             struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
                             size_t *nr_elems);
+/* host twin of one mfm_runrs_process_bits_device call: as mfm_hosttwin_runrs_call on the same state (the two may alternate on
+ * it), with the predicate words of `polarity` in `bits` and out_offset, max_words and *nr_words in 32-bit words.  It runs the
+ * inlines the kernels run (csrc/mfm_runrs.h). */
+int mfm_hosttwin_runrs_call_bits(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert,
+                                 uint32_t polarity, const int16_t *coeffs, size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending,
+                                 const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload,
+                                 size_t nr_gate_elems, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, uint32_t *bits,
+                                 size_t max_words, size_t *nr_words);
 /* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream */
 struct mfm_runais_state {       /* 264 bytes */
     uint64_t outs;              /* outputs of the stretch so far */
@@ -1582,6 +1646,13 @@ struct mfm_runais_state {       /* 264 bytes */
 int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
                              struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
                              const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags);
+/* the same on the burst resampler's bits form: runs / bits / totals are one mfm_runrs_process_bits_device call's result (or
+ * mfm_hosttwin_runrs_call_bits'), polarity its polarity (MFM_E_INVAL with a message unless MFM_BITS_POS).  PCM and bits calls may
+ * alternate on one state. */
+int mfm_hosttwin_runais_call_bits(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                  struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const uint32_t *bits, uint32_t polarity,
+                                  const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events,
+                                  uint32_t *flags);
 /* the per-channel state of the burst POCSAG stage, on the device and in the host twin: all zero at the start of a stream.
  * Fields a mode does not use are zero. */
 struct mfm_runpocsag_state {    /* 432 bytes */
@@ -1611,6 +1682,13 @@ int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_
                                 struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
                                 const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events,
                                 uint32_t *flags);
+/* the same on the burst resampler's bits form: runs / bits / totals are one mfm_runrs_process_bits_device call's result (or
+ * mfm_hosttwin_runrs_call_bits'), polarity its polarity (MFM_E_INVAL with a message unless MFM_BITS_NEG).  PCM and bits calls may
+ * alternate on one state. */
+int mfm_hosttwin_runpocsag_call_bits(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                     struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const uint32_t *bits,
+                                     uint32_t polarity, const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out,
+                                     size_t *nr_events, uint32_t *flags);
 /* the per-channel state of the burst FLEX stage, on the device and in the host twin, beside the channel's ring of 32 768 PCM
  * samples: all zero at the start of a stream.  Positions are stretch-relative.  Fields a mode does not use are zero. */
 struct mfm_runflex_state {      /* 88 bytes */

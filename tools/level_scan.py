@@ -98,7 +98,16 @@ stage against mfm_resampler -> mfm_pocsag, busy being synthesized POCSAG transmi
 sample of the burst events (the first runs of a call) equalled the host twin's.  --bench-runflex prints a line of the same build
 ("runflex_stage") for the burst chain burst resampler (16/25, 101 taps) -> burst FLEX stage against mfm_resampler -> mfm_flex, busy
 being synthesized FLEX frames of the four codings on every channel, the three masks all-closed, half-open (a squelch at the median
-window energy) and all-open."""
+window energy) and all-open.  A line after runpocsag_stage ("runbits_stage"; --bench-runbits prints that line alone) is the
+A/B of the burst chain's sign-bit path: burst resampler -> burst stage in the PCM form and in the bits form
+(mfm_runrs_process_bits_device -> mfm_run{ais,pocsag}_process_bits_device), alternating in one process on one gate call's device
+view, for AIS and POCSAG with the ratio, taps and window of their own lines, the busy rows of each and the three masks; per
+case the two means and standard deviations, bits over PCM, the difference with its standard error and the verdict of
+tools/exp/ab.py's rule (kept / worse beyond two standard errors, else neutral), and whether the two forms' events were identical.
+
+With --gate-bits (only with --gate-ais or --gate-pocsag) the scan routes burst resampler -> burst stage through the bits form:
+the same event files; resampled.jsonl keeps its line per run, without file_offset, and no chNNNN.rs.s16 is written, because no
+PCM leaves the resampler."""
 import argparse
 import ctypes as C
 import json
@@ -173,6 +182,25 @@ def scan(a):
         pocsag_index = open(os.path.join(a.gate_out, "pocsag.jsonl"), "w")
         pages_index = open(os.path.join(a.gate_out, "pages.jsonl"), "w")
 
+    bits_polarity = 0   # --gate-bits: the predicate the stage behind the resampler reads
+    if a.gate_bits:
+        bits_polarity = b.MFM_BITS_POS if ra else b.MFM_BITS_NEG
+
+    def run_stages():
+        """burst resampler and the stage behind it on the gate's last result"""
+        if bits_polarity:
+            rr.process_bits_device(*gate.device_view(), bits_polarity, stream=eng.stream)
+            (ra or rp).process_bits_device(rr.bits_view(), stream=eng.stream)
+            return
+        if rr:
+            rr.process_device(*gate.device_view(), stream=eng.stream)
+        if ra:
+            ra.process_device(*rr.device_view(), stream=eng.stream)
+        if rp:
+            rp.process_device(*rr.device_view(), stream=eng.stream)
+        if rf:
+            rf.process_device(*rr.device_view(), stream=eng.stream)
+
     rf, flex_index, flex_pagers = None, None, {}
     if a.gate_flex:   # main() has refused it without --gate-resample or beside another stage
         rf = pkg.RunFlex.behind(rr, device=a.device)
@@ -223,6 +251,18 @@ def scan(a):
             rs_index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * a.window, "first_out": int(r["first_out"]),
                                        "nr_out": int(r["nr_out"]), "begins": int(r["flags"]) & 1, "file_offset": at}) + "\n")
 
+    def write_resampled_runs(runs):
+        """--gate-bits: the runs alone, no PCM left the resampler"""
+        for r in runs:
+            rs_index.write(json.dumps({"channel": int(r["channel"]), "first_sample": int(r["first_window"]) * a.window,
+                                       "first_out": int(r["first_out"]), "nr_out": int(r["nr_out"]), "begins": int(r["flags"]) & 1}) + "\n")
+
+    def fetch_resampled():
+        if bits_polarity:
+            write_resampled_runs(rr.fetch_bits()[0])
+        else:
+            write_resampled(*rr.fetch())
+
     def write_runs(runs, payload):
         for r in runs:
             c, n_el = int(r["channel"]), int(r["nr_windows"]) * a.window * elems
@@ -258,19 +298,12 @@ def scan(a):
                 d_rec, rec_stride, nw, _ = lv.device_view()
                 rows = (d_iq, 2 * stride) if iq_form else (d_pcm, stride)
                 gate.process_device(rows[0], rows[1], nout, d_rec, rec_stride, nw, stream=eng.stream)
-                if rr:
-                    rr.process_device(*gate.device_view(), stream=eng.stream)
-                if ra:
-                    ra.process_device(*rr.device_view(), stream=eng.stream)
-                if rp:
-                    rp.process_device(*rr.device_view(), stream=eng.stream)
-                if rf:
-                    rf.process_device(*rr.device_view(), stream=eng.stream)
+                run_stages()
             rec = lv.fetch()
             if gate:
                 write_runs(*gate.fetch())
             if rr:
-                write_resampled(*rr.fetch())
+                fetch_resampled()
             if ra:
                 write_ais(ra.fetch())
             if rp:
@@ -289,17 +322,10 @@ def scan(a):
                                   "open_share": (float(opened[c]) / float(windows[c])) if windows[c] else 0.0}) + "\n")
     if gate:
         gate.flush_device(stream=eng.stream)  # the windows pre-roll still held back; none with P = 0
-        if rr:
-            rr.process_device(*gate.device_view(), stream=eng.stream)
-        if ra:
-            ra.process_device(*rr.device_view(), stream=eng.stream)
-        if rp:
-            rp.process_device(*rr.device_view(), stream=eng.stream)
-        if rf:
-            rf.process_device(*rr.device_view(), stream=eng.stream)
+        run_stages()
         write_runs(*gate.fetch())
         if rr:
-            write_resampled(*rr.fetch())
+            fetch_resampled()
             rs_index.close()
         if ra:
             write_ais(ra.fetch())
@@ -502,6 +528,7 @@ def bench(a):
         bench_runrs(a, pkg, torch, rows, in_stride, nout, timed)
         bench_runais(a, pkg, torch)
         bench_runpocsag(a, pkg, torch)
+        bench_runbits(a, pkg, torch)
     for o in (lv, eng):
         o.close()
 
@@ -1012,6 +1039,105 @@ def bench_runflex(a, pkg, torch):
     print(json.dumps(out))
 
 
+def bench_runbits(a, pkg, torch):
+    """the A/B of the sign-bit path: burst resampler -> burst stage in the PCM form and in the bits form on the device view one gate
+    call left (every call begins every stretch anew, as in bench_runrs), alternating in one process in rotating order; AIS and
+    POCSAG on the busy rows, ratio, taps and window of bench_runais / bench_runpocsag; all-open, half-open (a squelch at the median
+    window energy) and all-closed"""
+    b = pkg.binding
+    nch, W, I, D = a.bench_channels, a.window, 4, 5
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    taps = np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16)
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "runbits_stage", "channels": nch, "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I,
+           "decimate": D, "taps": int(taps.size), "reps": a.reps, "calls_per_rep": a.inner,
+           "rule": "kept / worse when the means differ by more than 2 standard errors of their difference, else neutral"}
+    for proto in ("ais", "pocsag"):
+        host = _busy_rows(pkg, nch, n) if proto == "ais" else _busy_pocsag_rows(pkg, nch, n)
+        polarity = b.MFM_BITS_POS if proto == "ais" else b.MFM_BITS_NEG
+        d_rows = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "half_open": scene["open"]}
+        keep, recs = [], {"half_open": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        # a chain of its own per form: a stage's state moves with every call, and the two forms must not see each other's
+        rr_p = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        rr_b = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        stage = pkg.RunAis if proto == "ais" else pkg.RunPocsag
+        st_p, st_b = stage.behind(rr_p), stage.behind(rr_b)
+        res = {}
+        for name in ("all_open", "half_open", "all_closed"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_pcm():
+                rr_p.process_device(*view)
+                st_p.process_device(*rr_p.device_view())
+
+            def run_bits():
+                rr_b.process_bits_device(*view, polarity)
+                st_b.process_bits_device(rr_b.bits_view())
+
+            variants = [("pcm", run_pcm), ("bits", run_bits)]
+            for _, fn in variants:
+                timed(fn, 3)
+            ev_p, ev_b = st_p.fetch(), st_b.fetch()
+            got = {v: [] for v, _ in variants}
+            for rep_ in range(a.reps):
+                k = rep_ % len(variants)
+                for vname, fn in variants[k:] + variants[:k]:
+                    got[vname].append(timed(fn, a.inner))
+            (pm, psd), (bm, bsd) = _stats(got["pcm"]), _stats(got["bits"])
+            se = math.sqrt(psd * psd / a.reps + bsd * bsd / a.reps)
+            d = bm - pm
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "events_per_call": int(len(ev_p)),
+                         "events_identical": bool(ev_p.tobytes() == ev_b.tobytes()), "pcm_ms": pm, "pcm_sd": psd, "bits_ms": bm, "bits_sd": bsd,
+                         "bits_over_pcm": bm / pm, "difference_ms": d, "difference_se": se,
+                         "verdict": "neutral" if abs(d) <= 2.0 * se else ("kept" if d < 0 else "worse")}
+            gate.close()
+        out[proto] = res
+        for o in (st_p, st_b, rr_p, rr_b, sq):
+            o.close()
+        del d_rows, keep
+    print(json.dumps(out))
+
+
+def bench_runbits_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runbits needs the GPU: there is no CPU path to time")
+    bench_runbits(a, pkg, torch)
+
+
 def bench_runflex_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -1061,10 +1187,13 @@ def main():
     ap.add_argument("--gate-ais", action="store_true", help="demodulate AIS on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--gate-pocsag", action="store_true", help="demodulate POCSAG on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--gate-flex", action="store_true", help="decode FLEX on the resampled runs on the device (with --gate-resample to 16 000 Hz)")
+    ap.add_argument("--gate-bits", action="store_true",
+                    help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-runais", action="store_true", help="the runais_stage line of --bench alone")
     ap.add_argument("--bench-runpocsag", action="store_true", help="the runpocsag_stage line of --bench alone")
     ap.add_argument("--bench-runflex", action="store_true", help="the runflex_stage line alone")
+    ap.add_argument("--bench-runbits", action="store_true", help="the runbits_stage line of --bench alone")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
@@ -1075,6 +1204,8 @@ def main():
         return bench_runpocsag_alone(a)
     if a.bench_runflex:
         return bench_runflex_alone(a)
+    if a.bench_runbits:
+        return bench_runbits_alone(a)
     if a.bench:
         return bench(a)
     if not a.config or not a.input:
@@ -1083,6 +1214,10 @@ def main():
         raise SystemExit("--gate-flex needs --gate-resample: the burst FLEX stage takes the burst resampler's runs")
     if a.gate_flex and (a.gate_ais or a.gate_pocsag):
         raise SystemExit("--gate-flex, --gate-pocsag and --gate-ais exclude each other: one stage reads the burst resampler's runs")
+    if a.gate_bits and a.gate_flex:
+        raise SystemExit("--gate-bits and --gate-flex exclude each other: the burst FLEX stage reads PCM values, not sign bits")
+    if a.gate_bits and a.gate_ais == a.gate_pocsag:
+        raise SystemExit("--gate-bits needs --gate-ais or --gate-pocsag (one of them): it is the path between the burst resampler and that stage")
     scan(a)
 
 

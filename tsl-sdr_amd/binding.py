@@ -73,6 +73,9 @@ ABI_SYMBOLS = [
     "mfm_runpocsag_fetch_state", "mfm_hosttwin_runpocsag_call",
     "mfm_runflex_create", "mfm_runflex_destroy", "mfm_runflex_process_device", "mfm_runflex_fetch", "mfm_runflex_device_view",
     "mfm_runflex_fetch_state", "mfm_hosttwin_runflex_call",
+    "mfm_runrs_process_bits_device", "mfm_runrs_bits_view", "mfm_runrs_fetch_bits", "mfm_runrs_get_bits_capacity",
+    "mfm_runais_process_bits_device", "mfm_runpocsag_process_bits_device",
+    "mfm_hosttwin_runrs_call_bits", "mfm_hosttwin_runais_call_bits", "mfm_hosttwin_runpocsag_call_bits",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -225,6 +228,12 @@ MFM_RUNRS_NO_WINDOW = (1 << 64) - 1                     # mfm_runrs_state.expect
 RUNRS_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("out_offset", "<u8"), ("first_out", "<u8"), ("channel", "<u4"),
                             ("nr_out", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 RUNRS_STATE_DTYPE = np.dtype([("expected", "<u8"), ("outs", "<u8"), ("phase", "<u4"), ("pending", "<u4")])
+
+
+class RunrsBitsView(C.Structure):
+    """struct mfm_runrs_bits_view: the burst resampler's bits form, valid until its next process call of either form"""
+    _fields_ = [("d_runs", C.c_void_p), ("d_bits", C.c_void_p), ("d_totals", C.c_void_p), ("polarity", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class RunaisConfig(C.Structure):
@@ -552,6 +561,18 @@ def load_library():
     lib.mfm_runrs_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_runrs_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.mfm_runrs_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.mfm_runrs_process_bits_device.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
+    lib.mfm_runrs_bits_view.argtypes = [vp, C.POINTER(RunrsBitsView)]
+    lib.mfm_runrs_fetch_bits.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_runrs_get_bits_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.mfm_runais_process_bits_device.argtypes = [vp, C.POINTER(RunrsBitsView), vp]
+    lib.mfm_runpocsag_process_bits_device.argtypes = [vp, C.POINTER(RunrsBitsView), vp]
+    lib.mfm_hosttwin_runrs_call_bits.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i16p, C.c_size_t, vp,
+                                                 i16p, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_hosttwin_runais_call_bits.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, C.c_size_t,
+                                                  szp, C.POINTER(C.c_uint32)]
+    lib.mfm_hosttwin_runpocsag_call_bits.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp,
+                                                     C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_runais_create.argtypes = [C.POINTER(vp), C.POINTER(RunaisConfig)]
     lib.mfm_runais_destroy.argtypes = [C.POINTER(vp)]
     lib.mfm_runais_destroy.restype = None
@@ -1594,6 +1615,51 @@ class RunResampler:
             self._raise(rc, "mfm_runrs_device_view")
         return r.value, p.value, t.value
 
+    def process_bits_device(self, d_runs, d_payload, d_totals, polarity, stream=None):
+        """as process_device, with one predicate bit per output (MFM_BITS_NEG: sample < 0, MFM_BITS_POS: sample > 0) in the
+        place of the int16; the result is read with bits_view() or fetch_bits()"""
+        rc = self.lib.mfm_runrs_process_bits_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), polarity,
+                                                    C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_process_bits_device")
+
+    def bits_view(self):
+        """RunrsBitsView of the last (bits) call: device addresses of its runs (out_offset in words), bit payload and totals"""
+        v = RunrsBitsView()
+        rc = self.lib.mfm_runrs_bits_view(self.h, C.byref(v))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_bits_view")
+        return v
+
+    def fetch_bits(self, max_runs=None, max_words=None):
+        """(runs, bits) of the last (bits) call: RUNRS_RUN_DTYPE [nr_runs] with out_offset in words, and uint32 [nr_words].
+        Errors as fetch()"""
+        nr, nw = C.c_size_t(), C.c_size_t()
+        if max_runs is None or max_words is None:
+            rc = self.lib.mfm_runrs_fetch_bits(self.h, None, 0, C.byref(nr), None, 0, C.byref(nw))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below, with the untouched buffers
+                self._raise(rc, "mfm_runrs_fetch_bits")
+            max_runs = nr.value if max_runs is None else max_runs
+            max_words = nw.value if max_words is None else max_words
+        runs = np.zeros(max(max_runs, 1), RUNRS_RUN_DTYPE)
+        bits = np.zeros(max(max_words, 1), np.uint32)
+        rc = self.lib.mfm_runrs_fetch_bits(self.h, runs.ctypes.data, max_runs, C.byref(nr), bits.ctypes.data, max_words, C.byref(nw))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runrs_fetch_bits")
+            except MfmError as err:
+                err.needed = (nr.value, nw.value)
+                err.buffers = (runs, bits)
+                raise
+        return runs[:nr.value].copy(), bits[:nw.value].copy()
+
+    def bits_capacity(self):
+        """(max_runs, max_words) of the bits form: max_words = max_out_elems // 32 + max_runs"""
+        nr, nw = C.c_uint32(), C.c_uint64()
+        rc = self.lib.mfm_runrs_get_bits_capacity(self.h, C.byref(nr), C.byref(nw))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_get_bits_capacity")
+        return nr.value, nw.value
 
     def capacity(self):
         """(max_runs, max_out_elems): the most runs and output elements one call can produce, which a stage behind sizes
@@ -1644,6 +1710,12 @@ class RunAis:
         rc = self.lib.mfm_runais_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), C.c_void_p(stream or 0))
         if rc < 0:
             self._raise(rc, "mfm_runais_process_device")
+
+    def process_bits_device(self, view, stream=None):
+        """as process_device, from a RunResampler's MFM_BITS_POS bits_view() instead of PCM"""
+        rc = self.lib.mfm_runais_process_bits_device(self.h, C.byref(view), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runais_process_bits_device")
 
     def fetch(self, max_events=None):
         """the events of the last call (RUNAIS_EVENT_DTYPE).  With max_events too small: MfmError(MFM_E_NOMEM) whose `needed`
@@ -1708,6 +1780,35 @@ def hosttwin_runais_call(state, runs, payload, totals=None, max_runs=None, max_o
     return out[:nr.value].copy()
 
 
+def hosttwin_runais_call_bits(state, runs, bits, polarity=MFM_BITS_POS, totals=None, max_runs=None, max_out_samples=None, max_events=0,
+                              max_out=None):
+    """mfm_hosttwin_runais_call_bits: hosttwin_runais_call on the burst resampler's bits form.  runs (out_offset in words)
+    and bits uint32 are one bits call's result, totals its four totals (default: the lengths, no flags); the same state may go
+    through PCM and bits calls in turn"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNAIS_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    bw = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+    t = np.array([rr.size, bw.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    nout = int(rr["nr_out"].astype(np.uint64).sum())
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_out_samples = max(nout, 1) if max_out_samples is None else max_out_samples
+    if max_out is None:
+        max_out = nout // 160 + rr.size
+    out = np.zeros(max(max_out, 1), RUNAIS_EVENT_DTYPE)
+    nr, fl = C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runais_call_bits(state.shape[0], max_runs, max_out_samples, max_events, state.ctypes.data,
+                                           rr.ctypes.data if rr.size else None, bw.ctypes.data if bw.size else None, polarity,
+                                           t.ctypes.data, out.ctypes.data, max_out, C.byref(nr), C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runais_call_bits", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.flags = nr.value, fl.value
+        raise err
+    return out[:nr.value].copy()
+
+
 def runais_to_ais_events(events, interpolate, decimate, window_samples):
     """mfm_ais_event records (AIS_EVENT_DTYPE, what host/mfm_ais.c's ais_decode_on_events takes) from the burst stage's: the
     stretch-relative sample numbers become positions of the channel's stream at the output rate, sample = stretch_window * W *
@@ -1763,6 +1864,12 @@ class RunPocsag:
         rc = self.lib.mfm_runpocsag_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), C.c_void_p(stream or 0))
         if rc < 0:
             self._raise(rc, "mfm_runpocsag_process_device")
+
+    def process_bits_device(self, view, stream=None):
+        """as process_device, from a RunResampler's MFM_BITS_NEG bits_view() instead of PCM"""
+        rc = self.lib.mfm_runpocsag_process_bits_device(self.h, C.byref(view), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runpocsag_process_bits_device")
 
     def fetch(self, max_events=None):
         """the events of the last call (RUNPOCSAG_EVENT_DTYPE).  With max_events too small: MfmError(MFM_E_NOMEM) whose `needed`
@@ -1830,6 +1937,35 @@ def hosttwin_runpocsag_call(state, runs, payload, totals=None, max_runs=None, ma
                                          out.ctypes.data, max_out, C.byref(nr), C.byref(fl))
     if rc < 0:
         err = MfmError(rc, "mfm_hosttwin_runpocsag_call", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.flags = nr.value, fl.value
+        raise err
+    return out[:nr.value].copy()
+
+
+def hosttwin_runpocsag_call_bits(state, runs, bits, polarity=MFM_BITS_NEG, totals=None, max_runs=None, max_out_samples=None, max_events=0,
+                                 max_out=None):
+    """mfm_hosttwin_runpocsag_call_bits: hosttwin_runpocsag_call on the burst resampler's bits form.  runs (out_offset in words)
+    and bits uint32 are one bits call's result, totals its four totals (default: the lengths, no flags); the same state may go
+    through PCM and bits calls in turn"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNPOCSAG_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    bw = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+    t = np.array([rr.size, bw.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    nout = int(rr["nr_out"].astype(np.uint64).sum())
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_out_samples = max(nout, 1) if max_out_samples is None else max_out_samples
+    if max_out is None:
+        max_out = 3 * (nout // RUNPOCSAG_MIN_SPACING) + 5 * rr.size
+    out = np.zeros(max(max_out, 1), RUNPOCSAG_EVENT_DTYPE)
+    nr, fl = C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runpocsag_call_bits(state.shape[0], max_runs, max_out_samples, max_events, state.ctypes.data,
+                                           rr.ctypes.data if rr.size else None, bw.ctypes.data if bw.size else None, polarity,
+                                           t.ctypes.data, out.ctypes.data, max_out, C.byref(nr), C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runpocsag_call_bits", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
         err.needed, err.flags = nr.value, fl.value
         raise err
     return out[:nr.value].copy()
@@ -2034,6 +2170,36 @@ def hosttwin_runrs_call(window_samples, coeffs_q14, interpolate, decimate, state
         err.needed = (nr.value, ne.value)
         raise err
     return runs[:nr.value].copy(), payload[:ne.value].copy()
+
+
+def hosttwin_runrs_call_bits(window_samples, coeffs_q14, interpolate, decimate, state, pending, gate_runs, gate_payload, polarity,
+                             invert=False, max_runs=None, max_words=None):
+    """mfm_hosttwin_runrs_call_bits: hosttwin_runrs_call with the predicate words of `polarity` in the place of the int16:
+    returns (runs, bits), out_offset in 32-bit words.  The same state and pending may go through both in turn"""
+    lib = load_library()
+    state, pending = np.asarray(state), np.asarray(pending)
+    co = np.ascontiguousarray(coeffs_q14, dtype=np.int16)
+    assert state.dtype == RUNRS_STATE_DTYPE and state.flags.c_contiguous and pending.dtype == np.int16 and pending.flags.c_contiguous
+    nch = state.shape[0]
+    assert pending.shape == (nch, runrs_phase_len(max(co.size, 1), max(interpolate, 1)))
+    gr = np.ascontiguousarray(gate_runs, dtype=GATE_RUN_DTYPE).reshape(-1)
+    gp = np.ascontiguousarray(gate_payload, dtype=np.int16).reshape(-1)
+    if max_runs is None:
+        max_runs = gr.size
+    if max_words is None:  # the PCM form's bound on the outputs, / 32, and at most one more word per run
+        max_words = ((gp.size + gr.size * pending.shape[1]) * max(interpolate, 1) // max(decimate, 1) + gr.size) // 32 + gr.size
+    runs = np.zeros(max(max_runs, 1), RUNRS_RUN_DTYPE)
+    bits = np.zeros(max(max_words, 1), np.uint32)
+    nr, nw = C.c_size_t(), C.c_size_t()
+    rc = lib.mfm_hosttwin_runrs_call_bits(nch, window_samples, interpolate, decimate, int(invert), polarity, _i16p(co) if co.size else None,
+                                          co.size, state.ctypes.data, _i16p(pending), gr.ctypes.data if gr.size else None, gr.size,
+                                          gp.ctypes.data if gp.size else None, gp.size, runs.ctypes.data, max_runs, C.byref(nr),
+                                          bits.ctypes.data, max_words, C.byref(nw))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runrs_call_bits", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
+        err.needed = (nr.value, nw.value)
+        raise err
+    return runs[:nr.value].copy(), bits[:nw.value].copy()
 
 
 class Flex:

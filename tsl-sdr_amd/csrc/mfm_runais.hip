@@ -14,6 +14,8 @@
  *   ra_slice_kernel    payload int16 -> 1 bit per sample.  A workgroup takes 256 words of one run's segment, which it finds
  *                      from its index by binary search in the scanned workgroup counts: the 8 history words (the channel's
  *                      carried tail, or zeros), then 32 samples per lane as four 16-byte loads, the run's end one by one.
+ *                      On the resampler's bits form (mfm_runais_process_bits_device) rb_slice_kernel of mfm_run_bits.hip
+ *                      runs in its place: the 32 sample bits of a word are one payload word, a 4-byte copy.
  *   ra_walk_kernel     one wave per run: mfm_ais.hip's SEARCH / RECEIVE loop in segment coordinates.  SEARCH computes the M
  *                      words in the walker, a segment word per lane and 63 words (2016 samples) per step (a lane gets the
  *                      words in front of its own by lane shifts, so every shift of the correlator is a constant), with the
@@ -40,6 +42,7 @@
 #include "../../include/multifm_hip.h"
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
+#include "mfm_run_bits.h"
 #include "mfm_runais.h"
 
 static_assert(sizeof(mfm_runais_event) == 200, "struct mfm_runais_event is 200 bytes");
@@ -49,7 +52,7 @@ static_assert(sizeof(mfm_runais_state) == 264 && offsetof(mfm_runais_state, pack
 namespace {
 
 constexpr uint32_t RA_SCAN_THREADS = 1024;
-constexpr uint32_t RA_SLICE_NT = 256;         /* slicer: threads = segment words per workgroup */
+constexpr uint32_t RA_SLICE_NT = MFM_RUN_BITS_SLICE_NT;         /* slicer: threads = segment words per workgroup */
 constexpr uint32_t RA_NONE = 0xffffffffu;     /* d_chan_last: the channel has no run in this call */
 constexpr uint32_t RA_T_EVENTS = 0, RA_T_RUNS = 1, RA_T_OVERFLOW = 2, RA_T_INPUT = 3; /* d_totals[] */
 constexpr uint32_t RA_RS_RUNS = 0, RA_RS_ELEMS = 1, RA_RS_OVERFLOW = 2, RA_RS_GATE = 3; /* the resampler's */
@@ -129,6 +132,7 @@ __device__ __forceinline__ uint32_t ra_m32(uint32_t qc, uint32_t qp)
 struct RaCall {
     const mfm_runrs_run *runs;
     const int16_t *payload;
+    const uint32_t *bits; /* the resampler's bits form: the payload of predicate words, and payload is NULL */
     const uint64_t *rtotals;
     const mfm_runais_state *chan_old;
     mfm_runais_state *chan_new;
@@ -179,10 +183,11 @@ __global__ __launch_bounds__(RA_SCAN_THREADS) void ra_plan_kernel(const RaCall A
 {
     __shared__ uint64_t lds[RA_SCAN_THREADS / 64];
     const uint64_t n = A.rtotals[RA_RS_RUNS], E = A.rtotals[RA_RS_ELEMS];
+    const bool words = A.bits != nullptr; /* E and out_offset count words of the bits payload */
     uint64_t over = 0, err = 0;
     if (A.rtotals[RA_RS_OVERFLOW] || A.rtotals[RA_RS_GATE]) {
         err = MFM_RUNAIS_IN_RUNRS;
-    } else if (E > A.cap_out) {
+    } else if (E > (words ? (uint64_t)A.cap_out / 32u + A.cap_runs : (uint64_t)A.cap_out)) {
         err = MFM_RUNAIS_IN_BAD_RUNS;
     } else if (n > A.cap_runs) {
         over = MFM_RUNAIS_OVER_RUNS;
@@ -206,7 +211,7 @@ __global__ __launch_bounds__(RA_SCAN_THREADS) void ra_plan_kernel(const RaCall A
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         const mfm_runrs_run run = A.runs[r];
-        bad |= mfm_runais_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old);
+        bad |= mfm_runais_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old, words);
         const uint32_t w = mfm_runais_seg_words(run.nr_out);
         so += run.nr_out;
         sw += w;
@@ -732,10 +737,14 @@ void mfm_runais_destroy(struct mfm_runais **pa)
     *pa = nullptr;
 }
 
-int mfm_runais_process_device(struct mfm_runais *a, const struct mfm_runrs_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
-                              void *stream)
+} /* extern "C" */
+
+namespace {
+
+/* one call in either form: d_payload (PCM) or d_bits (the resampler's bits form), the other NULL */
+int ra_process(mfm_runais *a, const mfm_runrs_run *d_runs, const int16_t *d_payload, const uint32_t *d_bits, const uint64_t *d_totals, void *stream)
 {
-    if (!a || !d_runs || !d_payload || !d_totals) {
+    if (!a || !d_runs || (!d_payload && !d_bits) || !d_totals) {
         return MFM_E_INVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -744,14 +753,23 @@ int mfm_runais_process_device(struct mfm_runais *a, const struct mfm_runrs_run *
         RA_TRY(hipStreamSynchronize(a->last_stream)); /* state lives on the device; keep calls ordered */
     }
     const uint32_t cur = a->cur;
-    const RaCall A{ d_runs,        d_payload,      d_totals,       a->d_chan[cur], a->d_chan[cur ^ 1u], a->d_run_state,
+    const RaCall A{ d_runs,        d_payload,      d_bits,         d_totals,       a->d_chan[cur], a->d_chan[cur ^ 1u], a->d_run_state,
                     a->d_seg,      a->d_seg_base,  a->d_slot_base, a->d_blk_base,  a->d_count,          a->d_ev_base,
                     a->d_chan_last, a->d_ctl,      a->d_totals,    a->d_slots,     a->d_events,         a->cfg.nr_channels,
                     a->cfg.max_runs, a->cfg.max_out_samples, (uint32_t)a->cap_events };
     hipLaunchKernelGGL(ra_plan_kernel, dim3(1), dim3(RA_SCAN_THREADS), 0, s, A);
     RA_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ra_slice_kernel, dim3((uint32_t)a->max_blocks), dim3(RA_SLICE_NT), 0, s, A);
-    RA_TRY(hipGetLastError());
+    if (d_bits) { /* the word copy of mfm_run_bits.hip in the place of the slicer */
+        const mfm_run_bits_slice B{ d_runs, d_bits, reinterpret_cast<const uint32_t *>(a->d_chan[cur]), a->d_blk_base, a->d_seg_base, a->d_ctl,
+                                    a->d_seg, RA_STATE_WORDS, RA_TAIL_WORD0, MFM_RUNAIS_HIST_WORDS };
+        if (mfm_internal_run_bits_slice(&B, (uint32_t)a->max_blocks, s) != MFM_OK) {
+            RA_TRY(hipGetLastError());
+            return MFM_E_DEVICE;
+        }
+    } else {
+        hipLaunchKernelGGL(ra_slice_kernel, dim3((uint32_t)a->max_blocks), dim3(RA_SLICE_NT), 0, s, A);
+        RA_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(ra_walk_kernel, dim3(a->cfg.max_runs), dim3(64), 0, s, A);
     RA_TRY(hipGetLastError());
     hipLaunchKernelGGL(ra_evscan_kernel, dim3(1), dim3(RA_SCAN_THREADS), 0, s, A);
@@ -764,6 +782,30 @@ int mfm_runais_process_device(struct mfm_runais *a, const struct mfm_runrs_run *
     a->last_stream = s;
     a->have_call = true;
     return MFM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int mfm_runais_process_device(struct mfm_runais *a, const struct mfm_runrs_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                              void *stream)
+{
+    if (!d_payload) {
+        return MFM_E_INVAL;
+    }
+    return ra_process(a, d_runs, d_payload, nullptr, d_totals, stream);
+}
+
+int mfm_runais_process_bits_device(struct mfm_runais *a, const struct mfm_runrs_bits_view *view, void *stream)
+{
+    if (!a || !view || !view->d_bits) {
+        return MFM_E_INVAL;
+    }
+    if (view->polarity != MFM_BITS_POS) {
+        return ra_fail(MFM_E_INVAL, "the burst AIS stage needs MFM_BITS_POS bits (bit = sample > 0)");
+    }
+    return ra_process(a, view->d_runs, nullptr, view->d_bits, view->d_totals, stream);
 }
 
 int mfm_runais_fetch(struct mfm_runais *a, struct mfm_runais_event *events, size_t max_events, size_t *nr_events)
@@ -930,11 +972,12 @@ void ra_host_walk(mfm_runais_state &st, const uint32_t *seg, const mfm_runrs_run
 
 } /* namespace */
 
-extern "C" {
+namespace {
 
-int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
-                             struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
-                             const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags)
+/* the host twin of one call in either form: bits != NULL is the resampler's bits form (totals[1] and out_offset in words) */
+int ra_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events, struct mfm_runais_state *state,
+                 const struct mfm_runrs_run *runs, const int16_t *payload, const uint32_t *bits, bool words, const uint64_t *totals,
+                 struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags)
 {
     if (!state || !totals || !nr_events || (!events && max_out)) {
         return MFM_E_INVAL;
@@ -959,18 +1002,18 @@ int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t m
     uint64_t over = 0, err = 0;
     if (totals[RA_RS_OVERFLOW] || totals[RA_RS_GATE]) {
         err = MFM_RUNAIS_IN_RUNRS;
-    } else if (E > max_out_samples) {
+    } else if (E > (words ? (uint64_t)max_out_samples / 32u + max_runs : (uint64_t)max_out_samples)) {
         err = MFM_RUNAIS_IN_BAD_RUNS;
     } else if (n > max_runs) {
         over = MFM_RUNAIS_OVER_RUNS;
     }
     if (!over && !err) {
-        if ((n && !runs) || (E && !payload)) {
+        if ((n && !runs) || (E && !(words ? (const void *)bits : (const void *)payload))) {
             return MFM_E_INVAL;
         }
         uint64_t to = 0, ts = 0;
         for (uint64_t r = 0; r < n; r++) {
-            err |= mfm_runais_check_run(runs[r], r ? &runs[r - 1] : nullptr, nr_channels, E, state);
+            err |= mfm_runais_check_run(runs[r], r ? &runs[r - 1] : nullptr, nr_channels, E, state, words);
             to += runs[r].nr_out;
             ts += mfm_runais_slots(runs[r].nr_out);
         }
@@ -1003,9 +1046,15 @@ int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t m
         for (uint32_t k = 0; k < MFM_RUNAIS_HIST_WORDS; k++) {
             seg[k] = st.tail[k]; /* zeros for a beginning run */
         }
-        for (uint32_t j = 0; j < run.nr_out; j++) {
-            if (payload[run.out_offset + j] > 0) {
-                seg[MFM_RUNAIS_HIST_WORDS + (j >> 5)] |= 1u << (j & 31u);
+        if (words) { /* the slicer's word copy */
+            for (uint32_t k = 0; k < (run.nr_out + 31u) / 32u; k++) {
+                seg[MFM_RUNAIS_HIST_WORDS + k] = bits[run.out_offset + k];
+            }
+        } else {
+            for (uint32_t j = 0; j < run.nr_out; j++) {
+                if (payload[run.out_offset + j] > 0) {
+                    seg[MFM_RUNAIS_HIST_WORDS + (j >> 5)] |= 1u << (j & 31u);
+                }
             }
         }
         ra_host_walk(st, seg.data(), run, (uint32_t)r, out);
@@ -1027,6 +1076,30 @@ int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t m
         memcpy(events, out.data(), out.size() * sizeof(mfm_runais_event));
     }
     return MFM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                             struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                             const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags)
+{
+    return ra_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, payload, nullptr, false, totals, events, max_out,
+                        nr_events, flags);
+}
+
+int mfm_hosttwin_runais_call_bits(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                  struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const uint32_t *bits, uint32_t polarity,
+                                  const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events,
+                                  uint32_t *flags)
+{
+    if (polarity != MFM_BITS_POS) {
+        return ra_fail(MFM_E_INVAL, "the burst AIS stage needs MFM_BITS_POS bits (bit = sample > 0)");
+    }
+    return ra_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, nullptr, bits, true, totals, events, max_out,
+                        nr_events, flags);
 }
 
 } /* extern "C" */

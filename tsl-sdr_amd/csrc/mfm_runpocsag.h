@@ -49,13 +49,15 @@ __host__ __device__ inline uint32_t mfm_runpocsag_slots(uint32_t nr_out)
 
 /*
  * The input-error flags of run `run` (0: it may be read).  prev: the run in front of it in the list (NULL for the first),
- * nr_elems: the resampler's total of output elements, state: the per-channel state the call started from.
+ * nr_elems: the resampler's total of output elements, state: the per-channel state the call started from.  words: the
+ * resampler's bits form, where out_offset and nr_elems count 32-bit words and the run owns (nr_out + 31) / 32 of them.
  */
 __host__ __device__ inline uint32_t mfm_runpocsag_check_run(const mfm_runrs_run &run, const mfm_runrs_run *prev, uint32_t nr_channels,
-                                                            uint64_t nr_elems, const mfm_runpocsag_state *state)
+                                                            uint64_t nr_elems, const mfm_runpocsag_state *state, bool words = false)
 {
+    const uint64_t owned = words ? ((uint64_t)run.nr_out + 31u) / 32u : run.nr_out;
     if (run.channel >= nr_channels || (prev && prev->channel > run.channel) || run.out_offset > nr_elems ||
-        run.nr_out > nr_elems - run.out_offset) {
+        owned > nr_elems - run.out_offset) {
         return MFM_RUNPOCSAG_IN_BAD_RUNS;
     }
     if (run.flags & MFM_RUNRS_BEGINS) {

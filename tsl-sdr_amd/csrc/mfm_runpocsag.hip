@@ -15,6 +15,8 @@
  *                      which it finds from its index by binary search in the scanned workgroup counts: the 75 history words
  *                      (the channel's carried tail, or zeros), then 32 samples per lane as four 16-byte loads, the run's end
  *                      one by one.
+ *                      On the resampler's bits form (mfm_runpocsag_process_bits_device) rb_slice_kernel of mfm_run_bits.hip
+ *                      runs in its place: the 32 sample bits of a word are one payload word, a 4-byte copy.
  *   rp_match_kernel    the free-running match words m[d] of the three rates over every segment, data parallel: a workgroup
  *                      takes the same 256 segment words as in the slicer, puts them and the 76 words in front (the
  *                      correlators reach 31 * 75 samples back) into LDS and every thread computes the three match words of
@@ -49,6 +51,7 @@
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_bch.h"
+#include "mfm_run_bits.h"
 #include "mfm_runpocsag.h"
 
 static_assert(sizeof(mfm_runpocsag_event) == 176 && offsetof(mfm_runpocsag_event, run) == 16 &&
@@ -61,7 +64,7 @@ static_assert(sizeof(mfm_runpocsag_state) == 432 && offsetof(mfm_runpocsag_state
 namespace {
 
 constexpr uint32_t RP_SCAN_THREADS = 1024;
-constexpr uint32_t RP_SLICE_NT = 256;         /* slicer: threads = segment words per workgroup */
+constexpr uint32_t RP_SLICE_NT = MFM_RUN_BITS_SLICE_NT;         /* slicer: threads = segment words per workgroup */
 constexpr uint32_t RP_NONE = 0xffffffffu;     /* d_chan_last: the channel has no run in this call */
 constexpr uint32_t RP_T_EVENTS = 0, RP_T_RUNS = 1, RP_T_OVERFLOW = 2, RP_T_INPUT = 3; /* d_totals[] */
 constexpr uint32_t RP_RS_RUNS = 0, RP_RS_ELEMS = 1, RP_RS_OVERFLOW = 2, RP_RS_GATE = 3; /* the resampler's */
@@ -180,6 +183,7 @@ __device__ __forceinline__ uint32_t rp_match32_exact(const uint32_t *tile, uint3
 struct RpCall {
     const mfm_runrs_run *runs;
     const int16_t *payload;
+    const uint32_t *bits; /* the resampler's bits form: the payload of predicate words, and payload is NULL */
     const uint64_t *rtotals;
     const mfm_runpocsag_state *chan_old;
     mfm_runpocsag_state *chan_new;
@@ -233,10 +237,11 @@ __global__ __launch_bounds__(RP_SCAN_THREADS) void rp_plan_kernel(const RpCall A
 {
     __shared__ uint64_t lds[RP_SCAN_THREADS / 64];
     const uint64_t n = A.rtotals[RP_RS_RUNS], E = A.rtotals[RP_RS_ELEMS];
+    const bool words = A.bits != nullptr; /* E and out_offset count words of the bits payload */
     uint64_t over = 0, err = 0;
     if (A.rtotals[RP_RS_OVERFLOW] || A.rtotals[RP_RS_GATE]) {
         err = MFM_RUNPOCSAG_IN_RUNRS;
-    } else if (E > A.cap_out) {
+    } else if (E > (words ? (uint64_t)A.cap_out / 32u + A.cap_runs : (uint64_t)A.cap_out)) {
         err = MFM_RUNPOCSAG_IN_BAD_RUNS;
     } else if (n > A.cap_runs) {
         over = MFM_RUNPOCSAG_OVER_RUNS;
@@ -260,7 +265,7 @@ __global__ __launch_bounds__(RP_SCAN_THREADS) void rp_plan_kernel(const RpCall A
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         const mfm_runrs_run run = A.runs[r];
-        bad |= mfm_runpocsag_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old);
+        bad |= mfm_runpocsag_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old, words);
         const uint32_t w = mfm_runpocsag_seg_words(run.nr_out);
         so += run.nr_out;
         sw += w;
@@ -969,10 +974,15 @@ void mfm_runpocsag_destroy(struct mfm_runpocsag **pp)
     *pp = nullptr;
 }
 
-int mfm_runpocsag_process_device(struct mfm_runpocsag *p, const struct mfm_runrs_run *d_runs, const int16_t *d_payload,
-                                 const uint64_t *d_totals, void *stream)
+} /* extern "C" */
+
+namespace {
+
+/* one call in either form: d_payload (PCM) or d_bits (the resampler's bits form), the other NULL */
+int rp_process(mfm_runpocsag *p, const mfm_runrs_run *d_runs, const int16_t *d_payload, const uint32_t *d_bits, const uint64_t *d_totals,
+               void *stream)
 {
-    if (!p || !d_runs || !d_payload || !d_totals) {
+    if (!p || !d_runs || (!d_payload && !d_bits) || !d_totals) {
         return MFM_E_INVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -981,14 +991,23 @@ int mfm_runpocsag_process_device(struct mfm_runpocsag *p, const struct mfm_runrs
         RP_TRY(hipStreamSynchronize(p->last_stream)); /* state lives on the device; keep calls ordered */
     }
     const uint32_t cur = p->cur;
-    const RpCall A{ d_runs,         d_payload,     d_totals,       p->d_chan[cur], p->d_chan[cur ^ 1u], p->d_run_state,
+    const RpCall A{ d_runs,         d_payload,     d_bits,         d_totals,       p->d_chan[cur], p->d_chan[cur ^ 1u], p->d_run_state,
                     p->d_seg,       p->d_plane,    p->d_summ,      p->d_seg_base, p->d_slot_base, p->d_blk_base,  p->d_count,          p->d_ev_base,
                     p->d_chan_last, p->d_ctl,      p->d_totals,    p->d_slots,     p->d_events,         p->d_bch,
                     p->cfg.nr_channels, p->cfg.max_runs, p->cfg.max_out_samples, (uint32_t)p->cap_events, (uint32_t)p->seg_words };
     hipLaunchKernelGGL(rp_plan_kernel, dim3(1), dim3(RP_SCAN_THREADS), 0, s, A);
     RP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(rp_slice_kernel, dim3((uint32_t)p->max_blocks), dim3(RP_SLICE_NT), 0, s, A);
-    RP_TRY(hipGetLastError());
+    if (d_bits) { /* the word copy of mfm_run_bits.hip in the place of the slicer */
+        const mfm_run_bits_slice B{ d_runs, d_bits, reinterpret_cast<const uint32_t *>(p->d_chan[cur]), p->d_blk_base, p->d_seg_base, p->d_ctl,
+                                    p->d_seg, RP_STATE_WORDS, RP_TAIL_WORD0, MFM_RUNPOCSAG_HIST_WORDS };
+        if (mfm_internal_run_bits_slice(&B, (uint32_t)p->max_blocks, s) != MFM_OK) {
+            RP_TRY(hipGetLastError());
+            return MFM_E_DEVICE;
+        }
+    } else {
+        hipLaunchKernelGGL(rp_slice_kernel, dim3((uint32_t)p->max_blocks), dim3(RP_SLICE_NT), 0, s, A);
+        RP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(rp_match_kernel, dim3((uint32_t)p->max_blocks), dim3(RP_SLICE_NT), 0, s, A);
     RP_TRY(hipGetLastError());
     hipLaunchKernelGGL(rp_walk_kernel, dim3(p->cfg.max_runs), dim3(64), 0, s, A);
@@ -1003,6 +1022,30 @@ int mfm_runpocsag_process_device(struct mfm_runpocsag *p, const struct mfm_runrs
     p->last_stream = s;
     p->have_call = true;
     return MFM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int mfm_runpocsag_process_device(struct mfm_runpocsag *p, const struct mfm_runrs_run *d_runs, const int16_t *d_payload,
+                                 const uint64_t *d_totals, void *stream)
+{
+    if (!d_payload) {
+        return MFM_E_INVAL;
+    }
+    return rp_process(p, d_runs, d_payload, nullptr, d_totals, stream);
+}
+
+int mfm_runpocsag_process_bits_device(struct mfm_runpocsag *p, const struct mfm_runrs_bits_view *view, void *stream)
+{
+    if (!p || !view || !view->d_bits) {
+        return MFM_E_INVAL;
+    }
+    if (view->polarity != MFM_BITS_NEG) {
+        return rp_fail(MFM_E_INVAL, "the burst POCSAG stage needs MFM_BITS_NEG bits (bit = sample < 0)");
+    }
+    return rp_process(p, view->d_runs, nullptr, view->d_bits, view->d_totals, stream);
 }
 
 int mfm_runpocsag_fetch(struct mfm_runpocsag *p, struct mfm_runpocsag_event *events, size_t max_events, size_t *nr_events)
@@ -1178,12 +1221,12 @@ void rp_host_walk(mfm_runpocsag_state &st, const uint32_t *seg, const mfm_runrs_
 
 } /* namespace */
 
-extern "C" {
+namespace {
 
-int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
-                                struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
-                                const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events,
-                                uint32_t *flags)
+/* the host twin of one call in either form: bits != NULL is the resampler's bits form (totals[1] and out_offset in words) */
+int rp_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events, struct mfm_runpocsag_state *state,
+                 const struct mfm_runrs_run *runs, const int16_t *payload, const uint32_t *bits, bool words, const uint64_t *totals,
+                 struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events, uint32_t *flags)
 {
     if (!state || !totals || !nr_events || (!events && max_out)) {
         return MFM_E_INVAL;
@@ -1208,18 +1251,18 @@ int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_
     uint64_t over = 0, err = 0;
     if (totals[RP_RS_OVERFLOW] || totals[RP_RS_GATE]) {
         err = MFM_RUNPOCSAG_IN_RUNRS;
-    } else if (E > max_out_samples) {
+    } else if (E > (words ? (uint64_t)max_out_samples / 32u + max_runs : (uint64_t)max_out_samples)) {
         err = MFM_RUNPOCSAG_IN_BAD_RUNS;
     } else if (n > max_runs) {
         over = MFM_RUNPOCSAG_OVER_RUNS;
     }
     if (!over && !err) {
-        if ((n && !runs) || (E && !payload)) {
+        if ((n && !runs) || (E && !(words ? (const void *)bits : (const void *)payload))) {
             return MFM_E_INVAL;
         }
         uint64_t to = 0, ts = 0;
         for (uint64_t r = 0; r < n; r++) {
-            err |= mfm_runpocsag_check_run(runs[r], r ? &runs[r - 1] : nullptr, nr_channels, E, state);
+            err |= mfm_runpocsag_check_run(runs[r], r ? &runs[r - 1] : nullptr, nr_channels, E, state, words);
             to += runs[r].nr_out;
             ts += mfm_runpocsag_slots(runs[r].nr_out);
         }
@@ -1252,9 +1295,15 @@ int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_
         for (uint32_t k = 0; k < MFM_RUNPOCSAG_HIST_WORDS; k++) {
             seg[k] = st.tail[k]; /* zeros for a beginning run */
         }
-        for (uint32_t j = 0; j < run.nr_out; j++) {
-            if (payload[run.out_offset + j] < 0) {
-                seg[MFM_RUNPOCSAG_HIST_WORDS + (j >> 5)] |= 1u << (j & 31u);
+        if (words) { /* the slicer's word copy */
+            for (uint32_t k = 0; k < (run.nr_out + 31u) / 32u; k++) {
+                seg[MFM_RUNPOCSAG_HIST_WORDS + k] = bits[run.out_offset + k];
+            }
+        } else {
+            for (uint32_t j = 0; j < run.nr_out; j++) {
+                if (payload[run.out_offset + j] < 0) {
+                    seg[MFM_RUNPOCSAG_HIST_WORDS + (j >> 5)] |= 1u << (j & 31u);
+                }
             }
         }
         rp_host_walk(st, seg.data(), run, (uint32_t)r, out);
@@ -1276,6 +1325,31 @@ int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_
         memcpy(events, out.data(), out.size() * sizeof(mfm_runpocsag_event));
     }
     return MFM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                                const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events,
+                                uint32_t *flags)
+{
+    return rp_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, payload, nullptr, false, totals, events, max_out,
+                        nr_events, flags);
+}
+
+int mfm_hosttwin_runpocsag_call_bits(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                     struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const uint32_t *bits,
+                                     uint32_t polarity, const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out,
+                                     size_t *nr_events, uint32_t *flags)
+{
+    if (polarity != MFM_BITS_NEG) {
+        return rp_fail(MFM_E_INVAL, "the burst POCSAG stage needs MFM_BITS_NEG bits (bit = sample < 0)");
+    }
+    return rp_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, nullptr, bits, true, totals, events, max_out,
+                        nr_events, flags);
 }
 
 } /* extern "C" */

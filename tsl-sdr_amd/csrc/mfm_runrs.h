@@ -85,4 +85,18 @@ __host__ __device__ inline int16_t mfm_runrs_sample(const int16_t *pend, uint32_
     return invert ? (int16_t)(-s) : s;
 }
 
+/* ---- the bits form (mfm_runrs_process_bits_device): one predicate bit per output in the place of the int16 ---- */
+
+/* words a run of nr_out outputs owns in the bits payload: output j is bit j % 32 of word out_offset + j / 32 */
+__host__ __device__ inline uint32_t mfm_runrs_bit_words(uint32_t nr_out)
+{
+    return (nr_out + 31u) / 32u;
+}
+
+/* the predicate of the Q14-rounded output: sample < 0 (MFM_BITS_NEG) or sample > 0 (MFM_BITS_POS) */
+__host__ __device__ inline bool mfm_runrs_bit(int16_t y, uint32_t polarity)
+{
+    return polarity == MFM_BITS_NEG ? y < 0 : y > 0;
+}
+
 #endif /* MFM_RUNRS_H */

@@ -27,6 +27,15 @@
  *                    when the call raised a flag, copies its state over.  The buffers are used in turn, so the FIR kernel
  *                    and this one read the old state while the new one is written.
  *
+ * The bodies of the scan and the FIR kernel are in mfm_runrs_kernels.h, with the form as a template parameter; this file holds
+ * their PCM instances, mfm_run_bits.hip the bits form's (rrb_scan_kernel, rrb_fir_kernel), so neither form pays for the other.
+ * The bits form (mfm_runrs_process_bits_device) is the same four kernels with the store replaced: the scan also scans the
+ * runs' word counts (mfm_runrs_bit_words) into out_offset, and the FIR kernel ballots the predicate of the rounded output.
+ * A thread's output u is tid + 256 u, so wave w holds outputs 256 u + 64 w .. + 63 of the workgroup: one ballot is two
+ * finished words of the run's bit payload, which lane 0 stores.  Workgroup bases are multiples of 1024 outputs and every
+ * run's bits start on a word, so no word is shared between workgroups or runs; lanes past the run's end contribute 0,
+ * which is what zeroes the tail of its last word.
+ *
  * Nothing is floating point and nothing goes through an atomic.
  */
 #include <hip/hip_runtime.h>
@@ -42,19 +51,16 @@ extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(con
 #include "mfm_numerics.h"
 #include "mfm_rs_plan.h"
 #include "mfm_runrs.h"
+#include "mfm_runrs_kernels.h"
+
+/* the bits form's scan and FIR kernels (mfm_run_bits.hip), queued on s between the plan and the state kernel */
+extern "C" __attribute__((visibility("hidden"))) int mfm_internal_runrs_bits_launch(const void *call, uint32_t np, uint32_t max_blocks,
+                                                                                   uint32_t lds_bytes, hipStream_t s);
 
 namespace {
 
-constexpr uint32_t RR_NT = 256, RR_OPT = 4, RR_OPB = RR_NT * RR_OPT; /* FIR kernel: threads, outputs per thread / per workgroup */
-constexpr uint32_t RR_SCAN_THREADS = 1024;
-constexpr uint32_t RR_NONE = 0xffffffffu;                            /* d_chan_last: the channel has no run in this call */
-constexpr uint32_t RR_T_RUNS = 0, RR_T_ELEMS = 1, RR_T_OVERFLOW = 2, RR_T_GATE = 3; /* d_totals[], ours and the gate's */
 constexpr uint32_t RR_MAX_RATIO_TERM = 1u << 20;                     /* I and D at most: 1024 D + I stays far below 2^32 */
 constexpr uint64_t RR_MAX_OUT = 1ull << 31;                          /* output elements per call at most */
-
-struct RrPlan { /* what the plan pass found for a run and the FIR and state kernels need again */
-    uint32_t p0, pending;
-};
 
 /* everything create derives from the configuration and the taps, without a device */
 struct RrGeom {
@@ -152,39 +158,6 @@ int rr_geometry(const mfm_runrs_config &cfg, const int16_t *coeffs, size_t nr_co
     return MFM_OK;
 }
 
-struct RrCall {
-    const mfm_gate_run *gruns;
-    const int16_t *gpayload;
-    const uint64_t *gtotals;
-    const mfm_runrs_state *chan_old;
-    mfm_runrs_state *chan_new;
-    const int16_t *pend_old; /* [C][pend_stride] */
-    int16_t *pend_new;
-    const int16_t *phase;    /* [I][plen] */
-    mfm_runrs_run *runs;
-    RrPlan *plan;
-    uint32_t *nblk;          /* [cap_runs] workgroups per run */
-    uint32_t *blk_base;      /* [cap_runs + 1] their exclusive scan */
-    uint32_t *bad;           /* [cap_runs] */
-    uint32_t *chan_last;     /* [C] */
-    uint32_t *ctl;           /* [0] workgroups of the FIR kernel, [1] runs */
-    uint64_t *totals;
-    int16_t *y;
-    uint64_t cap_runs, cap_elems, out_cap;
-    uint32_t C, W, I, D, plen, pend_stride, invert, coef_bytes;
-};
-
-/* 1 / 2 when the gate's totals say that nothing may be read: its own flags, or more than this object was made for */
-__device__ __forceinline__ bool rr_refused(const RrCall &A, uint64_t &over, uint64_t &gate)
-{
-    over = A.gtotals[RR_T_OVERFLOW] ? MFM_RUNRS_OVER_GATE : 0u;
-    gate = A.gtotals[RR_T_GATE] ? MFM_RUNRS_GATE_OUT_OF_STEP : 0u;
-    if (!over && !gate && (A.gtotals[RR_T_RUNS] > A.cap_runs || A.gtotals[RR_T_ELEMS] > A.cap_elems)) {
-        over = MFM_RUNRS_OVER_OWN;
-    }
-    return over || gate;
-}
-
 __global__ __launch_bounds__(256) void rr_plan_kernel(const RrCall A)
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -222,214 +195,15 @@ __global__ __launch_bounds__(256) void rr_plan_kernel(const RrCall A)
     }
 }
 
-/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
-__device__ __forceinline__ uint64_t rr_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
-        if (lane >= (uint32_t)o) {
-            inc += ((uint64_t)hi << 32) | lo;
-        }
-    }
-    if (lane == 63) {
-        lds[wave] = inc;
-    }
-    __syncthreads();
-    uint64_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < RR_SCAN_THREADS / 64; i++) {
-        const uint64_t t = lds[i];
-        base += i < wave ? t : 0u;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_kernel(const RrCall A)
 {
-    __shared__ uint64_t lds[RR_SCAN_THREADS / 64];
-    uint64_t over, gate;
-    if (rr_refused(A, over, gate)) {
-        if (threadIdx.x == 0) {
-            A.totals[RR_T_RUNS] = 0;
-            A.totals[RR_T_ELEMS] = 0;
-            A.totals[RR_T_OVERFLOW] = over;
-            A.totals[RR_T_GATE] = gate;
-            A.ctl[0] = 0;
-            A.ctl[1] = 0;
-        }
-        return;
-    }
-    const uint64_t n = A.gtotals[RR_T_RUNS]; /* <= cap_runs < 2^32 */
-    const uint64_t per = (n + RR_SCAN_THREADS - 1) / RR_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
-    uint64_t so = 0, sb = 0;
-    uint32_t sw = 0;
-#pragma unroll 1
-    for (uint64_t r = r0; r < r1; r++) {
-        so += A.runs[r].nr_out;
-        sb += A.nblk[r];
-        sw |= A.bad[r];
-    }
-    /* the workgroup counts ride in the scan of the outputs: a run has at most nr_out / 1024 + 1 of them, so their sum over
-     * fewer than 2^31 runs of fewer than 2^31 outputs stays below 2^32, and the outputs' sum below 2^62 */
-    uint64_t to, tb;
-    uint64_t bo = rr_block_scan(so, lds, &to);
-    uint64_t bb = rr_block_scan(sb, lds, &tb);
-    /* run lists that are not a gate's (overlapping payload ranges) could ask for more than the output holds */
-    const bool wrong = __syncthreads_or(sw != 0) != 0 || to > A.out_cap;
-#pragma unroll 1
-    for (uint64_t r = r0; r < r1; r++) {
-        A.runs[r].out_offset = bo;
-        A.blk_base[r] = (uint32_t)bb;
-        bo += A.runs[r].nr_out;
-        bb += A.nblk[r];
-    }
-    if (threadIdx.x == 0) {
-        A.blk_base[n] = (uint32_t)tb;
-        A.totals[RR_T_RUNS] = wrong ? 0u : n;
-        A.totals[RR_T_ELEMS] = wrong ? 0u : to;
-        A.totals[RR_T_OVERFLOW] = 0;
-        A.totals[RR_T_GATE] = wrong ? MFM_RUNRS_GATE_BAD_RUNS : 0u;
-        A.ctl[0] = wrong ? 0u : (uint32_t)tb;
-        A.ctl[1] = wrong ? 0u : (uint32_t)n;
-    }
+    rr_scan_body<false>(A);
 }
 
-/* eight samples as one 16-byte access */
-struct __attribute__((aligned(16))) rr_x8 {
-    uint32_t d[4];
-};
-
-__device__ __forceinline__ uint32_t rr_neg2(uint32_t w) /* both int16 halves negated on int16 storage */
-{
-    return ((0u - (w & 0xffffu)) & 0xffffu) | ((0u - (w >> 16)) << 16);
-}
-
-/* NP > 0: coefficient pairs of the thread's phase in registers, NP = pairs per phase rounded up to a multiple of 4 (the
- * padding pairs are zero); NP = 0: pairs read from LDS, any phase length */
 template <int NP>
 __global__ __launch_bounds__(RR_NT) void rr_fir_kernel(const RrCall A)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t rr_smem[];
-    const uint32_t b = blockIdx.x, tid = threadIdx.x;
-    if (b >= A.ctl[0]) { /* surplus workgroups: the launch is sized from the capacity */
-        return;
-    }
-    /* the run of workgroup b: the last r with blk_base[r] <= b (runs without output have no workgroup) */
-    uint32_t lo = 0, hi = A.ctl[1];
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (A.blk_base[mid] <= b) {
-            lo = mid;
-        } else {
-            hi = mid;
-        }
-    }
-    const uint32_t r = lo;
-    const mfm_gate_run g = A.gruns[r];
-    const RrPlan P = A.plan[r];
-    const uint32_t n_out = A.runs[r].nr_out, c = A.runs[r].channel;
-    const uint64_t y0 = A.runs[r].out_offset;
-    const uint32_t j0 = (b - A.blk_base[r]) * RR_OPB;
-    const uint32_t cnt = n_out - j0 < RR_OPB ? n_out - j0 : RR_OPB;
-    const uint64_t nsamp = (uint64_t)g.nr_windows * A.W;
-    const int16_t *run = A.gpayload + g.payload_offset;
-    const int16_t *pend = A.pend_old + (size_t)c * A.pend_stride;
-    const bool invert = A.invert != 0;
-
-    uint32_t *ph_s = reinterpret_cast<uint32_t *>(rr_smem); /* [I][plen / 2] coefficient pairs */
-    const uint32_t npairs = A.plen / 2u;                    /* plen is a multiple of 4 */
-    int16_t *x_s = reinterpret_cast<int16_t *>(rr_smem + A.coef_bytes);
-    /* filter/polyphase_fir.c:206-211 unrolled to output j of the run: position (p0 + j D) / I, phase (p0 + j D) % I.  One
-     * 64-bit division per workgroup; within it everything is relative and fits 32 bits (1024 D + I < 2^31) */
-    const uint64_t t0 = P.p0 + (uint64_t)j0 * A.D;
-    const uint64_t pos0 = t0 / A.I;
-    const uint32_t ph0 = (uint32_t)(t0 - pos0 * A.I);
-    /* x_s[0] is the sample `adj` in front of position pos0, where the payload is 16-byte aligned */
-    const int64_t e0 = (int64_t)pos0 - (int64_t)P.pending; /* position pos0 as an index into the run's samples */
-    const uint32_t adj = (uint32_t)((reinterpret_cast<uintptr_t>(run) / 2u + (uint64_t)e0) & 7u);
-    const uint32_t last_rel = (ph0 + (cnt - 1u) * A.D) / A.I;
-    const uint32_t nwin = (adj + last_rel + A.plen + 16u + 7u) & ~7u; /* <= x_cap (rr_geometry) */
-    for (uint32_t i = tid; i < A.I * npairs; i += RR_NT) {
-        ph_s[i] = reinterpret_cast<const uint32_t *>(A.phase)[i];
-    }
-    for (uint32_t k = tid; k < nwin / 8u; k += RR_NT) {
-        const int64_t e = e0 - (int64_t)adj + 8 * (int64_t)k;
-        if (e >= 0 && (uint64_t)e + 8u <= nsamp) {
-            rr_x8 w = *reinterpret_cast<const rr_x8 *>(run + e);
-            if (invert) {
-                w.d[0] = rr_neg2(w.d[0]);
-                w.d[1] = rr_neg2(w.d[1]);
-                w.d[2] = rr_neg2(w.d[2]);
-                w.d[3] = rr_neg2(w.d[3]);
-            }
-            *reinterpret_cast<rr_x8 *>(x_s + 8u * k) = w;
-        } else {
-#pragma unroll
-            for (uint32_t i = 0; i < 8; i++) {
-                x_s[8u * k + i] = mfm_runrs_sample(pend, P.pending, run, nsamp, e + (int64_t)P.pending + i, invert);
-            }
-        }
-    }
-    __syncthreads();
-    const uint32_t *x32 = reinterpret_cast<const uint32_t *>(x_s);
-
-    /* one division per thread: its outputs are RR_NT apart, so position and phase advance by constants */
-    const uint32_t t_first = ph0 + tid * A.D;
-    uint32_t pos = adj + t_first / A.I, ph = t_first % A.I;
-    const uint32_t step_pos = (RR_NT * A.D) / A.I, step_ph = (RR_NT * A.D) % A.I;
-    constexpr bool REGCOEF = NP > 0;
-    uint32_t cw[REGCOEF ? NP : 1];
-    if (REGCOEF) {
-        /* 256 D is a multiple of I: outputs tid, tid + 256, ... of this workgroup have the same phase */
-#pragma unroll
-        for (uint32_t i = 0; i < (uint32_t)NP; i++) {
-            cw[i] = i < npairs ? ph_s[ph * npairs + i] : 0u;
-        }
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < RR_OPT; u++) {
-        const uint32_t j = tid + u * RR_NT;
-        if (j >= cnt) {
-            break;
-        }
-        const uint32_t *xw = x32 + (pos >> 1);
-        const uint32_t sh = (pos & 1u) * 16u;
-        int32_t acc = 0; /* filter/utils.c:94-103, int32 wrap-around */
-        uint32_t lo2 = xw[0];
-        if (REGCOEF) {
-#pragma unroll
-            for (uint32_t i = 0; i < (uint32_t)NP; i++) {
-                const uint32_t hi2 = xw[i + 1];
-                const uint32_t pr = __builtin_amdgcn_alignbit(hi2, lo2, sh); /* samples pos + 2i, pos + 2i + 1 */
-                asm("v_dot2_i32_i16 %0, %1, %2, %0" : "+v"(acc) : "v"(pr), "v"(cw[i]));
-                lo2 = hi2;
-            }
-        } else {
-            const uint32_t *cp = ph_s + ph * npairs;
-            for (uint32_t i = 0; i < npairs; i++) {
-                const uint32_t hi2 = xw[i + 1];
-                const uint32_t pr = __builtin_amdgcn_alignbit(hi2, lo2, sh);
-                asm("v_dot2_i32_i16 %0, %1, %2, %0" : "+v"(acc) : "v"(pr), "v"(cp[i]));
-                lo2 = hi2;
-            }
-        }
-        asm volatile("s_nop 2" : "+v"(acc)); /* a DOT result needs 3 wait states before other VALU code reads it */
-        A.y[y0 + j0 + j] = (int16_t)mfm_r14_wide(acc); /* utils.c:112 */
-        pos += step_pos;
-        ph += step_ph;
-        if (ph >= A.I) {
-            ph -= A.I;
-            pos += 1u;
-        }
-    }
+    rr_fir_body<NP, false>(A);
 }
 
 __global__ __launch_bounds__(64) void rr_state_kernel(const RrCall A)
@@ -507,9 +281,98 @@ struct mfm_runrs {
     uint64_t *d_totals = nullptr;
     mfm_runrs_run *d_runs = nullptr;
     int16_t *d_out = nullptr;
+    uint32_t *d_bits = nullptr; /* the bits form's payload, bits_cap words */
+    uint64_t bits_cap = 0;
+    uint32_t last_polarity = 0; /* of the last call: 0 = the PCM form */
     hipStream_t last_stream = nullptr;
     bool have_call = false;
 };
+
+namespace {
+
+void rr_launch_fir(const RrGeom &g, const RrCall &A, hipStream_t s)
+{
+    const dim3 grid((uint32_t)g.max_blocks);
+    switch (g.np / 4u) {
+    case 1: hipLaunchKernelGGL((rr_fir_kernel<4>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    case 2: hipLaunchKernelGGL((rr_fir_kernel<8>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    case 3: hipLaunchKernelGGL((rr_fir_kernel<12>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    case 4: hipLaunchKernelGGL((rr_fir_kernel<16>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    case 5: hipLaunchKernelGGL((rr_fir_kernel<20>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    case 6: hipLaunchKernelGGL((rr_fir_kernel<24>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    case 7: hipLaunchKernelGGL((rr_fir_kernel<28>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    case 8: hipLaunchKernelGGL((rr_fir_kernel<32>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    default: hipLaunchKernelGGL((rr_fir_kernel<0>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
+    }
+}
+
+/* one call in either form: polarity 0 is the PCM form */
+int rr_process(mfm_runrs *rr, const mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals, uint32_t polarity, void *stream)
+{
+    if (!rr || !d_runs || !d_payload || !d_totals) {
+        return MFM_E_INVAL;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RR_TRY(hipSetDevice(rr->cfg.device));
+    if (rr->have_call && rr->last_stream != s) {
+        RR_TRY(hipStreamSynchronize(rr->last_stream)); /* state lives on the device; keep calls ordered */
+    }
+    const RrGeom &g = rr->g;
+    const uint32_t cur = rr->cur;
+    const bool bits = polarity != 0;
+    const RrCall A{ d_runs,      d_payload,       d_totals,  rr->d_chan[cur], rr->d_chan[cur ^ 1u], rr->d_pend[cur], rr->d_pend[cur ^ 1u],
+                    rr->d_phase, rr->d_runs,      rr->d_plan, rr->d_nblk,     rr->d_blk_base,       rr->d_bad,       rr->d_chan_last,
+                    rr->d_ctl,   rr->d_totals,    rr->d_out, g.cap_runs,      g.cap_elems,          g.out_cap,       g.C,
+                    g.W,         g.I,             g.D,       g.plen,          rr->pend_stride,      rr->cfg.invert,  g.coef_bytes,
+                    rr->d_bits,  polarity };
+    if (g.cap_runs) {
+        hipLaunchKernelGGL(rr_plan_kernel, dim3((uint32_t)((g.cap_runs + 255u) / 256u)), dim3(256), 0, s, A);
+        RR_TRY(hipGetLastError());
+    }
+    if (bits) {
+        if (mfm_internal_runrs_bits_launch(&A, g.np, (uint32_t)g.max_blocks, g.lds_bytes, s) != MFM_OK) {
+            RR_TRY(hipGetLastError());
+            return MFM_E_DEVICE;
+        }
+    } else {
+        hipLaunchKernelGGL(rr_scan_kernel, dim3(1), dim3(RR_SCAN_THREADS), 0, s, A);
+        RR_TRY(hipGetLastError());
+        if (g.max_blocks) {
+            rr_launch_fir(g, A, s);
+            RR_TRY(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(rr_state_kernel, dim3(g.C), dim3(64), 0, s, A);
+    RR_TRY(hipGetLastError());
+    rr->cur ^= 1u;
+    rr->last_stream = s;
+    rr->have_call = true;
+    rr->last_polarity = polarity;
+    return MFM_OK;
+}
+
+/* the message of a refused call, from its totals (NULL: the call was not refused) */
+const char *rr_refusal(const uint64_t *t)
+{
+    if (t[RR_T_GATE] & MFM_RUNRS_GATE_OUT_OF_STEP) {
+        return "the gate's call was out of step with its level stage";
+    }
+    if (t[RR_T_GATE]) {
+        return "the run list is not a gate's: a run names a channel or a payload range that does not exist";
+    }
+    if (t[RR_T_OVERFLOW] & MFM_RUNRS_OVER_GATE) {
+        return "the gate's call overflowed its max_open_windows";
+    }
+    if (t[RR_T_OVERFLOW]) {
+        return "the gate's call exceeds max_windows or max_runs";
+    }
+    return nullptr;
+}
+
+constexpr const char *RR_LAST_WAS_BITS = "the last call was mfm_runrs_process_bits_device: its result is read with mfm_runrs_fetch_bits or mfm_runrs_bits_view";
+constexpr const char *RR_LAST_WAS_PCM = "the last call was not mfm_runrs_process_bits_device: its result is read with mfm_runrs_fetch or mfm_runrs_device_view";
+
+} /* namespace */
 
 extern "C" {
 
@@ -565,6 +428,8 @@ int mfm_runrs_create(struct mfm_runrs **prr, const struct mfm_runrs_config *cfg,
     RR_TRY(hipMemset(rr->d_totals, 0, 4 * 8));
     RR_TRY(hipMalloc(&rr->d_runs, nruns * sizeof(mfm_runrs_run)));
     RR_TRY(hipMalloc(&rr->d_out, nout * 2));
+    rr->bits_cap = g.out_cap / 32u + g.cap_runs; /* a run of n outputs owns n / 32 words and at most one more */
+    RR_TRY(hipMalloc(&rr->d_bits, (size_t)(rr->bits_cap ? rr->bits_cap : 1) * 4));
     RR_TRY(hipDeviceSynchronize());
     return MFM_OK;
 }
@@ -591,6 +456,7 @@ void mfm_runrs_destroy(struct mfm_runrs **prr)
     (void)hipFree(rr->d_totals);
     (void)hipFree(rr->d_runs);
     (void)hipFree(rr->d_out);
+    (void)hipFree(rr->d_bits);
     delete rr;
     *prr = nullptr;
 }
@@ -598,47 +464,16 @@ void mfm_runrs_destroy(struct mfm_runrs **prr)
 int mfm_runrs_process_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
                              void *stream)
 {
-    if (!rr || !d_runs || !d_payload || !d_totals) {
-        return MFM_E_INVAL;
+    return rr_process(rr, d_runs, d_payload, d_totals, 0, stream);
+}
+
+int mfm_runrs_process_bits_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload,
+                                  const uint64_t *d_totals, uint32_t polarity, void *stream)
+{
+    if (polarity != MFM_BITS_NEG && polarity != MFM_BITS_POS) {
+        return rr_fail(MFM_E_INVAL, "polarity must be MFM_BITS_NEG or MFM_BITS_POS");
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    RR_TRY(hipSetDevice(rr->cfg.device));
-    if (rr->have_call && rr->last_stream != s) {
-        RR_TRY(hipStreamSynchronize(rr->last_stream)); /* state lives on the device; keep calls ordered */
-    }
-    const RrGeom &g = rr->g;
-    const uint32_t cur = rr->cur;
-    const RrCall A{ d_runs,      d_payload,       d_totals,  rr->d_chan[cur], rr->d_chan[cur ^ 1u], rr->d_pend[cur], rr->d_pend[cur ^ 1u],
-                    rr->d_phase, rr->d_runs,      rr->d_plan, rr->d_nblk,     rr->d_blk_base,       rr->d_bad,       rr->d_chan_last,
-                    rr->d_ctl,   rr->d_totals,    rr->d_out, g.cap_runs,      g.cap_elems,          g.out_cap,       g.C,
-                    g.W,         g.I,             g.D,       g.plen,          rr->pend_stride,      rr->cfg.invert,  g.coef_bytes };
-    if (g.cap_runs) {
-        hipLaunchKernelGGL(rr_plan_kernel, dim3((uint32_t)((g.cap_runs + 255u) / 256u)), dim3(256), 0, s, A);
-        RR_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(rr_scan_kernel, dim3(1), dim3(RR_SCAN_THREADS), 0, s, A);
-    RR_TRY(hipGetLastError());
-    if (g.max_blocks) {
-        const dim3 grid((uint32_t)g.max_blocks);
-        switch (g.np / 4u) {
-        case 1: hipLaunchKernelGGL((rr_fir_kernel<4>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        case 2: hipLaunchKernelGGL((rr_fir_kernel<8>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        case 3: hipLaunchKernelGGL((rr_fir_kernel<12>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        case 4: hipLaunchKernelGGL((rr_fir_kernel<16>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        case 5: hipLaunchKernelGGL((rr_fir_kernel<20>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        case 6: hipLaunchKernelGGL((rr_fir_kernel<24>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        case 7: hipLaunchKernelGGL((rr_fir_kernel<28>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        case 8: hipLaunchKernelGGL((rr_fir_kernel<32>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        default: hipLaunchKernelGGL((rr_fir_kernel<0>), grid, dim3(RR_NT), g.lds_bytes, s, A); break;
-        }
-        RR_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(rr_state_kernel, dim3(g.C), dim3(64), 0, s, A);
-    RR_TRY(hipGetLastError());
-    rr->cur ^= 1u;
-    rr->last_stream = s;
-    rr->have_call = true;
-    return MFM_OK;
+    return rr_process(rr, d_runs, d_payload, d_totals, polarity, stream);
 }
 
 int mfm_runrs_fetch(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
@@ -652,23 +487,17 @@ int mfm_runrs_fetch(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max
     if (!rr->have_call) {
         return MFM_OK;
     }
+    if (rr->last_polarity) {
+        return rr_fail(MFM_E_STATE, RR_LAST_WAS_BITS);
+    }
     RR_TRY(hipSetDevice(rr->cfg.device));
     RR_TRY(hipStreamSynchronize(rr->last_stream));
     uint64_t t[4];
     RR_TRY(hipMemcpy(t, rr->d_totals, sizeof(t), hipMemcpyDeviceToHost));
     *nr_runs = (size_t)t[RR_T_RUNS];
     *nr_elems = (size_t)t[RR_T_ELEMS];
-    if (t[RR_T_GATE] & MFM_RUNRS_GATE_OUT_OF_STEP) {
-        return rr_fail(MFM_E_STATE, "the gate's call was out of step with its level stage");
-    }
-    if (t[RR_T_GATE]) {
-        return rr_fail(MFM_E_STATE, "the run list is not a gate's: a run names a channel or a payload range that does not exist");
-    }
-    if (t[RR_T_OVERFLOW] & MFM_RUNRS_OVER_GATE) {
-        return rr_fail(MFM_E_STATE, "the gate's call overflowed its max_open_windows");
-    }
-    if (t[RR_T_OVERFLOW]) {
-        return rr_fail(MFM_E_STATE, "the gate's call exceeds max_windows or max_runs");
+    if (const char *why = rr_refusal(t)) {
+        return rr_fail(MFM_E_STATE, why);
     }
     if (t[RR_T_RUNS] > max_runs || t[RR_T_ELEMS] > max_elems) {
         return MFM_E_NOMEM;
@@ -687,6 +516,9 @@ int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_r
     if (!rr) {
         return MFM_E_INVAL;
     }
+    if (rr->have_call && rr->last_polarity) {
+        return rr_fail(MFM_E_STATE, RR_LAST_WAS_BITS);
+    }
     if (d_runs) {
         *d_runs = rr->d_runs;
     }
@@ -695,6 +527,71 @@ int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_r
     }
     if (d_totals) {
         *d_totals = rr->d_totals;
+    }
+    return MFM_OK;
+}
+
+int mfm_runrs_fetch_bits(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, uint32_t *bits, size_t max_words,
+                         size_t *nr_words)
+{
+    if (!rr || !nr_runs || !nr_words || (!runs && max_runs) || (!bits && max_words)) {
+        return MFM_E_INVAL;
+    }
+    *nr_runs = 0;
+    *nr_words = 0;
+    if (!rr->have_call) {
+        return MFM_OK;
+    }
+    if (!rr->last_polarity) {
+        return rr_fail(MFM_E_STATE, RR_LAST_WAS_PCM);
+    }
+    RR_TRY(hipSetDevice(rr->cfg.device));
+    RR_TRY(hipStreamSynchronize(rr->last_stream));
+    uint64_t t[4];
+    RR_TRY(hipMemcpy(t, rr->d_totals, sizeof(t), hipMemcpyDeviceToHost));
+    *nr_runs = (size_t)t[RR_T_RUNS];
+    *nr_words = (size_t)t[RR_T_ELEMS];
+    if (const char *why = rr_refusal(t)) {
+        return rr_fail(MFM_E_STATE, why);
+    }
+    if (t[RR_T_RUNS] > max_runs || t[RR_T_ELEMS] > max_words) {
+        return MFM_E_NOMEM;
+    }
+    if (t[RR_T_RUNS]) {
+        RR_TRY(hipMemcpy(runs, rr->d_runs, (size_t)t[RR_T_RUNS] * sizeof(mfm_runrs_run), hipMemcpyDeviceToHost));
+    }
+    if (t[RR_T_ELEMS]) {
+        RR_TRY(hipMemcpy(bits, rr->d_bits, (size_t)t[RR_T_ELEMS] * 4, hipMemcpyDeviceToHost));
+    }
+    return MFM_OK;
+}
+
+int mfm_runrs_bits_view(struct mfm_runrs *rr, struct mfm_runrs_bits_view *view)
+{
+    if (!rr || !view) {
+        return MFM_E_INVAL;
+    }
+    if (!rr->have_call || !rr->last_polarity) {
+        return rr_fail(MFM_E_STATE, RR_LAST_WAS_PCM);
+    }
+    view->d_runs = rr->d_runs;
+    view->d_bits = rr->d_bits;
+    view->d_totals = rr->d_totals;
+    view->polarity = rr->last_polarity;
+    view->reserved = 0;
+    return MFM_OK;
+}
+
+int mfm_runrs_get_bits_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *max_words)
+{
+    if (!rr) {
+        return MFM_E_INVAL;
+    }
+    if (max_runs) {
+        *max_runs = (uint32_t)rr->g.cap_runs;
+    }
+    if (max_words) {
+        *max_words = rr->bits_cap;
     }
     return MFM_OK;
 }
@@ -734,14 +631,19 @@ int mfm_hosttwin_runrs_plan(uint32_t interpolate, uint32_t decimate, uint32_t pl
     return MFM_OK;
 }
 
-int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert,
-                            const int16_t *coeffs, size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending,
-                            const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload, size_t nr_gate_elems,
-                            struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
-                            size_t *nr_elems)
+} /* extern "C" */
+
+namespace {
+
+/* the host twin of one call in either form: polarity 0 writes int16 into `payload`, otherwise predicate words into `bits` and
+ * max_elems / *nr_elems count words */
+int rr_twin_call(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert, const int16_t *coeffs,
+                 size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending, const struct mfm_gate_run *gate_runs, size_t nr_gate_runs,
+                 const int16_t *gate_payload, size_t nr_gate_elems, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs,
+                 int16_t *payload, uint32_t *bits, uint32_t polarity, size_t max_elems, size_t *nr_elems)
 {
     if (!state || !pending || !nr_runs || !nr_elems || (!gate_runs && nr_gate_runs) || (!gate_payload && nr_gate_elems) || (!runs && max_runs) ||
-        (!payload && max_elems)) {
+        (!payload && !bits && max_elems)) {
         return MFM_E_INVAL;
     }
     mfm_runrs_config cfg{};
@@ -770,7 +672,7 @@ int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint3
         const bool first = r == 0 || gate_runs[r - 1].channel != gr.channel;
         start[r] = mfm_runrs_start_of(state[gr.channel], first, gr.first_window);
         step[r] = mfm_runrs_plan_run(I, D, plen, start[r].phase, start[r].pending, nsamp);
-        total += step[r].nr_out;
+        total += polarity ? mfm_runrs_bit_words((uint32_t)step[r].nr_out) : step[r].nr_out;
     }
     *nr_runs = nr_gate_runs;
     *nr_elems = (size_t)total;
@@ -799,9 +701,17 @@ int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint3
                 const int32_t x = mfm_runrs_sample(pend, start[r].pending, run, nsamp, (int64_t)(pos + k), invert != 0);
                 acc += (uint32_t)(x * (int32_t)tab.phase[(size_t)ph * plen + k]);
             }
-            payload[at + j] = (int16_t)mfm_r14_wide((int32_t)acc); /* utils.c:112 */
+            const int16_t y = (int16_t)mfm_r14_wide((int32_t)acc); /* utils.c:112 */
+            if (!polarity) {
+                payload[at + j] = y;
+            } else {
+                if (j % 32u == 0) {
+                    bits[at + j / 32u] = 0; /* the tail of the run's last word stays zero */
+                }
+                bits[at + j / 32u] |= (mfm_runrs_bit(y, polarity) ? 1u : 0u) << (j % 32u);
+            }
         }
-        at += step[r].nr_out;
+        at += polarity ? mfm_runrs_bit_words((uint32_t)step[r].nr_out) : step[r].nr_out;
     }
     std::vector<int16_t> keep(plen);
     for (size_t r = 0; r < nr_gate_runs; r++) {
@@ -822,6 +732,33 @@ int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint3
         st.pending = step[r].pending;
     }
     return MFM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert,
+                            const int16_t *coeffs, size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending,
+                            const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload, size_t nr_gate_elems,
+                            struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
+                            size_t *nr_elems)
+{
+    return rr_twin_call(nr_channels, window_samples, interpolate, decimate, invert, coeffs, nr_coeffs, state, pending, gate_runs, nr_gate_runs,
+                        gate_payload, nr_gate_elems, runs, max_runs, nr_runs, payload, nullptr, 0, max_elems, nr_elems);
+}
+
+int mfm_hosttwin_runrs_call_bits(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert,
+                                 uint32_t polarity, const int16_t *coeffs, size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending,
+                                 const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload,
+                                 size_t nr_gate_elems, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, uint32_t *bits,
+                                 size_t max_words, size_t *nr_words)
+{
+    if (polarity != MFM_BITS_NEG && polarity != MFM_BITS_POS) {
+        return rr_fail(MFM_E_INVAL, "polarity must be MFM_BITS_NEG or MFM_BITS_POS");
+    }
+    return rr_twin_call(nr_channels, window_samples, interpolate, decimate, invert, coeffs, nr_coeffs, state, pending, gate_runs, nr_gate_runs,
+                        gate_payload, nr_gate_elems, runs, max_runs, nr_runs, nullptr, bits, polarity, max_words, nr_words);
 }
 
 } /* extern "C" */
