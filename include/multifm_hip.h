@@ -628,6 +628,17 @@ int mfm_pocsag_process_bits_device(struct mfm_pocsag *p, const struct mfm_bits_v
  */
 int mfm_pocsag_fetch_events(struct mfm_pocsag *p, struct mfm_pocsag_event *out, size_t max_events,
                             size_t *nr_events);
+/*
+ * Resume a stream at a position (the stage behind an engine that mfm_engine_seek() put there): afterwards the object is
+ * what mfm_pocsag_create() with the same configuration returns, except that the next sample it consumes has index
+ * samples_before.  Events are those of a fresh object for the same input with samples_before added to `sample`; the
+ * detector reset lies at samples_before (the registers read zero-filled in front of it, as at sample 0).  Everything the
+ * stream so far left is forgotten: walker state, bit window, the last call's events.  Waits for the object's queued work;
+ * synchronous, not for the hot path.  MFM_E_INVAL with a message, the object unchanged: no object, or samples_before >=
+ * 2^62 (the walk forms int64 differences of positions).  mfm_flex_seek, mfm_ais_seek, mfm_level_seek and mfm_gate_seek
+ * below mean the same for their stages.
+ */
+int mfm_pocsag_seek(struct mfm_pocsag *p, uint64_t samples_before);
 
 /*
  * ---- Pager stage: FLEX sync 1 / frame information word / sync 2 / block de-interleave -------
@@ -713,6 +724,10 @@ int mfm_flex_process_host(struct mfm_flex *f, const int16_t *pcm, size_t in_stri
  */
 int mfm_flex_fetch_events(struct mfm_flex *f, struct mfm_flex_event *events, size_t max_events, size_t *nr_events,
                           struct mfm_flex_frame_words *frames, size_t max_frames, size_t *nr_frames);
+/* As mfm_pocsag_seek: samples_before is added to `sample` and, in FRAME events, to `sync_sample` (0 in the others at any
+ * position); the history ring is emptied and the BS1 registers read zero-filled in front of samples_before, so the search
+ * opens at samples_before + 310. */
+int mfm_flex_seek(struct mfm_flex *f, uint64_t samples_before);
 
 /*
  * ---- AIS stage: slicer / preamble detector / NRZI + HDLC bit recovery / FCS check ------------------------------
@@ -771,6 +786,8 @@ int mfm_ais_process_bits_device(struct mfm_ais *p, const struct mfm_bits_view *v
  * overflowed its device-side event list (only possible with a caller-chosen max_events).
  */
 int mfm_ais_fetch_events(struct mfm_ais *p, struct mfm_ais_event *out, size_t max_events, size_t *nr_events);
+/* As mfm_pocsag_seek: samples_before is added to `sample` and `start_sample`; a packet that was being received is dropped. */
+int mfm_ais_seek(struct mfm_ais *p, uint64_t samples_before);
 
 /*
  * ---- Level stage: per-channel signal level and squelch -----------------------------------------------------------
@@ -858,6 +875,10 @@ int mfm_level_fetch(struct mfm_level *p, struct mfm_level_record *out, size_t ma
  * stay valid (d_open: current) until the next call.  Any of the four may be NULL. */
 int mfm_level_device_view(struct mfm_level *p, const struct mfm_level_record **d_records, size_t *record_stride, size_t *nr_windows,
                           const uint32_t **d_open);
+/* As mfm_pocsag_seek: samples_before / W is added to `window`; the sums of an unfinished window, x[-1] and the squelch
+ * (closed again, d_open included) are forgotten, and the last call's records.  Also MFM_E_INVAL when samples_before is not a
+ * multiple of window_samples: no fresh stage stands inside a window. */
+int mfm_level_seek(struct mfm_level *p, uint64_t samples_before);
 
 /*
  * ---- Gate stage: only open windows of a channel leave the GPU -------------------------------------------------------
@@ -963,6 +984,11 @@ int mfm_gate_set_preroll(struct mfm_gate *g, uint32_t preroll_windows);
  * result is empty.  Afterwards mfm_gate_process_* and a second flush return MFM_E_STATE.
  */
 int mfm_gate_flush_device(struct mfm_gate *g, void *stream);
+/* As mfm_pocsag_seek: samples_before / W is added to `first_window`.  The gate keeps its preroll_windows; history and open
+ * bits are emptied, a flush is undone, and the windows in front of samples_before do not exist (pre-roll emits none of
+ * them, as it emits none in front of window 0).  Also MFM_E_INVAL when samples_before is not a multiple of window_samples.
+ * A gate that was put elsewhere than the level stage it reads raises out-of-step on fetch, as any wrong `.window` does. */
+int mfm_gate_seek(struct mfm_gate *g, uint64_t samples_before);
 
 /*
  * ---- Burst resampler: the gate's runs through the rational resampler, on the device ----------------------------------

@@ -310,6 +310,15 @@ def _check_channel(ora, sy, got_ev, got_fw, want_ev, tag):
             assert np.array_equal(got_fw[int(g["frame_index"])]["words"], w["words"]), tag
 
 
+def _frames(sy, coding, k, **kw):
+    """k frames of one coding, each phase with some of RECORDS"""
+    out = []
+    for i in range(k):
+        ph = {p: sy.flex_phase_words([dict(r) for r in RECORDS[: 3 + (i + p) % 5]]) for p in sy.FLEX_CODINGS[coding]["phases"]}
+        out.append(sy.flex_frame_levels(coding, (3 + i) % 16, (7 * coding + i) % 128, ph, **kw))
+    return out
+
+
 def _flex_channels(sy, n_frames=2, seed=0):
     """nine channels: the four codings clean and noisy, damaged sync words, a long 800 Hz tone in front of a frame
     (a BS1 run far longer than 256 samples), DC offsets, silence and noise"""
@@ -317,11 +326,7 @@ def _flex_channels(sy, n_frames=2, seed=0):
     chans = []
 
     def frames(coding, k, **kw):
-        out = []
-        for i in range(k):
-            ph = {p: sy.flex_phase_words([dict(r) for r in RECORDS[: 3 + (i + p) % 5]]) for p in sy.FLEX_CODINGS[coding]["phases"]}
-            out.append(sy.flex_frame_levels(coding, (3 + i) % 16, (7 * coding + i) % 128, ph, **kw))
-        return out
+        return _frames(sy, coding, k, **kw)
 
     chans.append(sy.flex_pcm(frames(0, n_frames), lead=333, trail=900, noise=300, seed=1))
     chans.append(sy.flex_pcm(frames(1, n_frames), lead=1, trail=900, noise=1500, seed=2))

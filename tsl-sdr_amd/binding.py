@@ -76,6 +76,7 @@ ABI_SYMBOLS = [
     "mfm_runrs_process_bits_device", "mfm_runrs_bits_view", "mfm_runrs_fetch_bits", "mfm_runrs_get_bits_capacity",
     "mfm_runais_process_bits_device", "mfm_runpocsag_process_bits_device",
     "mfm_hosttwin_runrs_call_bits", "mfm_hosttwin_runais_call_bits", "mfm_hosttwin_runpocsag_call_bits",
+    "mfm_pocsag_seek", "mfm_flex_seek", "mfm_ais_seek", "mfm_level_seek", "mfm_gate_seek",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -401,6 +402,8 @@ def load_library():
     lib.mfm_engine_flush.argtypes = [vp]
     lib.mfm_engine_replay.argtypes = [vp, C.c_size_t, C.c_size_t]
     lib.mfm_engine_seek.argtypes = [vp, C.c_uint64]
+    for name in ("mfm_pocsag_seek", "mfm_flex_seek", "mfm_ais_seek", "mfm_level_seek", "mfm_gate_seek"):
+        getattr(lib, name).argtypes = [vp, C.c_uint64]
     lib.mfm_host_alloc.argtypes = [C.c_size_t]
     lib.mfm_host_alloc.restype = vp
     lib.mfm_host_free.argtypes = [vp]
@@ -1232,6 +1235,12 @@ class Pocsag:
         if rc < 0:
             raise MfmError(rc, "mfm_pocsag_process_bits_device", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
 
+    def seek(self, samples_before):
+        """mfm_pocsag_seek: a fresh stage whose next sample has index samples_before (added to every event's sample)"""
+        rc = self.lib.mfm_pocsag_seek(self.h, int(samples_before))
+        if rc < 0:
+            raise MfmError(rc, "mfm_pocsag_seek", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+
     def fetch_events(self):
         cap = self.nr_channels * self.max_events
         out = np.zeros(cap, POCSAG_EVENT_DTYPE)
@@ -1286,6 +1295,12 @@ class Ais:
         if rc < 0:
             raise MfmError(rc, "mfm_ais_process_bits_device", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
 
+    def seek(self, samples_before):
+        """mfm_ais_seek: a fresh stage whose next sample has index samples_before (added to sample and start_sample)"""
+        rc = self.lib.mfm_ais_seek(self.h, int(samples_before))
+        if rc < 0:
+            raise MfmError(rc, "mfm_ais_seek", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+
     def fetch_events(self):
         cap = self.nr_channels * self.max_events
         out = np.zeros(cap, AIS_EVENT_DTYPE)
@@ -1337,6 +1352,12 @@ class Level:
         rc = self.lib.mfm_level_process_device(self.h, C.c_void_p(d_rows), in_stride, nr_in, C.c_void_p(stream or 0))
         if rc < 0:
             raise MfmError(rc, "mfm_level_process_device", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+
+    def seek(self, samples_before):
+        """mfm_level_seek: a fresh stage whose next sample has index samples_before, a multiple of window_samples"""
+        rc = self.lib.mfm_level_seek(self.h, int(samples_before))
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_seek", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
 
     def fetch(self, max_records=None):
         """the last call's records as a structured array [C][windows]; with max_records too small: MfmError(MFM_E_NOMEM)
@@ -1417,6 +1438,12 @@ class Gate:
         rc = self.lib.mfm_gate_flush_device(self.h, C.c_void_p(stream or 0))
         if rc < 0:
             self._raise(rc, "mfm_gate_flush_device")
+
+    def seek(self, samples_before):
+        """mfm_gate_seek: a fresh gate with the same pre-roll whose next sample has index samples_before, a multiple of window_samples"""
+        rc = self.lib.mfm_gate_seek(self.h, int(samples_before))
+        if rc < 0:
+            raise MfmError(rc, "mfm_gate_seek", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
 
     def close(self):
         if self.h:
@@ -2239,6 +2266,12 @@ class Flex:
         rc = self.lib.mfm_flex_process_device(self.h, C.c_void_p(d_pcm), in_stride, nr_in, C.c_void_p(stream or 0))
         if rc < 0:
             raise MfmError(rc, "mfm_flex_process_device", self.lib.mfm_strerror(rc).decode())
+
+    def seek(self, samples_before):
+        """mfm_flex_seek: a fresh stage whose next sample has index samples_before (added to sample and sync_sample)"""
+        rc = self.lib.mfm_flex_seek(self.h, int(samples_before))
+        if rc < 0:
+            raise MfmError(rc, "mfm_flex_seek", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
 
     def fetch_events(self):
         cap_e, cap_f = self.nr_channels * self.max_events, self.nr_channels * self.max_frames

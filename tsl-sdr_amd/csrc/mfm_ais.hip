@@ -651,6 +651,43 @@ int mfm_ais_process_host(struct mfm_ais *p, const int16_t *pcm, size_t in_stride
     return rc;
 }
 
+int mfm_ais_seek(struct mfm_ais *p, uint64_t samples_before)
+{
+    if (!p) {
+        mfm_internal_set_error("mfm_ais_seek: no object");
+        return MFM_E_INVAL;
+    }
+    if (samples_before >= (1ull << 62)) {
+        mfm_internal_set_error("mfm_ais_seek: samples_before must stay below 2^62 (the walk forms int64 differences of positions)");
+        return MFM_E_INVAL;
+    }
+    AI_TRY(hipSetDevice(p->cfg.device));
+    if (p->have_call) {
+        AI_TRY(hipStreamSynchronize(p->last_stream));
+    }
+    /* what create leaves, with the window's word 0 on the group that holds samples_before: the bits in front of it are
+     * zero, and the detector reset lies on it */
+    const uint32_t C = p->cfg.nr_channels;
+    std::vector<AiChanState> st(C);
+    memset(st.data(), 0, (size_t)C * sizeof(AiChanState));
+    for (uint32_t c = 0; c < C; c++) {
+        st[c].mode = AI_SEARCH;
+        st[c].pos = st[c].r = samples_before;
+    }
+    for (int i = 0; i < 2; i++) {
+        AI_TRY(hipMemset(p->buf[i].base, 0, ((size_t)2 * C * p->buf[i].BW + (size_t)C * p->buf[i].SW) * 4));
+    }
+    AI_TRY(hipMemcpy(p->d_st, st.data(), (size_t)C * sizeof(AiChanState), hipMemcpyHostToDevice));
+    AI_TRY(hipMemset(p->d_evcount, 0, (size_t)C * 4));
+    AI_TRY(hipDeviceSynchronize());
+    p->cur = 0;
+    p->ws = samples_before & ~(uint64_t)(AI_GROUP - 1);
+    p->total = samples_before;
+    p->last_stream = nullptr;
+    p->have_call = false;
+    return MFM_OK;
+}
+
 int mfm_ais_fetch_events(struct mfm_ais *p, struct mfm_ais_event *out, size_t max_events, size_t *nr_events)
 {
     if (!p || !nr_events || (!out && max_events)) {

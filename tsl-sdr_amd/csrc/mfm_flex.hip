@@ -692,6 +692,39 @@ int mfm_flex_process_host(struct mfm_flex *f, const int16_t *pcm, size_t in_stri
     return rc;
 }
 
+int mfm_flex_seek(struct mfm_flex *f, uint64_t samples_before)
+{
+    if (!f) {
+        mfm_internal_set_error("mfm_flex_seek: no object");
+        return MFM_E_INVAL;
+    }
+    if (samples_before >= (1ull << 62)) {
+        mfm_internal_set_error("mfm_flex_seek: samples_before must stay below 2^62 (the walk forms int64 differences of positions)");
+        return MFM_E_INVAL;
+    }
+    FX_TRY(hipSetDevice(f->cfg.device));
+    if (f->have_call) {
+        FX_TRY(hipStreamSynchronize(f->last_stream));
+    }
+    /* what create leaves: an empty ring, and the registers zero-filled in front of samples_before, so the search opens 310
+     * samples behind it and reads no match bit that a sample of the ring took part in */
+    const size_t C = f->cfg.nr_channels;
+    std::vector<FxState> st(C);
+    memset(st.data(), 0, C * sizeof(FxState));
+    for (size_t c = 0; c < C; c++) {
+        st[c].mode = FX_SEARCH;
+        st[c].p = samples_before + (FX_DEAD - 1);
+    }
+    FX_TRY(hipMemset(f->d_hist, 0, C * FX_HIST * sizeof(int16_t)));
+    FX_TRY(hipMemcpy(f->d_st, st.data(), C * sizeof(FxState), hipMemcpyHostToDevice));
+    FX_TRY(hipMemset(f->d_counts, 0, C * 2 * sizeof(uint32_t)));
+    FX_TRY(hipDeviceSynchronize());
+    f->total = samples_before;
+    f->last_stream = nullptr;
+    f->have_call = false;
+    return MFM_OK;
+}
+
 int mfm_flex_fetch_events(struct mfm_flex *f, struct mfm_flex_event *events, size_t max_events, size_t *nr_events,
                           struct mfm_flex_frame_words *frames, size_t max_frames, size_t *nr_frames)
 {

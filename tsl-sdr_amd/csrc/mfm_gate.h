@@ -131,7 +131,8 @@ __host__ __device__ inline bool mfm_gate_walk_step(mfm_gate_walk &w, uint64_t ma
  * S[e + P] of 64 candidates then lie in two words.
  */
 
-/* candidates below this one are windows with k < 0: they do not exist and never go out */
+/* candidates below this one are windows in front of the stream's first (k < 0; after mfm_gate_seek: in front of the window
+ * it names): they do not exist and never go out.  k0 and, below, K count from the stream's first window */
 __host__ __device__ inline uint32_t mfm_gate_pre_skip(uint64_t k0, uint32_t P)
 {
     return k0 < P ? P - (uint32_t)k0 : 0u;

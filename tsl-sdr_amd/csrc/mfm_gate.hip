@@ -69,6 +69,7 @@ struct mfm_gate {
     uint64_t cap_runs = 0;
     uint32_t log2g = 0, npieces = 1;
     uint64_t pos = 0;          /* samples per channel consumed so far */
+    uint64_t k_first = 0;      /* the stream's first window: 0, or where mfm_gate_seek put it; no window in front of it exists */
     uint32_t *d_cnt_open = nullptr, *d_cnt_runs = nullptr, *d_bad = nullptr, *d_base_runs = nullptr, *d_base_open = nullptr, *d_slot = nullptr;
     uint64_t *d_totals = nullptr;
     mfm_gate_run *d_runs = nullptr;
@@ -101,6 +102,7 @@ struct GtRecs {
     const mfm_level_record *rec;
     size_t rec_stride;
     uint64_t k0;    /* the call's first record */
+    uint64_t kf;    /* the stream's first window (mfm_gate::k_first) */
     uint32_t nrec;  /* records the call brings */
     uint32_t nemit; /* candidates: nrec, at a flush P */
     uint32_t P;
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(256) void gt_count_kernel(const GtRecs R, const uin
     }
     const mfm_level_record *rc = R.rec + (size_t)c * R.rec_stride;
     const uint64_t prev = bits_in[c];
-    const uint32_t skip = mfm_gate_pre_skip(R.k0, R.P);
+    const uint32_t skip = mfm_gate_pre_skip(R.k0 - R.kf, R.P);
     mfm_gate_walk w{};
     uint32_t wrong = 0;
     uint64_t lo = gt_word(R, rc, prev, 0, lane, wrong);
@@ -238,7 +240,7 @@ __global__ __launch_bounds__(256) void gt_runs_kernel(const GtRecs R, const uint
         return;
     }
     const uint64_t prev = bits_in[c];
-    const uint32_t skip = mfm_gate_pre_skip(R.k0, R.P);
+    const uint32_t skip = mfm_gate_pre_skip(R.k0 - R.kf, R.P);
     const uint32_t bo = base_open[c];
     mfm_gate_run *rr = runs + base_runs[c];
     mfm_gate_walk w{};
@@ -258,7 +260,7 @@ __global__ __launch_bounds__(256) void gt_runs_kernel(const GtRecs R, const uint
                 uint32_t rank, len;
                 bool whole;
                 mfm_gate_run_at(w, mask, starts, lane, cnt, last, rank, len, whole);
-                rr[rank].first_window = R.k0 + e0 + lane - R.P; /* an open candidate lies at or above skip: k >= 0 */
+                rr[rank].first_window = R.k0 + e0 + lane - R.P; /* an open candidate lies at or above skip: k >= kf */
                 rr[rank].payload_offset = (uint64_t)at * We;
                 rr[rank].channel = c;
                 if (whole) {
@@ -474,8 +476,8 @@ int gt_call(mfm_gate *g, const int16_t *d_rows, size_t in_stride, size_t nr_in, 
 {
     const uint32_t C = g->cfg.nr_channels, P = g->P, We = g->We;
     const uint32_t nemit = flush ? P : cut.nwin;
-    const uint32_t hlen0 = mfm_gate_hist_len(cut.k0, cut.r0, P, We);
-    const GtRecs R{ d_records, record_stride, cut.k0, cut.nwin, nemit, P, C };
+    const uint32_t hlen0 = mfm_gate_hist_len(cut.k0 - g->k_first, cut.r0, P, We);
+    const GtRecs R{ d_records, record_stride, cut.k0, g->k_first, cut.nwin, nemit, P, C };
     const int16_t *hin = g->d_hist[g->cur];
     hipLaunchKernelGGL(gt_count_kernel, dim3((C + 3) / 4), dim3(256), 0, s, R, g->d_bits[g->cur], g->d_bits[g->cur ^ 1u], g->d_cnt_open,
                        g->d_cnt_runs, g->d_bad);
@@ -497,7 +499,7 @@ int gt_call(mfm_gate *g, const int16_t *d_rows, size_t in_stride, size_t nr_in, 
     if (flush) {
         g->flushed = true; /* the history is of no more use; the unfinished window is dropped */
     } else if (nr_in) {    /* nr_in == 0 leaves the history as it is, and the bits: S[0 .. P - 1] is prev */
-        const uint32_t hlen1 = mfm_gate_hist_len(cut.k0 + cut.nwin, cut.r1, P, We);
+        const uint32_t hlen1 = mfm_gate_hist_len(cut.k0 + cut.nwin - g->k_first, cut.r1, P, We);
         if (hlen1) {
             hipLaunchKernelGGL(gt_hist_kernel, dim3((hlen1 + 255) / 256, C), dim3(256), 0, s, d_rows, in_stride, hin, g->d_hist[g->cur ^ 1u],
                                g->hist_stride, hlen0, hlen1, (uint32_t)nr_in * g->E);
@@ -628,6 +630,39 @@ int mfm_gate_set_preroll(struct mfm_gate *g, uint32_t preroll_windows)
     }
     GT_TRY(hipSetDevice(g->cfg.device));
     return gt_size_for(g, P);
+}
+
+int mfm_gate_seek(struct mfm_gate *g, uint64_t samples_before)
+{
+    if (!g) {
+        return gt_fail(MFM_E_INVAL, "mfm_gate_seek: no object");
+    }
+    if (samples_before >= (1ull << 62)) {
+        return gt_fail(MFM_E_INVAL, "mfm_gate_seek: samples_before must stay below 2^62");
+    }
+    if (samples_before % g->W) {
+        return gt_fail(MFM_E_INVAL, "mfm_gate_seek: samples_before must be a multiple of window_samples (no fresh stage stands inside a window)");
+    }
+    GT_TRY(hipSetDevice(g->cfg.device));
+    if (g->have_call) {
+        GT_TRY(hipStreamSynchronize(g->last_stream));
+    }
+    /* what create and mfm_gate_set_preroll(P) leave: history and open bits empty, no result to fetch; the windows in front
+     * of samples_before do not exist, as those in front of 0 do not in a fresh stream */
+    const uint32_t C = g->cfg.nr_channels;
+    for (int i = 0; i < 2; i++) {
+        GT_TRY(hipMemset(g->d_hist[i], 0, (size_t)C * g->hist_stride * 2));
+        GT_TRY(hipMemset(g->d_bits[i], 0, (size_t)C * 8));
+    }
+    GT_TRY(hipMemset(g->d_totals, 0, 4 * 8));
+    GT_TRY(hipDeviceSynchronize());
+    g->cur = 0;
+    g->pos = samples_before;
+    g->k_first = samples_before / g->W;
+    g->last_stream = nullptr;
+    g->have_call = false;
+    g->flushed = false;
+    return MFM_OK;
 }
 
 int mfm_gate_process_device(struct mfm_gate *g, const int16_t *d_rows, size_t in_stride, size_t nr_in, const struct mfm_level_record *d_records,

@@ -504,6 +504,32 @@ int mfm_level_process_host(struct mfm_level *p, const int16_t *rows, size_t in_s
     return rc;
 }
 
+int mfm_level_seek(struct mfm_level *p, uint64_t samples_before)
+{
+    if (!p) {
+        return lv_inval("mfm_level_seek: no object");
+    }
+    if (samples_before >= (1ull << 62)) {
+        return lv_inval("mfm_level_seek: samples_before must stay below 2^62");
+    }
+    if (samples_before % p->cfg.window_samples) {
+        return lv_inval("mfm_level_seek: samples_before must be a multiple of window_samples (no fresh stage stands inside a window)");
+    }
+    LV_TRY(hipSetDevice(p->cfg.device));
+    if (p->have_call) {
+        LV_TRY(hipStreamSynchronize(p->last_stream));
+    }
+    const uint32_t C = p->cfg.nr_channels;
+    LV_TRY(hipMemset(p->d_st, 0, (size_t)C * sizeof(LvChan))); /* as create: nothing summed, x[-1] = 0, closed */
+    LV_TRY(hipMemset(p->d_open, 0, (size_t)C * 4));
+    LV_TRY(hipDeviceSynchronize());
+    p->pos = samples_before;
+    p->last_nwin = 0;
+    p->last_stream = nullptr;
+    p->have_call = false;
+    return MFM_OK;
+}
+
 int mfm_level_fetch(struct mfm_level *p, struct mfm_level_record *out, size_t max_records, size_t *nr_windows)
 {
     if (!p || !nr_windows || (!out && max_records)) {

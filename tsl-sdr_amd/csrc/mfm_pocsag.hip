@@ -941,6 +941,43 @@ int mfm_pocsag_process_host(struct mfm_pocsag *p, const int16_t *pcm, size_t in_
     return rc;
 }
 
+int mfm_pocsag_seek(struct mfm_pocsag *p, uint64_t samples_before)
+{
+    if (!p) {
+        mfm_internal_set_error("mfm_pocsag_seek: no object");
+        return MFM_E_INVAL;
+    }
+    if (samples_before >= (1ull << 62)) {
+        mfm_internal_set_error("mfm_pocsag_seek: samples_before must stay below 2^62 (the walk forms int64 differences of positions)");
+        return MFM_E_INVAL;
+    }
+    PG_TRY(hipSetDevice(p->cfg.device));
+    if (p->have_call) {
+        PG_TRY(hipStreamSynchronize(p->last_stream));
+    }
+    /* what create leaves, with the window's word 0 on the group that holds samples_before: the bits in front of it are
+     * zero, and the detector reset lies on it, so the registers read zero-filled there as they do at sample 0 */
+    const uint32_t C = p->cfg.nr_channels;
+    std::vector<PgChanState> st(C);
+    memset(st.data(), 0, (size_t)C * sizeof(PgChanState));
+    for (uint32_t c = 0; c < C; c++) {
+        st[c].mode = PG_SEARCH;
+        st[c].pos = st[c].r = samples_before;
+    }
+    for (int i = 0; i < 2; i++) {
+        PG_TRY(hipMemset(p->buf[i].base, 0, ((size_t)4 * C * p->buf[i].BW + (size_t)C * p->buf[i].SW) * 4));
+    }
+    PG_TRY(hipMemcpy(p->d_st, st.data(), (size_t)C * sizeof(PgChanState), hipMemcpyHostToDevice));
+    PG_TRY(hipMemset(p->d_evcount, 0, (size_t)C * 4));
+    PG_TRY(hipDeviceSynchronize());
+    p->cur = 0;
+    p->ws = samples_before & ~(uint64_t)(PG_GROUP - 1);
+    p->total = samples_before;
+    p->last_stream = nullptr;
+    p->have_call = false;
+    return MFM_OK;
+}
+
 int mfm_pocsag_fetch_events(struct mfm_pocsag *p, struct mfm_pocsag_event *out, size_t max_events, size_t *nr_events)
 {
     if (!p || !nr_events || (!out && max_events)) {
