@@ -1008,9 +1008,20 @@ int mfm_gate_seek(struct mfm_gate *g, uint64_t samples_before);
  * produces no output, and its runs still appear, with nr_out = 0.
  *
  * State.  Per channel, on the device: the window number expected next, the phase, the outputs so far, the pending count
- * and plen pending samples.  A run continues its channel's stretch exactly when its first_window equals the expected
- * number; otherwise it resets the state and begins a new stretch.  Within one call only a channel's first run can continue
- * (the gate's runs within a call are maximal).  A channel without a run in a call keeps its state.
+ * and plen pending samples; with the DC blocker on, the blocker's x_(n-1), y_(n-1) and acc as well.  A run continues its
+ * channel's stretch exactly when its first_window equals the expected number; otherwise it resets the state and begins a new
+ * stretch.  Within one call only a channel's first run can continue (the gate's runs within a call are maximal).  A channel
+ * without a run in a call keeps its state.
+ *
+ * DC blocker (decoder -b, decoder/decoder.c:580-673: resample, then dc_blocker_apply).  Off at create; switched on with
+ * mfm_runrs_set_dc_block before the first call.  With it on, the outputs of a stretch are exactly what
+ * filter/dc_blocker.h:72-93 returns on a fresh struct dc_blocker - dc_blocker_init(pole): p = (int16)((1 - pole) * 16384),
+ * x_n_1 = y_n_1 = acc = 0 - applied to the stretch's resampled PCM in stretch order, that PCM being the concatenation of the
+ * outputs of the stretch's runs.  The arithmetic is the reference's int32 arithmetic, wrapping, with the truncating shift;
+ * the carried y_(n-1) is the unclipped value, the stored sample its low 16 bits.  The result does not depend on how the
+ * stream was cut into calls, and everything else in a call's result (run list, out_offset, first_out, nr_out, flags, totals,
+ * refusals) is as without the blocker.  A run with nr_out == 0 changes nothing: it still begins a stretch with zero state,
+ * or continues one and leaves the state as it was.
  *
  * Result.  It replaces the previous call's: one mfm_runrs_run per input run, in the gate's order; a dense int16 payload in
  * that order (out_offset ascending, no gaps); d_totals[4] = { runs, output elements, overflow, gate error }.  Order and
@@ -1021,9 +1032,9 @@ int mfm_gate_seek(struct mfm_gate *g, uint64_t samples_before);
  *               does not exist (not a gate's run list)
  *
  * Refusals at create (MFM_E_INVAL with a message, never a fallback): the stage takes PCM payloads only (a gate with
- * elems_per_sample == 1); it has no DC blocker, and its sign-bit output is an entry of its own (below), so `flags` must be
- * 0; a ratio whose walk steps past a phase (mfm_rs_plan.h's rule, as mfm_resampler_create); a coefficient image I * plen int16
- * that, with the input window of one workgroup, exceeds MFM_RUNRS_MAX_LDS_BYTES.
+ * elems_per_sample == 1); its DC blocker (mfm_runrs_set_dc_block) and its sign-bit output (below) are entries of their own,
+ * so `flags` must be 0; a ratio whose walk steps past a phase (mfm_rs_plan.h's rule, as mfm_resampler_create); a coefficient
+ * image I * plen int16 that, with the input window of one workgroup, exceeds MFM_RUNRS_MAX_LDS_BYTES.
  */
 #define MFM_RUNRS_MAX_LDS_BYTES 49152u /* coefficient image + one workgroup's input window */
 #define MFM_RUNRS_BEGINS 1u            /* mfm_runrs_run.flags bit 0: the run begins a stretch */
@@ -1085,6 +1096,18 @@ int mfm_runrs_device_view(struct mfm_runrs *rr, const struct mfm_runrs_run **d_r
 /* The capacities fixed at create, which a stage behind sizes itself from: the most runs and the most output elements one call
  * can produce (max_runs as given or its default; ((max_windows * W + max_runs * plen) * I) / D + max_runs). */
 int mfm_runrs_get_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *max_out_elems);
+/*
+ * The DC blocker of the rule above, one fresh blocker per stretch.  Valid only before the first process call (MFM_E_STATE
+ * with a message afterwards).  on == 0 switches it off (the pole is not read): the object then queues the launches and
+ * returns the bits of one never touched.  Otherwise the pole is converted as mfm_resampler_create converts dc_pole,
+ * p = (int16)((1 - pole) * 16384); a pole for which that is not defined (not a number, or a product outside int16) is
+ * MFM_E_INVAL with a message.  With the blocker on mfm_runrs_process_bits_device returns MFM_E_INVAL with a message and the
+ * state does not move, as mfm_resampler_process_bits_device does with dc_block: the blocker filters the PCM the predicate
+ * would be taken from.
+ */
+int mfm_runrs_set_dc_block(struct mfm_runrs *rr, uint32_t on, double pole);
+/* The setting: *on 0 / 1, *dc_p the Q14 (1 - pole) in use (0 when off).  Either may be NULL. */
+int mfm_runrs_get_dc_block(struct mfm_runrs *rr, uint32_t *on, int32_t *dc_p);
 
 /*
  * The bits form: the sign-bit path of the burst chain.  The burst AIS stage looks only at sample > 0 and the burst POCSAG
@@ -1646,6 +1669,20 @@ int mfm_hosttwin_runrs_call_bits(uint32_t nr_channels, uint32_t window_samples, 
                                  const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload,
                                  size_t nr_gate_elems, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, uint32_t *bits,
                                  size_t max_words, size_t *nr_words);
+/* the per-channel state of the burst resampler's DC blocker (filter/dc_blocker.h's fields), on the device and in the host
+ * twin: all zero at the start of a stream */
+struct mfm_runrs_dc_state {     /* 16 bytes */
+    int32_t x_n_1, y_n_1, acc;
+    uint32_t reserved;          /* 0 */
+};
+/* host twin of the DC blocker of a burst resampler with mfm_runrs_set_dc_block(rr, 1, pole), no device needed: applies the rule
+ * in place to the result of one mfm_hosttwin_runrs_call (runs, nr_runs, payload, nr_elems = its *nr_elems); dc [nr_channels] is
+ * updated in place.  It runs the inlines the kernel runs (csrc/mfm_runrs_dc.h).  MFM_E_INVAL with a message for a pole
+ * mfm_runrs_set_dc_block refuses and for a run list that is not a burst resampler's: a channel >= nr_channels or channels not
+ * ascending, a run with MFM_RUNRS_BEGINS clear that is not its channel's first, a range beyond nr_elems; on any error nothing
+ * is written, the state included. */
+int mfm_hosttwin_runrs_dc_call(uint32_t nr_channels, double pole, struct mfm_runrs_dc_state *dc, const struct mfm_runrs_run *runs,
+                               size_t nr_runs, int16_t *payload, size_t nr_elems);
 /* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream */
 struct mfm_runais_state {       /* 264 bytes */
     uint64_t outs;              /* outputs of the stretch so far */

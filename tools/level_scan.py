@@ -3,7 +3,8 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
-           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-ais | --gate-pocsag | --gate-flex]]]
+           [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-dc-pole POLE]
+           [--gate-ais | --gate-pocsag | --gate-flex]]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -34,6 +35,12 @@ samples and DIR/resampled.jsonl one line per run:
 
 (first_sample in samples of the channel at the input rate, first_out the index of the run's first output within its stretch,
 begins 1 on a stretch's first run, file_offset in bytes of the .rs.s16 file).
+
+--gate-dc-pole POLE (with --gate-resample; the decoder's -b -p POLE) switches on the burst resampler's DC blocker: every stretch's
+resampled samples go through a fresh DC blocker with that pole, on the device, before they are written or read by the stage
+behind - --gate-ais, --gate-pocsag and --gate-flex see the blocked PCM with no change of their own.  A receiver tuned off a
+carrier by more than the deviation needs it: the sign of the samples is all the AIS and POCSAG slicers look at.  Not together
+with --gate-bits: the blocker filters the PCM the sign bits would be taken from.
 
 --gate-ais (with --gate-resample) queues the burst AIS stage behind the burst resampler on the same stream, the flush call
 included: every stretch goes through a fresh AIS demodulator, and DIR/ais.jsonl gets one line per candidate packet:
@@ -89,7 +96,11 @@ P = 0 line of the same run, "gate_ms_over_p0" per mask: the cost of the pre-roll
 dilated mask lets through in the steady state (every call emits the last P windows of the call before it, from the history, and
 all but the last P of its own).  With --form pcm a last line ("runrs_stage") times the burst resampler (4/5, 81 taps) behind the
 gate for the three masks, alternating in the same process with mfm_resampler_process_device (MFM_RS_FORCE_DOT2) on the full rows:
-all-open over that plain resampler as a ratio with its standard error, all-closed as an absolute time.  A line behind it
+all-open over that plain resampler as a ratio with its standard error, all-closed as an absolute time.  The line after it
+("runrs_dc_stage") times, for the same masks and alternating in the same way, the burst resampler with its DC blocker on (pole
+0.999), the burst resampler without it and the plain resampler with dc_block on the full rows: the blocker's cost per mask as a
+difference with its standard error, and the burst form over the full-row form as a ratio (--bench-runrs prints these two lines
+alone, behind the engine launch that makes the rows).  A line behind it
 ("runais_stage"; --bench-runais prints that line alone, without the engine) times the burst chain burst resampler -> burst AIS
 stage on a gate's device view against the plain chain mfm_resampler -> mfm_ais on the full rows, 4/5 with 41 taps, for the same
 three masks and for two row sets of its own: idle (noise) and busy (synthesized AIS frames on every channel).  A last line
@@ -164,6 +175,8 @@ def scan(a):
         co = np.array([int(float(t) * 16384.0) for t in json.load(open(a.resample_taps))["lpfCoeffs"]], np.int16)  # decoder.c:530-533
         rr = pkg.RunResampler(len(chans), co, interp, decim_rs, a.window, max_in_samples=a.block // decim + 8,
                               preroll_windows=int(a.gate_preroll), device=a.device)
+        if a.gate_dc_pole is not None:
+            rr.set_dc_block(a.gate_dc_pole)
         rs_index = open(os.path.join(a.gate_out, "resampled.jsonl"), "w")
     ra, ais_index = None, None
     if a.gate_ais:
@@ -498,6 +511,13 @@ def bench(a):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / inner
 
+    if a.bench_runrs:   # the two lines of the burst resampler alone, on the same rows
+        pg.close()
+        bench_runrs(a, pkg, torch, rows, in_stride, nout, timed)
+        bench_runrs_dc(a, pkg, torch, rows, in_stride, nout, timed)
+        for o in (lv, eng):
+            o.close()
+        return
     variants = [("level", run_level), ("pocsag_call", run_pocsag)]
     for _, fn in variants:
         timed(fn, 3)
@@ -526,6 +546,7 @@ def bench(a):
         p0 = line if P == 0 else p0
     if not iq_form:
         bench_runrs(a, pkg, torch, rows, in_stride, nout, timed)
+        bench_runrs_dc(a, pkg, torch, rows, in_stride, nout, timed)
         bench_runais(a, pkg, torch)
         bench_runpocsag(a, pkg, torch)
         bench_runbits(a, pkg, torch)
@@ -617,13 +638,11 @@ def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P=0, p0=None
     return out
 
 
-def bench_runrs(a, pkg, torch, rows, in_stride, nout, timed):
-    """the burst resampler behind the gate, 4/5 with 81 taps, on whole windows of the PCM rows.  Per mask one gate call leaves its
-    runs and payload in place and the stage is timed on that device view over and over: from the second call on a run's
-    first_window is behind what its channel expects, so every call begins every stretch anew and does the same work.  The plain
-    resampler (v_dot2 form forced) on the full rows alternates with it in the same process, in rotating order."""
+def _runrs_bench_scene(a, pkg, torch, rows, in_stride, nout):
+    """what bench_runrs and bench_runrs_dc time on: 4/5 with 81 taps on whole windows of the PCM rows, and the level records of the
+    three masks (all closed, all open, a squelch at the median window energy) on the device"""
     b = pkg.binding
-    nch, W, I, D = a.bench_channels, a.window, 4, 5
+    nch, W = a.bench_channels, a.window
     nw = nout // W
     nb = nw * W
     taps = (np.hanning(81) * 0.2 * 16384.0).astype(np.int16)
@@ -645,6 +664,27 @@ def bench_runrs(a, pkg, torch, rows, in_stride, nout, timed):
         t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
         keep.append(t)
         recs[name] = (t.data_ptr(), nw)
+    return taps, nw, nb, masks, recs, (sq, keep)
+
+
+def _runrs_totals(pkg, rr):
+    """(runs, output samples) of the last call, from the totals alone: the payload stays on the device"""
+    try:
+        rr.fetch(max_runs=0, max_elems=0)
+        return 0, 0
+    except pkg.MfmError as err:
+        if err.code != pkg.binding.MFM_E_NOMEM:
+            raise
+        return err.needed
+
+
+def bench_runrs(a, pkg, torch, rows, in_stride, nout, timed):
+    """the burst resampler behind the gate, 4/5 with 81 taps, on whole windows of the PCM rows.  Per mask one gate call leaves its
+    runs and payload in place and the stage is timed on that device view over and over: from the second call on a run's
+    first_window is behind what its channel expects, so every call begins every stretch anew and does the same work.  The plain
+    resampler (v_dot2 form forced) on the full rows alternates with it in the same process, in rotating order."""
+    nch, W, I, D = a.bench_channels, a.window, 4, 5
+    taps, nw, nb, masks, recs, (sq, _keep) = _runrs_bench_scene(a, pkg, torch, rows, in_stride, nout)
     plain = pkg.Resampler(nch, taps, I, D, nb, device=0, force_dot2=True)
     rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=nout, device=0)
 
@@ -664,13 +704,7 @@ def bench_runrs(a, pkg, torch, rows, in_stride, nout, timed):
         variants = [("runrs", run_rr), ("plain", run_plain)]
         for _, fn in variants:
             timed(fn, 3)
-        try:  # the totals alone: the payload stays on the device
-            rr.fetch(max_runs=0, max_elems=0)
-            nr_runs, nr_out = 0, 0
-        except pkg.MfmError as err:
-            if err.code != b.MFM_E_NOMEM:
-                raise
-            nr_runs, nr_out = err.needed
+        nr_runs, nr_out = _runrs_totals(pkg, rr)
         got = {n: [] for n, _ in variants}
         for rep in range(a.reps):
             k = rep % len(variants)
@@ -685,6 +719,55 @@ def bench_runrs(a, pkg, torch, rows, in_stride, nout, timed):
         gate.close()
     print(json.dumps(out))
     for o in (rr, plain, sq):
+        o.close()
+
+
+def bench_runrs_dc(a, pkg, torch, rows, in_stride, nout, timed):
+    """the burst resampler's DC blocker on the scene of bench_runrs: per mask the burst resampler with the blocker (pole 0.999), the
+    burst resampler without it and the plain resampler (v_dot2 form forced) with dc_block on the full rows, alternating in one
+    process in rotating order.  As there, every timed call begins every stretch anew, so each does the same work"""
+    nch, W, I, D, pole = a.bench_channels, a.window, 4, 5, 0.999
+    taps, nw, nb, masks, recs, (sq, _keep) = _runrs_bench_scene(a, pkg, torch, rows, in_stride, nout)
+    plain = pkg.Resampler(nch, taps, I, D, nb, device=0, force_dot2=True, dc_pole=pole)
+    rr_dc = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=nout, device=0)
+    rr_dc.set_dc_block(pole)
+    rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=nout, device=0)
+
+    def run_plain():
+        plain.process_device(rows, in_stride, nb)
+
+    out = {"bench": "runrs_dc_stage", "channels": nch, "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I,
+           "decimate": D, "taps": int(taps.size), "pole": pole, "dc_p": rr_dc.dc_block()[1], "reps": a.reps, "calls_per_rep": a.inner}
+    for name in ("all_closed", "all_open", "scene"):
+        gate = pkg.Gate(nch, nout, W, device=0)
+        gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+        view = gate.device_view()
+
+        def run_dc():
+            rr_dc.process_device(*view)
+
+        def run_rr():
+            rr.process_device(*view)
+
+        variants = [("runrs_dc", run_dc), ("runrs", run_rr), ("plain_dc", run_plain)]
+        for _, fn in variants:
+            timed(fn, 3)
+        nr_runs, nr_out = _runrs_totals(pkg, rr_dc)
+        got = {n: [] for n, _ in variants}
+        for rep in range(a.reps):
+            k = rep % len(variants)
+            for vname, fn in variants[k:] + variants[:k]:
+                got[vname].append(timed(fn, a.inner))
+        (dm, dsd), (rm, rsd), (pm, psd) = _stats(got["runrs_dc"]), _stats(got["runrs"]), _stats(got["plain_dc"])
+        cost_se = math.sqrt(dsd * dsd / a.reps + rsd * rsd / a.reps)
+        ratio = dm / pm
+        ratio_se = ratio * math.sqrt(dsd * dsd / a.reps / (dm * dm) + psd * psd / a.reps / (pm * pm))
+        out[name] = {"open_share": float(masks[name].astype(bool).mean()), "runs": int(nr_runs), "output_samples": int(nr_out),
+                     "runrs_dc_ms": dm, "runrs_dc_sd": dsd, "runrs_ms": rm, "runrs_sd": rsd, "plain_dot2_dc_ms": pm, "plain_dot2_dc_sd": psd,
+                     "dc_cost_ms": dm - rm, "dc_cost_se": cost_se, "runrs_dc_over_plain_dc": ratio, "runrs_dc_over_plain_dc_se": ratio_se}
+        gate.close()
+    print(json.dumps(out))
+    for o in (rr_dc, rr, plain, sq):
         o.close()
 
 
@@ -1184,12 +1267,15 @@ def main():
     ap.add_argument("--gate-preroll", default="0", help="pre-roll windows of the gate; with --bench one or several, as 0,1,4")
     ap.add_argument("--gate-resample", default=None, help="I/D: resample the gate's runs on the device (with --gate-out, --form pcm)")
     ap.add_argument("--resample-taps", default=None, help="JSON file whose lpfCoeffs are the resampler's taps")
+    ap.add_argument("--gate-dc-pole", type=float, default=None,
+                    help="the burst resampler's DC blocker with this pole, a fresh one per stretch (with --gate-resample, not with --gate-bits)")
     ap.add_argument("--gate-ais", action="store_true", help="demodulate AIS on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--gate-pocsag", action="store_true", help="demodulate POCSAG on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--gate-flex", action="store_true", help="decode FLEX on the resampled runs on the device (with --gate-resample to 16 000 Hz)")
     ap.add_argument("--gate-bits", action="store_true",
                     help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
     ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--bench-runrs", action="store_true", help="the runrs_stage and runrs_dc_stage lines of --bench alone")
     ap.add_argument("--bench-runais", action="store_true", help="the runais_stage line of --bench alone")
     ap.add_argument("--bench-runpocsag", action="store_true", help="the runpocsag_stage line of --bench alone")
     ap.add_argument("--bench-runflex", action="store_true", help="the runflex_stage line alone")
@@ -1206,7 +1292,7 @@ def main():
         return bench_runflex_alone(a)
     if a.bench_runbits:
         return bench_runbits_alone(a)
-    if a.bench:
+    if a.bench or a.bench_runrs:
         return bench(a)
     if not a.config or not a.input:
         ap.error("--config and --input are required (or --bench)")
@@ -1214,6 +1300,10 @@ def main():
         raise SystemExit("--gate-flex needs --gate-resample: the burst FLEX stage takes the burst resampler's runs")
     if a.gate_flex and (a.gate_ais or a.gate_pocsag):
         raise SystemExit("--gate-flex, --gate-pocsag and --gate-ais exclude each other: one stage reads the burst resampler's runs")
+    if a.gate_dc_pole is not None and not a.gate_resample:
+        raise SystemExit("--gate-dc-pole needs --gate-resample: it is the burst resampler's DC blocker")
+    if a.gate_dc_pole is not None and a.gate_bits:
+        raise SystemExit("--gate-dc-pole and --gate-bits exclude each other: the DC blocker filters the PCM the sign bits would be taken from")
     if a.gate_bits and a.gate_flex:
         raise SystemExit("--gate-bits and --gate-flex exclude each other: the burst FLEX stage reads PCM values, not sign bits")
     if a.gate_bits and a.gate_ais == a.gate_pocsag:

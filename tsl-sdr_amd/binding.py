@@ -77,6 +77,7 @@ ABI_SYMBOLS = [
     "mfm_runais_process_bits_device", "mfm_runpocsag_process_bits_device",
     "mfm_hosttwin_runrs_call_bits", "mfm_hosttwin_runais_call_bits", "mfm_hosttwin_runpocsag_call_bits",
     "mfm_pocsag_seek", "mfm_flex_seek", "mfm_ais_seek", "mfm_level_seek", "mfm_gate_seek",
+    "mfm_runrs_set_dc_block", "mfm_runrs_get_dc_block", "mfm_hosttwin_runrs_dc_call",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -229,6 +230,8 @@ MFM_RUNRS_NO_WINDOW = (1 << 64) - 1                     # mfm_runrs_state.expect
 RUNRS_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("out_offset", "<u8"), ("first_out", "<u8"), ("channel", "<u4"),
                             ("nr_out", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 RUNRS_STATE_DTYPE = np.dtype([("expected", "<u8"), ("outs", "<u8"), ("phase", "<u4"), ("pending", "<u4")])
+# struct mfm_runrs_dc_state (16 bytes): the per-channel state of the burst resampler's DC blocker, all zero at the start of a stream
+RUNRS_DC_STATE_DTYPE = np.dtype([("x_n_1", "<i4"), ("y_n_1", "<i4"), ("acc", "<i4"), ("reserved", "<u4")])
 
 
 class RunrsBitsView(C.Structure):
@@ -568,6 +571,9 @@ def load_library():
     lib.mfm_runrs_bits_view.argtypes = [vp, C.POINTER(RunrsBitsView)]
     lib.mfm_runrs_fetch_bits.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_runrs_get_bits_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.mfm_runrs_set_dc_block.argtypes = [vp, C.c_uint32, C.c_double]
+    lib.mfm_runrs_get_dc_block.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    lib.mfm_hosttwin_runrs_dc_call.argtypes = [C.c_uint32, C.c_double, vp, vp, C.c_size_t, vp, C.c_size_t]
     lib.mfm_runais_process_bits_device.argtypes = [vp, C.POINTER(RunrsBitsView), vp]
     lib.mfm_runpocsag_process_bits_device.argtypes = [vp, C.POINTER(RunrsBitsView), vp]
     lib.mfm_hosttwin_runrs_call_bits.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, i16p, C.c_size_t, vp,
@@ -1697,6 +1703,21 @@ class RunResampler:
             self._raise(rc, "mfm_runrs_get_capacity")
         return nr.value, ne.value
 
+    def set_dc_block(self, pole):
+        """mfm_runrs_set_dc_block: the DC blocker (decoder -b) with this pole behind the resampler, one fresh blocker per
+        stretch; None switches it off.  Only before the first process call"""
+        rc = self.lib.mfm_runrs_set_dc_block(self.h, int(pole is not None), float(pole if pole is not None else 0.0))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_set_dc_block")
+
+    def dc_block(self):
+        """(on, dc_p): whether the DC blocker is on, and its (1 - pole) in Q14 (0 when off)"""
+        on, p = C.c_uint32(), C.c_int32()
+        rc = self.lib.mfm_runrs_get_dc_block(self.h, C.byref(on), C.byref(p))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_get_dc_block")
+        return bool(on.value), p.value
+
 
 class RunAis:
     """mfm_runais: the runs of a RunResampler's device view through the AIS demodulator, one fresh demodulator per stretch;
@@ -2197,6 +2218,23 @@ def hosttwin_runrs_call(window_samples, coeffs_q14, interpolate, decimate, state
         err.needed = (nr.value, ne.value)
         raise err
     return runs[:nr.value].copy(), payload[:ne.value].copy()
+
+
+def hosttwin_runrs_dc_call(pole, dc, runs, payload):
+    """mfm_hosttwin_runrs_dc_call: the burst resampler's DC blocker on the CPU, on the (runs, payload) of one
+    hosttwin_runrs_call.  dc RUNRS_DC_STATE_DTYPE [C] (zeros at the start of a stream) and payload int16 are updated in
+    place; returns payload.  On an error neither is written"""
+    lib = load_library()
+    dc = np.asarray(dc)
+    assert dc.dtype == RUNRS_DC_STATE_DTYPE and dc.flags.c_contiguous and dc.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    out = np.asarray(payload)
+    assert out.dtype == np.int16 and out.flags.c_contiguous and out.ndim == 1
+    rc = lib.mfm_hosttwin_runrs_dc_call(dc.shape[0], float(pole), dc.ctypes.data, rr.ctypes.data if rr.size else None, rr.size,
+                                        out.ctypes.data if out.size else None, out.size)
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runrs_dc_call", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
+    return out
 
 
 def hosttwin_runrs_call_bits(window_samples, coeffs_q14, interpolate, decimate, state, pending, gate_runs, gate_payload, polarity,

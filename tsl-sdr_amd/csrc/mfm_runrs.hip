@@ -27,6 +27,16 @@
  *                    when the call raised a flag, copies its state over.  The buffers are used in turn, so the FIR kernel
  *                    and this one read the old state while the new one is written.
  *
+ *   rr_dc_kernel     (mfm_runrs_dc.hip) only with the DC blocker on (mfm_runrs_set_dc_block), between the FIR and the state
+ *                    kernel: one lane per run, in place on the output payload, one fresh blocker per stretch
+ *                    (mfm_runrs_dc.h).  The full-row form (mfm_dc_block_kernel) is a dependent chain with one lane per
+ *                    channel; here every run starts from a state
+ *                    that is known before the call - zeros, or the channel's from the call before - so the runs of a call are
+ *                    independent chains.  The blocker's state is kept in two buffers used in turn like the resampler's: a
+ *                    channel's first run reads the old one, its last run writes the new one (they may be lanes of different
+ *                    waves, so one buffer updated in place would be a race), and the state kernel copies over the channels
+ *                    without a run and every channel of a refused call.
+ *
  * The bodies of the scan and the FIR kernel are in mfm_runrs_kernels.h, with the form as a template parameter; this file holds
  * their PCM instances, mfm_run_bits.hip the bits form's (rrb_scan_kernel, rrb_fir_kernel), so neither form pays for the other.
  * The bits form (mfm_runrs_process_bits_device) is the same four kernels with the store replaced: the scan also scans the
@@ -51,11 +61,15 @@ extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(con
 #include "mfm_numerics.h"
 #include "mfm_rs_plan.h"
 #include "mfm_runrs.h"
+#include "mfm_runrs_dc.h"
 #include "mfm_runrs_kernels.h"
 
 /* the bits form's scan and FIR kernels (mfm_run_bits.hip), queued on s between the plan and the state kernel */
 extern "C" __attribute__((visibility("hidden"))) int mfm_internal_runrs_bits_launch(const void *call, uint32_t np, uint32_t max_blocks,
                                                                                    uint32_t lds_bytes, hipStream_t s);
+
+/* the DC blocker's kernel (mfm_runrs_dc.hip), queued on s between the FIR and the state kernel */
+extern "C" __attribute__((visibility("hidden"))) int mfm_internal_runrs_dc_launch(const void *call, uint32_t cap_runs, hipStream_t s);
 
 namespace {
 
@@ -223,6 +237,9 @@ __global__ __launch_bounds__(64) void rr_state_kernel(const RrCall A)
     if (last == RR_NONE || refused) { /* the state stays */
         if (tid == 0) {
             A.chan_new[c] = old;
+            if (A.dc_old) { /* the DC blocker's state likewise (a channel with a run: its last run's lane wrote it, rr_dc_kernel) */
+                A.dc_new[c] = A.dc_old[c];
+            }
         }
         for (uint32_t i = tid; i < old.pending; i += blockDim.x) {
             pn[i] = po[i];
@@ -275,6 +292,9 @@ struct mfm_runrs {
     int16_t *d_phase = nullptr;
     mfm_runrs_state *d_chan[2] = { nullptr, nullptr }; /* used in turn: a call reads [cur] and writes [cur ^ 1] */
     int16_t *d_pend[2] = { nullptr, nullptr };
+    mfm_runrs_dc_state *d_dc[2] = { nullptr, nullptr }; /* the DC blocker's, in turn with the two above; allocated by set_dc_block */
+    uint32_t dc_on = 0;
+    int32_t dc_p = 0;
     uint32_t cur = 0;
     RrPlan *d_plan = nullptr;
     uint32_t *d_nblk = nullptr, *d_blk_base = nullptr, *d_bad = nullptr, *d_chan_last = nullptr, *d_ctl = nullptr;
@@ -324,7 +344,8 @@ int rr_process(mfm_runrs *rr, const mfm_gate_run *d_runs, const int16_t *d_paylo
                     rr->d_phase, rr->d_runs,      rr->d_plan, rr->d_nblk,     rr->d_blk_base,       rr->d_bad,       rr->d_chan_last,
                     rr->d_ctl,   rr->d_totals,    rr->d_out, g.cap_runs,      g.cap_elems,          g.out_cap,       g.C,
                     g.W,         g.I,             g.D,       g.plen,          rr->pend_stride,      rr->cfg.invert,  g.coef_bytes,
-                    rr->d_bits,  polarity };
+                    rr->d_bits,  polarity,        rr->dc_on ? rr->d_dc[cur] : nullptr,      rr->dc_on ? rr->d_dc[cur ^ 1u] : nullptr,
+                    rr->dc_p };
     if (g.cap_runs) {
         hipLaunchKernelGGL(rr_plan_kernel, dim3((uint32_t)((g.cap_runs + 255u) / 256u)), dim3(256), 0, s, A);
         RR_TRY(hipGetLastError());
@@ -340,6 +361,12 @@ int rr_process(mfm_runrs *rr, const mfm_gate_run *d_runs, const int16_t *d_paylo
         if (g.max_blocks) {
             rr_launch_fir(g, A, s);
             RR_TRY(hipGetLastError());
+        }
+        if (rr->dc_on && g.cap_runs) { /* run count and flags are read on the device: sized from the capacity */
+            if (mfm_internal_runrs_dc_launch(&A, (uint32_t)g.cap_runs, s) != MFM_OK) {
+                RR_TRY(hipGetLastError());
+                return MFM_E_DEVICE;
+            }
         }
     }
     hipLaunchKernelGGL(rr_state_kernel, dim3(g.C), dim3(64), 0, s, A);
@@ -369,6 +396,7 @@ const char *rr_refusal(const uint64_t *t)
     return nullptr;
 }
 
+constexpr const char *RR_BAD_POLE = "the DC blocker's pole must be a number whose (1 - pole) * 16384 fits the int16 it is cut to (filter/dc_blocker.h:56)";
 constexpr const char *RR_LAST_WAS_BITS = "the last call was mfm_runrs_process_bits_device: its result is read with mfm_runrs_fetch_bits or mfm_runrs_bits_view";
 constexpr const char *RR_LAST_WAS_PCM = "the last call was not mfm_runrs_process_bits_device: its result is read with mfm_runrs_fetch or mfm_runrs_device_view";
 
@@ -446,6 +474,7 @@ void mfm_runrs_destroy(struct mfm_runrs **prr)
     for (int i = 0; i < 2; i++) {
         (void)hipFree(rr->d_chan[i]);
         (void)hipFree(rr->d_pend[i]);
+        (void)hipFree(rr->d_dc[i]);
     }
     (void)hipFree(rr->d_plan);
     (void)hipFree(rr->d_nblk);
@@ -473,7 +502,55 @@ int mfm_runrs_process_bits_device(struct mfm_runrs *rr, const struct mfm_gate_ru
     if (polarity != MFM_BITS_NEG && polarity != MFM_BITS_POS) {
         return rr_fail(MFM_E_INVAL, "polarity must be MFM_BITS_NEG or MFM_BITS_POS");
     }
+    if (rr && rr->dc_on) {
+        return rr_fail(MFM_E_INVAL, "the sign-bit output is not available with the DC blocker: it filters the PCM the predicate would be "
+                                    "taken from (mfm_runrs_process_device, or mfm_runrs_set_dc_block off)");
+    }
     return rr_process(rr, d_runs, d_payload, d_totals, polarity, stream);
+}
+
+int mfm_runrs_set_dc_block(struct mfm_runrs *rr, uint32_t on, double pole)
+{
+    if (!rr) {
+        return MFM_E_INVAL;
+    }
+    if (rr->have_call) {
+        return rr_fail(MFM_E_STATE, "mfm_runrs_set_dc_block is valid only before the first process call");
+    }
+    if (!on) {
+        rr->dc_on = 0;
+        rr->dc_p = 0;
+        return MFM_OK;
+    }
+    int32_t p = 0;
+    if (!mfm_runrs_dc_pole(pole, &p)) {
+        return rr_fail(MFM_E_INVAL, RR_BAD_POLE);
+    }
+    RR_TRY(hipSetDevice(rr->cfg.device));
+    for (int i = 0; i < 2; i++) {
+        if (!rr->d_dc[i]) {
+            RR_TRY(hipMalloc(&rr->d_dc[i], (size_t)rr->g.C * sizeof(mfm_runrs_dc_state)));
+        }
+        RR_TRY(hipMemset(rr->d_dc[i], 0, (size_t)rr->g.C * sizeof(mfm_runrs_dc_state)));
+    }
+    RR_TRY(hipDeviceSynchronize());
+    rr->dc_on = 1;
+    rr->dc_p = p;
+    return MFM_OK;
+}
+
+int mfm_runrs_get_dc_block(struct mfm_runrs *rr, uint32_t *on, int32_t *dc_p)
+{
+    if (!rr) {
+        return MFM_E_INVAL;
+    }
+    if (on) {
+        *on = rr->dc_on;
+    }
+    if (dc_p) {
+        *dc_p = rr->dc_p;
+    }
+    return MFM_OK;
 }
 
 int mfm_runrs_fetch(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_t max_runs, size_t *nr_runs, int16_t *payload, size_t max_elems,
@@ -759,6 +836,45 @@ int mfm_hosttwin_runrs_call_bits(uint32_t nr_channels, uint32_t window_samples, 
     }
     return rr_twin_call(nr_channels, window_samples, interpolate, decimate, invert, coeffs, nr_coeffs, state, pending, gate_runs, nr_gate_runs,
                         gate_payload, nr_gate_elems, runs, max_runs, nr_runs, nullptr, bits, polarity, max_words, nr_words);
+}
+
+int mfm_hosttwin_runrs_dc_call(uint32_t nr_channels, double pole, struct mfm_runrs_dc_state *dc, const struct mfm_runrs_run *runs,
+                               size_t nr_runs, int16_t *payload, size_t nr_elems)
+{
+    if (!nr_channels || !dc || (!runs && nr_runs) || (!payload && nr_elems)) {
+        return MFM_E_INVAL;
+    }
+    int32_t p = 0;
+    if (!mfm_runrs_dc_pole(pole, &p)) {
+        return rr_fail(MFM_E_INVAL, RR_BAD_POLE);
+    }
+    for (size_t r = 0; r < nr_runs; r++) {
+        const mfm_runrs_run &o = runs[r];
+        const bool first = r == 0 || runs[r - 1].channel != o.channel;
+        if (o.channel >= nr_channels || (r && runs[r - 1].channel > o.channel)) {
+            return rr_fail(MFM_E_INVAL, "the run list is not a burst resampler's: a channel does not exist or the channels do not ascend");
+        }
+        if (!first && 0u == (o.flags & MFM_RUNRS_BEGINS)) {
+            return rr_fail(MFM_E_INVAL, "the run list is not a burst resampler's: a run that continues a stretch is not its channel's first");
+        }
+        if (o.out_offset > nr_elems || o.nr_out > nr_elems - o.out_offset) {
+            return rr_fail(MFM_E_INVAL, "the run list is not a burst resampler's: a run's outputs lie beyond the payload");
+        }
+    }
+    for (size_t r = 0; r < nr_runs; r++) {
+        const mfm_runrs_run &o = runs[r];
+        const bool first = r == 0 || runs[r - 1].channel != o.channel;
+        const bool last = r + 1 == nr_runs || runs[r + 1].channel != o.channel;
+        mfm_runrs_dc_carry k = mfm_runrs_dc_start(dc + o.channel, first, o.flags);
+        int16_t *yy = payload + o.out_offset;
+        for (uint32_t i = 0; i < o.nr_out; i++) {
+            yy[i] = mfm_runrs_dc_sample(k, p, yy[i]);
+        }
+        if (last) {
+            dc[o.channel] = mfm_runrs_dc_leave(k);
+        }
+    }
+    return MFM_OK;
 }
 
 } /* extern "C" */

@@ -47,6 +47,9 @@ struct RrCall {
     uint32_t C, W, I, D, plen, pend_stride, invert, coef_bytes;
     uint32_t *bits;          /* the bits form: the payload of predicate words */
     uint32_t polarity;       /* the bits form: MFM_BITS_NEG or MFM_BITS_POS */
+    const mfm_runrs_dc_state *dc_old; /* [C] the DC blocker's state, NULL with the blocker off */
+    mfm_runrs_dc_state *dc_new;
+    int32_t dc_p;
 };
 
 /* 1 / 2 when the gate's totals say that nothing may be read: its own flags, or more than this object was made for */
