@@ -881,6 +881,49 @@ int mfm_level_device_view(struct mfm_level *p, const struct mfm_level_record **d
 int mfm_level_seek(struct mfm_level *p, uint64_t samples_before);
 
 /*
+ * The adaptive squelch: open_thr / close_thr of the config are two numbers for every channel, but across the channels of one
+ * wide-band capture the idle level differs (filter roll-off, gain slope, neighbours) and on a live stream it drifts.  With this
+ * setting every channel's squelch follows the channel's own noise floor, scanner-style.  Per channel, over completed windows in
+ * stream order, k_s the first window after create or the last mfm_level_seek, metric[k] the window's energy or diff_energy as
+ * the config's `metric` says:
+ *
+ *   floor[k]   the extremum of metric[j] for j in [max(k_s, k - M + 1), k], window k included, M = floor_windows: the MINIMUM for
+ *              MFM_LEVEL_OPEN_ABOVE (the idle level is the low side), the MAXIMUM for MFM_LEVEL_OPEN_BELOW.  It does not depend on
+ *              the squelch state.  A transmission longer than M windows drags the floor along and the squelch closes.
+ *   open side  ABOVE: metric * 256 >= floor * open_q8 and metric >= open_thr;  BELOW: metric * 256 <= floor * open_q8 and
+ *              metric <= open_thr.  False for the first warmup_windows windows after k_s.
+ *   bad        ABOVE: metric * 256 < floor * close_q8 or metric < close_thr;  BELOW: metric * 256 > floor * close_q8 or
+ *              metric > close_thr.
+ *
+ * The products are exact (no wrap).  The state machine is the one above, fed these two predicates: it starts closed, opens on an
+ * open-side window, hang_windows + 1 bad windows in a row close it, a window that is not bad resets the count.  The config's
+ * thresholds stay in force as absolute limits: a silent channel has floor 0, where every metric passes the ratio test, and a
+ * non-zero open_thr keeps it shut.  No limit is open_thr = close_thr = 0 (ABOVE) or UINT64_MAX (BELOW).  Like everything in this
+ * stage the result does not depend on how the stream is cut into calls.  Records, d_open and mfm_level_device_view are what they
+ * were: the gate and everything behind it take the adaptive verdict as it is.
+ */
+struct mfm_level_adaptive {      /* 24 bytes */
+    uint32_t floor_windows;      /* M, 1 .. 1024 */
+    uint32_t open_q8;            /* 1 .. 65536: ratio to the floor in 1/256 */
+    uint32_t close_q8;           /* 1 .. 65536; <= open_q8 for OPEN_ABOVE, >= open_q8 for OPEN_BELOW */
+    uint32_t warmup_windows;
+    uint32_t flags, reserved;    /* 0 */
+};
+/* Switch the adaptive squelch on (a) or off (NULL).  Only on a fresh object - after create or mfm_level_seek, before the next
+ * process call - else MFM_E_INVAL; MFM_E_INVAL with a mfm_last_error() message and the object unchanged for values out of range,
+ * ratios in the wrong order or non-zero flags / reserved.  mfm_level_seek keeps the setting and forgets the history of the floor
+ * and the warm-up count. */
+int mfm_level_set_adaptive(struct mfm_level *p, const struct mfm_level_adaptive *a);
+/* *on = 1 and *a = the setting, or *on = 0 and *a zeroed; either may be NULL */
+int mfm_level_get_adaptive(struct mfm_level *p, uint32_t *on, struct mfm_level_adaptive *a);
+/* The floors of the last call's windows, as mfm_level_fetch copies its records: nr_channels * *nr_windows values, channels
+ * ascending; MFM_E_NOMEM when max_values is smaller (nothing copied), 0 windows is a valid result.  mfm_level_floor_view is the
+ * device form, d_floor[channel * floor_stride + i], valid like mfm_level_device_view's records.  MFM_E_INVAL with the adaptive
+ * squelch off. */
+int mfm_level_fetch_floor(struct mfm_level *p, uint64_t *out, size_t max_values, size_t *nr_windows);
+int mfm_level_floor_view(struct mfm_level *p, const uint64_t **d_floor, size_t *floor_stride);
+
+/*
  * ---- Gate stage: only open windows of a channel leave the GPU -------------------------------------------------------
  * The consumer of the level stage's verdict: of rows that are still in HBM it packs the windows whose record says
  * `open` into one dense payload, with a run list that says which channel and which samples each piece is.  One short
@@ -1617,6 +1660,13 @@ void mfm_hosttwin_level_window(const int16_t *x, size_t nr_samples, uint32_t for
                                uint32_t *peak);
 uint32_t mfm_hosttwin_squelch_step(uint32_t sense, uint64_t open_thr, uint64_t close_thr, uint32_t hang_windows, uint64_t metric,
                                    uint32_t *open, uint32_t *bad);
+/* host twin of the adaptive squelch (mfm_level_set_adaptive; csrc/mfm_level.h, the inlines the kernel runs) for ONE channel:
+ * metric[0 .. nr_windows) are the windows from the first one after create or seek on; floor[k] and open[k] (either may be NULL)
+ * get window k's floor and the squelch state after it.  The floor is formed by its definition, window by window.  Nothing is
+ * checked and nothing is reported: the caller passes a setting mfm_level_set_adaptive would accept (with metric or the setting NULL,
+ * or floor_windows 0, the call returns with floor and open untouched). */
+void mfm_hosttwin_level_adaptive(const uint64_t *metric, size_t nr_windows, uint32_t sense, uint64_t open_thr, uint64_t close_thr,
+                                 uint32_t hang_windows, const struct mfm_level_adaptive *a, uint64_t *floor, uint32_t *open);
 /* host twin of one call of the gate stage (csrc/mfm_gate.h, the arithmetic its kernels run: the window cut of a call, run
  * formation, offsets), on the CPU with no device: pos = samples per channel consumed before the call, rows [channel][in_stride],
  * carry [channel][W * elems_per_sample] read and then updated, records [channel][record_stride].  0 with runs and payload filled;

@@ -3,6 +3,7 @@
 
     python tools/level_scan.py --config receiver.json --input capture.bin [--format cs16|cs8|cu8] [--form pcm|iq]
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
+           [--floor-windows M --open-ratio R --close-ratio R [--warmup N]]
            [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-dc-pole POLE]
            [--gate-ais | --gate-pocsag | --gate-flex]]]
 
@@ -13,7 +14,15 @@ lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per
 
 --form pcm runs the stage on the discriminator's PCM (a captured carrier LOWERS its energy: default sense below),
 --form iq on the filtered IQ (a carrier RAISES it: default sense above).  --summary adds one line per channel with the
-share of windows it was open.  The thresholds default to 0: read the levels off a first run, then set them.
+share of windows it was open.  The thresholds default to 0: read the levels off a first run, then set them - or let every
+channel follow its own noise floor:
+
+--floor-windows M --open-ratio R --close-ratio R [--warmup N] switch the adaptive squelch on (mfm_level_set_adaptive): the floor
+of a window is the smallest (sense above; the largest with sense below) metric of the channel's last M windows, that window
+included; a channel opens at R times its floor and a window is bad beyond the close ratio (R as a float, taken in 1/256:
+round(256 R)), and the first N windows open nothing.  --open-thr / --close-thr stay in force as absolute limits (with sense
+below and none given they are set to 2^64 - 1, no limit).  Every record line then carries "floor" behind "open", and a --summary
+line "median_floor", the lower median of the channel's floors.
 
 --gate-out DIR queues the gate stage behind the level stage on the engine's stream, on the rows the scan runs on (PCM, or
 IQ with --form iq): only the windows the squelch left open leave the device.  Per channel that ever opened DIR/chNNNN.s16
@@ -86,7 +95,11 @@ the place of the time:
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
 against the POCSAG stage's call on the same rows (idle input; its slicer, pg_slice_kernel, reads the same bytes) and
-against the engine launch with and without filtered IQ.  Level pass and comparison alternate in one process, in
+against the engine launch with and without filtered IQ.  A line behind it ("level_adaptive_stage"; --bench-level-adaptive prints
+that line alone, behind the engine launch that makes the rows) times the level pass with the adaptive squelch off and on (M = 64),
+two objects alternating in one process, with the difference, its standard error and the verdict of the same two-standard-error
+rule, and the adaptive pass at M = 64, 1 and 1024 (--bench-floor-windows gives other M's; the first is the one set against the
+fixed path).  Level pass and comparison alternate in one process, in
 rotating order; mean and standard deviation over --reps repetitions, a difference counts beyond two standard errors
 (the rule of tools/exp/ab.py).  One JSON line.  A second line times the gate stage on the same rows (whole windows of
 them) with every window closed, every window open and the mask a squelch at the median window energy leaves, each beside a
@@ -149,6 +162,9 @@ def scan(a):
     fs, centre, decim, taps, chans = read_config(a.config)
     iq_form = a.form == "iq"
     sense = a.sense or ("above" if iq_form else "below")
+    adaptive = a.floor_windows is not None
+    if adaptive and sense == "below" and a.open_thr == 0 and a.close_thr is None:
+        a.open_thr = (1 << 64) - 1   # no absolute limit on the low side
     eng = pkg.Engine(fs, decim, a.block, device=a.device, flags=b.MFM_F_DEVICE_ONLY)
     for freq, gain in chans:
         eng.add_channel(freq - centre, taps, gain, want_iq=iq_form)
@@ -158,6 +174,8 @@ def scan(a):
                    sense=b.MFM_LEVEL_OPEN_ABOVE if sense == "above" else b.MFM_LEVEL_OPEN_BELOW,
                    open_thr=a.open_thr, close_thr=a.close_thr if a.close_thr is not None else a.open_thr, hang_windows=a.hang,
                    device=a.device)
+    if adaptive:
+        lv.set_adaptive(a.floor_windows, int(round(256.0 * a.open_ratio)), int(round(256.0 * a.close_ratio)), a.warmup or 0)
     gate, index, started = None, None, set()
     elems = 2 if iq_form else 1
     if a.gate_out:
@@ -291,6 +309,7 @@ def scan(a):
     bytes_per_sample = 4 if a.format == "cs16" else 2
     windows = np.zeros(len(chans), np.int64)
     opened = np.zeros(len(chans), np.int64)
+    floors = [[] for _ in chans]
     out = sys.stdout
     with open(a.input, "rb") as f:
         while True:
@@ -313,6 +332,7 @@ def scan(a):
                 gate.process_device(rows[0], rows[1], nout, d_rec, rec_stride, nw, stream=eng.stream)
                 run_stages()
             rec = lv.fetch()
+            fl = lv.fetch_floor() if adaptive else None
             if gate:
                 write_runs(*gate.fetch())
             if rr:
@@ -324,15 +344,22 @@ def scan(a):
             if rf:
                 write_flex(*rf.fetch())
             for c, (freq, _) in enumerate(chans):
-                for r in rec[c]:
-                    out.write(json.dumps({"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
-                                          "diff_energy": int(r["diff_energy"]), "peak": int(r["peak"]), "open": int(r["open"])}) + "\n")
+                for i, r in enumerate(rec[c]):
+                    line = {"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
+                            "diff_energy": int(r["diff_energy"]), "peak": int(r["peak"]), "open": int(r["open"])}
+                    if adaptive:
+                        line["floor"] = int(fl[c, i])
+                        floors[c].append(int(fl[c, i]))
+                    out.write(json.dumps(line) + "\n")
             windows += rec.shape[1]
             opened += rec["open"].sum(axis=1).astype(np.int64)
     if a.summary:
         for c, (freq, _) in enumerate(chans):
-            out.write(json.dumps({"summary": True, "freq": freq, "channel": c, "windows": int(windows[c]), "open_windows": int(opened[c]),
-                                  "open_share": (float(opened[c]) / float(windows[c])) if windows[c] else 0.0}) + "\n")
+            line = {"summary": True, "freq": freq, "channel": c, "windows": int(windows[c]), "open_windows": int(opened[c]),
+                    "open_share": (float(opened[c]) / float(windows[c])) if windows[c] else 0.0}
+            if adaptive:
+                line["median_floor"] = sorted(floors[c])[(len(floors[c]) - 1) // 2] if floors[c] else 0
+            out.write(json.dumps(line) + "\n")
     if gate:
         gate.flush_device(stream=eng.stream)  # the windows pre-roll still held back; none with P = 0
         run_stages()
@@ -511,6 +538,12 @@ def bench(a):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / inner
 
+    if a.bench_level_adaptive:   # the line of the adaptive squelch alone, on the same rows
+        pg.close()
+        bench_level_adaptive(a, pkg, torch, rows, in_stride, nout, timed)
+        for o in (lv, eng):
+            o.close()
+        return
     if a.bench_runrs:   # the two lines of the burst resampler alone, on the same rows
         pg.close()
         bench_runrs(a, pkg, torch, rows, in_stride, nout, timed)
@@ -540,6 +573,7 @@ def bench(a):
            "engine_launch_ms_with_iq": engine_ms["iq"][0], "engine_launch_sd_with_iq": engine_ms["iq"][1]}
     print(json.dumps(res))
     pg.close()
+    bench_level_adaptive(a, pkg, torch, rows, in_stride, nout, timed)
     p0 = None
     for P in [int(x) for x in str(a.gate_preroll).split(",")]:
         line = bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P, p0)
@@ -552,6 +586,49 @@ def bench(a):
         bench_runbits(a, pkg, torch)
     for o in (lv, eng):
         o.close()
+
+
+def bench_level_adaptive(a, pkg, torch, rows, in_stride, nout, timed):
+    """the level pass with the adaptive squelch off and on (M = the first of --bench-floor-windows, 64; opens at 4, bad below 2
+    times the floor) on the rows the level pass was timed on, two objects alternating in one process in rotating order; then the
+    adaptive pass at every M of --bench-floor-windows (64, 1 and 1024), alternating likewise.  The two input kernels are the same in all of them: a difference is the finish kernels'"""
+    b = pkg.binding
+    nch, W, iq_form = a.bench_channels, a.window, a.form == "iq"
+    form = b.MFM_LEVEL_IQ if iq_form else b.MFM_LEVEL_PCM
+
+    def make(M):
+        lv = pkg.Level(nch, nout, W, form=form, device=0)
+        if M:
+            lv.set_adaptive(M, 1024, 512, 0)
+        return lv
+
+    def ab(variants):
+        for _, fn in variants:
+            timed(fn, 3)
+        got = {n: [] for n, _ in variants}
+        for rep in range(a.reps):
+            k = rep % len(variants)
+            for name, fn in variants[k:] + variants[:k]:
+                got[name].append(timed(fn, a.inner))
+        return {n: _stats(v) for n, v in got.items()}
+
+    ms = [int(x) for x in str(a.bench_floor_windows).split(",")]
+    objs = {M: make(M) for M in [0] + ms}
+    run = {M: (lambda lv=lv: lv.process_device(rows, in_stride, nout)) for M, lv in objs.items()}
+    first = ab([("fixed", run[0]), ("adaptive", run[ms[0]])])
+    (fm, fsd), (am, asd) = first["fixed"], first["adaptive"]
+    se = math.sqrt(fsd * fsd / a.reps + asd * asd / a.reps)
+    d = am - fm
+    by_m = ab([(str(M), run[M]) for M in ms])
+    out = {"bench": "level_adaptive_stage", "channels": nch, "form": a.form, "window": W, "outputs_per_channel": nout,
+           "windows_per_call": nout // W, "reps": a.reps, "calls_per_rep": a.inner, "floor_windows": ms[0], "open_q8": 1024, "close_q8": 512,
+           "fixed_ms": fm, "fixed_sd": fsd, "adaptive_ms": am, "adaptive_sd": asd, "adaptive_over_fixed": am / fm,
+           "difference_ms": d, "difference_se": se,
+           "verdict": "neutral" if abs(d) <= 2.0 * se else ("faster" if d < 0 else "slower"),
+           "adaptive_ms_by_floor_windows": {str(M): {"ms": by_m[str(M)][0], "sd": by_m[str(M)][1]} for M in ms}}
+    print(json.dumps(out))
+    for lv in objs.values():
+        lv.close()
 
 
 def bench_gate(a, pkg, torch, rt, lv, rows, in_stride, nout, timed, P=0, p0=None):
@@ -1260,6 +1337,10 @@ def main():
     ap.add_argument("--open-thr", type=int, default=0)
     ap.add_argument("--close-thr", type=int, default=None)
     ap.add_argument("--hang", type=int, default=0)
+    ap.add_argument("--floor-windows", type=int, default=None, help="M: the adaptive squelch on the floor of the last M windows")
+    ap.add_argument("--open-ratio", type=float, default=None, help="opens at this ratio to the floor (with --floor-windows)")
+    ap.add_argument("--close-ratio", type=float, default=None, help="a window is bad beyond this ratio to the floor (with --floor-windows)")
+    ap.add_argument("--warmup", type=int, default=None, help="windows after the start that open nothing (with --floor-windows)")
     ap.add_argument("--block", type=int, default=1 << 20)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--summary", action="store_true")
@@ -1275,6 +1356,8 @@ def main():
     ap.add_argument("--gate-bits", action="store_true",
                     help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
     ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--bench-level-adaptive", action="store_true", help="the level_adaptive_stage line of --bench alone")
+    ap.add_argument("--bench-floor-windows", default="64,1,1024", help="the M's of the level_adaptive_stage line; the first against the fixed path")
     ap.add_argument("--bench-runrs", action="store_true", help="the runrs_stage and runrs_dc_stage lines of --bench alone")
     ap.add_argument("--bench-runais", action="store_true", help="the runais_stage line of --bench alone")
     ap.add_argument("--bench-runpocsag", action="store_true", help="the runpocsag_stage line of --bench alone")
@@ -1292,10 +1375,14 @@ def main():
         return bench_runflex_alone(a)
     if a.bench_runbits:
         return bench_runbits_alone(a)
-    if a.bench or a.bench_runrs:
+    if a.bench or a.bench_runrs or a.bench_level_adaptive:
         return bench(a)
     if not a.config or not a.input:
         ap.error("--config and --input are required (or --bench)")
+    if (a.floor_windows is None) != (a.open_ratio is None) or (a.floor_windows is None) != (a.close_ratio is None):
+        raise SystemExit("--floor-windows, --open-ratio and --close-ratio go together: the adaptive squelch needs all three")
+    if a.warmup is not None and a.floor_windows is None:
+        raise SystemExit("--warmup needs --floor-windows: it is the adaptive squelch's warm-up")
     if a.gate_flex and not a.gate_resample:
         raise SystemExit("--gate-flex needs --gate-resample: the burst FLEX stage takes the burst resampler's runs")
     if a.gate_flex and (a.gate_ais or a.gate_pocsag):

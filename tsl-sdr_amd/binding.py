@@ -78,6 +78,7 @@ ABI_SYMBOLS = [
     "mfm_hosttwin_runrs_call_bits", "mfm_hosttwin_runais_call_bits", "mfm_hosttwin_runpocsag_call_bits",
     "mfm_pocsag_seek", "mfm_flex_seek", "mfm_ais_seek", "mfm_level_seek", "mfm_gate_seek",
     "mfm_runrs_set_dc_block", "mfm_runrs_get_dc_block", "mfm_hosttwin_runrs_dc_call",
+    "mfm_level_set_adaptive", "mfm_level_get_adaptive", "mfm_level_fetch_floor", "mfm_level_floor_view", "mfm_hosttwin_level_adaptive",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -177,6 +178,12 @@ class LevelConfig(C.Structure):
                 ("max_in_samples", C.c_uint32), ("form", C.c_uint32), ("window_samples", C.c_uint32),
                 ("metric", C.c_uint32), ("sense", C.c_uint32), ("open_thr", C.c_uint64), ("close_thr", C.c_uint64),
                 ("hang_windows", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LevelAdaptive(C.Structure):
+    """struct mfm_level_adaptive"""
+    _fields_ = [("floor_windows", C.c_uint32), ("open_q8", C.c_uint32), ("close_q8", C.c_uint32), ("warmup_windows", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class LevelRecord(C.Structure):
@@ -546,6 +553,13 @@ def load_library():
     lib.mfm_hosttwin_level_window.restype = None
     lib.mfm_hosttwin_squelch_step.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, u32p, u32p]
     lib.mfm_hosttwin_squelch_step.restype = C.c_uint32
+    lib.mfm_level_set_adaptive.argtypes = [vp, C.POINTER(LevelAdaptive)]
+    lib.mfm_level_get_adaptive.argtypes = [vp, u32p, C.POINTER(LevelAdaptive)]
+    lib.mfm_level_fetch_floor.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.mfm_level_floor_view.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.mfm_hosttwin_level_adaptive.argtypes = [u64p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(LevelAdaptive),
+                                                u64p, u32p]
+    lib.mfm_hosttwin_level_adaptive.restype = None
     szp = C.POINTER(C.c_size_t)
     lib.mfm_gate_create.argtypes = [C.POINTER(vp), C.POINTER(GateConfig)]
     lib.mfm_gate_destroy.argtypes = [C.POINTER(vp)]
@@ -1391,6 +1405,65 @@ class Level:
         if rc < 0:
             raise MfmError(rc, "mfm_level_device_view", self.lib.mfm_strerror(rc).decode())
         return rec.value, st.value, n.value, op.value
+
+    def set_adaptive(self, floor_windows=None, open_q8=0, close_q8=0, warmup_windows=0, flags=0, reserved=0):
+        """mfm_level_set_adaptive: the squelch on ratios (in 1/256) to the channel's own noise floor over the last floor_windows
+        windows; floor_windows None switches it off.  Only on a fresh object (after create or seek, before the next call)"""
+        a = None if floor_windows is None else LevelAdaptive(floor_windows, open_q8, close_q8, warmup_windows, flags, reserved)
+        rc = self.lib.mfm_level_set_adaptive(self.h, C.byref(a) if a is not None else None)
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_set_adaptive", (self.lib.mfm_last_error() if rc == MFM_E_INVAL else self.lib.mfm_strerror(rc)).decode())
+
+    def get_adaptive(self):
+        """mfm_level_get_adaptive: None when off, else dict(floor_windows, open_q8, close_q8, warmup_windows)"""
+        on, a = C.c_uint32(), LevelAdaptive()
+        rc = self.lib.mfm_level_get_adaptive(self.h, C.byref(on), C.byref(a))
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_get_adaptive", self.lib.mfm_strerror(rc).decode())
+        if not on.value:
+            return None
+        return dict(floor_windows=a.floor_windows, open_q8=a.open_q8, close_q8=a.close_q8, warmup_windows=a.warmup_windows)
+
+    def fetch_floor(self, max_values=None):
+        """the floors of the last call's windows, uint64 [C][windows]; with max_values too small: MfmError(MFM_E_NOMEM) whose
+        `needed` attribute is the count that would fit"""
+        n = C.c_size_t()
+        if max_values is None:
+            rc = self.lib.mfm_level_fetch_floor(self.h, None, 0, C.byref(n))
+            if rc not in (MFM_OK, MFM_E_NOMEM):
+                raise MfmError(rc, "mfm_level_fetch_floor", self.lib.mfm_last_error().decode() or self.lib.mfm_strerror(rc).decode())
+            max_values = self.nr_channels * n.value
+        out = np.zeros(max(max_values, 1), np.uint64)
+        rc = self.lib.mfm_level_fetch_floor(self.h, out.ctypes.data, max_values, C.byref(n))
+        if rc < 0:
+            err = MfmError(rc, "mfm_level_fetch_floor", (self.lib.mfm_last_error() if rc == MFM_E_INVAL else self.lib.mfm_strerror(rc)).decode())
+            err.needed = self.nr_channels * n.value
+            err.buffer = out
+            raise err
+        return out[:self.nr_channels * n.value].reshape(self.nr_channels, n.value).copy()
+
+    def floor_view(self):
+        """(d_floor, floor_stride): the device address of the last call's floors, d_floor[channel * floor_stride + i]"""
+        fl, st = C.c_void_p(), C.c_size_t()
+        rc = self.lib.mfm_level_floor_view(self.h, C.byref(fl), C.byref(st))
+        if rc < 0:
+            raise MfmError(rc, "mfm_level_floor_view", (self.lib.mfm_last_error() if rc == MFM_E_INVAL else self.lib.mfm_strerror(rc)).decode())
+        return fl.value, st.value
+
+
+def hosttwin_level_adaptive(metric, sense, open_thr, close_thr, hang_windows, floor_windows, open_q8, close_q8, warmup_windows=0):
+    """mfm_hosttwin_level_adaptive for one channel: metric uint64 [n], the windows from the first after create or seek on;
+    returns (floor uint64 [n], open uint32 [n])"""
+    lib = load_library()
+    m = np.ascontiguousarray(metric, dtype=np.uint64).reshape(-1)
+    n = m.size
+    buf = m if n else np.zeros(1, np.uint64)
+    fl, op = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)
+    a = LevelAdaptive(floor_windows, open_q8, close_q8, warmup_windows, 0, 0)
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    lib.mfm_hosttwin_level_adaptive(buf.ctypes.data_as(u64p), n, sense, int(open_thr), int(close_thr), hang_windows, C.byref(a),
+                                    fl.ctypes.data_as(u64p), op.ctypes.data_as(u32p))
+    return fl[:n], op[:n]
 
 
 def hosttwin_level_window(x, form=MFM_LEVEL_PCM, prev=0):

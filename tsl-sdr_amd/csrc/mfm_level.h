@@ -123,4 +123,72 @@ __host__ __device__ inline void mfm_level_squelch_step(uint32_t &open, uint32_t 
     }
 }
 
+/*
+ * ---- The adaptive squelch (mfm_level_set_adaptive): thresholds as ratios to the channel's own noise floor ----
+ *
+ * Per channel, over completed windows in stream order, k_s the first window after create or the last seek:
+ *
+ *   floor[k]   the extremum of metric[j], j in [max(k_s, k - M + 1), k] (window k included): the MINIMUM for OPEN_ABOVE (a carrier
+ *              raises the metric, the idle level is the low side), the MAXIMUM for OPEN_BELOW.  A minimum-statistics estimate: it
+ *              does not depend on the squelch state, so all floors of a call are computed in parallel.  A transmission longer
+ *              than M windows drags it along, and the squelch closes.
+ *   KEY        both senses run ONE sliding minimum: of metric for OPEN_ABOVE, of ~metric for OPEN_BELOW (the complement turns
+ *              the order round); a window in front of k_s has the key UINT64_MAX, the minimum's identity.
+ *   ratios     open_q8, close_q8 in 1/256.  metric * 256 against floor * q8 needs more than 64 bits (the metric reaches 2^61, a
+ *              ratio 2^16): mfm_level_mul32 forms the exact product of a 64-bit and a 32-bit factor as top * 2^32 + low.
+ *   open side  ABOVE: metric * 256 >= floor * open_q8 and metric >= open_thr;  BELOW: <= and <=.  False during the first
+ *              warmup_windows windows after k_s.
+ *   bad        ABOVE: metric * 256 < floor * close_q8 or metric < close_thr;  BELOW: > or >.
+ *
+ * The fixed thresholds of the config stay in force as absolute limits (a silent channel has floor 0, and every metric passes
+ * the ratio test there).  Only the two predicates feed the state machine, which is mfm_level_squelch_step's.
+ */
+struct mfm_level_wide {
+    uint64_t top;  /* the product >> 32 */
+    uint32_t low;  /* its low 32 bits */
+};
+
+/* a * b exactly: b < 2^32 and, so that `top` cannot wrap, b <= 2^31 (the callers' factors are 256 and a ratio <= 65536) */
+__host__ __device__ inline mfm_level_wide mfm_level_mul32(uint64_t a, uint32_t b)
+{
+    const uint64_t lo = (a & 0xffffffffull) * b, hi = (a >> 32) * b;
+    mfm_level_wide w;
+    w.top = hi + (lo >> 32);
+    w.low = (uint32_t)lo;
+    return w;
+}
+
+__host__ __device__ inline bool mfm_level_wide_ge(const mfm_level_wide &a, const mfm_level_wide &b)
+{
+    return a.top > b.top || (a.top == b.top && a.low >= b.low);
+}
+
+__host__ __device__ inline uint64_t mfm_level_floor_key(uint32_t below, uint64_t metric)
+{
+    return below ? ~metric : metric;
+}
+
+/* the two predicates of one window; warm: the window is one of the first warmup_windows */
+__host__ __device__ inline void mfm_level_adaptive_predicates(uint32_t below, uint64_t metric, uint64_t floor, uint32_t open_q8, uint32_t close_q8,
+                                                              uint64_t open_thr, uint64_t close_thr, bool warm, bool &on_open_side, bool &is_bad)
+{
+    const mfm_level_wide m = mfm_level_mul32(metric, 256u);
+    const mfm_level_wide fo = mfm_level_mul32(floor, open_q8), fc = mfm_level_mul32(floor, close_q8);
+    if (below) {
+        on_open_side = !warm && mfm_level_wide_ge(fo, m) && metric <= open_thr;
+        is_bad = !mfm_level_wide_ge(fc, m) || metric > close_thr;
+    } else {
+        on_open_side = !warm && mfm_level_wide_ge(m, fo) && metric >= open_thr;
+        is_bad = !mfm_level_wide_ge(m, fc) || metric < close_thr;
+    }
+}
+
+/* One step of the squelch on the two predicates: mfm_level_squelch_step itself, on a metric of 1 or 0 against thresholds of
+ * 1 (closed, only "on the open side" is looked at: 1 >= 1 opens; open, only "bad": 0 < 1 is bad). */
+__host__ __device__ inline void mfm_level_squelch_step_bits(uint32_t &open, uint32_t &bad, uint32_t hang, bool on_open_side, bool is_bad)
+{
+    const uint64_t metric = open ? (is_bad ? 0u : 1u) : (on_open_side ? 1u : 0u);
+    mfm_level_squelch_step(open, bad, 0u, 1u, 1u, hang, metric);
+}
+
 #endif /* MFM_LEVEL_H */

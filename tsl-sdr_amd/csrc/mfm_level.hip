@@ -24,6 +24,10 @@
  *                     order and keeps the unfinished window's sums, the last element and the squelch state on the
  *                     device.
  *
+ * With the adaptive squelch on (mfm_level_set_adaptive) lv_adaptive_finish_kernel (mfm_level_adaptive.hip, an object of its
+ * own) is queued in the place of lv_finish_kernel; this file holds its setting and its two buffers.  What the two finish
+ * kernels share is mfm_level_kernels.h.
+ *
  * Nothing is floating point, no result goes through an atomic, and the host never waits: how many windows a call
  * completes follows from the stream position alone.
  */
@@ -36,40 +40,17 @@
 #include "../../include/multifm_hip.h"
 
 #include "mfm_level.h"
+#include "mfm_level_kernels.h"
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 
 namespace {
 
+using namespace mfm_lv;
+
 constexpr uint32_t LV_SLOT = 4096; /* elements per slot at most: 8 steps of 512 */
 constexpr uint32_t LV_U = 8;       /* steps of one wave in flight */
 constexpr uint32_t LV_NARROW = 512; /* windows below this many elements: a lane per window */
-
-struct LvGeom {
-    uint64_t P;      /* absolute element position of the call's first element */
-    uint64_t g0;     /* absolute index of the first slot the call touches */
-    uint32_t N;      /* elements per channel in this call */
-    uint32_t We, B, nsub;
-    uint32_t nslots; /* slots the call touches */
-    uint32_t with_diff;
-};
-
-struct LvPart {
-    uint64_t energy, diff;
-    uint32_t peak, pad;
-};
-
-struct LvChan {
-    uint64_t energy, diff; /* of the unfinished window */
-    uint32_t peak;
-    uint32_t prev;         /* last element of the stream so far (PCM form), as uint16 */
-    uint32_t open, bad;
-};
-
-struct LvSquelch {
-    uint64_t open_thr, close_thr;
-    uint32_t use_diff, below, hang, pad;
-};
 
 /* elements [a, b) of the call's rows that slot s of the call covers */
 __device__ __forceinline__ void lv_slot_range(const LvGeom &G, uint32_t s, uint32_t &a, uint32_t &b)
@@ -84,25 +65,6 @@ __device__ __forceinline__ void lv_slot_range(const LvGeom &G, uint32_t s, uint3
     const uint64_t hi = en < G.P + G.N ? en : G.P + G.N;
     a = (uint32_t)(lo - G.P);
     b = (uint32_t)(hi - G.P);
-}
-
-__device__ __forceinline__ uint64_t lv_wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t lv_wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        const uint32_t w = (uint32_t)__shfl_xor((int)v, o);
-        v = w > v ? w : v;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(256) void lv_wide_kernel(const LvGeom G, const int16_t *x, size_t stride, const LvChan *st, LvPart *parts,
@@ -187,86 +149,21 @@ __global__ __launch_bounds__(256) void lv_narrow_kernel(const LvGeom G, const in
     parts[(size_t)c * parts_stride + s] = LvPart{ acc.energy, acc.diff, mfm_level_peak(acc), 0u };
 }
 
-struct LvFinish {
-    LvGeom G;
-    LvSquelch Q;
-    const int16_t *x;
-    size_t stride;
-    LvChan *st;
-    const LvPart *parts;
-    uint32_t parts_stride;
-    mfm_level_record *rec;
-    uint32_t rec_stride;
-    uint32_t *d_open;
-    uint64_t k0;   /* window the call's first element lies in */
-    uint32_t nwin; /* windows the call completes */
-    uint32_t tail; /* 1: elements of an unfinished window are left behind them */
-};
-
 __global__ __launch_bounds__(64) void lv_finish_kernel(const LvFinish L)
 {
     const uint32_t lane = threadIdx.x;
     const uint32_t c = blockIdx.x;
-    const LvGeom &G = L.G;
     const LvChan s = L.st[c];
     const LvPart *pc = L.parts + (size_t)c * L.parts_stride;
-    /* the call's slots of window k: [lo, hi) as indices into pc */
-    auto slots_of = [&](uint64_t k, uint32_t &lo, uint32_t &hi) {
-        const uint64_t f = k * G.nsub, e = f + G.nsub, g1 = G.g0 + G.nslots;
-        lo = (uint32_t)((f > G.g0 ? f : G.g0) - G.g0);
-        hi = (uint32_t)((e < g1 ? e : g1) - G.g0);
-    };
-    /* the sums of slots [lo, hi), every lane taking part; all lanes get the result */
-    auto wave_slots = [&](uint32_t lo, uint32_t hi, uint64_t &e, uint64_t &d, uint32_t &p) {
-        uint64_t le = 0, ld = 0;
-        uint32_t lp = 0;
-        for (uint32_t j = lo + lane; j < hi; j += 64) {
-            const LvPart t = pc[j];
-            le += t.energy;
-            ld += t.diff;
-            lp = t.peak > lp ? t.peak : lp;
-        }
-        e = lv_wave_sum(le);
-        d = lv_wave_sum(ld);
-        p = lv_wave_max(lp);
-    };
     uint32_t open = s.open, bad = s.bad;
     mfm_level_record *rc = L.rec + (size_t)c * L.rec_stride;
     for (uint32_t m0 = 0; m0 < L.nwin; m0 += 64) {
         const uint32_t m = m0 + lane;
         const uint32_t cnt = L.nwin - m0 < 64u ? L.nwin - m0 : 64u;
         const bool act = lane < cnt;
-        uint64_t e = 0, d = 0;
-        uint32_t p = 0;
-        if (G.nsub <= 64) { /* a lane per window */
-            if (act) {
-                uint32_t lo, hi;
-                slots_of(L.k0 + m, lo, hi);
-                for (uint32_t j = lo; j < hi; j++) {
-                    const LvPart t = pc[j];
-                    e += t.energy;
-                    d += t.diff;
-                    p = t.peak > p ? t.peak : p;
-                }
-            }
-        } else { /* long windows: the wave per window, lane j keeps window m0 + j */
-            for (uint32_t j = 0; j < cnt; j++) {
-                uint32_t lo, hi, wp;
-                uint64_t we, wd;
-                slots_of(L.k0 + m0 + j, lo, hi);
-                wave_slots(lo, hi, we, wd, wp);
-                if (lane == j) {
-                    e = we;
-                    d = wd;
-                    p = wp;
-                }
-            }
-        }
-        if (m == 0) { /* what earlier calls left of the first window */
-            e += s.energy;
-            d += s.diff;
-            p = s.peak > p ? s.peak : p;
-        }
+        uint64_t e, d;
+        uint32_t p;
+        lv_round_sums(L, s, pc, lane, m0, cnt, e, d, p);
         const uint64_t metric = L.Q.use_diff ? d : e;
         uint32_t my_open = 0;
         const int mlo = (int)(uint32_t)metric, mhi = (int)(uint32_t)(metric >> 32);
@@ -290,25 +187,7 @@ __global__ __launch_bounds__(64) void lv_finish_kernel(const LvFinish L)
             rc[m] = r;
         }
     }
-    /* the unfinished window behind them */
-    uint64_t te = 0, td = 0;
-    uint32_t tp = 0;
-    if (L.tail) {
-        uint32_t lo, hi;
-        slots_of(L.k0 + L.nwin, lo, hi);
-        wave_slots(lo, hi, te, td, tp);
-    }
-    if (lane == 0) {
-        LvChan o;
-        o.energy = te + (L.nwin ? 0ull : s.energy);
-        o.diff = td + (L.nwin ? 0ull : s.diff);
-        o.peak = L.nwin ? tp : (tp > s.peak ? tp : s.peak);
-        o.prev = G.with_diff && G.N ? (uint32_t)(uint16_t)L.x[(size_t)c * L.stride + G.N - 1] : s.prev;
-        o.open = open;
-        o.bad = bad;
-        L.st[c] = o;
-        L.d_open[c] = open;
-    }
+    lv_leave(L, s, pc, lane, c, open, bad); /* the unfinished window behind them, the last element, the squelch state */
 }
 
 thread_local char g_lv_error[256] = "";
@@ -346,6 +225,13 @@ struct mfm_level {
     uint32_t *d_open = nullptr;
     hipStream_t last_stream = nullptr;
     bool have_call = false;
+    /* the adaptive squelch (mfm_level_set_adaptive) */
+    bool fresh = true;        /* no process call since create or the last seek */
+    uint64_t fresh_pos = 0;   /* where create or the last seek put the stream: the floor looks no further back */
+    bool adaptive = false;
+    mfm_level_adaptive ad{};
+    uint64_t *d_hist = nullptr;  /* [channel][max(M - 1, 1)] */
+    uint64_t *d_floor = nullptr; /* [channel][max_win] */
 };
 
 extern "C" {
@@ -419,6 +305,8 @@ void mfm_level_destroy(struct mfm_level **pp)
     (void)hipFree(p->d_parts);
     (void)hipFree(p->d_rec);
     (void)hipFree(p->d_open);
+    (void)hipFree(p->d_hist);
+    (void)hipFree(p->d_floor);
     delete p;
     *pp = nullptr;
 }
@@ -475,9 +363,26 @@ int mfm_level_process_device(struct mfm_level *p, const int16_t *d_rows, size_t 
         F.k0 = k0;
         F.nwin = nwin;
         F.tail = (p->pos + nr_in) % W ? 1u : 0u;
-        hipLaunchKernelGGL(lv_finish_kernel, dim3(C), dim3(64), 0, s, F);
+        if (p->adaptive) { /* the same two input kernels, the adaptive finish kernel (mfm_level_adaptive.hip) behind them */
+            LvAdaptive A{};
+            A.M = p->ad.floor_windows;
+            A.open_q8 = p->ad.open_q8;
+            A.close_q8 = p->ad.close_q8;
+            A.warmup = p->ad.warmup_windows;
+            A.done = k0 - p->fresh_pos / W;
+            A.hist = p->d_hist;
+            A.hist_stride = A.M > 1 ? A.M - 1 : 1;
+            A.floor = p->d_floor;
+            A.floor_stride = p->max_win;
+            if (mfm_internal_level_adaptive_launch(&F, &A, C, s) != MFM_OK) {
+                return lv_inval("internal: the adaptive finish kernel was not queued");
+            }
+        } else {
+            hipLaunchKernelGGL(lv_finish_kernel, dim3(C), dim3(64), 0, s, F);
+        }
         LV_TRY(hipGetLastError());
     }
+    p->fresh = false;
     p->pos += nr_in;
     p->last_nwin = nwin;
     p->last_stream = s;
@@ -527,6 +432,106 @@ int mfm_level_seek(struct mfm_level *p, uint64_t samples_before)
     p->last_nwin = 0;
     p->last_stream = nullptr;
     p->have_call = false;
+    p->fresh = true; /* the adaptive setting stays; its history and warm-up count start over, both follow from fresh_pos */
+    p->fresh_pos = samples_before;
+    return MFM_OK;
+}
+
+int mfm_level_set_adaptive(struct mfm_level *p, const struct mfm_level_adaptive *a)
+{
+    if (!p) {
+        return lv_inval("mfm_level_set_adaptive: no object");
+    }
+    if (!p->fresh) {
+        return lv_inval("mfm_level_set_adaptive: only on a fresh object (after create or mfm_level_seek, before the next process call)");
+    }
+    if (a) {
+        if (0 == a->floor_windows || a->floor_windows > 1024u) {
+            return lv_inval("mfm_level_set_adaptive: floor_windows must be 1 .. 1024");
+        }
+        if (0 == a->open_q8 || a->open_q8 > 65536u || 0 == a->close_q8 || a->close_q8 > 65536u) {
+            return lv_inval("mfm_level_set_adaptive: open_q8 and close_q8 must be 1 .. 65536");
+        }
+        if (p->cfg.sense == MFM_LEVEL_OPEN_ABOVE ? a->close_q8 > a->open_q8 : a->close_q8 < a->open_q8) {
+            return lv_inval("mfm_level_set_adaptive: ratios in the wrong order: close_q8 <= open_q8 for OPEN_ABOVE, close_q8 >= open_q8 for OPEN_BELOW");
+        }
+        if (a->flags != 0 || a->reserved != 0) {
+            return lv_inval("mfm_level_set_adaptive: flags and reserved must be 0");
+        }
+    }
+    LV_TRY(hipSetDevice(p->cfg.device));
+    if (!a) {
+        p->adaptive = false;
+        return MFM_OK;
+    }
+    const uint32_t C = p->cfg.nr_channels;
+    const size_t hist = a->floor_windows > 1 ? a->floor_windows - 1 : 1;
+    uint64_t *d_hist = nullptr, *d_floor = nullptr;
+    if (hipMalloc(&d_hist, (size_t)C * hist * 8) != hipSuccess || hipMalloc(&d_floor, (size_t)C * p->max_win * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d_hist);
+        return MFM_E_NOMEM; /* the object is as it was */
+    }
+    (void)hipFree(p->d_hist); /* fresh: nothing queued reads them */
+    (void)hipFree(p->d_floor);
+    p->d_hist = d_hist;
+    p->d_floor = d_floor;
+    p->ad = *a;
+    p->adaptive = true;
+    return MFM_OK;
+}
+
+int mfm_level_get_adaptive(struct mfm_level *p, uint32_t *on, struct mfm_level_adaptive *a)
+{
+    if (!p) {
+        return MFM_E_INVAL;
+    }
+    if (on) {
+        *on = p->adaptive ? 1u : 0u;
+    }
+    if (a) {
+        *a = p->adaptive ? p->ad : mfm_level_adaptive{};
+    }
+    return MFM_OK;
+}
+
+int mfm_level_fetch_floor(struct mfm_level *p, uint64_t *out, size_t max_values, size_t *nr_windows)
+{
+    if (!p || !nr_windows || (!out && max_values)) {
+        return MFM_E_INVAL;
+    }
+    if (!p->adaptive) {
+        return lv_inval("mfm_level_fetch_floor: the adaptive squelch is off");
+    }
+    *nr_windows = p->last_nwin;
+    if (!p->have_call || 0 == p->last_nwin) {
+        return MFM_OK;
+    }
+    const uint32_t C = p->cfg.nr_channels;
+    if ((size_t)C * p->last_nwin > max_values) {
+        return MFM_E_NOMEM;
+    }
+    LV_TRY(hipSetDevice(p->cfg.device));
+    LV_TRY(hipStreamSynchronize(p->last_stream));
+    const size_t row = (size_t)p->last_nwin * 8;
+    LV_TRY(hipMemcpy2D(out, row, p->d_floor, (size_t)p->max_win * 8, row, C, hipMemcpyDeviceToHost));
+    return MFM_OK;
+}
+
+int mfm_level_floor_view(struct mfm_level *p, const uint64_t **d_floor, size_t *floor_stride)
+{
+    if (!p) {
+        return MFM_E_INVAL;
+    }
+    if (!p->adaptive) {
+        return lv_inval("mfm_level_floor_view: the adaptive squelch is off");
+    }
+    if (d_floor) {
+        *d_floor = p->d_floor;
+    }
+    if (floor_stride) {
+        *floor_stride = p->max_win;
+    }
     return MFM_OK;
 }
 
@@ -598,6 +603,35 @@ uint32_t mfm_hosttwin_squelch_step(uint32_t sense, uint64_t open_thr, uint64_t c
     }
     mfm_level_squelch_step(*open, *bad, sense == MFM_LEVEL_OPEN_BELOW ? 1u : 0u, open_thr, close_thr, hang_windows, metric);
     return *open;
+}
+
+void mfm_hosttwin_level_adaptive(const uint64_t *metric, size_t nr_windows, uint32_t sense, uint64_t open_thr, uint64_t close_thr,
+                                 uint32_t hang_windows, const struct mfm_level_adaptive *a, uint64_t *floor, uint32_t *open)
+{
+    if (!metric || !a || 0 == a->floor_windows) {
+        return;
+    }
+    const uint32_t below = sense == MFM_LEVEL_OPEN_BELOW ? 1u : 0u;
+    uint32_t op = 0, bad = 0;
+    for (size_t k = 0; k < nr_windows; k++) {
+        const size_t first = k + 1 > a->floor_windows ? k + 1 - a->floor_windows : 0;
+        uint64_t key = ~0ull; /* the sliding minimum of the keys, window by window: the definition, not the kernel's doubling */
+        for (size_t j = first; j <= k; j++) {
+            const uint64_t kj = mfm_level_floor_key(below, metric[j]);
+            key = kj < key ? kj : key;
+        }
+        const uint64_t f = mfm_level_floor_key(below, key);
+        bool on_open_side, is_bad;
+        mfm_level_adaptive_predicates(below, metric[k], f, a->open_q8, a->close_q8, open_thr, close_thr, k < a->warmup_windows, on_open_side,
+                                      is_bad);
+        mfm_level_squelch_step_bits(op, bad, hang_windows, on_open_side, is_bad);
+        if (floor) {
+            floor[k] = f;
+        }
+        if (open) {
+            open[k] = op;
+        }
+    }
 }
 
 } /* extern "C" */
