@@ -1189,6 +1189,25 @@ int mfm_runrs_fetch_bits(struct mfm_runrs *rr, struct mfm_runrs_run *runs, size_
                          size_t *nr_words);
 /* The capacities of the bits form: max_runs as mfm_runrs_get_capacity gives it, and max_out_elems / 32 + max_runs words. */
 int mfm_runrs_get_bits_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *max_words);
+/*
+ * The state between calls, for moving a stream between objects and for tests that place a stretch at a chosen position.
+ * struct mfm_runrs_state and struct mfm_runrs_dc_state are declared with the host twins below, which carry the same.
+ * mfm_runrs_fetch_state waits for the queued work and copies state [nr_channels], the pending samples [nr_channels][plen]
+ * (plen = ((nr_coeffs + interpolate - 1) / interpolate + 3) & ~3; NULL: not wanted) and the DC blocker's dc [nr_channels] (NULL:
+ * not wanted; MFM_E_STATE with a message when it is wanted and the blocker is off).
+ * mfm_runrs_store_state waits likewise and writes what the next process call reads: state and pending are required, dc is
+ * required with the blocker on and must be NULL with it off.  Every channel is validated first (csrc/mfm_runrs.h states the
+ * conditions: phase < interpolate, pending <= plen, outs and expected below 2^62 or expected = ~0 with the rest zero, the
+ * blocker's reserved 0); a state that fails gets MFM_E_INVAL with a message naming channel and field, and nothing is written.
+ * Capacities, the blocker's setting and the result of the last call (PCM or bits) stay as they were.  nr_channels must be the
+ * configuration's (MFM_E_INVAL).
+ */
+struct mfm_runrs_state;
+struct mfm_runrs_dc_state;
+int mfm_runrs_fetch_state(struct mfm_runrs *rr, struct mfm_runrs_state *state, int16_t *pending, struct mfm_runrs_dc_state *dc,
+                          size_t nr_channels);
+int mfm_runrs_store_state(struct mfm_runrs *rr, const struct mfm_runrs_state *state, const int16_t *pending,
+                          const struct mfm_runrs_dc_state *dc, size_t nr_channels);
 
 /*
  * ---- Burst AIS stage: the burst resampler's runs through the AIS demodulator, on the device -----------------------------
@@ -1288,6 +1307,13 @@ int mfm_runais_fetch(struct mfm_runais *a, struct mfm_runais_event *events, size
 /* For consumers that stay on the device: the last call's events and d_totals[4], valid until the next call.  Either may be
  * NULL. */
 int mfm_runais_device_view(struct mfm_runais *a, const struct mfm_runais_event **d_events, const uint64_t **d_totals);
+/* The per-channel state (struct mfm_runais_state, declared with the host twin below), for moving a stream between objects:
+ * fetch_state waits for the queued work and copies it out; store_state waits likewise, validates every channel
+ * (csrc/mfm_runais.h states the conditions) and writes what the next process call reads.  A state that fails gets MFM_E_INVAL
+ * with a message naming channel and field, and nothing is written.  The events of the last call stay readable. */
+struct mfm_runais_state;
+int mfm_runais_fetch_state(struct mfm_runais *a, struct mfm_runais_state *state, size_t nr_channels);
+int mfm_runais_store_state(struct mfm_runais *a, const struct mfm_runais_state *state, size_t nr_channels);
 
 /*
  * ---- Burst POCSAG stage: the burst resampler's runs through the POCSAG demodulator, on the device -----------------------
@@ -1404,6 +1430,10 @@ struct mfm_runpocsag_state;
 /* Wait for the last call and copy the per-channel state it left, state[nr_channels] (for tests and for moving a stream
  * between objects: it is what the host twin carries). */
 int mfm_runpocsag_fetch_state(struct mfm_runpocsag *p, struct mfm_runpocsag_state *state, size_t nr_channels);
+/* The way back: waits for the queued work, validates every channel (csrc/mfm_runpocsag.h states the conditions) and writes
+ * what the next process call reads.  A state that fails gets MFM_E_INVAL with a message naming channel and field, and nothing
+ * is written.  The events of the last call stay readable. */
+int mfm_runpocsag_store_state(struct mfm_runpocsag *p, const struct mfm_runpocsag_state *state, size_t nr_channels);
 
 /*
  * ---- Burst FLEX stage: the burst resampler's runs through the FLEX front half, on the device ------------------------------
@@ -1522,6 +1552,11 @@ struct mfm_runflex_state;
 /* Wait for the last call and copy the per-channel state it left, state[nr_channels], and, unless ring is NULL, the rings,
  * ring[nr_channels][32768] (for tests and for moving a stream between objects: it is what the host twin carries). */
 int mfm_runflex_fetch_state(struct mfm_runflex *f, struct mfm_runflex_state *state, int16_t *ring, size_t nr_channels);
+/* The way back: waits for the queued work, validates every channel (csrc/mfm_runflex.h states the conditions) and writes the
+ * state and the ring [nr_channels][32768] (both required) that the next process call reads.  A state that fails gets
+ * MFM_E_INVAL with a message naming channel and field, and nothing is written.  The events and frames of the last call stay
+ * readable. */
+int mfm_runflex_store_state(struct mfm_runflex *f, const struct mfm_runflex_state *state, const int16_t *ring, size_t nr_channels);
 
 /*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
@@ -1693,8 +1728,8 @@ int mfm_hosttwin_gate_call_preroll(uint32_t nr_channels, uint32_t window_samples
  * range. */
 int mfm_hosttwin_runrs_plan(uint32_t interpolate, uint32_t decimate, uint32_t plen, const uint32_t *phase, const uint32_t *pending,
                             const uint64_t *nr_samples, size_t n, uint64_t *nr_out, uint32_t *phase_out, uint32_t *pending_out);
-/* the per-channel state of the burst resampler as the host twin carries it: zero-filled except expected = ~0 (no stretch)
- * at the start of a stream */
+/* the per-channel state of the burst resampler, on the device and in the host twin: zero-filled except expected = ~0 (no
+ * stretch) at the start of a stream.  What a stored state must satisfy: csrc/mfm_runrs.h (mfm_runrs_state_check) */
 struct mfm_runrs_state {        /* 24 bytes */
     uint64_t expected;          /* window number that continues the channel's stretch */
     uint64_t outs;              /* outputs of the stretch so far */
@@ -1733,7 +1768,12 @@ struct mfm_runrs_dc_state {     /* 16 bytes */
  * is written, the state included. */
 int mfm_hosttwin_runrs_dc_call(uint32_t nr_channels, double pole, struct mfm_runrs_dc_state *dc, const struct mfm_runrs_run *runs,
                                size_t nr_runs, int16_t *payload, size_t nr_elems);
-/* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream */
+/* the validation mfm_runrs_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
+ * channel and field that fail (csrc/mfm_runrs.h).  plen as in mfm_hosttwin_runrs_call; dc may be NULL. */
+int mfm_hosttwin_runrs_state_check(uint32_t nr_channels, uint32_t interpolate, uint32_t plen, const struct mfm_runrs_state *state,
+                                   const struct mfm_runrs_dc_state *dc);
+/* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream.
+ * Fields a mode does not use are zero.  What a stored state must satisfy: csrc/mfm_runais.h (mfm_runais_state_check) */
 struct mfm_runais_state {       /* 264 bytes */
     uint64_t outs;              /* outputs of the stretch so far */
     uint64_t stretch_window;    /* first window of the stretch */
@@ -1766,8 +1806,11 @@ int mfm_hosttwin_runais_call_bits(uint32_t nr_channels, uint32_t max_runs, uint3
                                   struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const uint32_t *bits, uint32_t polarity,
                                   const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events,
                                   uint32_t *flags);
+/* the validation mfm_runais_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
+ * channel and field that fail (csrc/mfm_runais.h) */
+int mfm_hosttwin_runais_state_check(uint32_t nr_channels, const struct mfm_runais_state *state);
 /* the per-channel state of the burst POCSAG stage, on the device and in the host twin: all zero at the start of a stream.
- * Fields a mode does not use are zero. */
+ * Fields a mode does not use are zero.  What a stored state must satisfy: csrc/mfm_runpocsag.h (mfm_runpocsag_state_check) */
 struct mfm_runpocsag_state {    /* 432 bytes */
     uint64_t outs;              /* outputs of the stretch so far */
     uint64_t stretch_window;    /* first window of the stretch */
@@ -1802,8 +1845,12 @@ int mfm_hosttwin_runpocsag_call_bits(uint32_t nr_channels, uint32_t max_runs, ui
                                      struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const uint32_t *bits,
                                      uint32_t polarity, const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out,
                                      size_t *nr_events, uint32_t *flags);
+/* the validation mfm_runpocsag_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
+ * channel and field that fail (csrc/mfm_runpocsag.h) */
+int mfm_hosttwin_runpocsag_state_check(uint32_t nr_channels, const struct mfm_runpocsag_state *state);
 /* the per-channel state of the burst FLEX stage, on the device and in the host twin, beside the channel's ring of 32 768 PCM
- * samples: all zero at the start of a stream.  Positions are stretch-relative.  Fields a mode does not use are zero. */
+ * samples: all zero at the start of a stream.  Positions are stretch-relative.  Fields a mode does not use are zero.  What a
+ * stored state must satisfy: csrc/mfm_runflex.h (mfm_runflex_state_check) */
 struct mfm_runflex_state {      /* 88 bytes */
     uint64_t outs;              /* outputs of the stretch so far */
     uint64_t stretch_window;    /* first window of the stretch */
@@ -1834,6 +1881,9 @@ int mfm_hosttwin_runflex_call(uint32_t nr_channels, uint32_t max_runs, uint32_t 
                               const int16_t *payload, const uint64_t *totals, struct mfm_runflex_event *events, size_t max_out,
                               size_t *nr_events, struct mfm_flex_frame_words *frames, size_t max_out_frames, size_t *nr_frames,
                               uint32_t *flags);
+/* the validation mfm_runflex_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
+ * channel and field that fail (csrc/mfm_runflex.h) */
+int mfm_hosttwin_runflex_state_check(uint32_t nr_channels, const struct mfm_runflex_state *state);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

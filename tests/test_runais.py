@@ -24,7 +24,8 @@ import test_runrs as tr
 
 ROOT = tg.ROOT
 NEW_NAMES = ["mfm_runais_create", "mfm_runais_destroy", "mfm_runais_process_device", "mfm_runais_fetch", "mfm_runais_device_view",
-             "mfm_runrs_get_capacity", "mfm_hosttwin_runais_call"]
+             "mfm_runrs_get_capacity", "mfm_hosttwin_runais_call", "mfm_runais_fetch_state", "mfm_runais_store_state",
+             "mfm_hosttwin_runais_state_check"]
 RATIOS = [(4, 5, 41), (1, 1, 4)]   # interpolate, decimate, taps
 WINDOWS = [7, 64, 500]
 N48 = 24000                        # samples per channel at 48 kHz: 30 000 at 60 kHz in front of the 4/5 resampler

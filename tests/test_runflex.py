@@ -24,7 +24,8 @@ import test_runrs as tr
 
 ROOT = tg.ROOT
 NEW_NAMES = ["mfm_runflex_create", "mfm_runflex_destroy", "mfm_runflex_process_device", "mfm_runflex_fetch",
-             "mfm_runflex_device_view", "mfm_runflex_fetch_state", "mfm_hosttwin_runflex_call"]
+             "mfm_runflex_device_view", "mfm_runflex_fetch_state", "mfm_hosttwin_runflex_call", "mfm_runflex_store_state",
+             "mfm_hosttwin_runflex_state_check"]
 RATIOS = [(16, 25, 101), (1, 1, 4)]   # interpolate, decimate, taps
 WINDOWS = [7, 64, 500]
 NCH = 4

@@ -24,7 +24,8 @@ import test_runrs as tr
 
 ROOT = tg.ROOT
 NEW_NAMES = ["mfm_runpocsag_create", "mfm_runpocsag_destroy", "mfm_runpocsag_process_device", "mfm_runpocsag_fetch",
-             "mfm_runpocsag_device_view", "mfm_runpocsag_fetch_state", "mfm_hosttwin_runpocsag_call"]
+             "mfm_runpocsag_device_view", "mfm_runpocsag_fetch_state", "mfm_hosttwin_runpocsag_call", "mfm_runpocsag_store_state",
+             "mfm_hosttwin_runpocsag_state_check"]
 RATIOS = [(4, 5, 41), (1, 1, 4)]   # interpolate, decimate, taps
 WINDOWS = [7, 64, 500]
 NCH = 4

@@ -20,7 +20,8 @@ import test_level as tl
 
 ROOT = tg.ROOT
 NEW_NAMES = ["mfm_runrs_create", "mfm_runrs_destroy", "mfm_runrs_process_device", "mfm_runrs_fetch", "mfm_runrs_device_view",
-             "mfm_hosttwin_runrs_plan", "mfm_hosttwin_runrs_call"]
+             "mfm_hosttwin_runrs_plan", "mfm_hosttwin_runrs_call", "mfm_runrs_fetch_state", "mfm_runrs_store_state",
+             "mfm_hosttwin_runrs_state_check"]
 RATIOS = [(4, 5, 81), (16, 25, 821), (3, 7, 10), (1, 1, 4), (5, 2, 23)]   # interpolate, decimate, taps
 WINDOWS = [1, 7, 64, 500]
 MASKS = ["closed", "open", "short", "handover", "three"]

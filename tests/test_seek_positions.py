@@ -18,7 +18,7 @@ first.  Every GPU case feeds the object another stream with a transmission in it
 
 Behind them, window numbers above 2^32 through the burst chain (gate -> burst resampler -> burst POCSAG, AIS, FLEX): the host
 twins at pos = base, and on the device behind a seeked level stage and gate, against the oracle per stretch.  Stretch-relative
-positions above 2^32 in the burst stages stay out of reach: their state cannot be loaded from outside."""
+positions above 2^32 in the burst stages are test_burst_positions.py's, through the stages' state entries."""
 import numpy as np
 import pytest
 

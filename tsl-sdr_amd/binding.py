@@ -79,6 +79,10 @@ ABI_SYMBOLS = [
     "mfm_pocsag_seek", "mfm_flex_seek", "mfm_ais_seek", "mfm_level_seek", "mfm_gate_seek",
     "mfm_runrs_set_dc_block", "mfm_runrs_get_dc_block", "mfm_hosttwin_runrs_dc_call",
     "mfm_level_set_adaptive", "mfm_level_get_adaptive", "mfm_level_fetch_floor", "mfm_level_floor_view", "mfm_hosttwin_level_adaptive",
+    "mfm_runrs_fetch_state", "mfm_runrs_store_state", "mfm_runais_fetch_state", "mfm_runais_store_state",
+    "mfm_runpocsag_store_state", "mfm_runflex_store_state",
+    "mfm_hosttwin_runrs_state_check", "mfm_hosttwin_runais_state_check", "mfm_hosttwin_runpocsag_state_check",
+    "mfm_hosttwin_runflex_state_check",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -616,6 +620,16 @@ def load_library():
     lib.mfm_runflex_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_runflex_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.mfm_runflex_fetch_state.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.mfm_runrs_fetch_state.argtypes = [vp, vp, vp, vp, C.c_size_t]
+    lib.mfm_runrs_store_state.argtypes = [vp, vp, vp, vp, C.c_size_t]
+    lib.mfm_runais_fetch_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_runais_store_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_runpocsag_store_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_runflex_store_state.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.mfm_hosttwin_runrs_state_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    lib.mfm_hosttwin_runais_state_check.argtypes = [C.c_uint32, vp]
+    lib.mfm_hosttwin_runpocsag_state_check.argtypes = [C.c_uint32, vp]
+    lib.mfm_hosttwin_runflex_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                               C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -1669,6 +1683,7 @@ class RunResampler:
         if rc < 0:
             self._raise(rc, "mfm_runrs_create")
         self.nr_channels = nr_channels
+        self.plen = runrs_phase_len(co.size, interpolate)
 
     def close(self):
         if self.h:
@@ -1791,6 +1806,34 @@ class RunResampler:
             self._raise(rc, "mfm_runrs_get_dc_block")
         return bool(on.value), p.value
 
+    def fetch_state(self):
+        """mfm_runrs_fetch_state: (state, pending) as hosttwin_runrs_state has them, RUNRS_STATE_DTYPE [C] and int16 [C][plen], and
+        with the DC blocker on (state, pending, dc), dc RUNRS_DC_STATE_DTYPE [C]: what the host twins carry"""
+        dc_on = self.dc_block()[0]
+        state = np.zeros(self.nr_channels, RUNRS_STATE_DTYPE)
+        pending = np.zeros((self.nr_channels, self.plen), np.int16)
+        dc = np.zeros(self.nr_channels, RUNRS_DC_STATE_DTYPE) if dc_on else None
+        rc = self.lib.mfm_runrs_fetch_state(self.h, state.ctypes.data, pending.ctypes.data, dc.ctypes.data if dc_on else None,
+                                            self.nr_channels)
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_fetch_state")
+        return (state, pending, dc) if dc_on else (state, pending)
+
+    def store_state(self, state, pending, dc=None, nr_channels=None):
+        """mfm_runrs_store_state: what the next process call continues from.  Validated first: MfmError(MFM_E_INVAL) with a
+        message naming channel and field, and nothing written.  dc is required with the DC blocker on, None with it off"""
+        st = np.ascontiguousarray(state, dtype=RUNRS_STATE_DTYPE) if state is not None else None
+        pe = np.ascontiguousarray(pending, dtype=np.int16) if pending is not None else None
+        d = np.ascontiguousarray(dc, dtype=RUNRS_DC_STATE_DTYPE) if dc is not None else None
+        n = self.nr_channels if nr_channels is None else nr_channels
+        assert st is None or st.shape == (n,)
+        assert pe is None or pe.shape == (n, self.plen)
+        assert d is None or d.shape == (n,)
+        rc = self.lib.mfm_runrs_store_state(self.h, st.ctypes.data if st is not None else None, pe.ctypes.data if pe is not None else None,
+                                            d.ctypes.data if d is not None else None, n)
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_store_state")
+
 
 class RunAis:
     """mfm_runais: the runs of a RunResampler's device view through the AIS demodulator, one fresh demodulator per stretch;
@@ -1866,6 +1909,24 @@ class RunAis:
         if rc < 0:
             self._raise(rc, "mfm_runais_device_view")
         return e.value, t.value
+
+    def fetch_state(self):
+        """the per-channel state the last call left (RUNAIS_STATE_DTYPE [C]): what the host twin carries"""
+        out = np.zeros(self.nr_channels, RUNAIS_STATE_DTYPE)
+        rc = self.lib.mfm_runais_fetch_state(self.h, out.ctypes.data, self.nr_channels)
+        if rc < 0:
+            self._raise(rc, "mfm_runais_fetch_state")
+        return out
+
+    def store_state(self, state, nr_channels=None):
+        """mfm_runais_store_state: what the next process call continues from.  Validated first: MfmError(MFM_E_INVAL) with a
+        message naming channel and field, and nothing written"""
+        st = np.ascontiguousarray(state, dtype=RUNAIS_STATE_DTYPE) if state is not None else None
+        n = self.nr_channels if nr_channels is None else nr_channels
+        assert st is None or st.shape == (n,)
+        rc = self.lib.mfm_runais_store_state(self.h, st.ctypes.data if st is not None else None, n)
+        if rc < 0:
+            self._raise(rc, "mfm_runais_store_state")
 
 
 def hosttwin_runais_state(nr_channels):
@@ -2029,6 +2090,16 @@ class RunPocsag:
             self._raise(rc, "mfm_runpocsag_fetch_state")
         return out
 
+    def store_state(self, state, nr_channels=None):
+        """mfm_runpocsag_store_state: what the next process call continues from.  Validated first: MfmError(MFM_E_INVAL) with a
+        message naming channel and field, and nothing written"""
+        st = np.ascontiguousarray(state, dtype=RUNPOCSAG_STATE_DTYPE) if state is not None else None
+        n = self.nr_channels if nr_channels is None else nr_channels
+        assert st is None or st.shape == (n,)
+        rc = self.lib.mfm_runpocsag_store_state(self.h, st.ctypes.data if st is not None else None, n)
+        if rc < 0:
+            self._raise(rc, "mfm_runpocsag_store_state")
+
 
 def hosttwin_runpocsag_state(nr_channels):
     """the host twin's per-channel state at the start of a stream: RUNPOCSAG_STATE_DTYPE [C], all zero (no stretch)"""
@@ -2187,6 +2258,18 @@ class RunFlex:
             self._raise(rc, "mfm_runflex_fetch_state")
         return (out, ring) if with_ring else out
 
+    def store_state(self, state, ring, nr_channels=None):
+        """mfm_runflex_store_state: the state and the rings the next process call continues from.  Validated first:
+        MfmError(MFM_E_INVAL) with a message naming channel and field, and nothing written"""
+        st = np.ascontiguousarray(state, dtype=RUNFLEX_STATE_DTYPE) if state is not None else None
+        rg = np.ascontiguousarray(ring, dtype=np.int16) if ring is not None else None
+        n = self.nr_channels if nr_channels is None else nr_channels
+        assert st is None or st.shape == (n,)
+        assert rg is None or rg.shape == (n, RUNFLEX_RING)
+        rc = self.lib.mfm_runflex_store_state(self.h, st.ctypes.data if st is not None else None, rg.ctypes.data if rg is not None else None, n)
+        if rc < 0:
+            self._raise(rc, "mfm_runflex_store_state")
+
 
 def hosttwin_runflex_state(nr_channels):
     """the host twin's (state, ring) at the start of a stream: RUNFLEX_STATE_DTYPE [C] and int16 [C][32768], all zero"""
@@ -2244,6 +2327,43 @@ def hosttwin_runrs_state(nr_channels, nr_coeffs, interpolate):
     state = np.zeros(nr_channels, RUNRS_STATE_DTYPE)
     state["expected"] = MFM_RUNRS_NO_WINDOW
     return state, np.zeros((nr_channels, runrs_phase_len(nr_coeffs, interpolate)), np.int16)
+
+
+def _state_check(what, rc):
+    if rc < 0:
+        lib = load_library()
+        raise MfmError(rc, what, lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
+
+
+def hosttwin_runrs_state_check(state, interpolate, plen, dc=None):
+    """mfm_hosttwin_runrs_state_check: what RunResampler.store_state validates, on the CPU; MfmError(MFM_E_INVAL) with a message
+    naming the first channel and field that fail"""
+    st = np.ascontiguousarray(state, dtype=RUNRS_STATE_DTYPE)
+    d = np.ascontiguousarray(dc, dtype=RUNRS_DC_STATE_DTYPE) if dc is not None else None
+    assert st.ndim == 1 and (d is None or d.shape == st.shape)
+    _state_check("mfm_hosttwin_runrs_state_check", load_library().mfm_hosttwin_runrs_state_check(
+        st.shape[0], interpolate, plen, st.ctypes.data, d.ctypes.data if d is not None else None))
+
+
+def hosttwin_runais_state_check(state):
+    """mfm_hosttwin_runais_state_check: what RunAis.store_state validates, on the CPU"""
+    st = np.ascontiguousarray(state, dtype=RUNAIS_STATE_DTYPE)
+    assert st.ndim == 1
+    _state_check("mfm_hosttwin_runais_state_check", load_library().mfm_hosttwin_runais_state_check(st.shape[0], st.ctypes.data))
+
+
+def hosttwin_runpocsag_state_check(state):
+    """mfm_hosttwin_runpocsag_state_check: what RunPocsag.store_state validates, on the CPU"""
+    st = np.ascontiguousarray(state, dtype=RUNPOCSAG_STATE_DTYPE)
+    assert st.ndim == 1
+    _state_check("mfm_hosttwin_runpocsag_state_check", load_library().mfm_hosttwin_runpocsag_state_check(st.shape[0], st.ctypes.data))
+
+
+def hosttwin_runflex_state_check(state):
+    """mfm_hosttwin_runflex_state_check: what RunFlex.store_state validates, on the CPU"""
+    st = np.ascontiguousarray(state, dtype=RUNFLEX_STATE_DTYPE)
+    assert st.ndim == 1
+    _state_check("mfm_hosttwin_runflex_state_check", load_library().mfm_hosttwin_runflex_state_check(st.shape[0], st.ctypes.data))
 
 
 def hosttwin_runrs_plan(interpolate, decimate, plen, phase, pending, nr_samples):

@@ -505,17 +505,29 @@ __global__ __launch_bounds__(64) void ra_walk_kernel(const RaCall A)
     if (lane < RA_PACKET_WORDS) {
         dst->packet[lane] = pk[lane];
     }
-    if (lane == 0) {
-        dst->outs = end;
-        dst->stretch_window = stretch_window;
-        dst->pos = pos;
-        dst->r = rst;
-        dst->rd = rd;
-        dst->start = start;
-        dst->mode = mode;
-        dst->last_sample = last_sample;
-        dst->hist8 = hist8;
-        dst->cur_bit = cur_bit;
+    if (lane == 0) { /* in the canonical form (mfm_runais_canon): what the mode does not use is zero */
+        mfm_runais_state s;
+        s.outs = end;
+        s.stretch_window = stretch_window;
+        s.pos = pos;
+        s.r = rst;
+        s.rd = rd;
+        s.start = start;
+        s.mode = mode;
+        s.last_sample = last_sample;
+        s.hist8 = hist8;
+        s.cur_bit = cur_bit;
+        mfm_runais_canon(s);
+        dst->outs = s.outs;
+        dst->stretch_window = s.stretch_window;
+        dst->pos = s.pos;
+        dst->r = s.r;
+        dst->rd = s.rd;
+        dst->start = s.start;
+        dst->mode = s.mode;
+        dst->last_sample = s.last_sample;
+        dst->hist8 = s.hist8;
+        dst->cur_bit = s.cur_bit;
         dst->has_stretch = 1;
         dst->reserved = 0;
         A.count[r] = nev;
@@ -848,6 +860,51 @@ int mfm_runais_device_view(struct mfm_runais *a, const struct mfm_runais_event *
     return MFM_OK;
 }
 
+int mfm_hosttwin_runais_state_check(uint32_t nr_channels, const struct mfm_runais_state *state)
+{
+    if (!state || !nr_channels) {
+        return MFM_E_INVAL;
+    }
+    for (uint32_t c = 0; c < nr_channels; c++) {
+        if (const char *why = mfm_runais_state_check(state[c])) {
+            char msg[224];
+            snprintf(msg, sizeof(msg), "burst AIS state, channel %u: %s", c, why);
+            return ra_fail(MFM_E_INVAL, msg);
+        }
+    }
+    return MFM_OK;
+}
+
+int mfm_runais_fetch_state(struct mfm_runais *a, struct mfm_runais_state *state, size_t nr_channels)
+{
+    if (!a || !state || nr_channels != a->cfg.nr_channels) {
+        return MFM_E_INVAL;
+    }
+    RA_TRY(hipSetDevice(a->cfg.device));
+    if (a->have_call) {
+        RA_TRY(hipStreamSynchronize(a->last_stream));
+    }
+    RA_TRY(hipMemcpy(state, a->d_chan[a->cur], nr_channels * sizeof(mfm_runais_state), hipMemcpyDeviceToHost));
+    return MFM_OK;
+}
+
+int mfm_runais_store_state(struct mfm_runais *a, const struct mfm_runais_state *state, size_t nr_channels)
+{
+    if (!a || !state || nr_channels != a->cfg.nr_channels) {
+        return MFM_E_INVAL;
+    }
+    const int ok = mfm_hosttwin_runais_state_check(a->cfg.nr_channels, state);
+    if (ok != MFM_OK) {
+        return ok;
+    }
+    RA_TRY(hipSetDevice(a->cfg.device));
+    if (a->have_call) {
+        RA_TRY(hipStreamSynchronize(a->last_stream));
+    }
+    RA_TRY(hipMemcpy(a->d_chan[a->cur], state, nr_channels * sizeof(mfm_runais_state), hipMemcpyHostToDevice));
+    return MFM_OK;
+}
+
 } /* extern "C" */
 
 /* ---- the host twin: the same plan, segments and tail, the demodulator one sample at a time ---------------------------- */
@@ -968,6 +1025,7 @@ void ra_host_walk(mfm_runais_state &st, const uint32_t *seg, const mfm_runrs_run
     }
     st.outs = end;
     st.has_stretch = 1;
+    mfm_runais_canon(st);
 }
 
 } /* namespace */

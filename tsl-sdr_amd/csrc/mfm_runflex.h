@@ -42,6 +42,85 @@
 
 enum { MFM_RUNFLEX_SEARCH = 0, MFM_RUNFLEX_SYNC1 = 1, MFM_RUNFLEX_FRAME = 2 };
 
+#ifndef MFM_RUN_POS_LIMIT
+#define MFM_RUN_POS_LIMIT (1ull << 62) /* positions a stored state may hold stay below this, as the seek entries demand */
+#endif
+
+#define MFM_RUNFLEX_SYNC1_WAIT 1120u  /* SYNC1 waits while j + (1 .. 10) + 1110 >= outs: j is at most this far behind outs */
+#define MFM_RUNFLEX_FRAME_WAIT 28562u /* FRAME waits while the last block symbol, at most this far behind j, is >= outs */
+
+/*
+ * What a state handed in from outside (mfm_runflex_store_state) must satisfy before a kernel reads it; NULL when it does, else
+ * a message that names the field.  From what the walker indexes with: a continuing run has first_out == outs, and the search
+ * indexes the match plane with the unsigned p - first_out, so p >= outs; SYNC1 and FRAME read samples from j on out of the
+ * ring and the run, j a sample the stretch has seen and recent enough that the wait is not over yet (which keeps everything
+ * read within the ring's 32 768 samples); coding selects one of four rows; the swing values are int16 and cycle and frame the
+ * FIW's 4 and 7 bits.  Fields a mode does not use are zero (mfm_runflex_canon).  The ring is PCM: any value is a sample.
+ */
+inline const char *mfm_runflex_state_check(const mfm_runflex_state &st)
+{
+    if (st.has_stretch > 1u) {
+        return "has_stretch must be 0 or 1";
+    }
+    if (!st.has_stretch) {
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(&st);
+        for (uint32_t i = 0; i < sizeof(st) / 4u; i++) {
+            if (w[i]) {
+                return "has_stretch is 0 but another field is not 0";
+            }
+        }
+        return nullptr;
+    }
+    if (st.outs >= MFM_RUN_POS_LIMIT || st.stretch_window >= MFM_RUN_POS_LIMIT) {
+        return "outs and stretch_window must be below 2^62";
+    }
+    if (st.p >= MFM_RUN_POS_LIMIT || st.j >= MFM_RUN_POS_LIMIT) {
+        return "p and j must be below 2^62";
+    }
+    if (st.mode > MFM_RUNFLEX_FRAME) {
+        return "mode must be 0 (SEARCH), 1 (SYNC1) or 2 (FRAME)";
+    }
+    if (st.mode != MFM_RUNFLEX_FRAME) {
+        if (st.coding || st.a || st.b || st.inv_a || st.fiw_raw || st.fiw || st.cycle || st.frame || st.sample_range || st.sample_delta) {
+            return "coding, a, b, inv_a, fiw_raw, fiw, sample_range, sample_delta, cycle and frame must be 0 outside FRAME";
+        }
+    } else {
+        if (st.coding >= 4u) {
+            return "coding must be below 4 in FRAME";
+        }
+        if (st.sample_range != (int16_t)st.sample_range || st.sample_delta != (int16_t)st.sample_delta) {
+            return "sample_range and sample_delta must fit int16";
+        }
+        if (st.cycle >= 16u || st.frame >= 128u) {
+            return "cycle must be below 16 and frame below 128";
+        }
+    }
+    if (st.mode == MFM_RUNFLEX_SEARCH) {
+        if (st.j || st.eye) {
+            return "j and eye must be 0 in SEARCH";
+        }
+        if (st.p < st.outs) {
+            return "p must not be in front of outs in SEARCH";
+        }
+        if (st.run > st.outs || (st.run && st.p != st.outs)) {
+            return "run must be at most outs, and 0 unless p is outs";
+        }
+    } else {
+        if (st.p || st.run) {
+            return "p and run must be 0 outside SEARCH";
+        }
+        if (st.eye < 3u || st.eye > 255u) {
+            return "eye must be 3 .. 255 in SYNC1 and FRAME";
+        }
+        const uint64_t wait = st.mode == MFM_RUNFLEX_SYNC1 ? MFM_RUNFLEX_SYNC1_WAIT : MFM_RUNFLEX_FRAME_WAIT;
+        if (st.j >= st.outs || st.outs - st.j > wait) {
+            return st.mode == MFM_RUNFLEX_SYNC1 ? "j must be in front of outs by 1 .. 1120 samples in SYNC1"
+                                                : "j must be in front of outs by 1 .. 28562 samples in FRAME";
+        }
+    }
+    return nullptr;
+}
+
 /* words of a run's segment: history, bits, one word of padding (the views are cut out with a funnel shift over two words) */
 __host__ __device__ inline uint32_t mfm_runflex_seg_words(uint32_t nr_out)
 {

@@ -987,6 +987,39 @@ int mfm_runflex_fetch_state(struct mfm_runflex *p, struct mfm_runflex_state *sta
     return MFM_OK;
 }
 
+int mfm_hosttwin_runflex_state_check(uint32_t nr_channels, const struct mfm_runflex_state *state)
+{
+    if (!state || !nr_channels) {
+        return MFM_E_INVAL;
+    }
+    for (uint32_t c = 0; c < nr_channels; c++) {
+        if (const char *why = mfm_runflex_state_check(state[c])) {
+            char msg[224];
+            snprintf(msg, sizeof(msg), "burst FLEX state, channel %u: %s", c, why);
+            return rf_fail(MFM_E_INVAL, msg);
+        }
+    }
+    return MFM_OK;
+}
+
+int mfm_runflex_store_state(struct mfm_runflex *p, const struct mfm_runflex_state *state, const int16_t *ring, size_t nr_channels)
+{
+    if (!p || !state || !ring || nr_channels != p->cfg.nr_channels) {
+        return MFM_E_INVAL;
+    }
+    const int ok = mfm_hosttwin_runflex_state_check(p->cfg.nr_channels, state);
+    if (ok != MFM_OK) {
+        return ok;
+    }
+    RF_TRY(hipSetDevice(p->cfg.device));
+    if (p->have_call) {
+        RF_TRY(hipStreamSynchronize(p->last_stream));
+    }
+    RF_TRY(hipMemcpy(p->d_chan[p->cur], state, nr_channels * sizeof(mfm_runflex_state), hipMemcpyHostToDevice));
+    RF_TRY(hipMemcpy(p->d_ring, ring, nr_channels * MFM_RUNFLEX_RING * sizeof(int16_t), hipMemcpyHostToDevice));
+    return MFM_OK;
+}
+
 } /* extern "C" */
 
 /* ---- the host twin: the same plan, ring and state, the decoder one sample at a time through the search ------------------ */

@@ -34,6 +34,90 @@
 
 enum { MFM_RUNPOCSAG_SEARCH = 0, MFM_RUNPOCSAG_BATCH = 2, MFM_RUNPOCSAG_SYNCWORD = 3 };
 
+#ifndef MFM_RUN_POS_LIMIT
+#define MFM_RUN_POS_LIMIT (1ull << 62) /* positions a stored state may hold stay below this, as the seek entries demand */
+#endif
+
+/*
+ * What a state handed in from outside (mfm_runpocsag_store_state) must satisfy before a kernel reads it; NULL when it does,
+ * else a message that names the field.  From what the walker does with it: outs is the only position (the others are relative
+ * to it); the reset lies at outs - since_reset, which must exist and is tracked for 2400 samples; nr_eye counts matches of the
+ * stretch and is added to 32-bit run lengths; in BATCH and SYNCWORD the next bit is taken (spb - 1 - skip) mod 2^16 samples
+ * on, bit batch_word * 32 + batch_bit of 512 or bit nr_sync_bits of 32 comes next, and the words collected hold nothing from
+ * there on.  Fields a mode does not use are zero, as the walker leaves them.
+ */
+inline const char *mfm_runpocsag_state_check(const mfm_runpocsag_state &st)
+{
+    if (st.has_stretch > 1u) {
+        return "has_stretch must be 0 or 1";
+    }
+    if (!st.has_stretch) {
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(&st);
+        for (uint32_t i = 0; i < sizeof(st) / 4u; i++) {
+            if (w[i]) {
+                return "has_stretch is 0 but another field is not 0";
+            }
+        }
+        return nullptr;
+    }
+    if (st.outs >= MFM_RUN_POS_LIMIT || st.stretch_window >= MFM_RUN_POS_LIMIT) {
+        return "outs and stretch_window must be below 2^62";
+    }
+    if (st.mode != MFM_RUNPOCSAG_SEARCH && st.mode != MFM_RUNPOCSAG_BATCH && st.mode != MFM_RUNPOCSAG_SYNCWORD) {
+        return "mode must be 0 (SEARCH), 2 (BATCH) or 3 (SYNCWORD)";
+    }
+    if (st.mode == MFM_RUNPOCSAG_SEARCH) {
+        if (st.baud || st.spb || st.skip) {
+            return "baud, spb and skip must be 0 in SEARCH";
+        }
+        if (st.since_reset > MFM_RUNPOCSAG_HIST_BITS || st.since_reset > st.outs) {
+            return "since_reset must be at most 2400 and at most outs";
+        }
+        for (int d = 0; d < 3; d++) {
+            if (st.nr_eye[d] >= (1u << 31) || st.nr_eye[d] > st.outs) {
+                return "nr_eye must be below 2^31 and at most outs";
+            }
+        }
+    } else {
+        if (!((st.spb == 75u && st.baud == 512u) || (st.spb == 32u && st.baud == 1200u) || (st.spb == 16u && st.baud == 2400u))) {
+            return "spb and baud must be 75 / 512, 32 / 1200 or 16 / 2400 in BATCH and SYNCWORD";
+        }
+        if (st.skip > 0xffffu) {
+            return "skip must fit 16 bits";
+        }
+        if (st.since_reset || st.nr_eye[0] || st.nr_eye[1] || st.nr_eye[2]) {
+            return "since_reset and nr_eye must be 0 in BATCH and SYNCWORD";
+        }
+    }
+    if (st.mode == MFM_RUNPOCSAG_BATCH) {
+        if (st.batch_word >= 16u || st.batch_bit >= 32u) {
+            return "batch_word must be below 16 and batch_bit below 32";
+        }
+        for (uint32_t b = st.batch_word * 32u + st.batch_bit; b < 512u; b++) {
+            if ((st.batch[b >> 5] >> (b & 31u)) & 1u) {
+                return "batch must hold no bit from batch_word * 32 + batch_bit on";
+            }
+        }
+    } else {
+        if (st.batch_word || st.batch_bit) {
+            return "batch_word and batch_bit must be 0 outside BATCH";
+        }
+        for (uint32_t i = 0; i < 16u; i++) {
+            if (st.batch[i]) {
+                return "batch must be empty outside BATCH";
+            }
+        }
+    }
+    if (st.mode == MFM_RUNPOCSAG_SYNCWORD) {
+        if (st.nr_sync_bits >= 32u || (st.sync_word >> st.nr_sync_bits) != 0u) {
+            return "nr_sync_bits must be below 32 and sync_word hold no more bits than that";
+        }
+    } else if (st.nr_sync_bits || st.sync_word) {
+        return "nr_sync_bits and sync_word must be 0 outside SYNCWORD";
+    }
+    return nullptr;
+}
+
 /* words of a run's segment: history, bits, one word of padding (the tail is cut out with a funnel shift over two words) */
 __host__ __device__ inline uint32_t mfm_runpocsag_seg_words(uint32_t nr_out)
 {

@@ -1101,6 +1101,38 @@ int mfm_runpocsag_fetch_state(struct mfm_runpocsag *p, struct mfm_runpocsag_stat
     return MFM_OK;
 }
 
+int mfm_hosttwin_runpocsag_state_check(uint32_t nr_channels, const struct mfm_runpocsag_state *state)
+{
+    if (!state || !nr_channels) {
+        return MFM_E_INVAL;
+    }
+    for (uint32_t c = 0; c < nr_channels; c++) {
+        if (const char *why = mfm_runpocsag_state_check(state[c])) {
+            char msg[224];
+            snprintf(msg, sizeof(msg), "burst POCSAG state, channel %u: %s", c, why);
+            return rp_fail(MFM_E_INVAL, msg);
+        }
+    }
+    return MFM_OK;
+}
+
+int mfm_runpocsag_store_state(struct mfm_runpocsag *p, const struct mfm_runpocsag_state *state, size_t nr_channels)
+{
+    if (!p || !state || nr_channels != p->cfg.nr_channels) {
+        return MFM_E_INVAL;
+    }
+    const int ok = mfm_hosttwin_runpocsag_state_check(p->cfg.nr_channels, state);
+    if (ok != MFM_OK) {
+        return ok;
+    }
+    RP_TRY(hipSetDevice(p->cfg.device));
+    if (p->have_call) {
+        RP_TRY(hipStreamSynchronize(p->last_stream));
+    }
+    RP_TRY(hipMemcpy(p->d_chan[p->cur], state, nr_channels * sizeof(mfm_runpocsag_state), hipMemcpyHostToDevice));
+    return MFM_OK;
+}
+
 } /* extern "C" */
 
 /* ---- the host twin: the same plan, segments and tail, the decoder one sample at a time in the reference's own terms ------ */

@@ -22,6 +22,42 @@
 /* per-channel state between calls: struct mfm_runrs_state (include/multifm_hip.h); the pending samples stand beside it,
  * plen per channel, stored as received (inversion is applied on use) */
 
+#ifndef MFM_RUN_POS_LIMIT
+#define MFM_RUN_POS_LIMIT (1ull << 62) /* positions a stored state may hold stay below this, as the seek entries demand */
+#endif
+
+/*
+ * What a state handed in from outside (mfm_runrs_store_state) must satisfy before a kernel reads it; NULL when it does, else a
+ * message that names the field.  From what reads the state: mfm_runrs_plan_run needs phase < I (its numerator stays
+ * non-negative) and pending <= plen (the state kernel copies `pending` samples of a channel's plen); outs + nr_out and
+ * expected + nr_windows must not wrap; a channel without a stretch (expected = ~0) carries nothing.
+ */
+inline const char *mfm_runrs_state_check(const mfm_runrs_state &st, uint32_t I, uint32_t plen)
+{
+    if (st.expected == MFM_RUNRS_NO_WINDOW) {
+        return st.outs || st.phase || st.pending ? "expected is ~0 (no stretch) but outs, phase or pending is not 0" : nullptr;
+    }
+    if (st.expected >= MFM_RUN_POS_LIMIT) {
+        return "expected must be below 2^62 or ~0 (no stretch)";
+    }
+    if (st.outs >= MFM_RUN_POS_LIMIT) {
+        return "outs must be below 2^62";
+    }
+    if (st.phase >= I) {
+        return "phase must be below interpolate";
+    }
+    if (st.pending > plen) {
+        return "pending must be at most the phase length";
+    }
+    return nullptr;
+}
+
+/* the DC blocker's state is wrapping arithmetic throughout: only the reserved word is constrained */
+inline const char *mfm_runrs_dc_state_check(const mfm_runrs_dc_state &dc)
+{
+    return dc.reserved ? "the DC blocker's reserved must be 0" : nullptr;
+}
+
 /* what a run starts from */
 struct mfm_runrs_start {
     uint64_t first_out;

@@ -687,6 +687,80 @@ int mfm_runrs_get_capacity(struct mfm_runrs *rr, uint32_t *max_runs, uint64_t *m
     return MFM_OK;
 }
 
+int mfm_hosttwin_runrs_state_check(uint32_t nr_channels, uint32_t interpolate, uint32_t plen, const struct mfm_runrs_state *state,
+                                   const struct mfm_runrs_dc_state *dc)
+{
+    if (!state || !nr_channels) {
+        return MFM_E_INVAL;
+    }
+    for (uint32_t c = 0; c < nr_channels; c++) {
+        const char *why = mfm_runrs_state_check(state[c], interpolate, plen);
+        if (!why && dc) {
+            why = mfm_runrs_dc_state_check(dc[c]);
+        }
+        if (why) {
+            char msg[224];
+            snprintf(msg, sizeof(msg), "burst resampler state, channel %u: %s", c, why);
+            return rr_fail(MFM_E_INVAL, msg);
+        }
+    }
+    return MFM_OK;
+}
+
+int mfm_runrs_fetch_state(struct mfm_runrs *rr, struct mfm_runrs_state *state, int16_t *pending, struct mfm_runrs_dc_state *dc,
+                          size_t nr_channels)
+{
+    if (!rr || !state || nr_channels != rr->g.C) {
+        return MFM_E_INVAL;
+    }
+    if (dc && !rr->dc_on) {
+        return rr_fail(MFM_E_STATE, "the DC blocker is off: it has no state (mfm_runrs_set_dc_block)");
+    }
+    RR_TRY(hipSetDevice(rr->cfg.device));
+    if (rr->have_call) {
+        RR_TRY(hipStreamSynchronize(rr->last_stream));
+    }
+    const uint32_t cur = rr->cur;
+    RR_TRY(hipMemcpy(state, rr->d_chan[cur], nr_channels * sizeof(mfm_runrs_state), hipMemcpyDeviceToHost));
+    if (pending && rr->g.plen) {
+        RR_TRY(hipMemcpy2D(pending, (size_t)rr->g.plen * 2, rr->d_pend[cur], (size_t)rr->pend_stride * 2, (size_t)rr->g.plen * 2, nr_channels,
+                           hipMemcpyDeviceToHost));
+    }
+    if (dc) {
+        RR_TRY(hipMemcpy(dc, rr->d_dc[cur], nr_channels * sizeof(mfm_runrs_dc_state), hipMemcpyDeviceToHost));
+    }
+    return MFM_OK;
+}
+
+int mfm_runrs_store_state(struct mfm_runrs *rr, const struct mfm_runrs_state *state, const int16_t *pending,
+                          const struct mfm_runrs_dc_state *dc, size_t nr_channels)
+{
+    if (!rr || !state || !pending || nr_channels != rr->g.C) {
+        return MFM_E_INVAL;
+    }
+    if ((dc != nullptr) != (rr->dc_on != 0)) {
+        return rr_fail(MFM_E_INVAL, rr->dc_on ? "the DC blocker is on: its state is required" : "the DC blocker is off: its state must be NULL");
+    }
+    const int ok = mfm_hosttwin_runrs_state_check(rr->g.C, rr->g.I, rr->g.plen, state, dc);
+    if (ok != MFM_OK) {
+        return ok;
+    }
+    RR_TRY(hipSetDevice(rr->cfg.device));
+    if (rr->have_call) {
+        RR_TRY(hipStreamSynchronize(rr->last_stream));
+    }
+    const uint32_t cur = rr->cur;
+    RR_TRY(hipMemcpy(rr->d_chan[cur], state, nr_channels * sizeof(mfm_runrs_state), hipMemcpyHostToDevice));
+    if (rr->g.plen) {
+        RR_TRY(hipMemcpy2D(rr->d_pend[cur], (size_t)rr->pend_stride * 2, pending, (size_t)rr->g.plen * 2, (size_t)rr->g.plen * 2, nr_channels,
+                           hipMemcpyHostToDevice));
+    }
+    if (dc) {
+        RR_TRY(hipMemcpy(rr->d_dc[cur], dc, nr_channels * sizeof(mfm_runrs_dc_state), hipMemcpyHostToDevice));
+    }
+    return MFM_OK;
+}
+
 int mfm_hosttwin_runrs_plan(uint32_t interpolate, uint32_t decimate, uint32_t plen, const uint32_t *phase, const uint32_t *pending,
                             const uint64_t *nr_samples, size_t n, uint64_t *nr_out, uint32_t *phase_out, uint32_t *pending_out)
 {
