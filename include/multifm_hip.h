@@ -1210,6 +1210,84 @@ int mfm_runrs_store_state(struct mfm_runrs *rr, const struct mfm_runrs_state *st
                           const struct mfm_runrs_dc_state *dc, size_t nr_channels);
 
 /*
+ * ---- Run router: one gate feeds a burst chain per protocol ---------------------------------------------------------------
+ * A burst resampler has one ratio and one set of taps for all channels, and a burst decoder reads all of its runs.  A capture
+ * that carries several protocols (POCSAG at 38 400 Hz beside FLEX at 16 000 Hz in one paging band) therefore needs one burst
+ * chain per protocol, and each chain should see only the runs of its own channels.  The router stands between the gate and the
+ * burst resamplers: it partitions the gate's run list by a per-channel route table and leaves the payload where it is.  The
+ * burst resampler never assumes that payload_offset values are dense, so nothing is copied.  The reference has no counterpart.
+ *
+ * Input.  What mfm_gate_device_view returned after mfm_gate_process_device or mfm_gate_flush_device, and
+ * route_of_channel [nr_channels] given at create: a route 0 .. nr_routes - 1 per channel, or MFM_ROUTE_NONE for a channel
+ * whose runs go nowhere.
+ *
+ * Result per route k.  It replaces the previous call's.  The run list is the gate's mfm_gate_run records whose channel has
+ * route k: byte for byte, payload_offset untouched, in the gate's order (the partition is stable, so channels still ascend
+ * and a channel's runs keep their order).  d_payload is the gate's pointer.  d_totals[4] = { runs of route k, the gate's
+ * payload elements unchanged (the burst resampler uses them as the bound of the payload ranges), overflow (0 / 1), out of
+ * step (0 / 1) }.  Order and content are deterministic: no atomic decides a position.
+ *
+ * Refused calls.  When the gate's totals carry overflow or out-of-step the flag is passed on to every route; when the gate
+ * has more runs than the router's max_runs every route gets overflow = 1; when a run names a channel >= nr_channels (not a
+ * gate's run list) every route gets out of step = 1.  In all three cases every route gets 0 runs and 0 elements, and the
+ * burst resamplers behind refuse as they do behind a gate (MFM_RUNRS_OVER_GATE, MFM_RUNRS_GATE_OUT_OF_STEP) and keep their
+ * state.  The router itself carries no state between calls.
+ *
+ * Sizing what stands behind.  Channel numbers stay global, so events keep true channel numbers and stretch_window; a route's
+ * burst resampler is therefore created with the WHOLE gate's numbers (the same nr_channels, max_windows and max_runs), and its
+ * state and output buffers are sized for all channels.  Packing a dense payload per route would let the stages behind be
+ * sized to the route, at the price of a copy of every open window; the router does not do that.
+ *
+ * Refusals at create (MFM_E_INVAL with a message, never a fallback): nr_routes outside 1 .. MFM_RUNROUTE_MAX_ROUTES, a table
+ * entry that is neither below nr_routes nor MFM_ROUTE_NONE, non-zero flags, nr_channels or window_samples out of range, a
+ * default capacity asked for without max_in_samples.
+ */
+#define MFM_RUNROUTE_MAX_ROUTES 8u
+#define MFM_ROUTE_NONE 255u
+
+struct mfm_runroute; /* opaque */
+
+struct mfm_runroute_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;       /* 1 .. 65535, the gate's */
+    uint32_t nr_routes;         /* K: 1 .. MFM_RUNROUTE_MAX_ROUTES */
+    uint32_t window_samples;    /* W, the gate's; read only for the defaults below */
+    uint32_t max_windows;       /* as mfm_runrs_config.max_windows; read only where max_runs is 0 */
+    uint32_t max_runs;          /* most runs one gate call may carry; 0 = exactly the default of a burst resampler made from
+                                   the same numbers (mfm_runrs_config.max_runs) */
+    uint32_t max_in_samples;    /* the gate's; read only where max_runs is 0 */
+    uint32_t preroll_windows;   /* the gate's P; likewise */
+    uint32_t flags;             /* 0 */
+};
+
+int mfm_runroute_create(struct mfm_runroute **prt, const struct mfm_runroute_config *cfg, const uint8_t *route_of_channel);
+void mfm_runroute_destroy(struct mfm_runroute **prt);
+/*
+ * Partition the runs of one gate call.  Work is queued on `stream` (the gate call's, or one ordered behind it); no host
+ * synchronisation and no count is read on the host: the launch is sized from the capacity, and lanes that have no run return
+ * after reading the totals.  d_runs and d_totals are read until the queued work has run; d_payload is only handed on.
+ */
+int mfm_runroute_process_device(struct mfm_runroute *rt, const struct mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                                void *stream);
+/*
+ * For the burst resampler of route `route`: what it takes in the place of the gate's view.  d_runs (a buffer of max_runs
+ * records per route) and d_totals are fixed at create, so they are known without waiting; d_payload is the pointer the last
+ * mfm_runroute_process_device call was given (NULL before the first).  Any of the three may be NULL.  MFM_E_INVAL for a
+ * route >= nr_routes.
+ */
+int mfm_runroute_device_view(struct mfm_runroute *rt, uint32_t route, const struct mfm_gate_run **d_runs, const int16_t **d_payload,
+                             const uint64_t **d_totals);
+/*
+ * Wait for the last call, read route `route`'s totals into *nr_runs and *nr_elems (the gate's payload elements) and copy its
+ * runs.  MFM_E_NOMEM when max_runs is too small (nothing copied, *nr_runs says what is needed); MFM_E_STATE with a message
+ * when the call was refused (nothing copied).
+ */
+int mfm_runroute_fetch(struct mfm_runroute *rt, uint32_t route, struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, size_t *nr_elems);
+/* The run capacity fixed at create: max_runs as given or its default. */
+int mfm_runroute_get_capacity(struct mfm_runroute *rt, uint32_t *max_runs);
+
+/*
  * ---- Burst AIS stage: the burst resampler's runs through the AIS demodulator, on the device -----------------------------
  * The AIS stage above (mfm_ais_*) on ragged runs instead of full rows: its input is what mfm_runrs_device_view returns (the
  * run list, the dense resampled payload, the totals), all read on the device, and its output is AIS packet events.
@@ -1772,6 +1850,17 @@ int mfm_hosttwin_runrs_dc_call(uint32_t nr_channels, double pole, struct mfm_run
  * channel and field that fail (csrc/mfm_runrs.h).  plen as in mfm_hosttwin_runrs_call; dc may be NULL. */
 int mfm_hosttwin_runrs_state_check(uint32_t nr_channels, uint32_t interpolate, uint32_t plen, const struct mfm_runrs_state *state,
                                    const struct mfm_runrs_dc_state *dc);
+/* what mfm_runroute_create checks and derives, no device needed: MFM_OK with *max_runs = the router's run capacity (max_runs
+ * as given, or the burst resampler's default for the same numbers: one rule, csrc/mfm_runrs.h), or MFM_E_INVAL with the
+ * message create gives.  max_runs may be NULL. */
+int mfm_hosttwin_runroute_capacity(const struct mfm_runroute_config *cfg, const uint8_t *route_of_channel, uint32_t *max_runs);
+/* host twin of one mfm_runroute_process_device call, no device needed (csrc/mfm_runroute.h, the route lookup and the refusal
+ * predicate its kernel runs): gate_runs / gate_totals[4] are one gate call's result, max_runs the router's capacity.  Route
+ * k's list goes to runs + k * max_runs and its totals to totals + 4 * k (runs [nr_routes * max_runs], totals [nr_routes * 4]).
+ * A refused call returns MFM_OK as the device does, with the flags in every route's totals and `runs` untouched.
+ * MFM_E_INVAL with a message for a table or a nr_routes that create refuses. */
+int mfm_hosttwin_runroute_call(uint32_t nr_channels, uint32_t nr_routes, const uint8_t *route_of_channel, size_t max_runs,
+                               const struct mfm_gate_run *gate_runs, const uint64_t *gate_totals, struct mfm_gate_run *runs, uint64_t *totals);
 /* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream.
  * Fields a mode does not use are zero.  What a stored state must satisfy: csrc/mfm_runais.h (mfm_runais_state_check) */
 struct mfm_runais_state {       /* 264 bytes */

@@ -5,7 +5,7 @@
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
            [--floor-windows M --open-ratio R --close-ratio R [--warmup N]]
            [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-dc-pole POLE]
-           [--gate-ais | --gate-pocsag | --gate-flex]]]
+           [--gate-ais | --gate-pocsag | --gate-flex]] | --gate-route routes.json]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -91,6 +91,28 @@ the place of the time:
     {"proto": "flex", "type": "alphanumeric", "channel": 3, "first_sample": 4000, "baud": 3200, "frameNo": 42, "cycleNo": 5,
      "phaseNo": "A", "capCode": 123456, "fragment": false, "maildrop": false, "fragSeq": 3, "message": "HELLO"}
 
+--gate-route FILE (with --gate-out and --form pcm; not together with --gate-resample, --gate-dc-pole, --gate-bits or a stage flag)
+decodes a capture that mixes protocols in one pass: the run router (mfm_runroute_*) stands behind the gate and hands each route's
+burst chain only the runs of its own channels.  FILE is JSON:
+
+    {"routes": [{"name": "pocsag", "stage": "pocsag", "resample": "4/5", "taps": "filter.json", "channels": [0, 2, 5]},
+                {"name": "flex", "stage": "flex", "resample": "16/25", "taps": "flex.json", "dc_pole": 0.999, "channels": [1, 3]}]}
+
+up to eight routes; stage is ais, pocsag, flex or none (the resampler alone); resample and taps as --gate-resample and
+--resample-taps; dc_pole and bits (true / false) are optional and follow the rules of --gate-dc-pole and --gate-bits (bits only
+with ais or pocsag, never with dc_pole); a channel may stand in one route at most, and a channel in none is gated but goes no
+further.  Each route runs burst resampler -> stage on its view of the router, on the engine's stream, the flush call included, and
+writes under DIR/<name>/ the files the single-stage flags write under DIR, with the same line shapes: resampled.jsonl,
+chNNNN.rs.s16, ais.jsonl / pocsag.jsonl / flex.jsonl, pages.jsonl.  Channel numbers stay those of the configuration.
+DIR/index.jsonl and DIR/chNNNN.s16 are the gate's, as without the flag.
+
+    python tools/level_scan.py --bench-runroute [--window 1000] [--reps 8] [--inner 10]
+
+prints one line ("runroute_stage") for the run router at 64 and 1024 channels on idle rows and the three masks all-closed, half-open
+and all-open: the router call alone beside the burst resampler's call on an all-closed view, and a two-protocol capture (half the
+channels POCSAG at 4/5, half FLEX at 16/25) as router + one chain per route against two whole chains that each read every channel,
+alternating in one process in rotating order, with the difference, its standard error and the two-standard-error verdict.
+
     python tools/level_scan.py --bench [--bench-channels 64] [--form pcm|iq] [--window 4096] [--reps 8] [--gate-preroll 0,1,4]
 
 times the level pass on one 2^26-sample block of the 64- / 1024-channel plan (D = 96, 699 050 outputs per channel)
@@ -154,12 +176,161 @@ def read_config(path):
     return fs, centre, decim, taps, chans
 
 
+ROUTE_STAGES = ("ais", "pocsag", "flex", "none")
+MAX_ROUTES = 8   # MFM_RUNROUTE_MAX_ROUTES
+
+
+def read_routes(path, nr_channels):
+    """--gate-route FILE: {"routes": [{"name", "stage", "resample", "taps", "channels", and optionally "dc_pole", "bits"}]}, checked;
+    what is wrong ends the run with a message"""
+    routes = json.load(open(path))["routes"]
+    if not 1 <= len(routes) <= MAX_ROUTES:
+        raise SystemExit(f"--gate-route: {len(routes)} routes; the run router takes 1 .. {MAX_ROUTES}")
+    names, owner = set(), {}
+    for r in routes:
+        name = r.get("name", "")
+        if not name or name in names or os.sep in name or name in (".", ".."):
+            raise SystemExit(f"--gate-route: a route's name is its folder under --gate-out: {name!r} is empty, used twice or a path")
+        names.add(name)
+        if r.get("stage") not in ROUTE_STAGES:
+            raise SystemExit(f"--gate-route: route {name}: stage {r.get('stage')!r} is none of {', '.join(ROUTE_STAGES)}")
+        if not r.get("resample") or not r.get("taps"):
+            raise SystemExit(f"--gate-route: route {name} needs resample (I/D) and taps (a JSON file whose lpfCoeffs are the taps)")
+        if r.get("bits") and r["stage"] not in ("ais", "pocsag"):
+            raise SystemExit(f"--gate-route: route {name}: bits needs stage ais or pocsag: the burst FLEX stage reads PCM values, not sign bits")
+        if r.get("bits") and r.get("dc_pole") is not None:
+            raise SystemExit(f"--gate-route: route {name}: dc_pole and bits exclude each other: the DC blocker filters the PCM the sign "
+                             "bits would be taken from")
+        for c in r.get("channels", []):
+            if not isinstance(c, int) or not 0 <= c < nr_channels:
+                raise SystemExit(f"--gate-route: route {name}: channel {c!r} is not one of the configuration's {nr_channels}")
+            if c in owner:
+                raise SystemExit(f"--gate-route: channel {c} is in two routes ({owner[c]} and {name}): a channel has one route")
+            owner[c] = name
+        r["channels"] = list(r.get("channels", []))
+    return routes
+
+
+class BurstChain:
+    """burst resampler -> burst stage (ais, pocsag, flex or None) behind one run list - the gate's, or with --gate-route one
+    route's of the run router - and the files the two write under out_dir; view() returns the run list's device view"""
+
+    def __init__(self, pkg, out_dir, window, nr_channels, max_in_samples, preroll, device, view, resample, taps_file, dc_pole=None,
+                 stage=None, bits=False):
+        b = self.b = pkg.binding
+        self.out_dir, self.window, self.view = out_dir, window, view
+        interp, decim_rs = [int(x) for x in resample.split("/")]
+        co = np.array([int(float(t) * 16384.0) for t in json.load(open(taps_file))["lpfCoeffs"]], np.int16)  # decoder.c:530-533
+        self.rr = pkg.RunResampler(nr_channels, co, interp, decim_rs, window, max_in_samples=max_in_samples, preroll_windows=preroll,
+                                   device=device)
+        if dc_pole is not None:
+            self.rr.set_dc_block(dc_pole)
+        self.rs_index, self.rs_started = open(os.path.join(out_dir, "resampled.jsonl"), "w"), set()
+        self.stage = stage
+        self.st, self.st_index, self.pages_index, self.pagers = None, None, None, {}
+        if stage:
+            self.st = {"ais": pkg.RunAis, "pocsag": pkg.RunPocsag, "flex": pkg.RunFlex}[stage].behind(self.rr, device=device)
+            self.st_index = open(os.path.join(out_dir, stage + ".jsonl"), "w")
+        if stage in ("pocsag", "flex"):
+            self.pages_index = open(os.path.join(out_dir, "pages.jsonl"), "w")
+        # --gate-bits: the predicate the stage behind the resampler reads
+        self.bits_polarity = (b.MFM_BITS_POS if stage == "ais" else b.MFM_BITS_NEG) if bits else 0
+
+    def run(self, stream):
+        """burst resampler and the stage behind it on the run list's last result"""
+        rr, st = self.rr, self.st
+        if self.bits_polarity:
+            rr.process_bits_device(*self.view(), self.bits_polarity, stream=stream)
+            st.process_bits_device(rr.bits_view(), stream=stream)
+            return
+        rr.process_device(*self.view(), stream=stream)
+        if st:
+            st.process_device(*rr.device_view(), stream=stream)
+
+    def write(self):
+        """fetch the last call's results and append them to the files"""
+        if self.bits_polarity:
+            self.write_resampled_runs(self.rr.fetch_bits()[0])
+        else:
+            self.write_resampled(*self.rr.fetch())
+        if self.stage == "ais":
+            self.write_ais(self.st.fetch())
+        if self.stage == "pocsag":
+            self.write_pocsag(self.st.fetch())
+        if self.stage == "flex":
+            self.write_flex(*self.st.fetch())
+
+    def close(self):
+        for hp in self.pagers.values():
+            hp.close()
+        for f in (self.rs_index, self.st_index, self.pages_index):
+            if f:
+                f.close()
+        if self.st:
+            self.st.close()
+        self.rr.close()
+
+    def write_flex(self, events, frames):
+        """the events, and the messages of a fresh host FLEX pager per (channel, stretch)"""
+        b, pagers = self.b, self.pagers
+        for e in events:
+            c, first = int(e["channel"]), int(e["stretch_window"]) * self.window
+            line = {"channel": c, "first_sample": first}
+            line.update({f: int(e[f]) for f in FLEX_LINE_FIELDS})
+            self.st_index.write(json.dumps(line) + "\n")
+            if c not in pagers or pagers[c].first != first:
+                if c in pagers:
+                    pagers[c].close()
+                pagers[c] = HostFlexPager(c, first, self.pages_index)
+            pagers[c].on_events(b.runflex_to_flex_events(np.array([e], b.RUNFLEX_EVENT_DTYPE)), frames)
+
+    def write_pocsag(self, events):
+        """the events, and the pages of a fresh host pager per (channel, stretch)"""
+        b, pagers = self.b, self.pagers
+        for e in events:
+            c, first = int(e["channel"]), int(e["stretch_window"]) * self.window
+            self.st_index.write(json.dumps({"channel": c, "first_sample": first, "type": int(e["type"]), "baud": int(e["baud"]),
+                                            "sample": int(e["sample"]), "aux": int(e["aux"]), "nr_ok": int(e["nr_ok"]),
+                                            "fail_mask": int(e["fail_mask"]),
+                                            "corrected": ["%08x" % int(w) for w in e["corrected"]] if int(e["type"]) == 2 else []}) + "\n")
+            if c not in pagers or pagers[c].first != first:
+                if c in pagers:
+                    pagers[c].close()
+                pagers[c] = HostPager(c, first, self.pages_index)
+            pagers[c].on_events(b.runpocsag_to_pocsag_events(np.array([e], b.RUNPOCSAG_EVENT_DTYPE)))
+
+    def write_ais(self, events):
+        for e in events:
+            self.st_index.write(json.dumps({"channel": int(e["channel"]), "first_sample": int(e["stretch_window"]) * self.window,
+                                            "sample": int(e["sample"]), "start_sample": int(e["start_sample"]), "nr_bytes": int(e["nr_bytes"]),
+                                            "fcs_valid": int(e["fcs_valid"]), "bytes": bytes(e["bytes"][:int(e["nr_bytes"])]).hex()}) + "\n")
+
+    def write_resampled(self, runs, payload):
+        for r in runs:
+            c = int(r["channel"])
+            path = os.path.join(self.out_dir, "ch%04d.rs.s16" % c)
+            with open(path, "ab" if c in self.rs_started else "wb") as g:
+                at = g.tell()
+                payload[int(r["out_offset"]):int(r["out_offset"]) + int(r["nr_out"])].tofile(g)
+            self.rs_started.add(c)
+            self.rs_index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * self.window,
+                                            "first_out": int(r["first_out"]), "nr_out": int(r["nr_out"]), "begins": int(r["flags"]) & 1,
+                                            "file_offset": at}) + "\n")
+
+    def write_resampled_runs(self, runs):
+        """the bits form: the runs alone, no PCM left the resampler"""
+        for r in runs:
+            self.rs_index.write(json.dumps({"channel": int(r["channel"]), "first_sample": int(r["first_window"]) * self.window,
+                                            "first_out": int(r["first_out"]), "nr_out": int(r["nr_out"]), "begins": int(r["flags"]) & 1}) + "\n")
+
+
 def scan(a):
     import torch  # noqa: F401  (brings the HIP runtime up before the library does)
     from __graft_entry__ import load_package
     pkg = load_package()
     b = pkg.binding
     fs, centre, decim, taps, chans = read_config(a.config)
+    routes = read_routes(a.gate_route, len(chans)) if a.gate_route else None
     iq_form = a.form == "iq"
     sense = a.sense or ("above" if iq_form else "below")
     adaptive = a.floor_windows is not None
@@ -183,116 +354,41 @@ def scan(a):
         gate = pkg.Gate(len(chans), a.block // decim + 8, a.window, elems_per_sample=elems, device=a.device,
                         preroll_windows=int(a.gate_preroll))
         index = open(os.path.join(a.gate_out, "index.jsonl"), "w")
-    rr, rs_index, rs_started = None, None, set()
-    if a.gate_resample:
+    if a.gate_resample and (not gate or iq_form):
+        raise SystemExit("--gate-resample needs --gate-out and --form pcm: the burst resampler takes PCM payloads only")
+    if a.gate_resample and not a.resample_taps:
+        raise SystemExit("--gate-resample needs --resample-taps FILE")
+    if a.gate_ais and not a.gate_resample:
+        raise SystemExit("--gate-ais needs --gate-resample: the burst AIS stage takes the burst resampler's runs")
+    if a.gate_pocsag and not a.gate_resample:
+        raise SystemExit("--gate-pocsag needs --gate-resample: the burst POCSAG stage takes the burst resampler's runs")
+    if a.gate_pocsag and a.gate_ais:
+        raise SystemExit("--gate-pocsag and --gate-ais exclude each other: one stage reads the burst resampler's runs")
+    max_in = a.block // decim + 8
+    router, chains = None, []   # one chain behind the gate, or with --gate-route one per route behind the run router
+    if a.gate_resample:   # main() has refused --gate-flex without it or beside another stage
+        stage = "ais" if a.gate_ais else "pocsag" if a.gate_pocsag else "flex" if a.gate_flex else None
+        chains.append(BurstChain(pkg, a.gate_out, a.window, len(chans), max_in, int(a.gate_preroll), a.device, gate.device_view,
+                                 a.gate_resample, a.resample_taps, dc_pole=a.gate_dc_pole, stage=stage, bits=a.gate_bits))
+    if routes is not None:
         if not gate or iq_form:
-            raise SystemExit("--gate-resample needs --gate-out and --form pcm: the burst resampler takes PCM payloads only")
-        if not a.resample_taps:
-            raise SystemExit("--gate-resample needs --resample-taps FILE")
-        interp, decim_rs = [int(x) for x in a.gate_resample.split("/")]
-        co = np.array([int(float(t) * 16384.0) for t in json.load(open(a.resample_taps))["lpfCoeffs"]], np.int16)  # decoder.c:530-533
-        rr = pkg.RunResampler(len(chans), co, interp, decim_rs, a.window, max_in_samples=a.block // decim + 8,
-                              preroll_windows=int(a.gate_preroll), device=a.device)
-        if a.gate_dc_pole is not None:
-            rr.set_dc_block(a.gate_dc_pole)
-        rs_index = open(os.path.join(a.gate_out, "resampled.jsonl"), "w")
-    ra, ais_index = None, None
-    if a.gate_ais:
-        if not rr:
-            raise SystemExit("--gate-ais needs --gate-resample: the burst AIS stage takes the burst resampler's runs")
-        ra = pkg.RunAis.behind(rr, device=a.device)
-        ais_index = open(os.path.join(a.gate_out, "ais.jsonl"), "w")
-
-    rp, pocsag_index, pages_index, pagers = None, None, None, {}
-    if a.gate_pocsag:
-        if not rr:
-            raise SystemExit("--gate-pocsag needs --gate-resample: the burst POCSAG stage takes the burst resampler's runs")
-        if ra:
-            raise SystemExit("--gate-pocsag and --gate-ais exclude each other: one stage reads the burst resampler's runs")
-        rp = pkg.RunPocsag.behind(rr, device=a.device)
-        pocsag_index = open(os.path.join(a.gate_out, "pocsag.jsonl"), "w")
-        pages_index = open(os.path.join(a.gate_out, "pages.jsonl"), "w")
-
-    bits_polarity = 0   # --gate-bits: the predicate the stage behind the resampler reads
-    if a.gate_bits:
-        bits_polarity = b.MFM_BITS_POS if ra else b.MFM_BITS_NEG
+            raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
+        table = np.full(len(chans), b.MFM_ROUTE_NONE, np.uint8)
+        for k, r in enumerate(routes):
+            table[r["channels"]] = k
+        router = pkg.RunRouter.behind(table, len(routes), max_in, a.window, preroll_windows=int(a.gate_preroll), device=a.device)
+        for k, r in enumerate(routes):
+            os.makedirs(os.path.join(a.gate_out, r["name"]), exist_ok=True)
+            chains.append(BurstChain(pkg, os.path.join(a.gate_out, r["name"]), a.window, len(chans), max_in, int(a.gate_preroll), a.device,
+                                     lambda k=k: router.device_view(k), r["resample"], r["taps"], dc_pole=r.get("dc_pole"),
+                                     stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits"))))
 
     def run_stages():
-        """burst resampler and the stage behind it on the gate's last result"""
-        if bits_polarity:
-            rr.process_bits_device(*gate.device_view(), bits_polarity, stream=eng.stream)
-            (ra or rp).process_bits_device(rr.bits_view(), stream=eng.stream)
-            return
-        if rr:
-            rr.process_device(*gate.device_view(), stream=eng.stream)
-        if ra:
-            ra.process_device(*rr.device_view(), stream=eng.stream)
-        if rp:
-            rp.process_device(*rr.device_view(), stream=eng.stream)
-        if rf:
-            rf.process_device(*rr.device_view(), stream=eng.stream)
-
-    rf, flex_index, flex_pagers = None, None, {}
-    if a.gate_flex:   # main() has refused it without --gate-resample or beside another stage
-        rf = pkg.RunFlex.behind(rr, device=a.device)
-        flex_index = open(os.path.join(a.gate_out, "flex.jsonl"), "w")
-        pages_index = open(os.path.join(a.gate_out, "pages.jsonl"), "w")
-
-    def write_flex(events, frames):
-        """the events, and the messages of a fresh host FLEX pager per (channel, stretch)"""
-        for e in events:
-            c, first = int(e["channel"]), int(e["stretch_window"]) * a.window
-            line = {"channel": c, "first_sample": first}
-            line.update({f: int(e[f]) for f in FLEX_LINE_FIELDS})
-            flex_index.write(json.dumps(line) + "\n")
-            if c not in flex_pagers or flex_pagers[c].first != first:
-                if c in flex_pagers:
-                    flex_pagers[c].close()
-                flex_pagers[c] = HostFlexPager(c, first, pages_index)
-            flex_pagers[c].on_events(b.runflex_to_flex_events(np.array([e], b.RUNFLEX_EVENT_DTYPE)), frames)
-
-    def write_pocsag(events):
-        """the events, and the pages of a fresh host pager per (channel, stretch)"""
-        for e in events:
-            c, first = int(e["channel"]), int(e["stretch_window"]) * a.window
-            pocsag_index.write(json.dumps({"channel": c, "first_sample": first, "type": int(e["type"]), "baud": int(e["baud"]),
-                                           "sample": int(e["sample"]), "aux": int(e["aux"]), "nr_ok": int(e["nr_ok"]),
-                                           "fail_mask": int(e["fail_mask"]),
-                                           "corrected": ["%08x" % int(w) for w in e["corrected"]] if int(e["type"]) == 2 else []}) + "\n")
-            if c not in pagers or pagers[c].first != first:
-                if c in pagers:
-                    pagers[c].close()
-                pagers[c] = HostPager(c, first, pages_index)
-            pagers[c].on_events(b.runpocsag_to_pocsag_events(np.array([e], b.RUNPOCSAG_EVENT_DTYPE)))
-
-    def write_ais(events):
-        for e in events:
-            ais_index.write(json.dumps({"channel": int(e["channel"]), "first_sample": int(e["stretch_window"]) * a.window,
-                                        "sample": int(e["sample"]), "start_sample": int(e["start_sample"]), "nr_bytes": int(e["nr_bytes"]),
-                                        "fcs_valid": int(e["fcs_valid"]), "bytes": bytes(e["bytes"][:int(e["nr_bytes"])]).hex()}) + "\n")
-
-    def write_resampled(runs, payload):
-        for r in runs:
-            c = int(r["channel"])
-            path = os.path.join(a.gate_out, "ch%04d.rs.s16" % c)
-            with open(path, "ab" if c in rs_started else "wb") as g:
-                at = g.tell()
-                payload[int(r["out_offset"]):int(r["out_offset"]) + int(r["nr_out"])].tofile(g)
-            rs_started.add(c)
-            rs_index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * a.window, "first_out": int(r["first_out"]),
-                                       "nr_out": int(r["nr_out"]), "begins": int(r["flags"]) & 1, "file_offset": at}) + "\n")
-
-    def write_resampled_runs(runs):
-        """--gate-bits: the runs alone, no PCM left the resampler"""
-        for r in runs:
-            rs_index.write(json.dumps({"channel": int(r["channel"]), "first_sample": int(r["first_window"]) * a.window,
-                                       "first_out": int(r["first_out"]), "nr_out": int(r["nr_out"]), "begins": int(r["flags"]) & 1}) + "\n")
-
-    def fetch_resampled():
-        if bits_polarity:
-            write_resampled_runs(rr.fetch_bits()[0])
-        else:
-            write_resampled(*rr.fetch())
+        """the router, where there is one, and every chain on the gate's last result, all on the engine's stream"""
+        if router:
+            router.process_device(*gate.device_view(), stream=eng.stream)
+        for ch in chains:
+            ch.run(eng.stream)
 
     def write_runs(runs, payload):
         for r in runs:
@@ -335,14 +431,8 @@ def scan(a):
             fl = lv.fetch_floor() if adaptive else None
             if gate:
                 write_runs(*gate.fetch())
-            if rr:
-                fetch_resampled()
-            if ra:
-                write_ais(ra.fetch())
-            if rp:
-                write_pocsag(rp.fetch())
-            if rf:
-                write_flex(*rf.fetch())
+            for ch in chains:
+                ch.write()
             for c, (freq, _) in enumerate(chans):
                 for i, r in enumerate(rec[c]):
                     line = {"freq": freq, "channel": c, "window": int(r["window"]), "energy": int(r["energy"]),
@@ -364,29 +454,11 @@ def scan(a):
         gate.flush_device(stream=eng.stream)  # the windows pre-roll still held back; none with P = 0
         run_stages()
         write_runs(*gate.fetch())
-        if rr:
-            fetch_resampled()
-            rs_index.close()
-        if ra:
-            write_ais(ra.fetch())
-            ais_index.close()
-            ra.close()
-        if rp:
-            write_pocsag(rp.fetch())
-            for hp in pagers.values():
-                hp.close()
-            pocsag_index.close()
-            pages_index.close()
-            rp.close()
-        if rf:
-            write_flex(*rf.fetch())
-            for hp in flex_pagers.values():
-                hp.close()
-            flex_index.close()
-            pages_index.close()
-            rf.close()
-        if rr:
-            rr.close()
+        for ch in chains:
+            ch.write()
+            ch.close()
+        if router:
+            router.close()
         index.close()
         gate.close()
     lv.close()
@@ -1199,6 +1271,125 @@ def bench_runflex(a, pkg, torch):
     print(json.dumps(out))
 
 
+def bench_runroute(a, pkg, torch):
+    """the run router on the device view one gate call left, at 64 and 1024 channels, idle (noise) rows, the three masks of
+    runrs_stage.  (a) the router call alone beside the burst resampler's call on an all-closed view (a launch-overhead yardstick),
+    (b) a two-protocol capture, the first half of the channels POCSAG (4/5) and the second half FLEX (16/25): router + one burst
+    chain per route against two whole chains that each read every channel's runs.  Everything alternates in one process in
+    rotating order; every call begins every stretch anew, as in bench_runrs, so every call does the same work"""
+    b = pkg.binding
+    W, n = a.window, 1 << 15
+    nw = n // W
+    nb = nw * W
+    ptaps = np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16)
+    ftaps = np.round(pkg.synth.design_lpf(101, 0.45 / 25, 1.0) * 16 * 16384.0).astype(np.int16)
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    def ab(variants):
+        for _, fn in variants:
+            timed(fn, 3)
+        got = {v: [] for v, _ in variants}
+        for rep in range(a.reps):
+            j = rep % len(variants)
+            for vname, fn in variants[j:] + variants[:j]:
+                got[vname].append(timed(fn, a.inner))
+        return {v: _stats(x) for v, x in got.items()}
+
+    def verdict(x, y):
+        """x against y: the difference, its standard error, and tools/exp/ab.py's rule"""
+        d, se = x[0] - y[0], math.sqrt(x[1] * x[1] / a.reps + y[1] * y[1] / a.reps)
+        return {"difference_ms": d, "difference_se": se, "verdict": "neutral" if abs(d) <= 2.0 * se else ("faster" if d < 0 else "slower")}
+
+    out = {"bench": "runroute_stage", "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "reps": a.reps,
+           "calls_per_rep": a.inner, "routes": {"0": "pocsag 4/5, 41 taps, the first half of the channels",
+                                                "1": "flex 16/25, 101 taps, the second half"}}
+    rng = np.random.RandomState(1)
+    for nch in (64, 1024):
+        host = rng.randint(-3000, 3001, size=(nch, n)).astype(np.int16)
+        d_rows = torch.from_numpy(host).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "half_open": scene["open"]}
+        keep, recs = [], {"half_open": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        table = np.where(np.arange(nch) < nch // 2, 0, 1).astype(np.uint8)
+        router = pkg.RunRouter.behind(table, 2, n, W)
+        chains = {}
+        for side in ("routed", "full"):
+            rp_rr = pkg.RunResampler(nch, ptaps, 4, 5, W, max_in_samples=n, device=0)
+            rf_rr = pkg.RunResampler(nch, ftaps, 16, 25, W, max_in_samples=n, device=0)
+            chains[side] = (rp_rr, pkg.RunPocsag.behind(rp_rr), rf_rr, pkg.RunFlex.behind(rf_rr))
+        closed = pkg.Gate(nch, n, W, device=0)
+        closed.process_device(rows, in_stride, nb, recs["all_closed"][0], recs["all_closed"][1], nw)
+        closed_view = closed.device_view()
+        rr_closed = pkg.RunResampler(nch, ptaps, 4, 5, W, max_in_samples=n, device=0)
+        res = {}
+        for name in ("all_closed", "half_open", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_router():
+                router.process_device(*view)
+
+            def run_rr_closed():
+                rr_closed.process_device(*closed_view)
+
+            def run_chains(side, views):
+                rp_rr, rp, rf_rr, rf = chains[side]
+                rp_rr.process_device(*views[0])
+                rp.process_device(*rp_rr.device_view())
+                rf_rr.process_device(*views[1])
+                rf.process_device(*rf_rr.device_view())
+
+            def run_routed():
+                router.process_device(*view)
+                run_chains("routed", (router.device_view(0), router.device_view(1)))
+
+            def run_full():
+                run_chains("full", (view, view))
+
+            alone = ab([("router", run_router), ("runrs_all_closed", run_rr_closed)])
+            both = ab([("routed", run_routed), ("full", run_full)])
+            runs = [len(router.fetch(k)[0]) for k in range(2)]
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "gate_runs": sum(runs),
+                         "route_runs": runs, "router_ms": alone["router"][0], "router_sd": alone["router"][1],
+                         "runrs_all_closed_ms": alone["runrs_all_closed"][0], "runrs_all_closed_sd": alone["runrs_all_closed"][1],
+                         "routed_ms": both["routed"][0], "routed_sd": both["routed"][1], "full_ms": both["full"][0], "full_sd": both["full"][1],
+                         "routed_over_full": both["routed"][0] / both["full"][0], "routed_against_full": verdict(both["routed"], both["full"])}
+            gate.close()
+        out[str(nch)] = res
+        for side in chains.values():
+            for o in (side[1], side[3], side[0], side[2]):
+                o.close()
+        for o in (rr_closed, closed, router, sq):
+            o.close()
+        del d_rows, keep
+    print(json.dumps(out))
+
+
 def bench_runbits(a, pkg, torch):
     """the A/B of the sign-bit path: burst resampler -> burst stage in the PCM form and in the bits form on the device view one gate
     call left (every call begins every stretch anew, as in bench_runrs), alternating in one process in rotating order; AIS and
@@ -1298,6 +1489,15 @@ def bench_runbits_alone(a):
     bench_runbits(a, pkg, torch)
 
 
+def bench_runroute_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runroute needs the GPU: there is no CPU path to time")
+    bench_runroute(a, pkg, torch)
+
+
 def bench_runflex_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -1355,6 +1555,8 @@ def main():
     ap.add_argument("--gate-flex", action="store_true", help="decode FLEX on the resampled runs on the device (with --gate-resample to 16 000 Hz)")
     ap.add_argument("--gate-bits", action="store_true",
                     help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
+    ap.add_argument("--gate-route", default=None,
+                    help="JSON file of routes: one gate feeds a burst chain per protocol through the run router (with --gate-out, --form pcm)")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--bench-level-adaptive", action="store_true", help="the level_adaptive_stage line of --bench alone")
     ap.add_argument("--bench-floor-windows", default="64,1,1024", help="the M's of the level_adaptive_stage line; the first against the fixed path")
@@ -1363,6 +1565,7 @@ def main():
     ap.add_argument("--bench-runpocsag", action="store_true", help="the runpocsag_stage line of --bench alone")
     ap.add_argument("--bench-runflex", action="store_true", help="the runflex_stage line alone")
     ap.add_argument("--bench-runbits", action="store_true", help="the runbits_stage line of --bench alone")
+    ap.add_argument("--bench-runroute", action="store_true", help="the runroute_stage line alone: the run router at 64 and 1024 channels")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
@@ -1375,6 +1578,8 @@ def main():
         return bench_runflex_alone(a)
     if a.bench_runbits:
         return bench_runbits_alone(a)
+    if a.bench_runroute:
+        return bench_runroute_alone(a)
     if a.bench or a.bench_runrs or a.bench_level_adaptive:
         return bench(a)
     if not a.config or not a.input:
@@ -1383,6 +1588,13 @@ def main():
         raise SystemExit("--floor-windows, --open-ratio and --close-ratio go together: the adaptive squelch needs all three")
     if a.warmup is not None and a.floor_windows is None:
         raise SystemExit("--warmup needs --floor-windows: it is the adaptive squelch's warm-up")
+    if a.gate_route and (a.gate_resample or a.gate_ais or a.gate_pocsag or a.gate_flex or a.gate_bits or a.gate_dc_pole is not None):
+        raise SystemExit("--gate-route excludes --gate-resample, --gate-ais, --gate-pocsag, --gate-flex, --gate-bits and --gate-dc-pole: "
+                         "every route names its own resampler and stage")
+    if a.gate_route and (not a.gate_out or a.form != "pcm"):
+        raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
+    if a.gate_route:
+        read_routes(a.gate_route, len(read_config(a.config)[4]))   # what is wrong with FILE ends the run before anything is set up
     if a.gate_flex and not a.gate_resample:
         raise SystemExit("--gate-flex needs --gate-resample: the burst FLEX stage takes the burst resampler's runs")
     if a.gate_flex and (a.gate_ais or a.gate_pocsag):

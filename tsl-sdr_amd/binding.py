@@ -83,6 +83,8 @@ ABI_SYMBOLS = [
     "mfm_runpocsag_store_state", "mfm_runflex_store_state",
     "mfm_hosttwin_runrs_state_check", "mfm_hosttwin_runais_state_check", "mfm_hosttwin_runpocsag_state_check",
     "mfm_hosttwin_runflex_state_check",
+    "mfm_runroute_create", "mfm_runroute_destroy", "mfm_runroute_process_device", "mfm_runroute_device_view", "mfm_runroute_fetch",
+    "mfm_runroute_get_capacity", "mfm_hosttwin_runroute_capacity", "mfm_hosttwin_runroute_call",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -249,6 +251,17 @@ class RunrsBitsView(C.Structure):
     """struct mfm_runrs_bits_view: the burst resampler's bits form, valid until its next process call of either form"""
     _fields_ = [("d_runs", C.c_void_p), ("d_bits", C.c_void_p), ("d_totals", C.c_void_p), ("polarity", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class RunRouteConfig(C.Structure):
+    """struct mfm_runroute_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("nr_routes", C.c_uint32),
+                ("window_samples", C.c_uint32), ("max_windows", C.c_uint32), ("max_runs", C.c_uint32), ("max_in_samples", C.c_uint32),
+                ("preroll_windows", C.c_uint32), ("flags", C.c_uint32)]
+
+
+MFM_RUNROUTE_MAX_ROUTES = 8
+MFM_ROUTE_NONE = 255    # a channel whose runs go to no route
 
 
 class RunaisConfig(C.Structure):
@@ -630,6 +643,15 @@ def load_library():
     lib.mfm_hosttwin_runais_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runpocsag_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runflex_state_check.argtypes = [C.c_uint32, vp]
+    lib.mfm_runroute_create.argtypes = [C.POINTER(vp), C.POINTER(RunRouteConfig), vp]
+    lib.mfm_runroute_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runroute_destroy.restype = None
+    lib.mfm_runroute_process_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mfm_runroute_device_view.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runroute_fetch.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp, szp]
+    lib.mfm_runroute_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.mfm_hosttwin_runroute_capacity.argtypes = [C.POINTER(RunRouteConfig), vp, C.POINTER(C.c_uint32)]
+    lib.mfm_hosttwin_runroute_call.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
     lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                               C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -1833,6 +1855,133 @@ class RunResampler:
                                             d.ctypes.data if d is not None else None, n)
         if rc < 0:
             self._raise(rc, "mfm_runrs_store_state")
+
+
+def _route_table(route_of_channel):
+    t = np.ascontiguousarray(route_of_channel, dtype=np.uint8).reshape(-1)
+    return t, (t.ctypes.data if t.size else None)
+
+
+class RunRouter:
+    """mfm_runroute: the runs of a Gate's device view partitioned by a per-channel route table (a route below nr_routes, or
+    MFM_ROUTE_NONE), so that one gate feeds a burst chain per protocol.  Zero-copy: device_view(route) is that route's run list
+    with the gate's payload pointer, and goes where Gate.device_view() goes.  A route's RunResampler is made with the whole
+    gate's numbers (all channels): channel numbers stay global."""
+
+    def __init__(self, route_of_channel, nr_routes, window_samples=0, max_in_samples=0, preroll_windows=0, max_windows=0, max_runs=0,
+                 device=0, flags=0, abi_version=MFM_ABI_VERSION, nr_channels=None):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        table, ptr = _route_table(route_of_channel)
+        nch = table.size if nr_channels is None else nr_channels
+        cfg = RunRouteConfig(abi_version, device, nch, nr_routes, window_samples, max_windows, max_runs, max_in_samples, preroll_windows, flags)
+        rc = self.lib.mfm_runroute_create(C.byref(self.h), C.byref(cfg), ptr)
+        if rc < 0:
+            self._raise(rc, "mfm_runroute_create")
+        self.nr_channels = nch
+        self.nr_routes = nr_routes
+
+    @classmethod
+    def behind(cls, route_of_channel, nr_routes, max_in_samples, window_samples, preroll_windows=0, max_open_windows=0, device=0):
+        """a router sized for everything one call of a Gate made from these numbers can hand over (its max_in_samples,
+        window_samples, preroll_windows and max_open_windows): the capacity a RunResampler made from them has"""
+        return cls(route_of_channel, nr_routes, window_samples=window_samples, max_in_samples=max_in_samples,
+                   preroll_windows=preroll_windows, max_windows=max_open_windows, device=device)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runroute_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_payload, d_totals, stream=None):
+        """the three addresses of Gate.device_view(), after the gate's process_device or flush_device on the same stream"""
+        rc = self.lib.mfm_runroute_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals),
+                                                  C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runroute_process_device")
+
+    def device_view(self, route):
+        """(d_runs, d_payload, d_totals) of one route, for RunResampler.process_device / process_bits_device: its run list, the
+        gate's payload pointer and its four uint64 totals (runs, the gate's payload elements, overflow, out of step)"""
+        r, p, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runroute_device_view(self.h, route, C.byref(r), C.byref(p), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runroute_device_view")
+        return r.value, p.value, t.value
+
+    def fetch(self, route, max_runs=None):
+        """(runs, nr_elems) of one route of the last call: GATE_RUN_DTYPE [nr_runs] and the gate's payload elements.  With
+        max_runs too small: MfmError(MFM_E_NOMEM) whose `needed` attribute is the runs that would fit"""
+        nr, ne = C.c_size_t(), C.c_size_t()
+        if max_runs is None:
+            rc = self.lib.mfm_runroute_fetch(self.h, route, None, 0, C.byref(nr), C.byref(ne))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below, with the untouched buffer
+                self._raise(rc, "mfm_runroute_fetch")
+            max_runs = nr.value
+        runs = np.zeros(max(max_runs, 1), GATE_RUN_DTYPE)
+        rc = self.lib.mfm_runroute_fetch(self.h, route, runs.ctypes.data, max_runs, C.byref(nr), C.byref(ne))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runroute_fetch")
+            except MfmError as err:
+                err.needed = nr.value
+                err.buffers = (runs,)
+                raise
+        return runs[:nr.value].copy(), ne.value
+
+    def capacity(self):
+        """max_runs: the most runs one gate call may carry, as given or the RunResampler's default for the same numbers"""
+        nr = C.c_uint32()
+        rc = self.lib.mfm_runroute_get_capacity(self.h, C.byref(nr))
+        if rc < 0:
+            self._raise(rc, "mfm_runroute_get_capacity")
+        return nr.value
+
+
+def hosttwin_runroute_capacity(route_of_channel, nr_routes, window_samples=0, max_in_samples=0, preroll_windows=0, max_windows=0,
+                               max_runs=0, flags=0, abi_version=MFM_ABI_VERSION, nr_channels=None):
+    """mfm_hosttwin_runroute_capacity: what RunRouter(...) with these arguments checks and derives, without a device: the run
+    capacity, or MfmError(MFM_E_INVAL) with create's message"""
+    lib = load_library()
+    table, ptr = _route_table(route_of_channel)
+    nch = table.size if nr_channels is None else nr_channels
+    cfg = RunRouteConfig(abi_version, 0, nch, nr_routes, window_samples, max_windows, max_runs, max_in_samples, preroll_windows, flags)
+    cap = C.c_uint32()
+    rc = lib.mfm_hosttwin_runroute_capacity(C.byref(cfg), ptr, C.byref(cap))
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runroute_capacity", lib.mfm_last_error().decode())
+    return cap.value
+
+
+def hosttwin_runroute_call(route_of_channel, nr_routes, gate_runs, gate_totals, max_runs=None, runs=None):
+    """mfm_hosttwin_runroute_call: one call of the router on the CPU.  gate_runs GATE_RUN_DTYPE [n], gate_totals the gate's four
+    uint64; max_runs the router's capacity (default: len(gate_runs)).  Returns (runs, totals): GATE_RUN_DTYPE [nr_routes][max_runs]
+    (`runs` given: written in place; the used part of row k is totals[k][0] long) and uint64 [nr_routes][4]"""
+    lib = load_library()
+    table, ptr = _route_table(route_of_channel)
+    gr = np.ascontiguousarray(gate_runs, dtype=GATE_RUN_DTYPE)
+    gt = np.ascontiguousarray(gate_totals, dtype=np.uint64)
+    assert gt.shape == (4,)
+    max_runs = len(gr) if max_runs is None else max_runs
+    if runs is None:
+        runs = np.zeros((max(nr_routes, 1), max(max_runs, 1)), GATE_RUN_DTYPE)
+    assert runs.dtype == GATE_RUN_DTYPE and runs.flags.c_contiguous and runs.shape[1] == max(max_runs, 1)
+    totals = np.zeros((max(nr_routes, 1), 4), np.uint64)
+    stride = runs.shape[1]   # rows are max(max_runs, 1) apart: with max_runs 0 nothing is written
+    rc = lib.mfm_hosttwin_runroute_call(table.size, nr_routes, ptr, stride if max_runs else 0, gr.ctypes.data if gr.size else None,
+                                        gt.ctypes.data, runs.ctypes.data, totals.ctypes.data)
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runroute_call", lib.mfm_last_error().decode() or lib.mfm_strerror(rc).decode())
+    return runs, totals[:nr_routes]
 
 
 class RunAis:

@@ -58,6 +58,33 @@ inline const char *mfm_runrs_dc_state_check(const mfm_runrs_dc_state &dc)
     return dc.reserved ? "the DC blocker's reserved must be 0" : nullptr;
 }
 
+/*
+ * What one gate call can hand over, in windows and in runs, from the numbers of mfm_runrs_config (the run router,
+ * mfm_runroute.hip, sizes itself by the same rule): max_windows and max_runs as given, and for a 0 the gate's own default.
+ * false when a default is asked for and max_in_samples, which it is formed from, is 0.
+ */
+struct mfm_runrs_caps {
+    uint64_t windows, runs;
+};
+
+inline bool mfm_runrs_caps_of(uint32_t nr_channels, uint32_t window_samples, uint32_t max_windows, uint32_t max_runs, uint32_t max_in_samples,
+                              uint32_t preroll_windows, mfm_runrs_caps &c)
+{
+    const uint64_t max_win = max_in_samples ? (uint64_t)max_in_samples / window_samples + 1u : 0u;
+    const uint64_t per_chan = max_win > preroll_windows ? max_win : preroll_windows; /* a flush emits up to P windows */
+    if ((0 == max_windows || 0 == max_runs) && 0 == max_in_samples) {
+        return false;
+    }
+    c.windows = max_windows ? max_windows : (uint64_t)nr_channels * per_chan;
+    if (max_runs) {
+        c.runs = max_runs;
+    } else {
+        const uint64_t most = (uint64_t)nr_channels * ((per_chan + 1u) / 2u); /* two runs of a channel have a closed window between them */
+        c.runs = c.windows < most ? c.windows : most;
+    }
+    return true;
+}
+
 /* what a run starts from */
 struct mfm_runrs_start {
     uint64_t first_out;

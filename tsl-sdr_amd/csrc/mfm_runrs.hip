@@ -147,19 +147,13 @@ int rr_geometry(const mfm_runrs_config &cfg, const int16_t *coeffs, size_t nr_co
         return MFM_OK;
     }
     /* capacities: what one gate call can hand over */
-    const uint64_t max_win = cfg.max_in_samples ? (uint64_t)cfg.max_in_samples / g.W + 1u : 0u;
-    const uint64_t per_chan = max_win > cfg.preroll_windows ? max_win : cfg.preroll_windows; /* a flush emits up to P windows */
-    if ((0 == cfg.max_windows || 0 == cfg.max_runs) && 0 == cfg.max_in_samples) {
+    mfm_runrs_caps caps;
+    if (!mfm_runrs_caps_of(g.C, g.W, cfg.max_windows, cfg.max_runs, cfg.max_in_samples, cfg.preroll_windows, caps)) {
         snprintf(g.err, sizeof(g.err), "max_windows or max_runs is 0 (the gate's default) and max_in_samples is 0: give the gate's max_in_samples");
         return MFM_E_INVAL;
     }
-    g.cap_windows = cfg.max_windows ? cfg.max_windows : (uint64_t)g.C * per_chan;
-    if (cfg.max_runs) {
-        g.cap_runs = cfg.max_runs;
-    } else {
-        const uint64_t most = (uint64_t)g.C * ((per_chan + 1u) / 2u); /* two runs of a channel have a closed window between them */
-        g.cap_runs = g.cap_windows < most ? g.cap_windows : most;
-    }
+    g.cap_windows = caps.windows;
+    g.cap_runs = caps.runs;
     g.cap_elems = g.cap_windows * g.W;
     /* a run of n samples that meets p <= plen pending ones produces at most (n + p) I / D + 1 outputs */
     g.out_cap = ((g.cap_elems + g.cap_runs * g.plen) * g.I) / g.D + g.cap_runs;
