@@ -1236,7 +1236,8 @@ int mfm_runrs_store_state(struct mfm_runrs *rr, const struct mfm_runrs_state *st
  * Sizing what stands behind.  Channel numbers stay global, so events keep true channel numbers and stretch_window; a route's
  * burst resampler is therefore created with the WHOLE gate's numbers (the same nr_channels, max_windows and max_runs), and its
  * state and output buffers are sized for all channels.  Packing a dense payload per route would let the stages behind be
- * sized to the route, at the price of a copy of every open window; the router does not do that.
+ * sized to the route, at the price of a copy of every open window; a router made by mfm_runroute_create does not do that, one made
+ * by mfm_runroute_create_sets with MFM_RUNROUTE_F_PACK (below) does.
  *
  * Refusals at create (MFM_E_INVAL with a message, never a fallback): nr_routes outside 1 .. MFM_RUNROUTE_MAX_ROUTES, a table
  * entry that is neither below nr_routes nor MFM_ROUTE_NONE, non-zero flags, nr_channels or window_samples out of range, a
@@ -1286,6 +1287,64 @@ int mfm_runroute_device_view(struct mfm_runroute *rt, uint32_t route, const stru
 int mfm_runroute_fetch(struct mfm_runroute *rt, uint32_t route, struct mfm_gate_run *runs, size_t max_runs, size_t *nr_runs, size_t *nr_elems);
 /* The run capacity fixed at create: max_runs as given or its default. */
 int mfm_runroute_get_capacity(struct mfm_runroute *rt, uint32_t *max_runs);
+
+/*
+ * ---- Run router, the sets form: shared channels, and packed routes sized to the route ---------------------------------
+ * Paging carriers time-share one frequency between POCSAG and FLEX, so a channel may have to reach two chains; and a route's
+ * chain behind the zero-copy router is sized for all channels.  mfm_runroute_create_sets takes the same configuration and
+ * returns the same object type: mfm_runroute_process_device, _device_view, _fetch, _get_capacity and _destroy work on it
+ * unchanged.  mfm_runroute_create and what it refuses stay as they are.
+ *
+ * Input.  routes_of_channel [nr_channels]: a SET per channel, bit k set = the channel's runs go to route k, 0 = nowhere.  A
+ * bit at or above nr_routes is MFM_E_INVAL with a message that names the channel.  cfg->flags is 0 or MFM_RUNROUTE_F_PACK.
+ *
+ * Without PACK the router stays zero-copy with global channel numbers: route k's list is the gate's records whose channel's
+ * set has bit k, byte for byte, as a stable partition; a run of a shared channel stands in several lists.  Totals and the
+ * three refusals are those of the section above, and a table with one bit per channel gives byte for byte what
+ * mfm_runroute_create gives for the corresponding route table.
+ *
+ * With PACK every route gets route-local channel numbers and a dense payload of its own.  Route k's record i is the gate's
+ * record with `channel` replaced by the channel's rank among the route's channels (ascending: the numbering is fixed for the
+ * object's life, channels still ascend, and mfm_runroute_route_channels inverts it) and `payload_offset` replaced by the sum of
+ * nr_windows * W over the route's earlier records; first_window and nr_windows are untouched.  The route's payload holds
+ * exactly those windows, copied from the gate's payload at the gate's payload_offset (which need not be dense).  d_totals[4] =
+ * { runs, the route's payload elements, overflow, out of step }.  mfm_runroute_device_view returns the route's own payload
+ * buffer, fixed at create.  The list beyond the totals' runs and the payload beyond the totals' elements are not defined.
+ *
+ * Refused calls.  The gate's two flags, more runs than the router's max_runs and a run of a channel >= nr_channels flag every
+ * route as above.  Under PACK a run whose payload range does not lie within the gate's payload elements does the same (out of
+ * step: the copy would read it), and a route whose runs or windows in one call exceed its own capacity (below) gets
+ * overflow = 1 with 0 runs and 0 elements: nothing is written past the capacity and the other routes are unaffected.
+ *
+ * Sizing what stands behind: mfm_runroute_route_caps returns the three numbers to create route k's burst resampler with
+ * (mfm_runrs_config.nr_channels, max_windows, max_runs).  Without PACK, and for an object of mfm_runroute_create, these are the
+ * whole gate's: nr_channels, cfg->max_windows as given (0 stays 0, the burst resampler's default) and the router's max_runs.
+ * With PACK, for a route of n channels and per = max(max_in_samples / W + 1, preroll_windows):
+ *   nr_channels = n
+ *   max_windows = n * per, and no more than an explicit cfg->max_windows
+ *   max_runs    = min(max_windows, n * ((per + 1) / 2)), and no more than an explicit cfg->max_runs
+ * which is the burst resampler's own rule (mfm_runrs_config) for n channels.  With max_in_samples == 0 there is no default to
+ * form: max_windows and max_runs must both be given and are returned as given.  A burst resampler made from the three numbers
+ * never answers MFM_RUNRS_OVER_OWN to a call the router did not flag; with the defaults no route can overflow at all.
+ *
+ * Refusals at create (MFM_E_INVAL with a message): those of mfm_runroute_create, flags other than 0 or MFM_RUNROUTE_F_PACK,
+ * a set with a bit at or above nr_routes; under PACK a route without a channel, window_samples out of range, and
+ * max_in_samples == 0 without both max_windows and max_runs.
+ */
+#define MFM_RUNROUTE_F_PACK 1u
+
+int mfm_runroute_create_sets(struct mfm_runroute **prt, const struct mfm_runroute_config *cfg, const uint8_t *routes_of_channel);
+/* The global channel numbers of route `route`, ascending: under PACK local channel i is channels[i].  Valid for every router
+ * object.  *nr = the route's channels; MFM_E_NOMEM when max is too small (the first max are written). */
+int mfm_runroute_route_channels(struct mfm_runroute *rt, uint32_t route, uint32_t *channels, size_t max, size_t *nr);
+/* The numbers to create route `route`'s burst resampler with, by the rule above.  Any of the three may be NULL. */
+int mfm_runroute_route_caps(struct mfm_runroute *rt, uint32_t route, uint32_t *nr_channels, uint32_t *max_windows, uint32_t *max_runs);
+/*
+ * PACK only (MFM_E_INVAL with a message otherwise): wait for the last call as mfm_runroute_fetch does and copy route `route`'s
+ * payload.  *nr_elems = the route's payload elements; MFM_E_NOMEM when max_elems is too small (nothing copied); MFM_E_STATE
+ * with a message when the call or the route was refused.
+ */
+int mfm_runroute_fetch_payload(struct mfm_runroute *rt, uint32_t route, int16_t *payload, size_t max_elems, size_t *nr_elems);
 
 /*
  * ---- Burst AIS stage: the burst resampler's runs through the AIS demodulator, on the device -----------------------------
@@ -1861,6 +1920,22 @@ int mfm_hosttwin_runroute_capacity(const struct mfm_runroute_config *cfg, const 
  * MFM_E_INVAL with a message for a table or a nr_routes that create refuses. */
 int mfm_hosttwin_runroute_call(uint32_t nr_channels, uint32_t nr_routes, const uint8_t *route_of_channel, size_t max_runs,
                                const struct mfm_gate_run *gate_runs, const uint64_t *gate_totals, struct mfm_gate_run *runs, uint64_t *totals);
+/* what mfm_runroute_create_sets checks and mfm_runroute_route_caps then returns for `route`, no device needed: MFM_OK with the
+ * three numbers (any may be NULL), or MFM_E_INVAL with create's message */
+int mfm_hosttwin_runroute_route_caps(const struct mfm_runroute_config *cfg, const uint8_t *routes_of_channel, uint32_t route,
+                                     uint32_t *nr_channels, uint32_t *max_windows, uint32_t *max_runs);
+/* host twin of one mfm_runroute_process_device call on an object of mfm_runroute_create_sets, no device needed
+ * (csrc/mfm_runroute.h: the set lookup, the rank and the refusal predicates its kernels run).  flags is 0 or
+ * MFM_RUNROUTE_F_PACK; max_runs is the router's capacity.  Route k's list goes to runs + k * max_runs and its totals to
+ * totals + 4 * k.  Under PACK route_max_runs [nr_routes] and route_max_windows [nr_routes] are the routes' own capacities
+ * (what mfm_runroute_route_caps returns; none may exceed max_runs, or max_elems / window_samples), gate_payload is the gate's
+ * payload of gate_totals[1] elements, and route k's payload goes to payloads + k * max_elems; without PACK the four and
+ * window_samples are not read.  A refused call, or a refused route, returns MFM_OK as the device does, with the flags in the
+ * totals and nothing else written for it. */
+int mfm_hosttwin_runroute_sets_call(uint32_t nr_channels, uint32_t nr_routes, const uint8_t *routes_of_channel, uint32_t flags,
+                                    uint32_t window_samples, size_t max_runs, const uint32_t *route_max_runs, const uint32_t *route_max_windows,
+                                    const struct mfm_gate_run *gate_runs, const int16_t *gate_payload, const uint64_t *gate_totals,
+                                    struct mfm_gate_run *runs, uint64_t *totals, int16_t *payloads, size_t max_elems);
 /* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream.
  * Fields a mode does not use are zero.  What a stored state must satisfy: csrc/mfm_runais.h (mfm_runais_state_check) */
 struct mfm_runais_state {       /* 264 bytes */

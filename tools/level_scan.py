@@ -104,7 +104,17 @@ with ais or pocsag, never with dc_pole); a channel may stand in one route at mos
 further.  Each route runs burst resampler -> stage on its view of the router, on the engine's stream, the flush call included, and
 writes under DIR/<name>/ the files the single-stage flags write under DIR, with the same line shapes: resampled.jsonl,
 chNNNN.rs.s16, ais.jsonl / pocsag.jsonl / flex.jsonl, pages.jsonl.  Channel numbers stay those of the configuration.
-DIR/index.jsonl and DIR/chNNNN.s16 are the gate's, as without the flag.
+DIR/index.jsonl and DIR/chNNNN.s16 are the gate's, as without the flag.  Two optional keys beside "routes": "shared": true lets a
+channel stand in several routes (a carrier that time-shares POCSAG and FLEX reaches both chains), and "pack": true switches
+MFM_RUNROUTE_F_PACK on: every route gets a dense payload of its own and its chain is sized to its channels (every route then
+needs a channel); the files still carry the configuration's channel numbers.
+
+    python tools/level_scan.py --bench-runroute-pack [--window 1000] [--reps 8] [--inner 10] [--pack-only SHAPE/MASK]
+
+prints one line ("runroute_pack_stage"): packed routes against zero-copy routes at 64 and 1024 channels in 2 routes and 1024
+channels in 8, the three masks, as router + one chain per route in either form (mean and standard error, alternating in one
+process), the two router calls alone (their difference bounds the pack copy from above), the copy's bytes, and the device memory
+either form takes.  --pack-only 1024x2/half_open runs one case, for a kernel trace of its own.
 
     python tools/level_scan.py --bench-runroute [--window 1000] [--reps 8] [--inner 10]
 
@@ -181,9 +191,15 @@ MAX_ROUTES = 8   # MFM_RUNROUTE_MAX_ROUTES
 
 
 def read_routes(path, nr_channels):
-    """--gate-route FILE: {"routes": [{"name", "stage", "resample", "taps", "channels", and optionally "dc_pole", "bits"}]}, checked;
-    what is wrong ends the run with a message"""
-    routes = json.load(open(path))["routes"]
+    """--gate-route FILE: {"routes": [{"name", "stage", "resample", "taps", "channels", and optionally "dc_pole", "bits"}], and
+    optionally "shared": true (a channel may stand in several routes) and "pack": true (MFM_RUNROUTE_F_PACK: every route's chain
+    is sized to its channels)}, checked; what is wrong ends the run with a message.  Returns (routes, shared, pack)"""
+    doc = json.load(open(path))
+    routes = doc["routes"]
+    shared, pack = doc.get("shared", False), doc.get("pack", False)
+    for key, value in (("shared", shared), ("pack", pack)):
+        if not isinstance(value, bool):
+            raise SystemExit(f"--gate-route: \"{key}\" must be true or false, not {value!r}")
     if not 1 <= len(routes) <= MAX_ROUTES:
         raise SystemExit(f"--gate-route: {len(routes)} routes; the run router takes 1 .. {MAX_ROUTES}")
     names, owner = set(), {}
@@ -204,11 +220,13 @@ def read_routes(path, nr_channels):
         for c in r.get("channels", []):
             if not isinstance(c, int) or not 0 <= c < nr_channels:
                 raise SystemExit(f"--gate-route: route {name}: channel {c!r} is not one of the configuration's {nr_channels}")
-            if c in owner:
+            if c in owner and (not shared or owner[c] == name):
                 raise SystemExit(f"--gate-route: channel {c} is in two routes ({owner[c]} and {name}): a channel has one route")
             owner[c] = name
         r["channels"] = list(r.get("channels", []))
-    return routes
+        if pack and not r["channels"]:
+            raise SystemExit(f"--gate-route: route {name} has no channel: with \"pack\" every route's chain is sized to its channels")
+    return routes, shared, pack
 
 
 class BurstChain:
@@ -216,13 +234,21 @@ class BurstChain:
     route's of the run router - and the files the two write under out_dir; view() returns the run list's device view"""
 
     def __init__(self, pkg, out_dir, window, nr_channels, max_in_samples, preroll, device, view, resample, taps_file, dc_pole=None,
-                 stage=None, bits=False):
+                 stage=None, bits=False, caps=None, channels=None):
+        """caps and channels: behind a packed route of the run router, its route_caps() - the chain is sized to the route - and its
+        route_channels(), which turn the route-local channel numbers of everything fetched back into true ones"""
         b = self.b = pkg.binding
         self.out_dir, self.window, self.view = out_dir, window, view
+        self.channels = None if channels is None else np.asarray(channels, np.uint32)
         interp, decim_rs = [int(x) for x in resample.split("/")]
         co = np.array([int(float(t) * 16384.0) for t in json.load(open(taps_file))["lpfCoeffs"]], np.int16)  # decoder.c:530-533
-        self.rr = pkg.RunResampler(nr_channels, co, interp, decim_rs, window, max_in_samples=max_in_samples, preroll_windows=preroll,
-                                   device=device)
+        if caps is not None:
+            nr_channels, max_windows, max_runs = caps
+            self.rr = pkg.RunResampler(nr_channels, co, interp, decim_rs, window, max_in_samples=max_in_samples, preroll_windows=preroll,
+                                       max_windows=max_windows, max_runs=max_runs, device=device)
+        else:
+            self.rr = pkg.RunResampler(nr_channels, co, interp, decim_rs, window, max_in_samples=max_in_samples, preroll_windows=preroll,
+                                       device=device)
         if dc_pole is not None:
             self.rr.set_dc_block(dc_pole)
         self.rs_index, self.rs_started = open(os.path.join(out_dir, "resampled.jsonl"), "w"), set()
@@ -250,15 +276,24 @@ class BurstChain:
     def write(self):
         """fetch the last call's results and append them to the files"""
         if self.bits_polarity:
-            self.write_resampled_runs(self.rr.fetch_bits()[0])
+            self.write_resampled_runs(self.true_channels(self.rr.fetch_bits()[0]))
         else:
-            self.write_resampled(*self.rr.fetch())
+            runs, payload = self.rr.fetch()
+            self.write_resampled(self.true_channels(runs), payload)
         if self.stage == "ais":
-            self.write_ais(self.st.fetch())
+            self.write_ais(self.true_channels(self.st.fetch()))
         if self.stage == "pocsag":
-            self.write_pocsag(self.st.fetch())
+            self.write_pocsag(self.true_channels(self.st.fetch()))
         if self.stage == "flex":
-            self.write_flex(*self.st.fetch())
+            events, frames = self.st.fetch()
+            self.write_flex(self.true_channels(events), frames)
+
+    def true_channels(self, records):
+        """behind a packed route: the records with their route-local channel numbers mapped back, before anything is written"""
+        if self.channels is not None and len(records):
+            records = records.copy()
+            records["channel"] = self.channels[records["channel"]]
+        return records
 
     def close(self):
         for hp in self.pagers.values():
@@ -330,7 +365,7 @@ def scan(a):
     pkg = load_package()
     b = pkg.binding
     fs, centre, decim, taps, chans = read_config(a.config)
-    routes = read_routes(a.gate_route, len(chans)) if a.gate_route else None
+    routes, shared, pack = read_routes(a.gate_route, len(chans)) if a.gate_route else (None, False, False)
     iq_form = a.form == "iq"
     sense = a.sense or ("above" if iq_form else "below")
     adaptive = a.floor_windows is not None
@@ -373,15 +408,23 @@ def scan(a):
     if routes is not None:
         if not gate or iq_form:
             raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
-        table = np.full(len(chans), b.MFM_ROUTE_NONE, np.uint8)
-        for k, r in enumerate(routes):
-            table[r["channels"]] = k
-        router = pkg.RunRouter.behind(table, len(routes), max_in, a.window, preroll_windows=int(a.gate_preroll), device=a.device)
+        if shared or pack:   # a set of routes per channel
+            table = np.zeros(len(chans), np.uint8)
+            for k, r in enumerate(routes):
+                table[r["channels"]] |= 1 << k
+            router = pkg.RunRouter.behind(None, len(routes), max_in, a.window, preroll_windows=int(a.gate_preroll), device=a.device,
+                                          sets=table, pack=pack)
+        else:
+            table = np.full(len(chans), b.MFM_ROUTE_NONE, np.uint8)
+            for k, r in enumerate(routes):
+                table[r["channels"]] = k
+            router = pkg.RunRouter.behind(table, len(routes), max_in, a.window, preroll_windows=int(a.gate_preroll), device=a.device)
         for k, r in enumerate(routes):
             os.makedirs(os.path.join(a.gate_out, r["name"]), exist_ok=True)
+            sized = dict(caps=router.route_caps(k), channels=router.route_channels(k)) if pack else {}
             chains.append(BurstChain(pkg, os.path.join(a.gate_out, r["name"]), a.window, len(chans), max_in, int(a.gate_preroll), a.device,
                                      lambda k=k: router.device_view(k), r["resample"], r["taps"], dc_pole=r.get("dc_pole"),
-                                     stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits"))))
+                                     stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits")), **sized))
 
     def run_stages():
         """the router, where there is one, and every chain on the gate's last result, all on the engine's stream"""
@@ -1390,6 +1433,145 @@ def bench_runroute(a, pkg, torch):
     print(json.dumps(out))
 
 
+def bench_runroute_pack(a, pkg, torch):
+    """packed routes against zero-copy routes (RunRouter(sets=..., pack=True / False)) on the scene of bench_runroute: 64 and 1024
+    channels in 2 routes (POCSAG 4/5 and FLEX 16/25 halves) and 1024 channels in 8 routes (eighths, POCSAG and FLEX in turn), the
+    three masks.  Per shape and mask, alternating in one process in rotating order: (a) router + one chain per route, the chains
+    sized by route_caps() of either form; (b) the two router calls alone, whose difference is the pack copy and the partition's
+    window sums together - an upper bound of the copy kernel's time, beside the bytes it reads and writes.  The device bytes of
+    either form are the drop of free device memory across the creation of its objects"""
+    b = pkg.binding
+    W, n = a.window, 1 << 15
+    nw = n // W
+    nb = nw * W
+    taps = {"pocsag": (np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16), 4, 5),
+            "flex": (np.round(pkg.synth.design_lpf(101, 0.45 / 25, 1.0) * 16 * 16384.0).astype(np.int16), 16, 25)}
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    def ab(variants):
+        for _, fn in variants:
+            timed(fn, 3)
+        got = {v: [] for v, _ in variants}
+        for rep in range(a.reps):
+            j = rep % len(variants)
+            for vname, fn in variants[j:] + variants[:j]:
+                got[vname].append(timed(fn, a.inner))
+        return {v: (_stats(x)[0], _stats(x)[1] / math.sqrt(a.reps)) for v, x in got.items()}   # mean, standard error
+
+    def verdict(x, y):
+        """x against y: the difference, its standard error, and tools/exp/ab.py's rule"""
+        d, se = x[0] - y[0], math.sqrt(x[1] * x[1] + y[1] * y[1])
+        return {"difference_ms": d, "difference_se": se, "verdict": "neutral" if abs(d) <= 2.0 * se else ("faster" if d < 0 else "slower")}
+
+    def allocated(make):
+        """(the object, the device bytes its creation took)"""
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+        o = make()
+        torch.cuda.synchronize()
+        return o, free0 - torch.cuda.mem_get_info()[0]
+
+    out = {"bench": "runroute_pack_stage", "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "reps": a.reps,
+           "calls_per_rep": a.inner, "routes": "route k: channels [k C / K, (k + 1) C / K); pocsag 4/5, 41 taps for even k, flex 16/25, 101 taps for odd k",
+           "times": "mean and standard error of the mean over reps, ms per call",
+           "copy_bytes": "read and written by rt_pack_kernel: 2 * 2 bytes * the routes' payload elements"}
+    only = a.pack_only.split("/") if a.pack_only else None   # one case, for a kernel trace of its own
+    rng = np.random.RandomState(1)
+    for nch, K in ((64, 2), (1024, 2), (1024, 8)):
+        if only and only[0] != "%dx%d" % (nch, K):
+            continue
+        host = rng.randint(-3000, 3001, size=(nch, n)).astype(np.int16)
+        d_rows = torch.from_numpy(host).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "half_open": scene["open"]}
+        keep, recs = [], {"half_open": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        sets = (1 << (np.arange(nch) * K // nch)).astype(np.uint8)
+        stages = ["pocsag" if k % 2 == 0 else "flex" for k in range(K)]
+        forms, device_bytes = {}, {}
+        for form in ("zero_copy", "packed"):
+            router, total = allocated(lambda: pkg.RunRouter.behind(None, K, n, W, sets=sets, pack=form == "packed"))
+            chains = []
+            for k in range(K):
+                co, I, D = taps[stages[k]]
+                nc, mw, mr = router.route_caps(k)
+                rr, got = allocated(lambda: pkg.RunResampler(nc, co, I, D, W, max_in_samples=n, max_windows=mw, max_runs=mr, device=0))
+                total += got
+                st, got = allocated(lambda: (pkg.RunPocsag if stages[k] == "pocsag" else pkg.RunFlex).behind(rr))
+                total += got
+                chains.append((rr, st))
+            forms[form], device_bytes[form] = (router, chains), int(total)
+        res = {"device_bytes": device_bytes, "route_caps": {f: [list(forms[f][0].route_caps(k)) for k in range(K)] for f in forms}}
+        for name in ("all_closed", "half_open", "all_open"):
+            if only and only[1] != name:
+                continue
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_router(form):
+                forms[form][0].process_device(*view)
+
+            def run_form(form):
+                router, chains = forms[form]
+                router.process_device(*view)
+                for k, (rr, st) in enumerate(chains):
+                    rr.process_device(*router.device_view(k))
+                    st.process_device(*rr.device_view())
+
+            both = ab([("packed", lambda: run_form("packed")), ("zero_copy", lambda: run_form("zero_copy"))])
+            alone = ab([("packed", lambda: run_router("packed")), ("zero_copy", lambda: run_router("zero_copy"))])
+            run_form("packed")
+            run_form("zero_copy")
+            elems = [forms["packed"][0].fetch(k)[1] for k in range(K)]
+            runs = [len(forms["packed"][0].fetch(k)[0]) for k in range(K)]
+            same = all(forms["packed"][1][k][0].fetch()[1].tobytes() == forms["zero_copy"][1][k][0].fetch()[1].tobytes() for k in (0, K - 1))
+            copy_ms, copy_se = alone["packed"][0] - alone["zero_copy"][0], math.sqrt(alone["packed"][1] ** 2 + alone["zero_copy"][1] ** 2)
+            copy_bytes = 4 * sum(elems)
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "route_runs": runs, "route_elems": elems,
+                         "packed_ms": both["packed"][0], "packed_se": both["packed"][1], "zero_copy_ms": both["zero_copy"][0],
+                         "zero_copy_se": both["zero_copy"][1], "packed_over_zero_copy": both["packed"][0] / both["zero_copy"][0],
+                         "packed_against_zero_copy": verdict(both["packed"], both["zero_copy"]),
+                         "router_packed_ms": alone["packed"][0], "router_packed_se": alone["packed"][1],
+                         "router_zero_copy_ms": alone["zero_copy"][0], "router_zero_copy_se": alone["zero_copy"][1],
+                         "copy_ms_upper_bound": copy_ms, "copy_se": copy_se, "copy_bytes": copy_bytes,
+                         "copy_gb_per_s_lower_bound": (copy_bytes / (copy_ms * 1e-3) / 1e9) if copy_bytes and copy_ms > 0 else None,
+                         "resampled_payloads_equal": bool(same)}
+            gate.close()
+        out["%dx%d" % (nch, K)] = res
+        for router, chains in forms.values():
+            for rr, st in chains:
+                st.close()
+                rr.close()
+            router.close()
+        sq.close()
+        del d_rows, keep
+    print(json.dumps(out))
+
+
 def bench_runbits(a, pkg, torch):
     """the A/B of the sign-bit path: burst resampler -> burst stage in the PCM form and in the bits form on the device view one gate
     call left (every call begins every stretch anew, as in bench_runrs), alternating in one process in rotating order; AIS and
@@ -1498,6 +1680,15 @@ def bench_runroute_alone(a):
     bench_runroute(a, pkg, torch)
 
 
+def bench_runroute_pack_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runroute-pack needs the GPU: there is no CPU path to time")
+    bench_runroute_pack(a, pkg, torch)
+
+
 def bench_runflex_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -1566,6 +1757,10 @@ def main():
     ap.add_argument("--bench-runflex", action="store_true", help="the runflex_stage line alone")
     ap.add_argument("--bench-runbits", action="store_true", help="the runbits_stage line of --bench alone")
     ap.add_argument("--bench-runroute", action="store_true", help="the runroute_stage line alone: the run router at 64 and 1024 channels")
+    ap.add_argument("--bench-runroute-pack", action="store_true",
+                    help="the runroute_pack_stage line: packed routes against zero-copy routes at 64 and 1024 channels, 2 and 8 routes")
+    ap.add_argument("--pack-only", default=None, metavar="SHAPE/MASK",
+                    help="with --bench-runroute-pack: one case alone, e.g. 1024x2/half_open, for a kernel trace of its own")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
@@ -1580,6 +1775,8 @@ def main():
         return bench_runbits_alone(a)
     if a.bench_runroute:
         return bench_runroute_alone(a)
+    if a.bench_runroute_pack:
+        return bench_runroute_pack_alone(a)
     if a.bench or a.bench_runrs or a.bench_level_adaptive:
         return bench(a)
     if not a.config or not a.input:

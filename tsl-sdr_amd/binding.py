@@ -85,6 +85,8 @@ ABI_SYMBOLS = [
     "mfm_hosttwin_runflex_state_check",
     "mfm_runroute_create", "mfm_runroute_destroy", "mfm_runroute_process_device", "mfm_runroute_device_view", "mfm_runroute_fetch",
     "mfm_runroute_get_capacity", "mfm_hosttwin_runroute_capacity", "mfm_hosttwin_runroute_call",
+    "mfm_runroute_create_sets", "mfm_runroute_route_channels", "mfm_runroute_route_caps", "mfm_runroute_fetch_payload",
+    "mfm_hosttwin_runroute_route_caps", "mfm_hosttwin_runroute_sets_call",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -262,6 +264,7 @@ class RunRouteConfig(C.Structure):
 
 MFM_RUNROUTE_MAX_ROUTES = 8
 MFM_ROUTE_NONE = 255    # a channel whose runs go to no route
+MFM_RUNROUTE_F_PACK = 1  # mfm_runroute_create_sets: route-local channels and a dense payload per route
 
 
 class RunaisConfig(C.Structure):
@@ -652,6 +655,14 @@ def load_library():
     lib.mfm_runroute_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runroute_capacity.argtypes = [C.POINTER(RunRouteConfig), vp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runroute_call.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp]
+    u32p = C.POINTER(C.c_uint32)
+    lib.mfm_runroute_create_sets.argtypes = [C.POINTER(vp), C.POINTER(RunRouteConfig), vp]
+    lib.mfm_runroute_route_channels.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
+    lib.mfm_runroute_route_caps.argtypes = [vp, C.c_uint32, u32p, u32p, u32p]
+    lib.mfm_runroute_fetch_payload.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
+    lib.mfm_hosttwin_runroute_route_caps.argtypes = [C.POINTER(RunRouteConfig), vp, C.c_uint32, u32p, u32p, u32p]
+    lib.mfm_hosttwin_runroute_sets_call.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp, vp, vp, vp, vp,
+                                                    vp, C.c_size_t]
     lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                               C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -1866,27 +1877,77 @@ class RunRouter:
     """mfm_runroute: the runs of a Gate's device view partitioned by a per-channel route table (a route below nr_routes, or
     MFM_ROUTE_NONE), so that one gate feeds a burst chain per protocol.  Zero-copy: device_view(route) is that route's run list
     with the gate's payload pointer, and goes where Gate.device_view() goes.  A route's RunResampler is made with the whole
-    gate's numbers (all channels): channel numbers stay global."""
+    gate's numbers (all channels): channel numbers stay global.
 
-    def __init__(self, route_of_channel, nr_routes, window_samples=0, max_in_samples=0, preroll_windows=0, max_windows=0, max_runs=0,
-                 device=0, flags=0, abi_version=MFM_ABI_VERSION, nr_channels=None):
+    With sets= in the place of route_of_channel (mfm_runroute_create_sets) a channel's byte is a set of routes, bit k = route k, so a
+    channel may feed several chains.  pack=True (MFM_RUNROUTE_F_PACK, sets form only) gives every route route-local channel
+    numbers and a dense payload of its own: route_caps(k) are the numbers its RunResampler is made with, route_channels(k) maps
+    its local channels back, fetch_payload(k) reads its payload."""
+
+    def __init__(self, route_of_channel=None, nr_routes=0, window_samples=0, max_in_samples=0, preroll_windows=0, max_windows=0, max_runs=0,
+                 device=0, flags=0, abi_version=MFM_ABI_VERSION, nr_channels=None, sets=None, pack=False):
         self.lib = load_library()
         self.h = C.c_void_p()
-        table, ptr = _route_table(route_of_channel)
+        if sets is not None and route_of_channel is not None:
+            raise ValueError("RunRouter takes route_of_channel or sets=, not both")
+        if pack and sets is None:
+            raise ValueError("pack=True needs sets=: mfm_runroute_create takes no flags")
+        table, ptr = _route_table(route_of_channel if sets is None else sets)
         nch = table.size if nr_channels is None else nr_channels
+        flags |= MFM_RUNROUTE_F_PACK if pack else 0
         cfg = RunRouteConfig(abi_version, device, nch, nr_routes, window_samples, max_windows, max_runs, max_in_samples, preroll_windows, flags)
-        rc = self.lib.mfm_runroute_create(C.byref(self.h), C.byref(cfg), ptr)
+        create = "mfm_runroute_create" if sets is None else "mfm_runroute_create_sets"
+        rc = getattr(self.lib, create)(C.byref(self.h), C.byref(cfg), ptr)
         if rc < 0:
-            self._raise(rc, "mfm_runroute_create")
+            self._raise(rc, create)
         self.nr_channels = nch
         self.nr_routes = nr_routes
+        self.pack = bool(flags & MFM_RUNROUTE_F_PACK)
 
     @classmethod
-    def behind(cls, route_of_channel, nr_routes, max_in_samples, window_samples, preroll_windows=0, max_open_windows=0, device=0):
+    def behind(cls, route_of_channel, nr_routes, max_in_samples, window_samples, preroll_windows=0, max_open_windows=0, device=0, sets=None,
+               pack=False):
         """a router sized for everything one call of a Gate made from these numbers can hand over (its max_in_samples,
         window_samples, preroll_windows and max_open_windows): the capacity a RunResampler made from them has"""
         return cls(route_of_channel, nr_routes, window_samples=window_samples, max_in_samples=max_in_samples,
-                   preroll_windows=preroll_windows, max_windows=max_open_windows, device=device)
+                   preroll_windows=preroll_windows, max_windows=max_open_windows, device=device, sets=sets, pack=pack)
+
+    def route_channels(self, route):
+        """the global channel numbers of one route, ascending (uint32): under pack, local channel i is element i"""
+        out = np.zeros(max(self.nr_channels, 1), np.uint32)
+        nr = C.c_size_t()
+        rc = self.lib.mfm_runroute_route_channels(self.h, route, out.ctypes.data, self.nr_channels, C.byref(nr))
+        if rc < 0:
+            self._raise(rc, "mfm_runroute_route_channels")
+        return out[:nr.value].copy()
+
+    def route_caps(self, route):
+        """(nr_channels, max_windows, max_runs) to make one route's RunResampler with: the whole gate's without pack (max_windows
+        as given to the router, 0 = the resampler's default), the route's own under pack"""
+        n, w, r = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        rc = self.lib.mfm_runroute_route_caps(self.h, route, C.byref(n), C.byref(w), C.byref(r))
+        if rc < 0:
+            self._raise(rc, "mfm_runroute_route_caps")
+        return n.value, w.value, r.value
+
+    def fetch_payload(self, route, max_elems=None):
+        """pack only: one route's dense int16 payload of the last call.  With max_elems too small: MfmError(MFM_E_NOMEM) whose
+        `needed` attribute is the elements that would fit"""
+        ne = C.c_size_t()
+        if max_elems is None:
+            rc = self.lib.mfm_runroute_fetch_payload(self.h, route, None, 0, C.byref(ne))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below
+                self._raise(rc, "mfm_runroute_fetch_payload")
+            max_elems = ne.value
+        payload = np.zeros(max(max_elems, 1), np.int16)
+        rc = self.lib.mfm_runroute_fetch_payload(self.h, route, payload.ctypes.data, max_elems, C.byref(ne))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runroute_fetch_payload")
+            except MfmError as err:
+                err.needed = ne.value
+                raise
+        return payload[:ne.value].copy()
 
     def close(self):
         if self.h:
@@ -1981,6 +2042,62 @@ def hosttwin_runroute_call(route_of_channel, nr_routes, gate_runs, gate_totals, 
                                         gt.ctypes.data, runs.ctypes.data, totals.ctypes.data)
     if rc < 0:
         raise MfmError(rc, "mfm_hosttwin_runroute_call", lib.mfm_last_error().decode() or lib.mfm_strerror(rc).decode())
+    return runs, totals[:nr_routes]
+
+
+def hosttwin_runroute_route_caps(sets, nr_routes, route, window_samples=0, max_in_samples=0, preroll_windows=0, max_windows=0, max_runs=0,
+                                 pack=False, flags=0, abi_version=MFM_ABI_VERSION, nr_channels=None):
+    """mfm_hosttwin_runroute_route_caps: what RunRouter(sets=..., pack=...) with these arguments checks, and what its
+    route_caps(route) then returns, without a device: (nr_channels, max_windows, max_runs), or MfmError(MFM_E_INVAL) with create's
+    message"""
+    lib = load_library()
+    table, ptr = _route_table(sets)
+    nch = table.size if nr_channels is None else nr_channels
+    flags |= MFM_RUNROUTE_F_PACK if pack else 0
+    cfg = RunRouteConfig(abi_version, 0, nch, nr_routes, window_samples, max_windows, max_runs, max_in_samples, preroll_windows, flags)
+    n, w, r = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runroute_route_caps(C.byref(cfg), ptr, route, C.byref(n), C.byref(w), C.byref(r))
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runroute_route_caps", lib.mfm_last_error().decode())
+    return n.value, w.value, r.value
+
+
+def hosttwin_runroute_sets_call(sets, nr_routes, gate_runs, gate_totals, max_runs=None, pack=False, window_samples=0, gate_payload=None,
+                                route_max_runs=None, route_max_windows=None, flags=0):
+    """mfm_hosttwin_runroute_sets_call: one call of a router made with sets= on the CPU.  As hosttwin_runroute_call; under pack
+    gate_payload is the gate's int16 payload of gate_totals[1] elements and route_max_runs / route_max_windows are the routes' own
+    capacities (default: no limit below the call's own runs and windows).  Returns (runs, totals) and under pack (runs, totals,
+    payloads): payloads int16 [nr_routes][max_elems], the used part of row k is totals[k][1] long"""
+    lib = load_library()
+    table, ptr = _route_table(sets)
+    gr = np.ascontiguousarray(gate_runs, dtype=GATE_RUN_DTYPE)
+    gt = np.ascontiguousarray(gate_totals, dtype=np.uint64)
+    assert gt.shape == (4,)
+    max_runs = len(gr) if max_runs is None else max_runs
+    flags |= MFM_RUNROUTE_F_PACK if pack else 0
+    K = max(nr_routes, 1)
+    runs = np.zeros((K, max(max_runs, 1)), GATE_RUN_DTYPE)
+    totals = np.zeros((K, 4), np.uint64)
+    stride = runs.shape[1] if max_runs else 0
+    rmr = rmw = gp = payloads = None
+    max_elems = 0
+    if flags & MFM_RUNROUTE_F_PACK:
+        all_windows = int(gr["nr_windows"].astype(np.uint64).sum())
+        rmr = np.ascontiguousarray(np.full(K, max_runs) if route_max_runs is None else route_max_runs, dtype=np.uint32)
+        rmw = np.ascontiguousarray(np.full(K, all_windows) if route_max_windows is None else route_max_windows, dtype=np.uint32)
+        assert rmr.shape == rmw.shape == (K,)
+        gp = np.ascontiguousarray(np.zeros(0, np.int16) if gate_payload is None else gate_payload, dtype=np.int16).reshape(-1)
+        assert gp.size >= int(gt[1]), "gate_payload is shorter than gate_totals[1]"
+        max_elems = max(int(rmw.max()) * window_samples, 1)
+        payloads = np.zeros((K, max_elems), np.int16)
+    rc = lib.mfm_hosttwin_runroute_sets_call(table.size, nr_routes, ptr, flags, window_samples, stride, rmr.ctypes.data if rmr is not None else None,
+                                             rmw.ctypes.data if rmw is not None else None, gr.ctypes.data if gr.size else None,
+                                             gp.ctypes.data if gp is not None and gp.size else None, gt.ctypes.data, runs.ctypes.data,
+                                             totals.ctypes.data, payloads.ctypes.data if payloads is not None else None, max_elems)
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runroute_sets_call", lib.mfm_last_error().decode() or lib.mfm_strerror(rc).decode())
+    if flags & MFM_RUNROUTE_F_PACK:
+        return runs, totals[:nr_routes], payloads
     return runs, totals[:nr_routes]
 
 

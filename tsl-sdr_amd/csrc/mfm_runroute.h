@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/multifm_hip.h"
+#include "mfm_runrs.h"
 
 /* d_totals[], the gate's and each route's */
 #define MFM_RUNROUTE_T_RUNS 0
@@ -40,6 +41,81 @@ __host__ __device__ inline bool mfm_runroute_refused(const uint64_t *gate_totals
         overflow = 1u;
     }
     return overflow || out_of_step;
+}
+
+/*
+ * ---- the sets form (mfm_runroute_create_sets): a channel's byte is a SET of routes, bit k = route k; under
+ * MFM_RUNROUTE_F_PACK each route gets route-local channel numbers, dense offsets and a payload of its own.  Stated once for
+ * the kernels of mfm_runroute_sets.hip and for mfm_hosttwin_runroute_sets_call.
+ */
+
+/* the routes of a run's channel: the table's byte, the empty set for a channel that does not exist */
+__host__ __device__ inline uint32_t mfm_runroute_set_of(const uint8_t *routes_of_channel, uint32_t nr_channels, uint32_t channel)
+{
+    return mfm_runroute_bad_channel(channel, nr_channels) ? 0u : routes_of_channel[channel];
+}
+
+__host__ __device__ inline bool mfm_runroute_in_route(uint32_t set, uint32_t route)
+{
+    return ((set >> route) & 1u) != 0;
+}
+
+/* Route-local channel numbers: the rank of channel c in route k is the number of channels below c whose set has bit k, so a
+ * route's local numbers ascend with the global ones.  The ranks of all channels stand in one table [nr_channels][nr_routes],
+ * built once per object by mfm_runroute_build_ranks (count[k] = the route's channels) and read by mfm_runroute_rank_of. */
+inline void mfm_runroute_build_ranks(const uint8_t *routes_of_channel, uint32_t nr_channels, uint32_t nr_routes, uint32_t *rank, uint32_t *count)
+{
+    for (uint32_t k = 0; k < nr_routes; k++) {
+        count[k] = 0;
+    }
+    for (uint32_t c = 0; c < nr_channels; c++) {
+        for (uint32_t k = 0; k < nr_routes; k++) {
+            rank[(size_t)c * nr_routes + k] = count[k];
+            count[k] += mfm_runroute_in_route(routes_of_channel[c], k) ? 1u : 0u;
+        }
+    }
+}
+
+__host__ __device__ inline uint32_t mfm_runroute_rank_of(const uint32_t *rank, uint32_t nr_routes, uint32_t channel, uint32_t route)
+{
+    return rank[(size_t)channel * nr_routes + route];
+}
+
+/* PACK copies a run's windows, so a run whose payload range does not lie within the gate's payload elements is not a gate's
+ * run: the call is refused (out of step), as a bad channel is.  Written so that nothing wraps. */
+__host__ __device__ inline bool mfm_runroute_bad_range(uint64_t payload_offset, uint32_t nr_windows, uint32_t window_samples, uint64_t gate_elems)
+{
+    const uint64_t len = (uint64_t)nr_windows * window_samples; /* < 2^52 */
+    return payload_offset > gate_elems || len > gate_elems - payload_offset;
+}
+
+/* PACK: a route whose runs or windows of one call exceed the capacities mfm_runroute_route_caps gives for it gets overflow = 1
+ * with 0 runs and 0 elements; the other routes are unaffected */
+__host__ __device__ inline bool mfm_runroute_route_over(uint64_t runs, uint64_t windows, uint64_t cap_runs, uint64_t cap_windows)
+{
+    return runs > cap_runs || windows > cap_windows;
+}
+
+/*
+ * What mfm_runroute_route_caps returns under PACK for a route of n channels (n >= 1): mfm_runrs_caps_of applied to n, never
+ * above an explicit max_windows / max_runs.  With max_in_samples == 0 there is no default to form and both must be explicit:
+ * they are returned as given.  false: max_in_samples is 0 and one of the two is 0.
+ */
+inline bool mfm_runroute_pack_caps(uint32_t n, uint32_t window_samples, uint32_t max_windows, uint32_t max_runs, uint32_t max_in_samples,
+                                   uint32_t preroll_windows, mfm_runrs_caps &c)
+{
+    if (0 == max_in_samples) {
+        c.windows = max_windows;
+        c.runs = max_runs;
+        return max_windows && max_runs;
+    }
+    mfm_runrs_caps own;
+    (void)mfm_runrs_caps_of(n, window_samples, 0u, 0u, max_in_samples, preroll_windows, own);
+    c.windows = max_windows && max_windows < own.windows ? max_windows : own.windows;
+    (void)mfm_runrs_caps_of(n, window_samples, (uint32_t)(c.windows < 0xffffffffull ? c.windows : 0xffffffffull), 0u, max_in_samples,
+                            preroll_windows, own);
+    c.runs = max_runs && max_runs < own.runs ? max_runs : own.runs;
+    return true;
 }
 
 #endif /* MFM_RUNROUTE_H */

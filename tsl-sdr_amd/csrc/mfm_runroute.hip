@@ -32,6 +32,7 @@
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_runroute.h"
+#include "mfm_runroute_obj.h"
 #include "mfm_runrs.h"
 
 namespace {
@@ -212,17 +213,6 @@ const char *rt_geometry(const mfm_runroute_config &cfg, const uint8_t *route_of_
         }                                                                                                    \
     } while (0)
 
-struct mfm_runroute {
-    mfm_runroute_config cfg{};
-    uint64_t cap_runs = 0;
-    uint8_t *d_table = nullptr;
-    mfm_gate_run *d_runs = nullptr; /* [K][cap_runs] */
-    uint64_t *d_totals = nullptr;   /* [K][4] */
-    const int16_t *d_payload = nullptr; /* the last call's: the gate's */
-    hipStream_t last_stream = nullptr;
-    bool have_call = false;
-};
-
 extern "C" {
 
 int mfm_hosttwin_runroute_capacity(const struct mfm_runroute_config *cfg, const uint8_t *route_of_channel, uint32_t *max_runs)
@@ -264,6 +254,11 @@ int mfm_runroute_create(struct mfm_runroute **prt, const struct mfm_runroute_con
     rt->cap_runs = cap;
     const size_t K = cfg->nr_routes, nruns = (size_t)(cap ? cap : 1);
     *prt = rt; /* from here on the caller's destroy frees what was allocated */
+    rt->h_table = new (std::nothrow) uint8_t[cfg->nr_channels]; /* for mfm_runroute_route_channels */
+    if (!rt->h_table) {
+        return MFM_E_NOMEM;
+    }
+    memcpy(rt->h_table, route_of_channel, cfg->nr_channels);
     RT_TRY(hipSetDevice(cfg->device));
     RT_TRY(hipMalloc(&rt->d_table, cfg->nr_channels));
     RT_TRY(hipMemcpy(rt->d_table, route_of_channel, cfg->nr_channels, hipMemcpyHostToDevice));
@@ -285,6 +280,7 @@ void mfm_runroute_destroy(struct mfm_runroute **prt)
     (void)hipFree(rt->d_table);
     (void)hipFree(rt->d_runs);
     (void)hipFree(rt->d_totals);
+    mfm_runroute_sets_free(rt);
     delete rt;
     *prt = nullptr;
 }
@@ -299,6 +295,9 @@ int mfm_runroute_process_device(struct mfm_runroute *rt, const struct mfm_gate_r
     RT_TRY(hipSetDevice(rt->cfg.device));
     if (rt->have_call && rt->last_stream != s) {
         RT_TRY(hipStreamSynchronize(rt->last_stream)); /* the result buffers are reused: keep calls ordered */
+    }
+    if (rt->sets) { /* made by mfm_runroute_create_sets: the kernels of mfm_runroute_sets.hip */
+        return mfm_runroute_sets_process(rt, d_runs, d_payload, d_totals, s);
     }
     const RtCall A{ d_runs, d_totals, rt->d_table, rt->d_runs, rt->d_totals, rt->cap_runs, rt->cfg.nr_channels, rt->cfg.nr_routes };
     /* one workgroup whatever the capacity: it walks as many strips as the gate's run count, read on the device, asks for */
@@ -323,7 +322,7 @@ int mfm_runroute_device_view(struct mfm_runroute *rt, uint32_t route, const stru
         *d_runs = rt->d_runs + (size_t)route * (size_t)(rt->cap_runs ? rt->cap_runs : 1);
     }
     if (d_payload) {
-        *d_payload = rt->d_payload;
+        *d_payload = rt->pack ? rt->d_pack + rt->pack_base[route] : rt->d_payload; /* PACK: the route's own, fixed at create */
     }
     if (d_totals) {
         *d_totals = rt->d_totals + 4u * route;
