@@ -1208,6 +1208,28 @@ int mfm_runrs_fetch_state(struct mfm_runrs *rr, struct mfm_runrs_state *state, i
                           size_t nr_channels);
 int mfm_runrs_store_state(struct mfm_runrs *rr, const struct mfm_runrs_state *state, const int16_t *pending,
                           const struct mfm_runrs_dc_state *dc, size_t nr_channels);
+/*
+ * The view entries: a resampler sized to a part of a payload reads that payload in place.  They are
+ * mfm_runrs_process_device and mfm_runrs_process_bits_device with the two meanings of d_totals[1] taken apart.  The plain
+ * entries read it as how much payload exists (the bound of every run's range payload_offset .. + nr_windows * W) and as the load
+ * that must fit max_windows * W.  Here *d_payload_elems, one uint64 on the device, is how much payload exists, and d_totals[1] is
+ * read only as the load (MFM_RUNRS_OVER_OWN when it exceeds max_windows * W).  That is what a local route of the run router
+ * hands over (mfm_runroute_create_local below): mfm_runroute_device_view's three addresses and mfm_runroute_bound_view's.
+ *
+ * Everything else is the rule of the plain entries, to the bit: stretches, the per-channel state and its two buffers, the
+ * refusals and their flags, the DC blocker (mfm_runrs_set_dc_block works with the PCM view entry), the bits entry's MFM_E_INVAL
+ * with the blocker on, and mfm_runrs_fetch, _device_view, _bits_view, _fetch_bits, _fetch_state and _store_state.  View calls and
+ * plain calls may alternate on one object, and a stretch continues across them.  A run longer than max_windows * W cannot
+ * belong to a load that fits and is refused as a range that does not exist is (MFM_RUNRS_GATE_BAD_RUNS).
+ *
+ * Safe misuse.  A local route's view handed to the PLAIN entries is either refused (MFM_RUNRS_GATE_BAD_RUNS: a run whose range
+ * ends beyond the route's load) or right; it never reads outside the gate's payload, because the load is at most the gate's
+ * total.
+ */
+int mfm_runrs_process_view_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                                  const uint64_t *d_payload_elems, void *stream);
+int mfm_runrs_process_bits_view_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload,
+                                       const uint64_t *d_totals, const uint64_t *d_payload_elems, uint32_t polarity, void *stream);
 
 /*
  * ---- Run router: one gate feeds a burst chain per protocol ---------------------------------------------------------------
@@ -1345,6 +1367,48 @@ int mfm_runroute_route_caps(struct mfm_runroute *rt, uint32_t route, uint32_t *n
  * with a message when the call or the route was refused.
  */
 int mfm_runroute_fetch_payload(struct mfm_runroute *rt, uint32_t route, int16_t *payload, size_t max_elems, size_t *nr_elems);
+
+/*
+ * ---- Run router, the local form: route-local channel numbers on the gate's payload in place -----------------------------
+ * The two forms above each pay for what the other avoids: the zero-copy forms keep global channel numbers, so every route's
+ * chain is sized for all channels; PACK sizes the chain to the route and copies every open window to do so.  The local form
+ * gives PACK's channel numbers and capacities without the copy: the payload stays the gate's and payload_offset stays the
+ * gate's, and the burst resampler behind reads it through its view entries (mfm_runrs_process_view_device below), which take
+ * the bound of the payload ranges apart from the load.  mfm_runroute_create_local is a creator of its own, not a flag, and
+ * returns the same object type: mfm_runroute_process_device, _device_view, _fetch, _get_capacity, _route_channels, _route_caps
+ * and _destroy work on it; mfm_runroute_fetch_payload answers MFM_E_INVAL as for every object without PACK.  The other two
+ * creators and what they refuse stay as they are.
+ *
+ * Input.  routes_of_channel [nr_channels], a SET per channel exactly as for mfm_runroute_create_sets (bit k = route k, 0 =
+ * nowhere, a channel may stand in several routes).  cfg->flags must be 0.
+ *
+ * Result per route k.  Record i is the gate's record with `channel` replaced by the channel's rank among the route's channels
+ * (PACK's numbering: fixed for the object's life, ascending, inverted by mfm_runroute_route_channels); first_window, nr_windows
+ * and payload_offset are untouched; the partition is stable.  mfm_runroute_device_view returns as d_payload the gate's pointer
+ * handed to the last call.  d_totals[4] = { runs, the route's LOAD = the sum of nr_windows * W over its records, overflow, out
+ * of step }, and mfm_runroute_fetch's *nr_elems is that load.  The load is what the route's resampler must hold; it is NOT a
+ * bound of the payload offsets, which range over the gate's whole payload.  That bound is mfm_runroute_bound_view's: one uint64
+ * at an address fixed at create, which every process call writes with the gate's payload elements (d_totals[1] of the gate), or
+ * with 0 when the call is refused for the whole router.  On objects of the other two creators mfm_runroute_bound_view is
+ * MFM_E_INVAL with a message: their totals carry the bound themselves.
+ *
+ * Refused calls.  The gate's two flags, more runs than the router's max_runs and a run of a channel >= nr_channels flag every
+ * route, as above.  A route whose runs or windows in one call exceed its own capacity gets overflow = 1 with 0 runs and 0
+ * elements, and the other routes are unaffected, as under PACK.  A payload range outside the gate's elements is left to the
+ * resampler's view entry, as in the zero-copy forms: nothing is copied, so nothing is read here.
+ *
+ * Sizing what stands behind: mfm_runroute_route_caps returns PACK's rule (n channels, n * per windows, the run bound of the
+ * burst resampler's own rule for n channels).  A burst resampler made from the three numbers never answers MFM_RUNRS_OVER_OWN
+ * through its view entry to a call the router did not flag.
+ *
+ * Refusals at create (MFM_E_INVAL with a message): those of mfm_runroute_create_sets under PACK - a route without a channel,
+ * window_samples out of range, max_in_samples == 0 without both max_windows and max_runs, a set with a bit at or above
+ * nr_routes - and non-zero flags.
+ */
+int mfm_runroute_create_local(struct mfm_runroute **prt, const struct mfm_runroute_config *cfg, const uint8_t *routes_of_channel);
+/* The address of the bound, for mfm_runrs_process_view_device's d_payload_elems: fixed at create, written by every process
+ * call on its stream. */
+int mfm_runroute_bound_view(struct mfm_runroute *rt, const uint64_t **d_payload_elems);
 
 /*
  * ---- Burst AIS stage: the burst resampler's runs through the AIS demodulator, on the device -----------------------------
@@ -1877,7 +1941,9 @@ struct mfm_runrs_state {        /* 24 bytes */
  * (nr_gate_runs, nr_gate_elems: its totals), state [nr_channels] and pending [nr_channels][plen] are updated in place, plen =
  * ((nr_coeffs + interpolate - 1) / interpolate + 3) & ~3.  MFM_E_INVAL for what create refuses and for a run list that is not a
  * gate's, MFM_E_NOMEM when max_runs or max_elems is too small (*nr_runs / *nr_elems say what is needed); on any error nothing
- * is written, the state included. */
+ * is written, the state included.  It is the twin of mfm_runrs_process_view_device as well: nr_gate_elems is a bound of the
+ * payload ranges only and there is no capacity test, so a local route's run list (mfm_runroute_create_local) goes in with the
+ * gate's payload and the gate's total as nr_gate_elems. */
 int mfm_hosttwin_runrs_call(uint32_t nr_channels, uint32_t window_samples, uint32_t interpolate, uint32_t decimate, uint32_t invert,
                             const int16_t *coeffs, size_t nr_coeffs, struct mfm_runrs_state *state, int16_t *pending,
                             const struct mfm_gate_run *gate_runs, size_t nr_gate_runs, const int16_t *gate_payload, size_t nr_gate_elems,
@@ -1936,6 +2002,17 @@ int mfm_hosttwin_runroute_sets_call(uint32_t nr_channels, uint32_t nr_routes, co
                                     uint32_t window_samples, size_t max_runs, const uint32_t *route_max_runs, const uint32_t *route_max_windows,
                                     const struct mfm_gate_run *gate_runs, const int16_t *gate_payload, const uint64_t *gate_totals,
                                     struct mfm_gate_run *runs, uint64_t *totals, int16_t *payloads, size_t max_elems);
+/* host twin of one mfm_runroute_process_device call on an object of mfm_runroute_create_local, no device needed
+ * (csrc/mfm_runroute.h: the set lookup, the rank and the refusal predicates its kernel runs).  max_runs is the router's
+ * capacity, route_max_runs [nr_routes] and route_max_windows [nr_routes] the routes' own (what mfm_runroute_route_caps returns;
+ * no route_max_runs may exceed max_runs).  Route k's list goes to runs + k * max_runs and its totals to totals + 4 * k;
+ * *payload_elems is what the call leaves behind mfm_runroute_bound_view.  The gate's payload is not an argument: nothing of it
+ * is read.  A refused call, or a refused route, returns MFM_OK as the device does, with the flags in the totals and nothing else
+ * written for it.  MFM_E_INVAL with a message for a table, a nr_routes or a window_samples that create refuses. */
+int mfm_hosttwin_runroute_local_call(uint32_t nr_channels, uint32_t nr_routes, const uint8_t *routes_of_channel, uint32_t window_samples,
+                                     size_t max_runs, const uint32_t *route_max_runs, const uint32_t *route_max_windows,
+                                     const struct mfm_gate_run *gate_runs, const uint64_t *gate_totals, struct mfm_gate_run *runs,
+                                     uint64_t *totals, uint64_t *payload_elems);
 /* the per-channel state of the burst AIS stage, on the device and in the host twin: all zero at the start of a stream.
  * Fields a mode does not use are zero.  What a stored state must satisfy: csrc/mfm_runais.h (mfm_runais_state_check) */
 struct mfm_runais_state {       /* 264 bytes */

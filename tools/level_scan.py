@@ -107,7 +107,17 @@ chNNNN.rs.s16, ais.jsonl / pocsag.jsonl / flex.jsonl, pages.jsonl.  Channel numb
 DIR/index.jsonl and DIR/chNNNN.s16 are the gate's, as without the flag.  Two optional keys beside "routes": "shared": true lets a
 channel stand in several routes (a carrier that time-shares POCSAG and FLEX reaches both chains), and "pack": true switches
 MFM_RUNROUTE_F_PACK on: every route gets a dense payload of its own and its chain is sized to its channels (every route then
-needs a channel); the files still carry the configuration's channel numbers.
+needs a channel); the files still carry the configuration's channel numbers.  "local": true (never beside "pack"; every route
+needs a channel here too) makes the router with mfm_runroute_create_local: the chains are sized to their routes as under "pack",
+but nothing is copied - each route's burst resampler reads the gate's payload in place through its view entries.  The files are
+those of "pack", byte for byte.
+
+    python tools/level_scan.py --bench-runroute-local [--window 1000] [--reps 8] [--inner 10]
+
+prints one line ("runroute_local_stage"): the three forms of the router - zero-copy with global channel numbers, packed, local -
+on the cases of --bench-runroute-pack, as router + one chain per route (mean, standard deviation and standard error, alternating
+in one process in rotating order), local against packed and against zero-copy with the two-standard-error verdict, the three
+router calls alone, and the device memory each form takes.
 
     python tools/level_scan.py --bench-runroute-pack [--window 1000] [--reps 8] [--inner 10] [--pack-only SHAPE/MASK]
 
@@ -190,16 +200,27 @@ ROUTE_STAGES = ("ais", "pocsag", "flex", "none")
 MAX_ROUTES = 8   # MFM_RUNROUTE_MAX_ROUTES
 
 
+class Routes(list):
+    """the routes of a --gate-route file; `local` is the file's "local" key"""
+    local = False
+
+
 def read_routes(path, nr_channels):
     """--gate-route FILE: {"routes": [{"name", "stage", "resample", "taps", "channels", and optionally "dc_pole", "bits"}], and
-    optionally "shared": true (a channel may stand in several routes) and "pack": true (MFM_RUNROUTE_F_PACK: every route's chain
-    is sized to its channels)}, checked; what is wrong ends the run with a message.  Returns (routes, shared, pack)"""
+    optionally "shared": true (a channel may stand in several routes), "pack": true (MFM_RUNROUTE_F_PACK: every route's chain
+    is sized to its channels) and "local": true (mfm_runroute_create_local: sized likewise, on the gate's payload in place; not
+    beside "pack")}, checked; what is wrong ends the run with a message.  Returns (routes, shared, pack); routes.local is the
+    third key"""
     doc = json.load(open(path))
-    routes = doc["routes"]
-    shared, pack = doc.get("shared", False), doc.get("pack", False)
-    for key, value in (("shared", shared), ("pack", pack)):
+    routes = Routes(doc["routes"])
+    shared, pack, local = doc.get("shared", False), doc.get("pack", False), doc.get("local", False)
+    for key, value in (("shared", shared), ("pack", pack), ("local", local)):
         if not isinstance(value, bool):
             raise SystemExit(f"--gate-route: \"{key}\" must be true or false, not {value!r}")
+    if local and pack:
+        raise SystemExit("--gate-route: \"local\" and \"pack\" exclude each other: both size every route's chain to its channels, "
+                         "\"pack\" on a copy of the route's windows and \"local\" on the gate's payload in place")
+    routes.local = local
     if not 1 <= len(routes) <= MAX_ROUTES:
         raise SystemExit(f"--gate-route: {len(routes)} routes; the run router takes 1 .. {MAX_ROUTES}")
     names, owner = set(), {}
@@ -224,8 +245,9 @@ def read_routes(path, nr_channels):
                 raise SystemExit(f"--gate-route: channel {c} is in two routes ({owner[c]} and {name}): a channel has one route")
             owner[c] = name
         r["channels"] = list(r.get("channels", []))
-        if pack and not r["channels"]:
-            raise SystemExit(f"--gate-route: route {name} has no channel: with \"pack\" every route's chain is sized to its channels")
+        if (pack or local) and not r["channels"]:
+            raise SystemExit(f"--gate-route: route {name} has no channel: with \"{'pack' if pack else 'local'}\" every route's chain is "
+                             "sized to its channels")
     return routes, shared, pack
 
 
@@ -234,11 +256,12 @@ class BurstChain:
     route's of the run router - and the files the two write under out_dir; view() returns the run list's device view"""
 
     def __init__(self, pkg, out_dir, window, nr_channels, max_in_samples, preroll, device, view, resample, taps_file, dc_pole=None,
-                 stage=None, bits=False, caps=None, channels=None):
-        """caps and channels: behind a packed route of the run router, its route_caps() - the chain is sized to the route - and its
-        route_channels(), which turn the route-local channel numbers of everything fetched back into true ones"""
+                 stage=None, bits=False, caps=None, channels=None, bound=None):
+        """caps and channels: behind a packed or a local route of the run router, its route_caps() - the chain is sized to the route -
+        and its route_channels(), which turn the route-local channel numbers of everything fetched back into true ones.  bound:
+        behind a local route, the router's bound_view(): the resampler then reads the gate's payload through its view entries"""
         b = self.b = pkg.binding
-        self.out_dir, self.window, self.view = out_dir, window, view
+        self.out_dir, self.window, self.view, self.bound = out_dir, window, view, bound
         self.channels = None if channels is None else np.asarray(channels, np.uint32)
         interp, decim_rs = [int(x) for x in resample.split("/")]
         co = np.array([int(float(t) * 16384.0) for t in json.load(open(taps_file))["lpfCoeffs"]], np.int16)  # decoder.c:530-533
@@ -266,10 +289,16 @@ class BurstChain:
         """burst resampler and the stage behind it on the run list's last result"""
         rr, st = self.rr, self.st
         if self.bits_polarity:
-            rr.process_bits_device(*self.view(), self.bits_polarity, stream=stream)
+            if self.bound is not None:
+                rr.process_bits_view_device(*self.view(), self.bound, self.bits_polarity, stream=stream)
+            else:
+                rr.process_bits_device(*self.view(), self.bits_polarity, stream=stream)
             st.process_bits_device(rr.bits_view(), stream=stream)
             return
-        rr.process_device(*self.view(), stream=stream)
+        if self.bound is not None:
+            rr.process_view_device(*self.view(), self.bound, stream=stream)
+        else:
+            rr.process_device(*self.view(), stream=stream)
         if st:
             st.process_device(*rr.device_view(), stream=stream)
 
@@ -289,7 +318,7 @@ class BurstChain:
             self.write_flex(self.true_channels(events), frames)
 
     def true_channels(self, records):
-        """behind a packed route: the records with their route-local channel numbers mapped back, before anything is written"""
+        """behind a packed or a local route: the records with their route-local channel numbers mapped back, before anything is written"""
         if self.channels is not None and len(records):
             records = records.copy()
             records["channel"] = self.channels[records["channel"]]
@@ -366,6 +395,7 @@ def scan(a):
     b = pkg.binding
     fs, centre, decim, taps, chans = read_config(a.config)
     routes, shared, pack = read_routes(a.gate_route, len(chans)) if a.gate_route else (None, False, False)
+    local = routes is not None and routes.local
     iq_form = a.form == "iq"
     sense = a.sense or ("above" if iq_form else "below")
     adaptive = a.floor_windows is not None
@@ -408,12 +438,12 @@ def scan(a):
     if routes is not None:
         if not gate or iq_form:
             raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
-        if shared or pack:   # a set of routes per channel
+        if shared or pack or local:   # a set of routes per channel
             table = np.zeros(len(chans), np.uint8)
             for k, r in enumerate(routes):
                 table[r["channels"]] |= 1 << k
             router = pkg.RunRouter.behind(None, len(routes), max_in, a.window, preroll_windows=int(a.gate_preroll), device=a.device,
-                                          sets=table, pack=pack)
+                                          sets=table, pack=pack, local=local)
         else:
             table = np.full(len(chans), b.MFM_ROUTE_NONE, np.uint8)
             for k, r in enumerate(routes):
@@ -421,7 +451,9 @@ def scan(a):
             router = pkg.RunRouter.behind(table, len(routes), max_in, a.window, preroll_windows=int(a.gate_preroll), device=a.device)
         for k, r in enumerate(routes):
             os.makedirs(os.path.join(a.gate_out, r["name"]), exist_ok=True)
-            sized = dict(caps=router.route_caps(k), channels=router.route_channels(k)) if pack else {}
+            sized = dict(caps=router.route_caps(k), channels=router.route_channels(k)) if pack or local else {}
+            if local:
+                sized["bound"] = router.bound_view()
             chains.append(BurstChain(pkg, os.path.join(a.gate_out, r["name"]), a.window, len(chans), max_in, int(a.gate_preroll), a.device,
                                      lambda k=k: router.device_view(k), r["resample"], r["taps"], dc_pole=r.get("dc_pole"),
                                      stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits")), **sized))
@@ -1572,6 +1604,141 @@ def bench_runroute_pack(a, pkg, torch):
     print(json.dumps(out))
 
 
+def bench_runroute_local(a, pkg, torch):
+    """the three forms of the run router on the cases of bench_runroute_pack (64 and 1024 channels in 2 routes, 1024 in 8; all
+    closed, half open, all open): zero-copy with global channel numbers (RunRouter(sets=...)), packed (pack=True) and local
+    (local=True, the chains through the view entries).  Per shape and mask, alternating in one process in rotating order: (a)
+    router + one chain per route, the chains sized by route_caps() of each form; (b) the three router calls alone.  The device
+    bytes of a form are the drop of free device memory across the creation of its objects"""
+    b = pkg.binding
+    W, n = a.window, 1 << 15
+    nw = n // W
+    nb = nw * W
+    taps = {"pocsag": (np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16), 4, 5),
+            "flex": (np.round(pkg.synth.design_lpf(101, 0.45 / 25, 1.0) * 16 * 16384.0).astype(np.int16), 16, 25)}
+    names = ("zero_copy", "packed", "local")
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    def ab(variants):
+        for _, fn in variants:
+            timed(fn, 3)
+        got = {v: [] for v, _ in variants}
+        for rep in range(a.reps):
+            j = rep % len(variants)
+            for vname, fn in variants[j:] + variants[:j]:
+                got[vname].append(timed(fn, a.inner))
+        return {v: (_stats(x)[0], _stats(x)[1], _stats(x)[1] / math.sqrt(a.reps)) for v, x in got.items()}   # mean, sd, standard error
+
+    def verdict(x, y):
+        """x against y: the difference, its standard error, and tools/exp/ab.py's rule"""
+        d, se = x[0] - y[0], math.sqrt(x[2] * x[2] + y[2] * y[2])
+        return {"difference_ms": d, "difference_se": se, "ratio": x[0] / y[0],
+                "verdict": "neutral" if abs(d) <= 2.0 * se else ("faster" if d < 0 else "slower")}
+
+    def allocated(make):
+        """(the object, the device bytes its creation took)"""
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+        o = make()
+        torch.cuda.synchronize()
+        return o, free0 - torch.cuda.mem_get_info()[0]
+
+    out = {"bench": "runroute_local_stage", "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "reps": a.reps,
+           "calls_per_rep": a.inner, "routes": "route k: channels [k C / K, (k + 1) C / K); pocsag 4/5, 41 taps for even k, flex 16/25, 101 taps for odd k",
+           "times": "[mean, standard deviation, standard error of the mean] over reps, ms per call",
+           "forms": "zero_copy: global channel numbers, chains of all channels; packed: MFM_RUNROUTE_F_PACK; local: mfm_runroute_create_local + view entries"}
+    rng = np.random.RandomState(1)
+    for nch, K in ((64, 2), (1024, 2), (1024, 8)):
+        host = rng.randint(-3000, 3001, size=(nch, n)).astype(np.int16)
+        d_rows = torch.from_numpy(host).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "half_open": scene["open"]}
+        keep, recs = [], {"half_open": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        sets = (1 << (np.arange(nch) * K // nch)).astype(np.uint8)
+        stages = ["pocsag" if k % 2 == 0 else "flex" for k in range(K)]
+        forms, device_bytes = {}, {}
+        for form in names:
+            router, total = allocated(lambda: pkg.RunRouter.behind(None, K, n, W, sets=sets, pack=form == "packed", local=form == "local"))
+            chains = []
+            for k in range(K):
+                co, I, D = taps[stages[k]]
+                nc, mw, mr = router.route_caps(k)
+                rr, got = allocated(lambda: pkg.RunResampler(nc, co, I, D, W, max_in_samples=n, max_windows=mw, max_runs=mr, device=0))
+                total += got
+                st, got = allocated(lambda: (pkg.RunPocsag if stages[k] == "pocsag" else pkg.RunFlex).behind(rr))
+                total += got
+                chains.append((rr, st))
+            forms[form], device_bytes[form] = (router, chains), int(total)
+        res = {"device_bytes": device_bytes, "route_caps": {f: [list(forms[f][0].route_caps(k)) for k in range(K)] for f in forms}}
+        for name in ("all_closed", "half_open", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_router(form):
+                forms[form][0].process_device(*view)
+
+            def run_form(form):
+                router, chains = forms[form]
+                router.process_device(*view)
+                for k, (rr, st) in enumerate(chains):
+                    if form == "local":
+                        rr.process_view_device(*router.device_view(k), router.bound_view())
+                    else:
+                        rr.process_device(*router.device_view(k))
+                    st.process_device(*rr.device_view())
+
+            both = ab([(f, lambda f=f: run_form(f)) for f in names])
+            alone = ab([(f, lambda f=f: run_router(f)) for f in names])
+            for f in names:
+                run_form(f)
+            runs = [len(forms["local"][0].fetch(k)[0]) for k in range(K)]
+            loads = [forms["local"][0].fetch(k)[1] for k in range(K)]
+            same = all(forms["local"][1][k][0].fetch()[1].tobytes() == forms[f][1][k][0].fetch()[1].tobytes()
+                       for k in (0, K - 1) for f in ("packed", "zero_copy"))
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "route_runs": runs, "route_loads": loads,
+                         "chain_ms": {f: list(both[f]) for f in names}, "router_ms": {f: list(alone[f]) for f in names},
+                         "local_against_packed": verdict(both["local"], both["packed"]),
+                         "local_against_zero_copy": verdict(both["local"], both["zero_copy"]),
+                         "router_local_against_packed": verdict(alone["local"], alone["packed"]),
+                         "router_local_against_zero_copy": verdict(alone["local"], alone["zero_copy"]),
+                         "resampled_payloads_equal": bool(same)}
+            gate.close()
+        out["%dx%d" % (nch, K)] = res
+        for router, chains in forms.values():
+            for rr, st in chains:
+                st.close()
+                rr.close()
+            router.close()
+        sq.close()
+        del d_rows, keep
+    print(json.dumps(out))
+
+
 def bench_runbits(a, pkg, torch):
     """the A/B of the sign-bit path: burst resampler -> burst stage in the PCM form and in the bits form on the device view one gate
     call left (every call begins every stretch anew, as in bench_runrs), alternating in one process in rotating order; AIS and
@@ -1689,6 +1856,15 @@ def bench_runroute_pack_alone(a):
     bench_runroute_pack(a, pkg, torch)
 
 
+def bench_runroute_local_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runroute-local needs the GPU: there is no CPU path to time")
+    bench_runroute_local(a, pkg, torch)
+
+
 def bench_runflex_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -1761,6 +1937,8 @@ def main():
                     help="the runroute_pack_stage line: packed routes against zero-copy routes at 64 and 1024 channels, 2 and 8 routes")
     ap.add_argument("--pack-only", default=None, metavar="SHAPE/MASK",
                     help="with --bench-runroute-pack: one case alone, e.g. 1024x2/half_open, for a kernel trace of its own")
+    ap.add_argument("--bench-runroute-local", action="store_true",
+                    help="the runroute_local_stage line: zero-copy, packed and local routes at 64 and 1024 channels, 2 and 8 routes")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
@@ -1777,6 +1955,8 @@ def main():
         return bench_runroute_alone(a)
     if a.bench_runroute_pack:
         return bench_runroute_pack_alone(a)
+    if a.bench_runroute_local:
+        return bench_runroute_local_alone(a)
     if a.bench or a.bench_runrs or a.bench_level_adaptive:
         return bench(a)
     if not a.config or not a.input:

@@ -87,6 +87,8 @@ ABI_SYMBOLS = [
     "mfm_runroute_get_capacity", "mfm_hosttwin_runroute_capacity", "mfm_hosttwin_runroute_call",
     "mfm_runroute_create_sets", "mfm_runroute_route_channels", "mfm_runroute_route_caps", "mfm_runroute_fetch_payload",
     "mfm_hosttwin_runroute_route_caps", "mfm_hosttwin_runroute_sets_call",
+    "mfm_runroute_create_local", "mfm_runroute_bound_view", "mfm_hosttwin_runroute_local_call",
+    "mfm_runrs_process_view_device", "mfm_runrs_process_bits_view_device",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -602,6 +604,8 @@ def load_library():
     lib.mfm_runrs_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.mfm_runrs_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.mfm_runrs_process_bits_device.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
+    lib.mfm_runrs_process_view_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.mfm_runrs_process_bits_view_device.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp]
     lib.mfm_runrs_bits_view.argtypes = [vp, C.POINTER(RunrsBitsView)]
     lib.mfm_runrs_fetch_bits.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
     lib.mfm_runrs_get_bits_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
@@ -663,6 +667,9 @@ def load_library():
     lib.mfm_hosttwin_runroute_route_caps.argtypes = [C.POINTER(RunRouteConfig), vp, C.c_uint32, u32p, u32p, u32p]
     lib.mfm_hosttwin_runroute_sets_call.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp, vp, vp, vp, vp,
                                                     vp, C.c_size_t]
+    lib.mfm_runroute_create_local.argtypes = [C.POINTER(vp), C.POINTER(RunRouteConfig), vp]
+    lib.mfm_runroute_bound_view.argtypes = [vp, C.POINTER(vp)]
+    lib.mfm_hosttwin_runroute_local_call.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                               C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -1777,6 +1784,22 @@ class RunResampler:
         if rc < 0:
             self._raise(rc, "mfm_runrs_process_bits_device")
 
+    def process_view_device(self, d_runs, d_payload, d_totals, d_payload_elems, stream=None):
+        """mfm_runrs_process_view_device: as process_device behind a local route of the run router, RunRouter(local=True): the
+        three addresses of its device_view(route) and the address of its bound_view().  A run's payload range is checked against
+        the uint64 at d_payload_elems (how much payload exists); the totals' elements are only the load that must fit the capacity"""
+        rc = self.lib.mfm_runrs_process_view_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals),
+                                                    C.c_void_p(d_payload_elems), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_process_view_device")
+
+    def process_bits_view_device(self, d_runs, d_payload, d_totals, d_payload_elems, polarity, stream=None):
+        """mfm_runrs_process_bits_view_device: process_bits_device with the bound of process_view_device"""
+        rc = self.lib.mfm_runrs_process_bits_view_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals),
+                                                         C.c_void_p(d_payload_elems), polarity, C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runrs_process_bits_view_device")
+
     def bits_view(self):
         """RunrsBitsView of the last (bits) call: device addresses of its runs (out_offset in words), bit payload and totals"""
         v = RunrsBitsView()
@@ -1882,35 +1905,51 @@ class RunRouter:
     With sets= in the place of route_of_channel (mfm_runroute_create_sets) a channel's byte is a set of routes, bit k = route k, so a
     channel may feed several chains.  pack=True (MFM_RUNROUTE_F_PACK, sets form only) gives every route route-local channel
     numbers and a dense payload of its own: route_caps(k) are the numbers its RunResampler is made with, route_channels(k) maps
-    its local channels back, fetch_payload(k) reads its payload."""
+    its local channels back, fetch_payload(k) reads its payload.
+
+    local=True (mfm_runroute_create_local, with sets=, never with pack) gives pack's route-local channel numbers and route_caps()
+    on the gate's payload in place: nothing is copied, device_view(k) carries the gate's payload pointer and the route's own
+    load, and a route's RunResampler takes it through process_view_device / process_bits_view_device with bound_view()."""
 
     def __init__(self, route_of_channel=None, nr_routes=0, window_samples=0, max_in_samples=0, preroll_windows=0, max_windows=0, max_runs=0,
-                 device=0, flags=0, abi_version=MFM_ABI_VERSION, nr_channels=None, sets=None, pack=False):
+                 device=0, flags=0, abi_version=MFM_ABI_VERSION, nr_channels=None, sets=None, pack=False, local=False):
         self.lib = load_library()
         self.h = C.c_void_p()
         if sets is not None and route_of_channel is not None:
             raise ValueError("RunRouter takes route_of_channel or sets=, not both")
         if pack and sets is None:
             raise ValueError("pack=True needs sets=: mfm_runroute_create takes no flags")
+        if local and (sets is None or pack):
+            raise ValueError("local=True needs sets= and excludes pack=True: mfm_runroute_create_local takes a table of sets and no flags")
         table, ptr = _route_table(route_of_channel if sets is None else sets)
         nch = table.size if nr_channels is None else nr_channels
         flags |= MFM_RUNROUTE_F_PACK if pack else 0
         cfg = RunRouteConfig(abi_version, device, nch, nr_routes, window_samples, max_windows, max_runs, max_in_samples, preroll_windows, flags)
-        create = "mfm_runroute_create" if sets is None else "mfm_runroute_create_sets"
+        create = "mfm_runroute_create" if sets is None else "mfm_runroute_create_local" if local else "mfm_runroute_create_sets"
         rc = getattr(self.lib, create)(C.byref(self.h), C.byref(cfg), ptr)
         if rc < 0:
             self._raise(rc, create)
         self.nr_channels = nch
         self.nr_routes = nr_routes
         self.pack = bool(flags & MFM_RUNROUTE_F_PACK)
+        self.local = bool(local)
 
     @classmethod
     def behind(cls, route_of_channel, nr_routes, max_in_samples, window_samples, preroll_windows=0, max_open_windows=0, device=0, sets=None,
-               pack=False):
+               pack=False, local=False):
         """a router sized for everything one call of a Gate made from these numbers can hand over (its max_in_samples,
         window_samples, preroll_windows and max_open_windows): the capacity a RunResampler made from them has"""
         return cls(route_of_channel, nr_routes, window_samples=window_samples, max_in_samples=max_in_samples,
-                   preroll_windows=preroll_windows, max_windows=max_open_windows, device=device, sets=sets, pack=pack)
+                   preroll_windows=preroll_windows, max_windows=max_open_windows, device=device, sets=sets, pack=pack, local=local)
+
+    def bound_view(self):
+        """local=True only: the device address of one uint64, fixed at create, that every process_device call writes with the gate's
+        payload elements (0 for a call refused for the whole router): RunResampler.process_view_device's d_payload_elems"""
+        p = C.c_void_p()
+        rc = self.lib.mfm_runroute_bound_view(self.h, C.byref(p))
+        if rc < 0:
+            self._raise(rc, "mfm_runroute_bound_view")
+        return p.value
 
     def route_channels(self, route):
         """the global channel numbers of one route, ascending (uint32): under pack, local channel i is element i"""
@@ -1972,7 +2011,8 @@ class RunRouter:
 
     def device_view(self, route):
         """(d_runs, d_payload, d_totals) of one route, for RunResampler.process_device / process_bits_device: its run list, the
-        gate's payload pointer and its four uint64 totals (runs, the gate's payload elements, overflow, out of step)"""
+        gate's payload pointer and its four uint64 totals (runs, the gate's payload elements, overflow, out of step).  Under local
+        the second total is the route's load, and the view goes to process_view_device / process_bits_view_device with bound_view()"""
         r, p, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
         rc = self.lib.mfm_runroute_device_view(self.h, route, C.byref(r), C.byref(p), C.byref(t))
         if rc < 0:
@@ -1980,7 +2020,8 @@ class RunRouter:
         return r.value, p.value, t.value
 
     def fetch(self, route, max_runs=None):
-        """(runs, nr_elems) of one route of the last call: GATE_RUN_DTYPE [nr_runs] and the gate's payload elements.  With
+        """(runs, nr_elems) of one route of the last call: GATE_RUN_DTYPE [nr_runs] and the gate's payload elements (under pack the
+        route's own payload elements, under local the route's load: the samples of its records).  With
         max_runs too small: MfmError(MFM_E_NOMEM) whose `needed` attribute is the runs that would fit"""
         nr, ne = C.c_size_t(), C.c_size_t()
         if max_runs is None:
@@ -2099,6 +2140,36 @@ def hosttwin_runroute_sets_call(sets, nr_routes, gate_runs, gate_totals, max_run
     if flags & MFM_RUNROUTE_F_PACK:
         return runs, totals[:nr_routes], payloads
     return runs, totals[:nr_routes]
+
+
+def hosttwin_runroute_local_call(sets, nr_routes, gate_runs, gate_totals, window_samples, max_runs=None, route_max_runs=None,
+                                 route_max_windows=None):
+    """mfm_hosttwin_runroute_local_call: one call of a router made with sets= and local=True on the CPU.  As
+    hosttwin_runroute_sets_call under pack without the payloads: route_max_runs / route_max_windows are the routes' own capacities
+    (default: no limit below the call's own runs and windows).  Returns (runs, totals, payload_elems): GATE_RUN_DTYPE
+    [nr_routes][max_runs] with route-local channel numbers and the gate's payload offsets, uint64 [nr_routes][4] whose [k][1] is
+    the route's load, and what the call leaves behind RunRouter.bound_view()"""
+    lib = load_library()
+    table, ptr = _route_table(sets)
+    gr = np.ascontiguousarray(gate_runs, dtype=GATE_RUN_DTYPE)
+    gt = np.ascontiguousarray(gate_totals, dtype=np.uint64)
+    assert gt.shape == (4,)
+    max_runs = len(gr) if max_runs is None else max_runs
+    K = max(nr_routes, 1)
+    runs = np.zeros((K, max(max_runs, 1)), GATE_RUN_DTYPE)
+    totals = np.zeros((K, 4), np.uint64)
+    stride = runs.shape[1] if max_runs else 0
+    all_windows = int(gr["nr_windows"].astype(np.uint64).sum())
+    rmr = np.ascontiguousarray(np.full(K, max_runs) if route_max_runs is None else route_max_runs, dtype=np.uint32)
+    rmw = np.ascontiguousarray(np.full(K, all_windows) if route_max_windows is None else route_max_windows, dtype=np.uint32)
+    assert rmr.shape == rmw.shape == (K,)
+    bound = C.c_uint64()
+    rc = lib.mfm_hosttwin_runroute_local_call(table.size, nr_routes, ptr, window_samples, stride, rmr.ctypes.data, rmw.ctypes.data,
+                                              gr.ctypes.data if gr.size else None, gt.ctypes.data, runs.ctypes.data, totals.ctypes.data,
+                                              C.byref(bound))
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runroute_local_call", lib.mfm_last_error().decode() or lib.mfm_strerror(rc).decode())
+    return runs, totals[:nr_routes], bound.value
 
 
 class RunAis:

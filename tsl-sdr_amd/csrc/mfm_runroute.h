@@ -118,4 +118,31 @@ inline bool mfm_runroute_pack_caps(uint32_t n, uint32_t window_samples, uint32_t
     return true;
 }
 
+/*
+ * ---- the local form (mfm_runroute_create_local): PACK's route-local channel numbers, capacities and per-route overflow on the
+ * gate's payload in place.  The set lookup, the rank, mfm_runroute_route_over and mfm_runroute_pack_caps above are its rules
+ * too; a payload range is not looked at (nothing is copied: it is the burst resampler's view entry that checks it, against the
+ * bound the router hands on).  Stated once for the kernel of mfm_runroute_local.hip and for mfm_hosttwin_runroute_local_call.
+ */
+
+/* the kernel's form of a routed record's channel: the record's third 64-bit word (channel | nr_windows << 32) with the channel
+ * replaced by its rank in the route */
+__host__ __device__ inline uint64_t mfm_runroute_local_word(uint64_t word, uint32_t local_channel)
+{
+    return (word & 0xffffffff00000000ull) | local_channel;
+}
+
+/* a route's load, its totals' elements: the windows of its records times W; below 2^52 for a route within its capacity */
+__host__ __device__ inline uint64_t mfm_runroute_load(uint64_t windows, uint32_t window_samples)
+{
+    return windows * window_samples;
+}
+
+/* the bound the router hands to the burst resampler's view entry: the gate's payload elements, 0 for a call refused for the
+ * whole router */
+__host__ __device__ inline uint64_t mfm_runroute_bound(bool refused, uint64_t gate_elems)
+{
+    return refused ? 0u : gate_elems;
+}
+
 #endif /* MFM_RUNROUTE_H */

@@ -280,6 +280,7 @@ void mfm_runroute_destroy(struct mfm_runroute **prt)
     (void)hipFree(rt->d_table);
     (void)hipFree(rt->d_runs);
     (void)hipFree(rt->d_totals);
+    (void)hipFree(rt->d_bound);
     mfm_runroute_sets_free(rt);
     delete rt;
     *prt = nullptr;
@@ -295,6 +296,9 @@ int mfm_runroute_process_device(struct mfm_runroute *rt, const struct mfm_gate_r
     RT_TRY(hipSetDevice(rt->cfg.device));
     if (rt->have_call && rt->last_stream != s) {
         RT_TRY(hipStreamSynchronize(rt->last_stream)); /* the result buffers are reused: keep calls ordered */
+    }
+    if (rt->local) { /* made by mfm_runroute_create_local: the kernel of mfm_runroute_local.hip */
+        return mfm_runroute_local_process(rt, d_runs, d_payload, d_totals, s);
     }
     if (rt->sets) { /* made by mfm_runroute_create_sets: the kernels of mfm_runroute_sets.hip */
         return mfm_runroute_sets_process(rt, d_runs, d_payload, d_totals, s);

@@ -322,15 +322,21 @@ struct RsGeometry {
     mfm_runrs_caps route[RS_K] = {}; /* PACK */
 };
 
-const char *rs_geometry(const mfm_runroute_config &cfg, const uint8_t *routes_of_channel, RsGeometry &G, char *err, size_t cap)
+/* local: for mfm_runroute_create_local, which takes no flag and whose routes are sized as PACK's are, without a payload of
+ * their own */
+const char *rs_geometry(const mfm_runroute_config &cfg, const uint8_t *routes_of_channel, RsGeometry &G, char *err, size_t cap, bool local = false)
 {
     if (cfg.abi_version != MFM_ABI_VERSION) {
         return "abi_version is not MFM_ABI_VERSION";
     }
+    if (local && cfg.flags != 0) {
+        return "flags must be 0: mfm_runroute_create_local takes none, and MFM_RUNROUTE_F_PACK belongs to mfm_runroute_create_sets";
+    }
     if (cfg.flags & ~MFM_RUNROUTE_F_PACK) {
         return "flags must be 0 or MFM_RUNROUTE_F_PACK";
     }
-    const bool pack = (cfg.flags & MFM_RUNROUTE_F_PACK) != 0;
+    const bool pack = local || (cfg.flags & MFM_RUNROUTE_F_PACK) != 0; /* the routes are sized to their channels */
+    const char *form = local ? "behind mfm_runroute_create_local" : "under MFM_RUNROUTE_F_PACK";
     if (const char *m = rs_table_check(cfg.nr_channels, cfg.nr_routes, routes_of_channel, err, cap)) {
         return m;
     }
@@ -359,12 +365,13 @@ const char *rs_geometry(const mfm_runroute_config &cfg, const uint8_t *routes_of
     uint64_t tiles = 0;
     for (uint32_t k = 0; k < cfg.nr_routes; k++) {
         if (0 == G.nr_of[k]) {
-            snprintf(err, cap, "route %u has no channel: under MFM_RUNROUTE_F_PACK a route's stages are sized to its channels", k);
+            snprintf(err, cap, "route %u has no channel: %s a route's stages are sized to its channels", k, form);
             return err;
         }
         if (!mfm_runroute_pack_caps(G.nr_of[k], cfg.window_samples, cfg.max_windows, cfg.max_runs, cfg.max_in_samples, cfg.preroll_windows,
                                     G.route[k])) {
-            return "MFM_RUNROUTE_F_PACK with max_in_samples 0 needs max_windows and max_runs";
+            return local ? "mfm_runroute_create_local with max_in_samples 0 needs max_windows and max_runs"
+                         : "MFM_RUNROUTE_F_PACK with max_in_samples 0 needs max_windows and max_runs";
         }
         if (G.route[k].runs > G.cap_runs) { /* a route's list is a row of the router's capacity; the rule never gives more */
             G.route[k].runs = G.cap_runs;
@@ -374,7 +381,7 @@ const char *rs_geometry(const mfm_runroute_config &cfg, const uint8_t *routes_of
         }
         tiles += (G.route[k].windows * cfg.window_samples + RT_TILE - 1u) / RT_TILE;
     }
-    if (tiles >= (1ull << 31)) {
+    if (!local && tiles >= (1ull << 31)) { /* the local form copies nothing */
         return "the routes' payload capacities together must stay below 2^31 tiles of 8192 elements";
     }
     return nullptr;
@@ -393,6 +400,22 @@ const char *rs_geometry(const mfm_runroute_config &cfg, const uint8_t *routes_of
     } while (0)
 
 extern "C" {
+
+const char *mfm_runroute_local_geometry(const struct mfm_runroute_config *cfg, const uint8_t *routes_of_channel, uint64_t *cap_runs,
+                                        uint32_t *nr_of, uint64_t *route_runs, uint64_t *route_windows, char *err, size_t cap)
+{
+    RsGeometry G;
+    if (const char *m = rs_geometry(*cfg, routes_of_channel, G, err, cap, true)) {
+        return m;
+    }
+    *cap_runs = G.cap_runs;
+    for (uint32_t k = 0; k < RS_K; k++) {
+        nr_of[k] = G.nr_of[k];
+        route_runs[k] = G.route[k].runs;
+        route_windows[k] = G.route[k].windows;
+    }
+    return nullptr;
+}
 
 void mfm_runroute_sets_free(struct mfm_runroute *rt)
 {
@@ -542,14 +565,15 @@ int mfm_runroute_route_caps(struct mfm_runroute *rt, uint32_t route, uint32_t *n
     if (route >= rt->cfg.nr_routes) {
         return rs_fail(MFM_E_INVAL, "route must be below nr_routes");
     }
+    const bool sized = rt->pack || rt->local; /* the route's own numbers */
     if (nr_channels) {
-        *nr_channels = rt->pack ? rt->nr_of[route] : rt->cfg.nr_channels;
+        *nr_channels = sized ? rt->nr_of[route] : rt->cfg.nr_channels;
     }
     if (max_windows) {
-        *max_windows = rt->pack ? (uint32_t)rt->cap_route_windows[route] : rt->cfg.max_windows;
+        *max_windows = sized ? (uint32_t)rt->cap_route_windows[route] : rt->cfg.max_windows;
     }
     if (max_runs) {
-        *max_runs = (uint32_t)(rt->pack ? rt->cap_route_runs[route] : rt->cap_runs);
+        *max_runs = (uint32_t)(sized ? rt->cap_route_runs[route] : rt->cap_runs);
     }
     return MFM_OK;
 }

@@ -46,6 +46,10 @@
  * run's bits start on a word, so no word is shared between workgroups or runs; lanes past the run's end contribute 0,
  * which is what zeroes the tail of its last word.
  *
+ * The view entries (mfm_runrs_process_view_device, mfm_runrs_process_bits_view_device: a resampler sized to a local route of the
+ * run router reads the gate's payload in place) queue rrv_plan_kernel (mfm_runrs_view.hip) in the place of rr_plan_kernel - the
+ * same body, with a run's range checked against a bound of its own instead of the totals' elements - and everything else as it is.
+ *
  * Nothing is floating point and nothing goes through an atomic.
  */
 #include <hip/hip_runtime.h>
@@ -70,6 +74,10 @@ extern "C" __attribute__((visibility("hidden"))) int mfm_internal_runrs_bits_lau
 
 /* the DC blocker's kernel (mfm_runrs_dc.hip), queued on s between the FIR and the state kernel */
 extern "C" __attribute__((visibility("hidden"))) int mfm_internal_runrs_dc_launch(const void *call, uint32_t cap_runs, hipStream_t s);
+
+/* the view entries' plan kernel (mfm_runrs_view.hip), queued on s in the place of rr_plan_kernel */
+extern "C" __attribute__((visibility("hidden"))) int mfm_internal_runrs_view_plan_launch(const void *call, const uint64_t *d_payload_elems,
+                                                                                        uint32_t cap_runs, hipStream_t s);
 
 namespace {
 
@@ -168,39 +176,7 @@ int rr_geometry(const mfm_runrs_config &cfg, const int16_t *coeffs, size_t nr_co
 
 __global__ __launch_bounds__(256) void rr_plan_kernel(const RrCall A)
 {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t over, gate;
-    if (rr_refused(A, over, gate) || r >= A.gtotals[RR_T_RUNS]) { /* surplus lanes, and every lane of a refused call */
-        return;
-    }
-    const uint64_t n = A.gtotals[RR_T_RUNS];
-    const mfm_gate_run g = A.gruns[r];
-    const uint64_t nsamp = (uint64_t)g.nr_windows * A.W;
-    if (g.channel >= A.C || g.payload_offset > A.gtotals[RR_T_ELEMS] || nsamp > A.gtotals[RR_T_ELEMS] - g.payload_offset) {
-        A.bad[r] = 1; /* not a gate's run: the scan raises the flag and nothing goes out */
-        A.nblk[r] = 0;
-        A.runs[r].nr_out = 0;
-        return;
-    }
-    const bool first = r == 0 || A.gruns[r - 1].channel != g.channel;
-    const bool last = r + 1 == n || A.gruns[r + 1].channel != g.channel;
-    const mfm_runrs_start s = mfm_runrs_start_of(A.chan_old[g.channel], first, g.first_window);
-    const mfm_runrs_step st = mfm_runrs_plan_run(A.I, A.D, A.plen, s.phase, s.pending, nsamp);
-    mfm_runrs_run o;
-    o.first_window = g.first_window;
-    o.out_offset = 0; /* the scan */
-    o.first_out = s.first_out;
-    o.channel = g.channel;
-    o.nr_out = (uint32_t)st.nr_out; /* below 2^31: nsamp is within the capacity */
-    o.flags = s.begins ? MFM_RUNRS_BEGINS : 0u;
-    o.reserved = 0;
-    A.runs[r] = o;
-    A.plan[r] = RrPlan{ s.phase, s.pending };
-    A.nblk[r] = (uint32_t)((st.nr_out + RR_OPB - 1u) / RR_OPB);
-    A.bad[r] = 0;
-    if (last) {
-        A.chan_last[g.channel] = (uint32_t)r;
-    }
+    rr_plan_body<false>(A, nullptr);
 }
 
 __global__ __launch_bounds__(RR_SCAN_THREADS) void rr_scan_kernel(const RrCall A)
@@ -320,10 +296,12 @@ void rr_launch_fir(const RrGeom &g, const RrCall &A, hipStream_t s)
     }
 }
 
-/* one call in either form: polarity 0 is the PCM form */
-int rr_process(mfm_runrs *rr, const mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals, uint32_t polarity, void *stream)
+/* one call in either form: polarity 0 is the PCM form.  view: the view entries, whose plan kernel (mfm_runrs_view.hip) checks a
+ * run's payload range against *d_payload_elems; everything behind it is queued as without */
+int rr_process(mfm_runrs *rr, const mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals, uint32_t polarity, void *stream,
+               bool view = false, const uint64_t *d_payload_elems = nullptr)
 {
-    if (!rr || !d_runs || !d_payload || !d_totals) {
+    if (!rr || !d_runs || !d_payload || !d_totals || (view && !d_payload_elems)) {
         return MFM_E_INVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -340,7 +318,12 @@ int rr_process(mfm_runrs *rr, const mfm_gate_run *d_runs, const int16_t *d_paylo
                     g.W,         g.I,             g.D,       g.plen,          rr->pend_stride,      rr->cfg.invert,  g.coef_bytes,
                     rr->d_bits,  polarity,        rr->dc_on ? rr->d_dc[cur] : nullptr,      rr->dc_on ? rr->d_dc[cur ^ 1u] : nullptr,
                     rr->dc_p };
-    if (g.cap_runs) {
+    if (g.cap_runs && view) {
+        if (mfm_internal_runrs_view_plan_launch(&A, d_payload_elems, (uint32_t)g.cap_runs, s) != MFM_OK) {
+            RR_TRY(hipGetLastError());
+            return MFM_E_DEVICE;
+        }
+    } else if (g.cap_runs) {
         hipLaunchKernelGGL(rr_plan_kernel, dim3((uint32_t)((g.cap_runs + 255u) / 256u)), dim3(256), 0, s, A);
         RR_TRY(hipGetLastError());
     }
@@ -501,6 +484,25 @@ int mfm_runrs_process_bits_device(struct mfm_runrs *rr, const struct mfm_gate_ru
                                     "taken from (mfm_runrs_process_device, or mfm_runrs_set_dc_block off)");
     }
     return rr_process(rr, d_runs, d_payload, d_totals, polarity, stream);
+}
+
+int mfm_runrs_process_view_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                                  const uint64_t *d_payload_elems, void *stream)
+{
+    return rr_process(rr, d_runs, d_payload, d_totals, 0, stream, true, d_payload_elems);
+}
+
+int mfm_runrs_process_bits_view_device(struct mfm_runrs *rr, const struct mfm_gate_run *d_runs, const int16_t *d_payload,
+                                       const uint64_t *d_totals, const uint64_t *d_payload_elems, uint32_t polarity, void *stream)
+{
+    if (polarity != MFM_BITS_NEG && polarity != MFM_BITS_POS) {
+        return rr_fail(MFM_E_INVAL, "polarity must be MFM_BITS_NEG or MFM_BITS_POS");
+    }
+    if (rr && rr->dc_on) {
+        return rr_fail(MFM_E_INVAL, "the sign-bit output is not available with the DC blocker: it filters the PCM the predicate would be "
+                                    "taken from (mfm_runrs_process_view_device, or mfm_runrs_set_dc_block off)");
+    }
+    return rr_process(rr, d_runs, d_payload, d_totals, polarity, stream, true, d_payload_elems);
 }
 
 int mfm_runrs_set_dc_block(struct mfm_runrs *rr, uint32_t on, double pole)

@@ -1,8 +1,9 @@
 /*
- * mfm_runrs_kernels.h - the device code of the burst resampler's scan and FIR kernels (see mfm_runrs.hip for the four kernels
- * and what each does), as bodies with the form as a template parameter: mfm_runrs.hip instantiates the PCM form
+ * mfm_runrs_kernels.h - the device code of the burst resampler's plan, scan and FIR kernels (see mfm_runrs.hip for the four
+ * kernels and what each does), as bodies with the form as a template parameter: mfm_runrs.hip instantiates the PCM form
  * (rr_scan_kernel, rr_fir_kernel<NP>), mfm_run_bits.hip the bits form (rrb_scan_kernel, rrb_fir_kernel<NP>), so the two
- * forms share every line but the store and neither pays for the other.
+ * forms share every line but the store and neither pays for the other; the plan body is rr_plan_kernel's there and, with the
+ * bound of the payload ranges taken apart from the load, rrv_plan_kernel's in mfm_runrs_view.hip (the view entries).
  */
 #ifndef MFM_RUNRS_KERNELS_H
 #define MFM_RUNRS_KERNELS_H
@@ -61,6 +62,54 @@ __device__ __forceinline__ bool rr_refused(const RrCall &A, uint64_t &over, uint
         over = MFM_RUNRS_OVER_OWN;
     }
     return over || gate;
+}
+
+/*
+ * The plan pass, one lane per run (mfm_runrs.hip describes it).  VIEW is the one difference between rr_plan_kernel and the view
+ * entries' rrv_plan_kernel (mfm_runrs_view.hip): what a run's payload range is checked against.  Without it that is the totals'
+ * own elements, the payload being the gate's whole; with it *payload_elems, how much payload exists, while the totals' elements
+ * are only the load rr_refused holds against the capacity (a local route's of the run router).  The FIR and the state kernel read
+ * a run's range only from runs this pass let through, so the bound here is the bound of every read.
+ */
+template <bool VIEW>
+__device__ __forceinline__ void rr_plan_body(const RrCall &A, const uint64_t *payload_elems)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t over, gate;
+    if (rr_refused(A, over, gate) || r >= A.gtotals[RR_T_RUNS]) { /* surplus lanes, and every lane of a refused call */
+        return;
+    }
+    const uint64_t n = A.gtotals[RR_T_RUNS];
+    const uint64_t exists = VIEW ? *payload_elems : A.gtotals[RR_T_ELEMS];
+    const mfm_gate_run g = A.gruns[r];
+    const uint64_t nsamp = (uint64_t)g.nr_windows * A.W;
+    /* VIEW: the load is within cap_elems (rr_refused), so a run of the list it belongs to is; one that is longer is not of that
+     * list, and everything behind counts on a run's samples being within the capacity, as they are without VIEW */
+    if (g.channel >= A.C || g.payload_offset > exists || nsamp > exists - g.payload_offset || (VIEW && nsamp > A.cap_elems)) {
+        A.bad[r] = 1; /* not a gate's run: the scan raises the flag and nothing goes out */
+        A.nblk[r] = 0;
+        A.runs[r].nr_out = 0;
+        return;
+    }
+    const bool first = r == 0 || A.gruns[r - 1].channel != g.channel;
+    const bool last = r + 1 == n || A.gruns[r + 1].channel != g.channel;
+    const mfm_runrs_start s = mfm_runrs_start_of(A.chan_old[g.channel], first, g.first_window);
+    const mfm_runrs_step st = mfm_runrs_plan_run(A.I, A.D, A.plen, s.phase, s.pending, nsamp);
+    mfm_runrs_run o;
+    o.first_window = g.first_window;
+    o.out_offset = 0; /* the scan */
+    o.first_out = s.first_out;
+    o.channel = g.channel;
+    o.nr_out = (uint32_t)st.nr_out; /* below 2^31: nsamp is within the capacity */
+    o.flags = s.begins ? MFM_RUNRS_BEGINS : 0u;
+    o.reserved = 0;
+    A.runs[r] = o;
+    A.plan[r] = RrPlan{ s.phase, s.pending };
+    A.nblk[r] = (uint32_t)((st.nr_out + RR_OPB - 1u) / RR_OPB);
+    A.bad[r] = 0;
+    if (last) {
+        A.chan_last[g.channel] = (uint32_t)r;
+    }
 }
 
 /* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
