@@ -1515,6 +1515,50 @@ int mfm_runais_device_view(struct mfm_runais *a, const struct mfm_runais_event *
 struct mfm_runais_state;
 int mfm_runais_fetch_state(struct mfm_runais *a, struct mfm_runais_state *state, size_t nr_channels);
 int mfm_runais_store_state(struct mfm_runais *a, const struct mfm_runais_state *state, size_t nr_channels);
+/*
+ * Stretch-end records: how each stretch ended and what the closing squelch cut.  Off at create; with the report on, one record
+ * per stretch over the whole stream.  Events, totals and state are those of an object with the report off, and with it off a
+ * process call queues exactly the launches it queued before the report existed.
+ *
+ * Rule.  A stretch of channel c ends in one of three ways.
+ *   (a) A call that is not refused holds a run r that is c's first run of the call and has MFM_RUNRS_BEGINS, and the state the
+ *       call started from has has_stretch == 1.  The record is taken from that carried state; run = r.
+ *   (b) A call that is not refused holds a run r of c whose successor r + 1 in the list is also of channel c (that successor
+ *       necessarily begins a stretch).  The record is taken from the state r's walk ended in; run = r + 1.
+ *   (c) The end call below, at the end of a stream behind the gate's flush: every channel with has_stretch == 1 gets a record,
+ *       channels ascending, run = 0xffffffff, and afterwards every channel's state is all zero.  The end call replaces the
+ *       previous result: the event list is empty and the totals read { 0, 0, 0, 0 }.  After it a continuing run is
+ *       MFM_RUNAIS_IN_OUT_OF_STEP (the channel has no stretch) and a beginning run is fine.
+ * The records of a process call follow run-list order, (a) in front of (b) where a run yields both: channels ascending, stream
+ * order within a channel.  A refused call writes no record and moves no state; the same input in calls that fit yields the
+ * right records.  A record's content does not depend on how the stream was cut into calls, only the call it appears in does.
+ * A run with nr_out == 0 begins or continues its stretch as before, and a stretch of such runs alone still gets a record, with
+ * outs = 0 and mode SEARCH.  A process call holds at most max_runs records and an end call at most nr_channels: the capacity
+ * allocated when the report is switched on is the larger of the two.
+ *
+ * mode 1 (RECEIVE) says a packet was cut: its preamble matched at start_sample and nr_bits bits had been kept.
+ */
+struct mfm_runais_end {         /* 48 bytes */
+    uint64_t stretch_window;    /* first window of the stretch: its first input sample is stretch_window * W */
+    uint64_t outs;              /* resampled outputs of the whole stretch */
+    uint64_t start_sample;      /* RECEIVE: as the event of the packet would have reported it; 0 in SEARCH */
+    uint32_t channel;
+    uint32_t run;               /* index, in this call's run list, of the run that begins the next stretch; 0xffffffff: end call */
+    uint32_t mode;              /* 0 SEARCH, 1 RECEIVE */
+    uint32_t nr_bits;           /* RECEIVE: bits of the packet kept so far */
+    uint32_t reserved[2];       /* 0 */
+};
+/* Switch the report on or off.  Valid only before the first process call: MFM_E_STATE with a message afterwards. */
+int mfm_runais_set_end_report(struct mfm_runais *a, int on);
+/* (c) above, queued on `stream` like a process call.  MFM_E_STATE with a message when the report is off. */
+int mfm_runais_end_stretches_device(struct mfm_runais *a, void *stream);
+/* Wait for the last call (process or end) and copy its records.  MFM_E_NOMEM when max_ends is too small (nothing copied,
+ * *nr_ends = needed); MFM_E_STATE with a message when the report is off, before the first call, or when the last call was
+ * refused. */
+int mfm_runais_fetch_ends(struct mfm_runais *a, struct mfm_runais_end *ends, size_t max_ends, size_t *nr_ends);
+/* For consumers that stay on the device: the last call's records and d_end_totals[2] = { records, records with mode != 0 },
+ * valid until the next call.  Either may be NULL.  MFM_E_STATE with a message when the report is off. */
+int mfm_runais_ends_view(struct mfm_runais *a, const struct mfm_runais_end **d_ends, const uint64_t **d_end_totals);
 
 /*
  * ---- Burst POCSAG stage: the burst resampler's runs through the POCSAG demodulator, on the device -----------------------
@@ -1635,6 +1679,52 @@ int mfm_runpocsag_fetch_state(struct mfm_runpocsag *p, struct mfm_runpocsag_stat
  * what the next process call reads.  A state that fails gets MFM_E_INVAL with a message naming channel and field, and nothing
  * is written.  The events of the last call stay readable. */
 int mfm_runpocsag_store_state(struct mfm_runpocsag *p, const struct mfm_runpocsag_state *state, size_t nr_channels);
+/*
+ * Stretch-end records, as the burst AIS stage's: off at create, one record per stretch over the whole stream, and nothing
+ * else changes with the report on or off.
+ *
+ * Rule.  A stretch of channel c ends (a) in front of a run r that is c's first of a call that is not refused and has
+ * MFM_RUNRS_BEGINS while the state the call started from has has_stretch == 1 (the record of that carried state, run = r);
+ * (b) behind a run r of such a call whose successor r + 1 is also of channel c (the record of the state r's walk ended in,
+ * run = r + 1); (c) at the end call: every channel with has_stretch == 1, channels ascending, run = 0xffffffff, after which
+ * every state is all zero, the event list is empty, the totals read { 0, 0, 0, 0 }, a continuing run is
+ * MFM_RUNPOCSAG_IN_OUT_OF_STEP and a beginning run is fine.  Records follow run-list order, (a) in front of (b).  A refused
+ * call writes no record and moves no state.  Content does not depend on how the stream was cut into calls.  A stretch of runs
+ * with nr_out == 0 alone gets a record with outs = 0 and mode SEARCH.  At most max_runs records per process call and
+ * nr_channels per end call.
+ *
+ * The cut batch.  Every codeword of a batch is BCH-protected on its own, so the whole words of a batch the squelch cut
+ * (mode 2, words 0 .. nr_words - 1) are corrected here exactly as a BATCH event's are: masked with 0x7fffffff, the stage's own
+ * decoder, nr_ok the words accepted in front of the first failure (at most nr_words), fail_mask with bits below nr_words only.
+ * raw[] is the batch as collected, the nr_bits bits of the word in progress included; corrected[z] is 0 from nr_words on.
+ */
+struct mfm_runpocsag_end {      /* 184 bytes */
+    uint64_t stretch_window;    /* first window of the stretch: its first input sample is stretch_window * W */
+    uint64_t outs;              /* resampled outputs of the whole stretch */
+    uint32_t channel;
+    uint32_t run;               /* index, in this call's run list, of the run that begins the next stretch; 0xffffffff: end call */
+    uint32_t mode;              /* 0 SEARCH, 2 BATCH, 3 SYNCWORD */
+    uint32_t baud;              /* BATCH / SYNCWORD: 512 / 1200 / 2400 */
+    uint32_t nr_words;          /* BATCH: whole words collected */
+    uint32_t nr_bits;           /* BATCH: bits of the word in progress */
+    uint32_t nr_sync_bits;      /* SYNCWORD: bits of the sync slot collected */
+    uint32_t reserved;          /* 0 */
+    uint32_t nr_ok;
+    uint32_t fail_mask;
+    uint32_t raw[16];
+    uint32_t corrected[16];
+};
+/* Switch the report on or off.  Valid only before the first process call: MFM_E_STATE with a message afterwards. */
+int mfm_runpocsag_set_end_report(struct mfm_runpocsag *p, int on);
+/* (c) above, queued on `stream` like a process call.  MFM_E_STATE with a message when the report is off. */
+int mfm_runpocsag_end_stretches_device(struct mfm_runpocsag *p, void *stream);
+/* Wait for the last call (process or end) and copy its records.  MFM_E_NOMEM when max_ends is too small (nothing copied,
+ * *nr_ends = needed); MFM_E_STATE with a message when the report is off, before the first call, or when the last call was
+ * refused. */
+int mfm_runpocsag_fetch_ends(struct mfm_runpocsag *p, struct mfm_runpocsag_end *ends, size_t max_ends, size_t *nr_ends);
+/* The last call's records and d_end_totals[2] = { records, records with mode != 0 } on the device, valid until the next call.
+ * Either may be NULL.  MFM_E_STATE with a message when the report is off. */
+int mfm_runpocsag_ends_view(struct mfm_runpocsag *p, const struct mfm_runpocsag_end **d_ends, const uint64_t **d_end_totals);
 
 /*
  * ---- Burst FLEX stage: the burst resampler's runs through the FLEX front half, on the device ------------------------------
@@ -1758,6 +1848,49 @@ int mfm_runflex_fetch_state(struct mfm_runflex *f, struct mfm_runflex_state *sta
  * MFM_E_INVAL with a message naming channel and field, and nothing is written.  The events and frames of the last call stay
  * readable. */
 int mfm_runflex_store_state(struct mfm_runflex *f, const struct mfm_runflex_state *state, const int16_t *ring, size_t nr_channels);
+/*
+ * Stretch-end records, as the burst AIS stage's: off at create, one record per stretch over the whole stream, and nothing
+ * else changes with the report on or off.
+ *
+ * Rule.  A stretch of channel c ends (a) in front of a run r that is c's first of a call that is not refused and has
+ * MFM_RUNRS_BEGINS while the state the call started from has has_stretch == 1 (the record of that carried state, run = r);
+ * (b) behind a run r of such a call whose successor r + 1 is also of channel c (the record of the state r's walk ended in,
+ * run = r + 1); (c) at the end call: every channel with has_stretch == 1, channels ascending, run = 0xffffffff, after which
+ * every state is all zero (the rings stay: a beginning run never reads one), the event and frame lists are empty, the totals
+ * read { 0, 0, 0, 0 }, a continuing run is MFM_RUNFLEX_IN_OUT_OF_STEP and a beginning run is fine.  Records follow run-list
+ * order, (a) in front of (b).  A refused call writes no record and moves no state.  Content does not depend on how the stream
+ * was cut into calls.  A stretch of runs with nr_out == 0 alone gets a record with outs = 0 and mode SEARCH.  At most max_runs
+ * records per process call and nr_channels per end call.
+ *
+ * mode 1 (SYNC1): the squelch closed between the end of the BS1 run at sample j and the frame information word; mode 2
+ * (FRAME): between the FIW, whose last bit lay at j, and the last block symbol, and cycle / frame / coding / fiw are the FRAME
+ * event's that never came.
+ */
+struct mfm_runflex_end {        /* 64 bytes */
+    uint64_t stretch_window;    /* first window of the stretch: its first input sample is stretch_window * W */
+    uint64_t outs;              /* resampled outputs of the whole stretch */
+    uint64_t j;                 /* as mfm_runflex_state.j; 0 in SEARCH */
+    uint32_t channel;
+    uint32_t run;               /* index, in this call's run list, of the run that begins the next stretch; 0xffffffff: end call */
+    uint32_t mode;              /* 0 SEARCH, 1 SYNC1, 2 FRAME */
+    uint32_t eye;               /* SYNC1 / FRAME */
+    uint32_t coding;            /* FRAME, as are fiw, cycle and frame */
+    uint32_t fiw;
+    uint32_t cycle;
+    uint32_t frame;
+    uint32_t reserved[2];       /* 0 */
+};
+/* Switch the report on or off.  Valid only before the first process call: MFM_E_STATE with a message afterwards. */
+int mfm_runflex_set_end_report(struct mfm_runflex *f, int on);
+/* (c) above, queued on `stream` like a process call.  MFM_E_STATE with a message when the report is off. */
+int mfm_runflex_end_stretches_device(struct mfm_runflex *f, void *stream);
+/* Wait for the last call (process or end) and copy its records.  MFM_E_NOMEM when max_ends is too small (nothing copied,
+ * *nr_ends = needed); MFM_E_STATE with a message when the report is off, before the first call, or when the last call was
+ * refused. */
+int mfm_runflex_fetch_ends(struct mfm_runflex *f, struct mfm_runflex_end *ends, size_t max_ends, size_t *nr_ends);
+/* The last call's records and d_end_totals[2] = { records, records with mode != 0 } on the device, valid until the next call.
+ * Either may be NULL.  MFM_E_STATE with a message when the report is off. */
+int mfm_runflex_ends_view(struct mfm_runflex *f, const struct mfm_runflex_end **d_ends, const uint64_t **d_end_totals);
 
 /*
  * ---- Mueller-Muller clock recovery (BASELINE.json configs[3]: "mueller_muller slicer") -------------------------
@@ -2050,6 +2183,17 @@ int mfm_hosttwin_runais_call_bits(uint32_t nr_channels, uint32_t max_runs, uint3
 /* the validation mfm_runais_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
  * channel and field that fail (csrc/mfm_runais.h) */
 int mfm_hosttwin_runais_state_check(uint32_t nr_channels, const struct mfm_runais_state *state);
+/* mfm_hosttwin_runais_call with the stretch-end records of the call (mfm_runais_fetch_ends' of an object with the report on):
+ * at most max_ends are written, *nr_ends is their number; MFM_E_NOMEM when max_ends is too small (*nr_ends = needed), and on
+ * any error nothing is written, the state included.  There is no twin for the bits form: records do not depend on the form. */
+int mfm_hosttwin_runais_call_ends(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                  struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                                  const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags,
+                                  struct mfm_runais_end *ends, size_t max_ends, size_t *nr_ends);
+/* host twin of mfm_runais_end_stretches_device and its fetch: a record for every channel with a stretch, then state
+ * [nr_channels] all zero; MFM_E_NOMEM when max_ends is too small (*nr_ends = needed, nothing written) */
+int mfm_hosttwin_runais_end_stretches(uint32_t nr_channels, struct mfm_runais_state *state, struct mfm_runais_end *ends, size_t max_ends,
+                                      size_t *nr_ends);
 /* the per-channel state of the burst POCSAG stage, on the device and in the host twin: all zero at the start of a stream.
  * Fields a mode does not use are zero.  What a stored state must satisfy: csrc/mfm_runpocsag.h (mfm_runpocsag_state_check) */
 struct mfm_runpocsag_state {    /* 432 bytes */
@@ -2089,6 +2233,14 @@ int mfm_hosttwin_runpocsag_call_bits(uint32_t nr_channels, uint32_t max_runs, ui
 /* the validation mfm_runpocsag_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
  * channel and field that fail (csrc/mfm_runpocsag.h) */
 int mfm_hosttwin_runpocsag_state_check(uint32_t nr_channels, const struct mfm_runpocsag_state *state);
+/* mfm_hosttwin_runpocsag_call with the stretch-end records of the call, as mfm_hosttwin_runais_call_ends */
+int mfm_hosttwin_runpocsag_call_ends(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                     struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                                     const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events,
+                                     uint32_t *flags, struct mfm_runpocsag_end *ends, size_t max_ends, size_t *nr_ends);
+/* host twin of mfm_runpocsag_end_stretches_device and its fetch, as mfm_hosttwin_runais_end_stretches */
+int mfm_hosttwin_runpocsag_end_stretches(uint32_t nr_channels, struct mfm_runpocsag_state *state, struct mfm_runpocsag_end *ends,
+                                         size_t max_ends, size_t *nr_ends);
 /* the per-channel state of the burst FLEX stage, on the device and in the host twin, beside the channel's ring of 32 768 PCM
  * samples: all zero at the start of a stream.  Positions are stretch-relative.  Fields a mode does not use are zero.  What a
  * stored state must satisfy: csrc/mfm_runflex.h (mfm_runflex_state_check) */
@@ -2125,6 +2277,15 @@ int mfm_hosttwin_runflex_call(uint32_t nr_channels, uint32_t max_runs, uint32_t 
 /* the validation mfm_runflex_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
  * channel and field that fail (csrc/mfm_runflex.h) */
 int mfm_hosttwin_runflex_state_check(uint32_t nr_channels, const struct mfm_runflex_state *state);
+/* mfm_hosttwin_runflex_call with the stretch-end records of the call, as mfm_hosttwin_runais_call_ends */
+int mfm_hosttwin_runflex_call_ends(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                   uint32_t max_frames, struct mfm_runflex_state *state, int16_t *ring, const struct mfm_runrs_run *runs,
+                                   const int16_t *payload, const uint64_t *totals, struct mfm_runflex_event *events, size_t max_out,
+                                   size_t *nr_events, struct mfm_flex_frame_words *frames, size_t max_out_frames, size_t *nr_frames,
+                                   uint32_t *flags, struct mfm_runflex_end *ends, size_t max_ends, size_t *nr_ends);
+/* host twin of mfm_runflex_end_stretches_device and its fetch, as mfm_hosttwin_runais_end_stretches (the rings are not touched) */
+int mfm_hosttwin_runflex_end_stretches(uint32_t nr_channels, struct mfm_runflex_state *state, struct mfm_runflex_end *ends,
+                                       size_t max_ends, size_t *nr_ends);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

@@ -91,6 +91,20 @@ the place of the time:
     {"proto": "flex", "type": "alphanumeric", "channel": 3, "first_sample": 4000, "baud": 3200, "frameNo": 42, "cycleNo": 5,
      "phaseNo": "A", "capCode": 123456, "fragment": false, "maildrop": false, "fragSeq": 3, "message": "HELLO"}
 
+--gate-ends (with --gate-ais, --gate-pocsag or --gate-flex, with or without --gate-bits, or with --gate-route, where it applies to
+every route's stage) switches the stage's stretch-end report on, ends the open stretches behind the gate's flush and writes
+DIR/ends.jsonl beside the events (under a route: DIR/NAME/ends.jsonl), one line per stretch: channel, first_sample (the stretch's
+first input sample, stretch_window * W), outs, mode (0: nothing was being collected when the squelch closed) and the stage's
+fields - AIS start_sample and nr_bits of the cut packet; POCSAG baud, nr_words, nr_bits, nr_sync_bits, nr_ok, fail_mask and the
+corrected words below nr_ok of the cut batch; FLEX j, eye, coding, fiw, cycle and frame.  With --summary a last line per chain
+carries stretches, cut and cut_by_mode.  Without the flag nothing the tool writes changes.
+
+    python tools/level_scan.py --bench-runends [--window 1000] [--reps 8] [--inner 10] [--runends-parent LIB]
+
+prints one JSON line ("run_ends_stage"): the process call of each burst stage at 64 and 1024 channels on the half-open mask, the
+report off and on in turn (and the same entry of LIB, another build of the library, as a third variant): means, standard
+deviations, on over off with its standard error, and off against LIB by the rule of tools/exp/ab.py.
+
 --gate-route FILE (with --gate-out and --form pcm; not together with --gate-resample, --gate-dc-pole, --gate-bits or a stage flag)
 decodes a capture that mixes protocols in one pass: the run router (mfm_runroute_*) stands behind the gate and hands each route's
 burst chain only the runs of its own channels.  FILE is JSON:
@@ -251,15 +265,22 @@ def read_routes(path, nr_channels):
     return routes, shared, pack
 
 
+# --gate-ends: the fields of a stretch-end record a line of ends.jsonl carries beside channel, first_sample, outs and mode
+ENDS_LINE_FIELDS = {"ais": ("start_sample", "nr_bits"), "pocsag": ("baud", "nr_words", "nr_bits", "nr_sync_bits", "nr_ok", "fail_mask"),
+                    "flex": ("j", "eye", "coding", "fiw", "cycle", "frame")}
+ENDS_MODE_NAMES = {"ais": {1: "receive"}, "pocsag": {2: "batch", 3: "syncword"}, "flex": {1: "sync1", 2: "frame"}}
+
+
 class BurstChain:
     """burst resampler -> burst stage (ais, pocsag, flex or None) behind one run list - the gate's, or with --gate-route one
     route's of the run router - and the files the two write under out_dir; view() returns the run list's device view"""
 
     def __init__(self, pkg, out_dir, window, nr_channels, max_in_samples, preroll, device, view, resample, taps_file, dc_pole=None,
-                 stage=None, bits=False, caps=None, channels=None, bound=None):
+                 stage=None, bits=False, caps=None, channels=None, bound=None, ends=False):
         """caps and channels: behind a packed or a local route of the run router, its route_caps() - the chain is sized to the route -
         and its route_channels(), which turn the route-local channel numbers of everything fetched back into true ones.  bound:
-        behind a local route, the router's bound_view(): the resampler then reads the gate's payload through its view entries"""
+        behind a local route, the router's bound_view(): the resampler then reads the gate's payload through its view entries.
+        ends (--gate-ends): the stage's stretch-end report, one line per stretch in ends.jsonl"""
         b = self.b = pkg.binding
         self.out_dir, self.window, self.view, self.bound = out_dir, window, view, bound
         self.channels = None if channels is None else np.asarray(channels, np.uint32)
@@ -282,6 +303,10 @@ class BurstChain:
             self.st_index = open(os.path.join(out_dir, stage + ".jsonl"), "w")
         if stage in ("pocsag", "flex"):
             self.pages_index = open(os.path.join(out_dir, "pages.jsonl"), "w")
+        self.ends_index, self.stretches, self.cut_by_mode = None, 0, {}
+        if stage and ends:
+            self.st.set_end_report(True)
+            self.ends_index = open(os.path.join(out_dir, "ends.jsonl"), "w")
         # --gate-bits: the predicate the stage behind the resampler reads
         self.bits_polarity = (b.MFM_BITS_POS if stage == "ais" else b.MFM_BITS_NEG) if bits else 0
 
@@ -316,6 +341,30 @@ class BurstChain:
         if self.stage == "flex":
             events, frames = self.st.fetch()
             self.write_flex(self.true_channels(events), frames)
+        if self.ends_index:
+            self.write_ends(self.true_channels(self.st.fetch_ends()))
+
+    def end(self, stream):
+        """--gate-ends, behind the gate's flush: the stretches still open end here"""
+        if self.ends_index:
+            self.st.end_stretches(stream=stream)
+            self.write_ends(self.true_channels(self.st.fetch_ends()))
+
+    def write_ends(self, ends):
+        """one line per stretch: where it began in the input, how many outputs it had, what state it ended in"""
+        for e in ends:
+            line = {"channel": int(e["channel"]), "first_sample": int(e["stretch_window"]) * self.window, "outs": int(e["outs"]),
+                    "mode": int(e["mode"])}
+            line.update({f: int(e[f]) for f in ENDS_LINE_FIELDS[self.stage]})
+            if self.stage == "pocsag":   # the whole codewords of the batch the squelch cut, as far as the BCH accepted them
+                line["corrected"] = ["%08x" % int(w) for w in e["corrected"][:int(e["nr_ok"])]]
+            self.ends_index.write(json.dumps(line) + "\n")
+            self.stretches += 1
+            if line["mode"]:
+                self.cut_by_mode[ENDS_MODE_NAMES[self.stage][line["mode"]]] = self.cut_by_mode.get(ENDS_MODE_NAMES[self.stage][line["mode"]], 0) + 1
+
+    def ends_summary(self):
+        return {"stretches": self.stretches, "cut": sum(self.cut_by_mode.values()), "cut_by_mode": dict(sorted(self.cut_by_mode.items()))}
 
     def true_channels(self, records):
         """behind a packed or a local route: the records with their route-local channel numbers mapped back, before anything is written"""
@@ -327,7 +376,7 @@ class BurstChain:
     def close(self):
         for hp in self.pagers.values():
             hp.close()
-        for f in (self.rs_index, self.st_index, self.pages_index):
+        for f in (self.rs_index, self.st_index, self.pages_index, self.ends_index):
             if f:
                 f.close()
         if self.st:
@@ -434,7 +483,7 @@ def scan(a):
     if a.gate_resample:   # main() has refused --gate-flex without it or beside another stage
         stage = "ais" if a.gate_ais else "pocsag" if a.gate_pocsag else "flex" if a.gate_flex else None
         chains.append(BurstChain(pkg, a.gate_out, a.window, len(chans), max_in, int(a.gate_preroll), a.device, gate.device_view,
-                                 a.gate_resample, a.resample_taps, dc_pole=a.gate_dc_pole, stage=stage, bits=a.gate_bits))
+                                 a.gate_resample, a.resample_taps, dc_pole=a.gate_dc_pole, stage=stage, bits=a.gate_bits, ends=a.gate_ends))
     if routes is not None:
         if not gate or iq_form:
             raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
@@ -456,7 +505,8 @@ def scan(a):
                 sized["bound"] = router.bound_view()
             chains.append(BurstChain(pkg, os.path.join(a.gate_out, r["name"]), a.window, len(chans), max_in, int(a.gate_preroll), a.device,
                                      lambda k=k: router.device_view(k), r["resample"], r["taps"], dc_pole=r.get("dc_pole"),
-                                     stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits")), **sized))
+                                     stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits")), ends=a.gate_ends,
+                                     **sized))
 
     def run_stages():
         """the router, where there is one, and every chain on the gate's last result, all on the engine's stream"""
@@ -529,8 +579,15 @@ def scan(a):
         gate.flush_device(stream=eng.stream)  # the windows pre-roll still held back; none with P = 0
         run_stages()
         write_runs(*gate.fetch())
-        for ch in chains:
+        for k, ch in enumerate(chains):
             ch.write()
+            ch.end(eng.stream)
+            if a.summary and ch.ends_index:
+                line = {"summary": True, "ends": True}
+                if routes is not None:
+                    line["route"] = routes[k]["name"]
+                line.update(ch.ends_summary())
+                out.write(json.dumps(line) + "\n")
             ch.close()
         if router:
             router.close()
@@ -1829,6 +1886,103 @@ def bench_runbits(a, pkg, torch):
     print(json.dumps(out))
 
 
+def bench_runends(a, pkg, torch):
+    """what the stretch-end report costs: each of the three burst stages at 64 and 1024 channels on the half-open mask of the
+    stages' own lines (the squelch on the median window energy), the stage's process call alone on the device view one burst
+    resampler call left (every call begins every stretch anew, so every call does the same work and a stretch ends behind every
+    run that has a successor on its channel).  Report off and report on alternate in one process in rotating order; with
+    --runends-parent LIB a third variant calls the same entry of that library (the parent commit's build) on the same buffers,
+    which is the figure "off is free" is read from"""
+    b = pkg.binding
+    W = a.window
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    cases = {"ais": (4, 5, np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16), _busy_rows, pkg.RunAis, b.RunaisConfig),
+             "pocsag": (4, 5, np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16), _busy_pocsag_rows, pkg.RunPocsag,
+                        b.RunPocsagConfig),
+             "flex": (16, 25, np.round(pkg.synth.design_lpf(101, 0.45 / 25, 1.0) * 16 * 16384.0).astype(np.int16), _busy_flex_rows, pkg.RunFlex,
+                      b.RunFlexConfig)}
+    parent = C.CDLL(os.path.abspath(a.runends_parent)) if a.runends_parent else None
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "run_ends_stage", "window": W, "samples_per_channel": nb, "mask": "half_open", "reps": a.reps, "calls_per_rep": a.inner,
+           "parent": bool(parent)}
+    for stage, (I, D, taps, rows_of, Stage, Config) in cases.items():
+        for nch in (64, 1024):
+            d_rows = torch.from_numpy(np.ascontiguousarray(rows_of(pkg, nch, n))).cuda()
+            rows, in_stride = d_rows.data_ptr(), n
+            probe = pkg.Level(nch, n, W, device=0)
+            probe.process_device(rows, in_stride, nb)
+            thr = int(np.median(probe.fetch()["energy"]))
+            probe.close()
+            sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+            sq.process_device(rows, in_stride, nb)
+            open_share = float(sq.fetch()["open"].astype(bool).mean())
+            d_scene, scene_stride, _, _ = sq.device_view()
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, d_scene, scene_stride, nw)
+            rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+            rr.process_device(*gate.device_view())
+            view = rr.device_view()
+            nr_runs = len(rr.fetch()[0])
+            off, on = Stage.behind(rr), Stage.behind(rr)
+            on.set_end_report(True)
+            variants = [("off", lambda: off.process_device(*view)), ("on", lambda: on.process_device(*view))]
+            ph = C.c_void_p()
+            if parent:
+                max_runs, max_out = rr.capacity()
+                cfg = Config(b.MFM_ABI_VERSION, 0, nch, max_runs, max_out, 0, 0, 0) if stage == "flex" else \
+                    Config(b.MFM_ABI_VERSION, 0, nch, max_runs, max_out, 0, 0)
+                create, process = getattr(parent, f"mfm_run{stage}_create"), getattr(parent, f"mfm_run{stage}_process_device")
+                process.argtypes = [C.c_void_p] * 5
+                assert create(C.byref(ph), C.byref(cfg)) == 0
+                variants.insert(0, ("parent", lambda: process(ph, view[0], view[1], view[2], None)))
+            for _, fn in variants:
+                timed(fn, 3)
+            ends = on.fetch_ends()
+            got = {v: [] for v, _ in variants}
+            for r in range(a.reps):
+                k = r % len(variants)
+                for vname, fn in variants[k:] + variants[:k]:
+                    got[vname].append(timed(fn, a.inner))
+            res = {"runs_per_call": nr_runs, "open_share": open_share, "records_per_call": len(ends), "cut_per_call": int((ends["mode"] != 0).sum())}
+            for vname in got:
+                res[vname + "_ms"], res[vname + "_sd"] = _stats(got[vname])
+            (fm, fsd), (nm, nsd) = _stats(got["off"]), _stats(got["on"])
+            res["on_over_off"] = nm / fm
+            res["on_over_off_se"] = nm / fm * math.sqrt(fsd * fsd / a.reps / (fm * fm) + nsd * nsd / a.reps / (nm * nm))
+            if parent:   # tools/exp/ab.py's rule: worse only beyond two standard errors of the difference of the means
+                pm, psd = _stats(got["parent"])
+                res["off_minus_parent_ms"], res["two_se"] = fm - pm, 2.0 * math.sqrt(fsd * fsd / a.reps + psd * psd / a.reps)
+                res["off_vs_parent"] = "worse" if fm - pm > res["two_se"] else "kept" if pm - fm > res["two_se"] else "neutral"
+                torch.cuda.synchronize()
+                getattr(parent, f"mfm_run{stage}_destroy")(C.byref(ph))
+            out[f"{stage}_{nch}"] = res
+            for o in (on, off, rr, gate, sq):
+                o.close()
+            del d_rows
+    print(json.dumps(out))
+
+
+def bench_runends_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runends needs the GPU: there is no CPU path to time")
+    bench_runends(a, pkg, torch)
+
+
 def bench_runbits_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -1922,6 +2076,8 @@ def main():
     ap.add_argument("--gate-flex", action="store_true", help="decode FLEX on the resampled runs on the device (with --gate-resample to 16 000 Hz)")
     ap.add_argument("--gate-bits", action="store_true",
                     help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
+    ap.add_argument("--gate-ends", action="store_true",
+                    help="with --gate-ais, --gate-pocsag, --gate-flex or --gate-route: one line per stretch in ends.jsonl, how it ended and what the squelch cut")
     ap.add_argument("--gate-route", default=None,
                     help="JSON file of routes: one gate feeds a burst chain per protocol through the run router (with --gate-out, --form pcm)")
     ap.add_argument("--bench", action="store_true")
@@ -1939,6 +2095,10 @@ def main():
                     help="with --bench-runroute-pack: one case alone, e.g. 1024x2/half_open, for a kernel trace of its own")
     ap.add_argument("--bench-runroute-local", action="store_true",
                     help="the runroute_local_stage line: zero-copy, packed and local routes at 64 and 1024 channels, 2 and 8 routes")
+    ap.add_argument("--bench-runends", action="store_true",
+                    help="the run_ends_stage line: the three burst stages at 64 and 1024 channels, the stretch-end report off and on")
+    ap.add_argument("--runends-parent", default=None, metavar="LIB",
+                    help="with --bench-runends: a third variant, the same stage entry of this library (the parent commit's build)")
     ap.add_argument("--bench-channels", type=int, default=64)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--inner", type=int, default=10)
@@ -1949,6 +2109,8 @@ def main():
         return bench_runpocsag_alone(a)
     if a.bench_runflex:
         return bench_runflex_alone(a)
+    if a.bench_runends:
+        return bench_runends_alone(a)
     if a.bench_runbits:
         return bench_runbits_alone(a)
     if a.bench_runroute:
@@ -1972,6 +2134,8 @@ def main():
         raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
     if a.gate_route:
         read_routes(a.gate_route, len(read_config(a.config)[4]))   # what is wrong with FILE ends the run before anything is set up
+    if a.gate_ends and not (a.gate_ais or a.gate_pocsag or a.gate_flex or a.gate_route):
+        raise SystemExit("--gate-ends needs --gate-ais, --gate-pocsag, --gate-flex or --gate-route: it is the burst stage's stretch-end report")
     if a.gate_flex and not a.gate_resample:
         raise SystemExit("--gate-flex needs --gate-resample: the burst FLEX stage takes the burst resampler's runs")
     if a.gate_flex and (a.gate_ais or a.gate_pocsag):

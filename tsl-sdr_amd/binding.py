@@ -83,6 +83,11 @@ ABI_SYMBOLS = [
     "mfm_runpocsag_store_state", "mfm_runflex_store_state",
     "mfm_hosttwin_runrs_state_check", "mfm_hosttwin_runais_state_check", "mfm_hosttwin_runpocsag_state_check",
     "mfm_hosttwin_runflex_state_check",
+    "mfm_runais_set_end_report", "mfm_runais_end_stretches_device", "mfm_runais_fetch_ends", "mfm_runais_ends_view",
+    "mfm_runpocsag_set_end_report", "mfm_runpocsag_end_stretches_device", "mfm_runpocsag_fetch_ends", "mfm_runpocsag_ends_view",
+    "mfm_runflex_set_end_report", "mfm_runflex_end_stretches_device", "mfm_runflex_fetch_ends", "mfm_runflex_ends_view",
+    "mfm_hosttwin_runais_call_ends", "mfm_hosttwin_runpocsag_call_ends", "mfm_hosttwin_runflex_call_ends",
+    "mfm_hosttwin_runais_end_stretches", "mfm_hosttwin_runpocsag_end_stretches", "mfm_hosttwin_runflex_end_stretches",
     "mfm_runroute_create", "mfm_runroute_destroy", "mfm_runroute_process_device", "mfm_runroute_device_view", "mfm_runroute_fetch",
     "mfm_runroute_get_capacity", "mfm_hosttwin_runroute_capacity", "mfm_hosttwin_runroute_call",
     "mfm_runroute_create_sets", "mfm_runroute_route_channels", "mfm_runroute_route_caps", "mfm_runroute_fetch_payload",
@@ -650,6 +655,18 @@ def load_library():
     lib.mfm_hosttwin_runais_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runpocsag_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runflex_state_check.argtypes = [C.c_uint32, vp]
+    for st in ("runais", "runpocsag", "runflex"):
+        getattr(lib, f"mfm_{st}_set_end_report").argtypes = [vp, C.c_int]
+        getattr(lib, f"mfm_{st}_end_stretches_device").argtypes = [vp, vp]
+        getattr(lib, f"mfm_{st}_fetch_ends").argtypes = [vp, vp, C.c_size_t, szp]
+        getattr(lib, f"mfm_{st}_ends_view").argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        getattr(lib, f"mfm_hosttwin_{st}_end_stretches").argtypes = [C.c_uint32, vp, vp, C.c_size_t, szp]
+    lib.mfm_hosttwin_runais_call_ends.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
+                                                  C.POINTER(C.c_uint32), vp, C.c_size_t, szp]
+    lib.mfm_hosttwin_runpocsag_call_ends.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
+                                                     C.POINTER(C.c_uint32), vp, C.c_size_t, szp]
+    lib.mfm_hosttwin_runflex_call_ends.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                                   C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32), vp, C.c_size_t, szp]
     lib.mfm_runroute_create.argtypes = [C.POINTER(vp), C.POINTER(RunRouteConfig), vp]
     lib.mfm_runroute_destroy.argtypes = [C.POINTER(vp)]
     lib.mfm_runroute_destroy.restype = None
@@ -2172,10 +2189,183 @@ def hosttwin_runroute_local_call(sets, nr_routes, gate_runs, gate_totals, window
     return runs, totals[:nr_routes], bound.value
 
 
-class RunAis:
+# numpy views of the stretch-end records: struct mfm_runais_end (48 bytes), mfm_runpocsag_end (184), mfm_runflex_end (64)
+RUNAIS_END_DTYPE = np.dtype([("stretch_window", "<u8"), ("outs", "<u8"), ("start_sample", "<u8"), ("channel", "<u4"), ("run", "<u4"),
+                             ("mode", "<u4"), ("nr_bits", "<u4"), ("reserved", "<u4", (2,))])
+RUNPOCSAG_END_DTYPE = np.dtype([("stretch_window", "<u8"), ("outs", "<u8"), ("channel", "<u4"), ("run", "<u4"), ("mode", "<u4"),
+                                ("baud", "<u4"), ("nr_words", "<u4"), ("nr_bits", "<u4"), ("nr_sync_bits", "<u4"), ("reserved", "<u4"),
+                                ("nr_ok", "<u4"), ("fail_mask", "<u4"), ("raw", "<u4", (16,)), ("corrected", "<u4", (16,))])
+RUNFLEX_END_DTYPE = np.dtype([("stretch_window", "<u8"), ("outs", "<u8"), ("j", "<u8"), ("channel", "<u4"), ("run", "<u4"),
+                              ("mode", "<u4"), ("eye", "<u4"), ("coding", "<u4"), ("fiw", "<u4"), ("cycle", "<u4"), ("frame", "<u4"),
+                              ("reserved", "<u4", (2,))])
+assert (RUNAIS_END_DTYPE.itemsize, RUNPOCSAG_END_DTYPE.itemsize, RUNFLEX_END_DTYPE.itemsize) == (48, 184, 64)
+RUN_ENDS_NO_RUN = 0xffffffff   # `run` of a record the end call wrote
+
+
+class _RunEnds:
+    """the stretch-end report of a burst stage (mfm_<stage>_set_end_report and kin): one record per stretch that says how it
+    ended and what the closing squelch cut.  Off at create."""
+    _ends_stage = None   # "runais" / "runpocsag" / "runflex"
+    _ends_dtype = None
+
+    def _ends_fn(self, what):
+        return getattr(self.lib, f"mfm_{self._ends_stage}_{what}"), f"mfm_{self._ends_stage}_{what}"
+
+    def set_end_report(self, on=True):
+        """valid only before the first process call: MfmError(MFM_E_STATE) afterwards"""
+        fn, name = self._ends_fn("set_end_report")
+        rc = fn(self.h, 1 if on else 0)
+        if rc < 0:
+            self._raise(rc, name)
+
+    def end_stretches(self, stream=None):
+        """the end of a stream, behind the gate's flush: a record for every channel with a stretch, then no channel has one"""
+        fn, name = self._ends_fn("end_stretches_device")
+        rc = fn(self.h, C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, name)
+
+    def fetch_ends(self, max_ends=None):
+        """the records of the last call, process or end (a structured array of the stage's END dtype).  With max_ends too small:
+        MfmError(MFM_E_NOMEM) whose `needed` attribute is the number that would fit"""
+        fn, name = self._ends_fn("fetch_ends")
+        nr = C.c_size_t()
+        if max_ends is None:
+            rc = fn(self.h, None, 0, C.byref(nr))
+            if rc not in (MFM_OK, MFM_E_NOMEM):
+                self._raise(rc, name)
+            max_ends = nr.value
+        out = np.zeros(max(max_ends, 1), self._ends_dtype)
+        rc = fn(self.h, out.ctypes.data, max_ends, C.byref(nr))
+        if rc < 0:
+            try:
+                self._raise(rc, name)
+            except MfmError as err:
+                err.needed = nr.value
+                err.buffer = out
+                raise
+        return out[:nr.value].copy()
+
+    def ends_view(self):
+        """(d_ends, d_end_totals): device addresses of the last call's records and of { records, records with mode != 0 }"""
+        fn, name = self._ends_fn("ends_view")
+        e, t = C.c_void_p(), C.c_void_p()
+        rc = fn(self.h, C.byref(e), C.byref(t))
+        if rc < 0:
+            self._raise(rc, name)
+        return e.value, t.value
+
+
+def _twin_ends_error(lib, rc, what, **attrs):
+    err = MfmError(rc, what, lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+    for k, v in attrs.items():
+        setattr(err, k, v)
+    return err
+
+
+def _twin_call_args(runs, payload, totals, max_runs, max_out_samples):
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    pl = np.ascontiguousarray(payload, dtype=np.int16).reshape(-1)
+    t = np.array([rr.size, pl.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    return rr, pl, t, (max(rr.size, 1) if max_runs is None else max_runs), (max(pl.size, 1) if max_out_samples is None else max_out_samples)
+
+
+def hosttwin_runais_call_ends(state, runs, payload, totals=None, max_runs=None, max_out_samples=None, max_events=0, max_out=None,
+                              max_ends=None):
+    """mfm_hosttwin_runais_call_ends: hosttwin_runais_call with the stretch-end records of the call; returns (events, ends).
+    max_ends too small: MfmError(MFM_E_NOMEM) with `needed_ends`, nothing written"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNAIS_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr, pl, t, max_runs, max_out_samples = _twin_call_args(runs, payload, totals, max_runs, max_out_samples)
+    max_out = pl.size // 160 + rr.size if max_out is None else max_out
+    max_ends = rr.size if max_ends is None else max_ends
+    out, ends = np.zeros(max(max_out, 1), RUNAIS_EVENT_DTYPE), np.zeros(max(max_ends, 1), RUNAIS_END_DTYPE)
+    nr, fl, ne = C.c_size_t(), C.c_uint32(), C.c_size_t()
+    rc = lib.mfm_hosttwin_runais_call_ends(state.shape[0], max_runs, max_out_samples, max_events, state.ctypes.data,
+                                           rr.ctypes.data if rr.size else None, pl.ctypes.data if pl.size else None, t.ctypes.data,
+                                           out.ctypes.data, max_out, C.byref(nr), C.byref(fl), ends.ctypes.data, max_ends, C.byref(ne))
+    if rc < 0:
+        raise _twin_ends_error(lib, rc, "mfm_hosttwin_runais_call_ends", needed=nr.value, flags=fl.value, needed_ends=ne.value)
+    return out[:nr.value].copy(), ends[:ne.value].copy()
+
+
+def hosttwin_runpocsag_call_ends(state, runs, payload, totals=None, max_runs=None, max_out_samples=None, max_events=0, max_out=None,
+                                 max_ends=None):
+    """mfm_hosttwin_runpocsag_call_ends: hosttwin_runpocsag_call with the stretch-end records of the call; returns (events, ends)"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNPOCSAG_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr, pl, t, max_runs, max_out_samples = _twin_call_args(runs, payload, totals, max_runs, max_out_samples)
+    max_out = int(sum(runpocsag_slots(int(n)) for n in rr["nr_out"])) if max_out is None else max_out
+    max_ends = rr.size if max_ends is None else max_ends
+    out, ends = np.zeros(max(max_out, 1), RUNPOCSAG_EVENT_DTYPE), np.zeros(max(max_ends, 1), RUNPOCSAG_END_DTYPE)
+    nr, fl, ne = C.c_size_t(), C.c_uint32(), C.c_size_t()
+    rc = lib.mfm_hosttwin_runpocsag_call_ends(state.shape[0], max_runs, max_out_samples, max_events, state.ctypes.data,
+                                              rr.ctypes.data if rr.size else None, pl.ctypes.data if pl.size else None, t.ctypes.data,
+                                              out.ctypes.data, max_out, C.byref(nr), C.byref(fl), ends.ctypes.data, max_ends, C.byref(ne))
+    if rc < 0:
+        raise _twin_ends_error(lib, rc, "mfm_hosttwin_runpocsag_call_ends", needed=nr.value, flags=fl.value, needed_ends=ne.value)
+    return out[:nr.value].copy(), ends[:ne.value].copy()
+
+
+def hosttwin_runflex_call_ends(state, runs, payload, totals=None, max_runs=None, max_out_samples=None, max_events=0, max_frames=0,
+                               max_out=None, max_out_frames=None, max_ends=None):
+    """mfm_hosttwin_runflex_call_ends: hosttwin_runflex_call with the stretch-end records of the call; returns (events, frames,
+    ends)"""
+    lib = load_library()
+    st, ring = state
+    assert st.dtype == RUNFLEX_STATE_DTYPE and st.flags.c_contiguous and st.ndim == 1
+    assert ring.dtype == np.int16 and ring.flags.c_contiguous and ring.shape == (st.shape[0], RUNFLEX_RING)
+    rr, pl, t, max_runs, max_out_samples = _twin_call_args(runs, payload, totals, max_runs, max_out_samples)
+    max_out = pl.size // RUNFLEX_EVENT_SPACING + rr.size if max_out is None else max_out
+    max_out_frames = pl.size // RUNFLEX_FRAME_SPACING + rr.size if max_out_frames is None else max_out_frames
+    max_ends = rr.size if max_ends is None else max_ends
+    ev, fw = np.zeros(max(max_out, 1), RUNFLEX_EVENT_DTYPE), np.zeros(max(max_out_frames, 1), FLEX_FRAME_DTYPE)
+    ends = np.zeros(max(max_ends, 1), RUNFLEX_END_DTYPE)
+    nev, nf, fl, ne = C.c_size_t(), C.c_size_t(), C.c_uint32(), C.c_size_t()
+    rc = lib.mfm_hosttwin_runflex_call_ends(st.shape[0], max_runs, max_out_samples, max_events, max_frames, st.ctypes.data, ring.ctypes.data,
+                                            rr.ctypes.data if rr.size else None, pl.ctypes.data if pl.size else None, t.ctypes.data,
+                                            ev.ctypes.data, max_out, C.byref(nev), fw.ctypes.data, max_out_frames, C.byref(nf), C.byref(fl),
+                                            ends.ctypes.data, max_ends, C.byref(ne))
+    if rc < 0:
+        raise _twin_ends_error(lib, rc, "mfm_hosttwin_runflex_call_ends", needed=nev.value, needed_frames=nf.value, flags=fl.value,
+                               needed_ends=ne.value)
+    return ev[:nev.value].copy(), fw[:nf.value].copy(), ends[:ne.value].copy()
+
+
+def _twin_end_stretches(name, st, dtype, end_dtype, max_ends):
+    lib = load_library()
+    assert st.dtype == dtype and st.flags.c_contiguous and st.ndim == 1
+    max_ends = st.shape[0] if max_ends is None else max_ends
+    ends, ne = np.zeros(max(max_ends, 1), end_dtype), C.c_size_t()
+    rc = getattr(lib, name)(st.shape[0], st.ctypes.data, ends.ctypes.data, max_ends, C.byref(ne))
+    if rc < 0:
+        raise _twin_ends_error(lib, rc, name, needed_ends=ne.value)
+    return ends[:ne.value].copy()
+
+
+def hosttwin_runais_end_stretches(state, max_ends=None):
+    """mfm_hosttwin_runais_end_stretches: the end call on the CPU; returns the records, state is all zero afterwards"""
+    return _twin_end_stretches("mfm_hosttwin_runais_end_stretches", np.asarray(state), RUNAIS_STATE_DTYPE, RUNAIS_END_DTYPE, max_ends)
+
+
+def hosttwin_runpocsag_end_stretches(state, max_ends=None):
+    """mfm_hosttwin_runpocsag_end_stretches: the end call on the CPU; returns the records, state is all zero afterwards"""
+    return _twin_end_stretches("mfm_hosttwin_runpocsag_end_stretches", np.asarray(state), RUNPOCSAG_STATE_DTYPE, RUNPOCSAG_END_DTYPE, max_ends)
+
+
+def hosttwin_runflex_end_stretches(state, max_ends=None):
+    """mfm_hosttwin_runflex_end_stretches: the end call on the CPU; state = (state, ring), the ring is not touched"""
+    return _twin_end_stretches("mfm_hosttwin_runflex_end_stretches", state[0], RUNFLEX_STATE_DTYPE, RUNFLEX_END_DTYPE, max_ends)
+
+
+class RunAis(_RunEnds):
     """mfm_runais: the runs of a RunResampler's device view through the AIS demodulator, one fresh demodulator per stretch;
     one RUNAIS_EVENT_DTYPE per candidate packet.  max_runs and max_out_samples are the burst resampler's capacities
     (RunAis.behind reads them); max_events 0 is a bound that cannot overflow."""
+    _ends_stage, _ends_dtype = "runais", RUNAIS_END_DTYPE
 
     def __init__(self, nr_channels, max_runs, max_out_samples, max_events=0, device=0, flags=0, abi_version=MFM_ABI_VERSION):
         self.lib = load_library()
@@ -2344,10 +2534,11 @@ def runais_to_ais_events(events, interpolate, decimate, window_samples):
     return out
 
 
-class RunPocsag:
+class RunPocsag(_RunEnds):
     """mfm_runpocsag: the runs of a RunResampler's device view (38 400 Hz) through the POCSAG demodulator, one fresh demodulator
     per stretch; RUNPOCSAG_EVENT_DTYPE records.  max_runs and max_out_samples are the burst resampler's capacities
     (RunPocsag.behind reads them); max_events 0 is a bound that cannot overflow."""
+    _ends_stage, _ends_dtype = "runpocsag", RUNPOCSAG_END_DTYPE
 
     def __init__(self, nr_channels, max_runs, max_out_samples, max_events=0, device=0, flags=0, abi_version=MFM_ABI_VERSION):
         self.lib = load_library()
@@ -2512,10 +2703,11 @@ def runpocsag_to_pocsag_events(events):
     return out
 
 
-class RunFlex:
+class RunFlex(_RunEnds):
     """mfm_runflex: the runs of a RunResampler's device view (16 000 Hz) through the FLEX front half, one fresh decoder per
     stretch; RUNFLEX_EVENT_DTYPE records and FLEX_FRAME_DTYPE words.  max_runs and max_out_samples are the burst resampler's
     capacities (RunFlex.behind reads them); max_events 0 and max_frames 0 are bounds that cannot overflow."""
+    _ends_stage, _ends_dtype = "runflex", RUNFLEX_END_DTYPE
 
     def __init__(self, nr_channels, max_runs, max_out_samples, max_events=0, max_frames=0, device=0, flags=0,
                  abi_version=MFM_ABI_VERSION):

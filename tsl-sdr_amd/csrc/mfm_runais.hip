@@ -43,6 +43,7 @@
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_run_bits.h"
+#include "mfm_run_ends.h"
 #include "mfm_runais.h"
 
 static_assert(sizeof(mfm_runais_event) == 200, "struct mfm_runais_event is 200 bytes");
@@ -669,6 +670,7 @@ struct mfm_runais {
     mfm_runais_event *d_slots = nullptr, *d_events = nullptr;
     hipStream_t last_stream = nullptr;
     bool have_call = false;
+    MfmRunEnds ends; /* the stretch-end report (mfm_run_ends.h); off at create */
 };
 
 extern "C" {
@@ -745,6 +747,7 @@ void mfm_runais_destroy(struct mfm_runais **pa)
     (void)hipFree(a->d_totals);
     (void)hipFree(a->d_slots);
     (void)hipFree(a->d_events);
+    (void)mfm_internal_run_ends_set(&a->ends, MFM_RUN_ENDS_AIS, false, 0, 0);
     delete a;
     *pa = nullptr;
 }
@@ -788,6 +791,13 @@ int ra_process(mfm_runais *a, const mfm_runrs_run *d_runs, const int16_t *d_payl
     RA_TRY(hipGetLastError());
     hipLaunchKernelGGL(ra_compact_kernel, dim3(a->cfg.max_runs), dim3(64), 0, s, A);
     RA_TRY(hipGetLastError());
+    if (a->ends.on) { /* behind the walk, in front of the state kernel */
+        const MfmRunEndsCall E{ d_runs, a->d_chan[cur], a->d_run_state, a->d_ctl, nullptr, a->cfg.nr_channels, a->cfg.max_runs };
+        const int re = mfm_internal_run_ends_process(&a->ends, MFM_RUN_ENDS_AIS, &E, s);
+        if (re != MFM_OK) {
+            return re;
+        }
+    }
     hipLaunchKernelGGL(ra_state_kernel, dim3(a->cfg.nr_channels), dim3(64), 0, s, A);
     RA_TRY(hipGetLastError());
     a->cur ^= 1u;
@@ -903,6 +913,28 @@ int mfm_runais_store_state(struct mfm_runais *a, const struct mfm_runais_state *
     }
     RA_TRY(hipMemcpy(a->d_chan[a->cur], state, nr_channels * sizeof(mfm_runais_state), hipMemcpyHostToDevice));
     return MFM_OK;
+}
+
+/* ---- the stretch-end report: kernels and launchers in mfm_run_ends.hip ---- */
+
+int mfm_runais_set_end_report(struct mfm_runais *a, int on)
+{
+    return mfm_run_ends_entry_set(a, MFM_RUN_ENDS_AIS, on, ra_fail);
+}
+
+int mfm_runais_end_stretches_device(struct mfm_runais *a, void *stream)
+{
+    return mfm_run_ends_entry_flush(a, MFM_RUN_ENDS_AIS, nullptr, stream, ra_fail);
+}
+
+int mfm_runais_fetch_ends(struct mfm_runais *a, struct mfm_runais_end *ends, size_t max_ends, size_t *nr_ends)
+{
+    return mfm_run_ends_entry_fetch(a, MFM_RUN_ENDS_AIS, ends, max_ends, nr_ends, ra_fail, ra_refusal);
+}
+
+int mfm_runais_ends_view(struct mfm_runais *a, const struct mfm_runais_end **d_ends, const uint64_t **d_end_totals)
+{
+    return mfm_run_ends_entry_view(a, d_ends, d_end_totals, ra_fail);
 }
 
 } /* extern "C" */
@@ -1035,12 +1067,16 @@ namespace {
 /* the host twin of one call in either form: bits != NULL is the resampler's bits form (totals[1] and out_offset in words) */
 int ra_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events, struct mfm_runais_state *state,
                  const struct mfm_runrs_run *runs, const int16_t *payload, const uint32_t *bits, bool words, const uint64_t *totals,
-                 struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags)
+                 struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags,
+                 struct mfm_runais_end *ends = nullptr, size_t max_ends = 0, size_t *nr_ends = nullptr) /* nr_ends: with the records */
 {
-    if (!state || !totals || !nr_events || (!events && max_out)) {
+    if (!state || !totals || !nr_events || (!events && max_out) || (nr_ends && !ends && max_ends)) {
         return MFM_E_INVAL;
     }
     *nr_events = 0;
+    if (nr_ends) {
+        *nr_ends = 0;
+    }
     if (flags) {
         *flags = 0;
     }
@@ -1125,6 +1161,13 @@ int ra_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_sampl
     if (out.size() > max_out) {
         return MFM_E_NOMEM; /* nothing written, the state included */
     }
+    if (nr_ends) { /* from the state the call started with, before it moves */
+        *nr_ends = mfm_run_ends_host_call(runs, n, state, left.data(), ends, 0, mfm_runais_end_of);
+        if (*nr_ends > max_ends) {
+            return MFM_E_NOMEM;
+        }
+        (void)mfm_run_ends_host_call(runs, n, state, left.data(), ends, max_ends, mfm_runais_end_of);
+    }
     for (uint64_t r = 0; r < n; r++) {
         if (r + 1 == n || runs[r + 1].channel != runs[r].channel) {
             state[runs[r].channel] = left[r];
@@ -1146,6 +1189,24 @@ int mfm_hosttwin_runais_call(uint32_t nr_channels, uint32_t max_runs, uint32_t m
 {
     return ra_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, payload, nullptr, false, totals, events, max_out,
                         nr_events, flags);
+}
+
+int mfm_hosttwin_runais_call_ends(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                  struct mfm_runais_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                                  const uint64_t *totals, struct mfm_runais_event *events, size_t max_out, size_t *nr_events, uint32_t *flags,
+                                  struct mfm_runais_end *ends, size_t max_ends, size_t *nr_ends)
+{
+    if (!nr_ends) {
+        return MFM_E_INVAL;
+    }
+    return ra_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, payload, nullptr, false, totals, events, max_out,
+                        nr_events, flags, ends, max_ends, nr_ends);
+}
+
+int mfm_hosttwin_runais_end_stretches(uint32_t nr_channels, struct mfm_runais_state *state, struct mfm_runais_end *ends, size_t max_ends,
+                                      size_t *nr_ends)
+{
+    return mfm_run_ends_host_flush(nr_channels, state, ends, max_ends, nr_ends, mfm_runais_end_of);
 }
 
 int mfm_hosttwin_runais_call_bits(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,

@@ -44,6 +44,7 @@
 
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_bch.h"
+#include "mfm_run_ends.h"
 #include "mfm_runflex.h"
 
 static_assert(sizeof(mfm_flex_event) == 88 && sizeof(mfm_runflex_event) == 104 && offsetof(mfm_runflex_event, run) == 88 &&
@@ -777,6 +778,7 @@ struct mfm_runflex {
     MfmBchTables *d_bch = nullptr; /* owned by mfm_pocsag.hip, one per device */
     hipStream_t last_stream = nullptr;
     bool have_call = false;
+    MfmRunEnds ends; /* the stretch-end report (mfm_run_ends.h); off at create */
 };
 
 extern "C" {
@@ -875,6 +877,7 @@ void mfm_runflex_destroy(struct mfm_runflex **pf)
     (void)hipFree(p->d_fslots);
     (void)hipFree(p->d_fdesc);
     (void)hipFree(p->d_frames);
+    (void)mfm_internal_run_ends_set(&p->ends, MFM_RUN_ENDS_FLEX, false, 0, 0);
     delete p;
     *pf = nullptr;
 }
@@ -913,6 +916,13 @@ int mfm_runflex_process_device(struct mfm_runflex *p, const struct mfm_runrs_run
     RF_TRY(hipGetLastError());
     hipLaunchKernelGGL(rf_ring_kernel, dim3(RF_RING_BLOCKS, p->cfg.nr_channels), dim3(256), 0, s, A);
     RF_TRY(hipGetLastError());
+    if (p->ends.on) { /* behind the walk, in front of the state kernel */
+        const MfmRunEndsCall E{ d_runs, p->d_chan[cur], p->d_run_state, p->d_ctl, p->d_bch, p->cfg.nr_channels, p->cfg.max_runs };
+        const int re = mfm_internal_run_ends_process(&p->ends, MFM_RUN_ENDS_FLEX, &E, s);
+        if (re != MFM_OK) {
+            return re;
+        }
+    }
     hipLaunchKernelGGL(rf_state_kernel, dim3(p->cfg.nr_channels), dim3(64), 0, s, A);
     RF_TRY(hipGetLastError());
     p->cur ^= 1u;
@@ -1018,6 +1028,29 @@ int mfm_runflex_store_state(struct mfm_runflex *p, const struct mfm_runflex_stat
     RF_TRY(hipMemcpy(p->d_chan[p->cur], state, nr_channels * sizeof(mfm_runflex_state), hipMemcpyHostToDevice));
     RF_TRY(hipMemcpy(p->d_ring, ring, nr_channels * MFM_RUNFLEX_RING * sizeof(int16_t), hipMemcpyHostToDevice));
     return MFM_OK;
+}
+
+
+/* ---- the stretch-end report: kernels and launchers in mfm_run_ends.hip ---- */
+
+int mfm_runflex_set_end_report(struct mfm_runflex *p, int on)
+{
+    return mfm_run_ends_entry_set(p, MFM_RUN_ENDS_FLEX, on, rf_fail);
+}
+
+int mfm_runflex_end_stretches_device(struct mfm_runflex *p, void *stream)
+{
+    return mfm_run_ends_entry_flush(p, MFM_RUN_ENDS_FLEX, p ? p->d_bch : nullptr, stream, rf_fail);
+}
+
+int mfm_runflex_fetch_ends(struct mfm_runflex *p, struct mfm_runflex_end *ends, size_t max_ends, size_t *nr_ends)
+{
+    return mfm_run_ends_entry_fetch(p, MFM_RUN_ENDS_FLEX, ends, max_ends, nr_ends, rf_fail, rf_refusal);
+}
+
+int mfm_runflex_ends_view(struct mfm_runflex *p, const struct mfm_runflex_end **d_ends, const uint64_t **d_end_totals)
+{
+    return mfm_run_ends_entry_view(p, d_ends, d_end_totals, rf_fail);
 }
 
 } /* extern "C" */
@@ -1229,19 +1262,24 @@ void rf_host_walk(mfm_runflex_state &S, const RfHostIn &I, uint32_t r, std::vect
 
 } /* namespace */
 
-extern "C" {
+namespace {
 
-int mfm_hosttwin_runflex_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
-                              uint32_t max_frames, struct mfm_runflex_state *state, int16_t *ring, const struct mfm_runrs_run *runs,
-                              const int16_t *payload, const uint64_t *totals, struct mfm_runflex_event *events, size_t max_out,
-                              size_t *nr_events, struct mfm_flex_frame_words *frames, size_t max_out_frames, size_t *nr_frames,
-                              uint32_t *flags)
+/* the host twin of one call; nr_ends != NULL: with the stretch-end records */
+int rf_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events, uint32_t max_frames,
+                 struct mfm_runflex_state *state, int16_t *ring, const struct mfm_runrs_run *runs, const int16_t *payload,
+                 const uint64_t *totals, struct mfm_runflex_event *events, size_t max_out, size_t *nr_events,
+                 struct mfm_flex_frame_words *frames, size_t max_out_frames, size_t *nr_frames, uint32_t *flags,
+                 struct mfm_runflex_end *ends, size_t max_ends, size_t *nr_ends)
 {
-    if (!state || !ring || !totals || !nr_events || !nr_frames || (!events && max_out) || (!frames && max_out_frames)) {
+    if (!state || !ring || !totals || !nr_events || !nr_frames || (!events && max_out) || (!frames && max_out_frames) ||
+        (nr_ends && !ends && max_ends)) {
         return MFM_E_INVAL;
     }
     *nr_events = 0;
     *nr_frames = 0;
+    if (nr_ends) {
+        *nr_ends = 0;
+    }
     if (flags) {
         *flags = 0;
     }
@@ -1314,6 +1352,13 @@ int mfm_hosttwin_runflex_call(uint32_t nr_channels, uint32_t max_runs, uint32_t 
     if (out.size() > max_out || fw.size() > max_out_frames) {
         return MFM_E_NOMEM; /* nothing written, state and ring included */
     }
+    if (nr_ends) { /* from the state the call started with, before it moves */
+        *nr_ends = mfm_run_ends_host_call(runs, n, state, left.data(), ends, 0, mfm_runflex_end_of);
+        if (*nr_ends > max_ends) {
+            return MFM_E_NOMEM;
+        }
+        (void)mfm_run_ends_host_call(runs, n, state, left.data(), ends, max_ends, mfm_runflex_end_of);
+    }
     for (uint64_t r = 0; r < n; r++) {
         if (r + 1 == n || runs[r + 1].channel != runs[r].channel) {
             const mfm_runrs_run &run = runs[r];
@@ -1333,6 +1378,39 @@ int mfm_hosttwin_runflex_call(uint32_t nr_channels, uint32_t max_runs, uint32_t 
         memcpy(frames, fw.data(), fw.size() * sizeof(mfm_flex_frame_words));
     }
     return MFM_OK;
+}
+
+} /* namespace */
+
+extern "C" {
+
+int mfm_hosttwin_runflex_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                              uint32_t max_frames, struct mfm_runflex_state *state, int16_t *ring, const struct mfm_runrs_run *runs,
+                              const int16_t *payload, const uint64_t *totals, struct mfm_runflex_event *events, size_t max_out,
+                              size_t *nr_events, struct mfm_flex_frame_words *frames, size_t max_out_frames, size_t *nr_frames,
+                              uint32_t *flags)
+{
+    return rf_twin_call(nr_channels, max_runs, max_out_samples, max_events, max_frames, state, ring, runs, payload, totals, events, max_out,
+                        nr_events, frames, max_out_frames, nr_frames, flags, nullptr, 0, nullptr);
+}
+
+int mfm_hosttwin_runflex_call_ends(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                   uint32_t max_frames, struct mfm_runflex_state *state, int16_t *ring, const struct mfm_runrs_run *runs,
+                                   const int16_t *payload, const uint64_t *totals, struct mfm_runflex_event *events, size_t max_out,
+                                   size_t *nr_events, struct mfm_flex_frame_words *frames, size_t max_out_frames, size_t *nr_frames,
+                                   uint32_t *flags, struct mfm_runflex_end *ends, size_t max_ends, size_t *nr_ends)
+{
+    if (!nr_ends) {
+        return MFM_E_INVAL;
+    }
+    return rf_twin_call(nr_channels, max_runs, max_out_samples, max_events, max_frames, state, ring, runs, payload, totals, events, max_out,
+                        nr_events, frames, max_out_frames, nr_frames, flags, ends, max_ends, nr_ends);
+}
+
+int mfm_hosttwin_runflex_end_stretches(uint32_t nr_channels, struct mfm_runflex_state *state, struct mfm_runflex_end *ends,
+                                       size_t max_ends, size_t *nr_ends)
+{
+    return mfm_run_ends_host_flush(nr_channels, state, ends, max_ends, nr_ends, mfm_runflex_end_of);
 }
 
 } /* extern "C" */

@@ -52,6 +52,7 @@
 extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_bch.h"
 #include "mfm_run_bits.h"
+#include "mfm_run_ends.h"
 #include "mfm_runpocsag.h"
 
 static_assert(sizeof(mfm_runpocsag_event) == 176 && offsetof(mfm_runpocsag_event, run) == 16 &&
@@ -884,6 +885,7 @@ struct mfm_runpocsag {
     MfmBchTables *d_bch = nullptr; /* owned by mfm_pocsag.hip, one per device */
     hipStream_t last_stream = nullptr;
     bool have_call = false;
+    MfmRunEnds ends; /* the stretch-end report (mfm_run_ends.h); off at create */
 };
 
 extern "C" {
@@ -970,6 +972,7 @@ void mfm_runpocsag_destroy(struct mfm_runpocsag **pp)
     (void)hipFree(p->d_totals);
     (void)hipFree(p->d_slots);
     (void)hipFree(p->d_events);
+    (void)mfm_internal_run_ends_set(&p->ends, MFM_RUN_ENDS_POCSAG, false, 0, 0);
     delete p;
     *pp = nullptr;
 }
@@ -1016,6 +1019,13 @@ int rp_process(mfm_runpocsag *p, const mfm_runrs_run *d_runs, const int16_t *d_p
     RP_TRY(hipGetLastError());
     hipLaunchKernelGGL(rp_compact_kernel, dim3(p->cfg.max_runs), dim3(64), 0, s, A);
     RP_TRY(hipGetLastError());
+    if (p->ends.on) { /* behind the walk, in front of the state kernel */
+        const MfmRunEndsCall E{ d_runs, p->d_chan[cur], p->d_run_state, p->d_ctl, p->d_bch, p->cfg.nr_channels, p->cfg.max_runs };
+        const int re = mfm_internal_run_ends_process(&p->ends, MFM_RUN_ENDS_POCSAG, &E, s);
+        if (re != MFM_OK) {
+            return re;
+        }
+    }
     hipLaunchKernelGGL(rp_state_kernel, dim3(p->cfg.nr_channels), dim3(128), 0, s, A);
     RP_TRY(hipGetLastError());
     p->cur ^= 1u;
@@ -1131,6 +1141,28 @@ int mfm_runpocsag_store_state(struct mfm_runpocsag *p, const struct mfm_runpocsa
     }
     RP_TRY(hipMemcpy(p->d_chan[p->cur], state, nr_channels * sizeof(mfm_runpocsag_state), hipMemcpyHostToDevice));
     return MFM_OK;
+}
+
+/* ---- the stretch-end report: kernels and launchers in mfm_run_ends.hip ---- */
+
+int mfm_runpocsag_set_end_report(struct mfm_runpocsag *p, int on)
+{
+    return mfm_run_ends_entry_set(p, MFM_RUN_ENDS_POCSAG, on, rp_fail);
+}
+
+int mfm_runpocsag_end_stretches_device(struct mfm_runpocsag *p, void *stream)
+{
+    return mfm_run_ends_entry_flush(p, MFM_RUN_ENDS_POCSAG, p ? p->d_bch : nullptr, stream, rp_fail);
+}
+
+int mfm_runpocsag_fetch_ends(struct mfm_runpocsag *p, struct mfm_runpocsag_end *ends, size_t max_ends, size_t *nr_ends)
+{
+    return mfm_run_ends_entry_fetch(p, MFM_RUN_ENDS_POCSAG, ends, max_ends, nr_ends, rp_fail, rp_refusal);
+}
+
+int mfm_runpocsag_ends_view(struct mfm_runpocsag *p, const struct mfm_runpocsag_end **d_ends, const uint64_t **d_end_totals)
+{
+    return mfm_run_ends_entry_view(p, d_ends, d_end_totals, rp_fail);
 }
 
 } /* extern "C" */
@@ -1255,15 +1287,25 @@ void rp_host_walk(mfm_runpocsag_state &st, const uint32_t *seg, const mfm_runrs_
 
 namespace {
 
+/* a stretch-end record on the host: the BCH through the host copy of the stage's tables */
+void rp_end_of(const mfm_runpocsag_state &s, uint32_t channel, uint32_t run, mfm_runpocsag_end &e)
+{
+    mfm_runpocsag_end_of(mfm_internal_bch_host_tables(), s, channel, run, e);
+}
+
 /* the host twin of one call in either form: bits != NULL is the resampler's bits form (totals[1] and out_offset in words) */
 int rp_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events, struct mfm_runpocsag_state *state,
                  const struct mfm_runrs_run *runs, const int16_t *payload, const uint32_t *bits, bool words, const uint64_t *totals,
-                 struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events, uint32_t *flags)
+                 struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events, uint32_t *flags,
+                 struct mfm_runpocsag_end *ends = nullptr, size_t max_ends = 0, size_t *nr_ends = nullptr) /* nr_ends: with the records */
 {
-    if (!state || !totals || !nr_events || (!events && max_out)) {
+    if (!state || !totals || !nr_events || (!events && max_out) || (nr_ends && !ends && max_ends)) {
         return MFM_E_INVAL;
     }
     *nr_events = 0;
+    if (nr_ends) {
+        *nr_ends = 0;
+    }
     if (flags) {
         *flags = 0;
     }
@@ -1348,6 +1390,13 @@ int rp_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_sampl
     if (out.size() > max_out) {
         return MFM_E_NOMEM; /* nothing written, the state included */
     }
+    if (nr_ends) { /* from the state the call started with, before it moves */
+        *nr_ends = mfm_run_ends_host_call(runs, n, state, left.data(), ends, 0, rp_end_of);
+        if (*nr_ends > max_ends) {
+            return MFM_E_NOMEM;
+        }
+        (void)mfm_run_ends_host_call(runs, n, state, left.data(), ends, max_ends, rp_end_of);
+    }
     for (uint64_t r = 0; r < n; r++) {
         if (r + 1 == n || runs[r + 1].channel != runs[r].channel) {
             state[runs[r].channel] = left[r];
@@ -1370,6 +1419,24 @@ int mfm_hosttwin_runpocsag_call(uint32_t nr_channels, uint32_t max_runs, uint32_
 {
     return rp_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, payload, nullptr, false, totals, events, max_out,
                         nr_events, flags);
+}
+
+int mfm_hosttwin_runpocsag_call_ends(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
+                                     struct mfm_runpocsag_state *state, const struct mfm_runrs_run *runs, const int16_t *payload,
+                                     const uint64_t *totals, struct mfm_runpocsag_event *events, size_t max_out, size_t *nr_events,
+                                     uint32_t *flags, struct mfm_runpocsag_end *ends, size_t max_ends, size_t *nr_ends)
+{
+    if (!nr_ends) {
+        return MFM_E_INVAL;
+    }
+    return rp_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, payload, nullptr, false, totals, events, max_out,
+                        nr_events, flags, ends, max_ends, nr_ends);
+}
+
+int mfm_hosttwin_runpocsag_end_stretches(uint32_t nr_channels, struct mfm_runpocsag_state *state, struct mfm_runpocsag_end *ends,
+                                         size_t max_ends, size_t *nr_ends)
+{
+    return mfm_run_ends_host_flush(nr_channels, state, ends, max_ends, nr_ends, rp_end_of);
 }
 
 int mfm_hosttwin_runpocsag_call_bits(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_samples, uint32_t max_events,
