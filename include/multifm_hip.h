@@ -1929,6 +1929,113 @@ int mfm_mm_process_device(struct mfm_mm *m, const int16_t *d_pcm, size_t in_stri
 int mfm_mm_process_host(struct mfm_mm *m, const int16_t *pcm, size_t in_stride, size_t nr_in, int16_t *decisions,
                         size_t dec_stride, uint32_t *counts);
 
+/*
+ * ---- Burst Mueller-Muller stage: the burst resampler's runs through the clock recovery loop, on the device ----------------
+ * The stage above (mfm_mm_*) on ragged runs instead of full rows: its input is what mfm_runrs_device_view returns (the run
+ * list, the dense resampled payload, the totals), all read on the device, and its output is the decisions of every run: the
+ * clock-recovered symbols of a burst, for a consumer of its own (a 2-FSK channel none of the burst decoders understands).
+ *
+ * Stretch means what it means for the burst resampler; this stage does not track windows.  Run r continues its channel's
+ * stretch exactly when MFM_RUNRS_BEGINS is clear in runs[r].flags, otherwise it begins a new one.
+ *
+ * Rule.  The decisions of a stretch are the concatenation of the decisions of its runs, and they are exactly what a fresh
+ * struct mueller_muller, initialised by mm_init(kw, km, samples_per_bit, error_min, error_max) (pager/mueller_muller.c:10-33),
+ * returns when the stretch's resampled PCM is fed through mm_process (:41-115) in pieces of fewer than 2^22 samples each: the
+ * same float operations in the same order, without contraction, bit-identical to oracle/pocsag_oracle.c's restatement.  The
+ * reference's float sample position only ever holds whole numbers there (csrc/mfm_runmm.h), so the result does not depend on
+ * the cutting and the stage keeps the position as an integer.  A decision is the sample picked (:71); its index is always
+ * below the stretch's length so far, and no sample behind a run is read: there is no look-ahead column here.  The next
+ * decision may lie beyond the end of a run, or of several short ones: the whole-sample distance still to skip travels in the
+ * state (next_offset); a run shorter than it produces no decision and shortens it.  A run with nr_out == 0 changes nothing
+ * and still begins or continues its stretch.  Decisions do not depend on how the stream was cut into calls.
+ *
+ * No lag.  A decision never looks ahead: it is reported by the call and run that holds its sample, and nothing is pending at
+ * a stretch's end.
+ *
+ * State.  Per channel, on the device (struct mfm_runmm_state below, which the host twin carries too): the loop's w, m and
+ * last_sample, the distance to the next decision, the outputs and the decisions of the stretch so far and the stretch's first
+ * window.  Two state buffers are used in turn: a channel's first run reads the old state, its last run leaves the new one.  A
+ * channel without a run in a call keeps its state.  Only a channel's first run of a call can continue a stretch, so every run
+ * of a call is walked independently: the runs, not the arithmetic, are the stage's parallelism.
+ *
+ * Result.  It replaces the previous call's: one struct mfm_runmm_run per input run, in the resampler's order, and one dense
+ * int16 payload of decisions in run order; dec_offset ascends and there are no gaps.  d_totals[4] = { runs, decisions,
+ * overflow, input error }.  Order and offsets are deterministic: the walk of a run writes into a slot range given by a scan,
+ * and the ranges are packed afterwards.
+ *
+ * Decision bound.  No step is shorter than s = floor(error_min - |km| * 32768) >= 1 samples (:86-96), so a run holds at most
+ * nr_out / s + 1 decisions and a call at most the sum of that over its runs.
+ *
+ * Refused calls produce nothing, leave the per-channel state untouched and raise a flag that mfm_runmm_fetch reports as
+ * MFM_E_STATE with a message:
+ *   overflow     MFM_RUNMM_OVER_RUNS: more runs than max_runs; MFM_RUNMM_OVER_DECISIONS: the call's decision bound exceeds
+ *                max_decisions (by the bound, not by the count, so "does it fit" does not depend on the signal)
+ *   input error  MFM_RUNMM_IN_RUNRS, MFM_RUNMM_IN_OUT_OF_STEP, MFM_RUNMM_IN_BAD_RUNS: the burst POCSAG stage's conditions of
+ *                the same names, checked before anything of the payload is read.
+ *
+ * Refusals at create (MFM_E_INVAL with a message, before a device is looked for): mfm_mm_create's conditions on the five
+ * floats (kw finite, error_min <= error_max, samples_per_bit >= 1 - and below 2^20, it is the first step -, s >= 1, error_max
+ * + |km| * 32768 < 2^20), capacities that are zero or reach 2^28 runs or 2^31 samples, flags other than 0.  max_in_samples has
+ * no counterpart: the position is an integer per run.
+ */
+#define MFM_RUNMM_OVER_RUNS 1u
+#define MFM_RUNMM_OVER_DECISIONS 2u
+#define MFM_RUNMM_IN_RUNRS 1u
+#define MFM_RUNMM_IN_OUT_OF_STEP 2u
+#define MFM_RUNMM_IN_BAD_RUNS 4u
+
+struct mfm_runmm_run {          /* 40 bytes */
+    uint64_t first_window;      /* the resampler run's */
+    uint64_t dec_offset;        /* in int16 elements of the decision payload */
+    uint64_t first_dec;         /* index of the run's first decision within its stretch */
+    uint32_t channel;
+    uint32_t nr_dec;
+    uint32_t flags;             /* MFM_RUNRS_BEGINS, copied */
+    uint32_t reserved;          /* 0 */
+};
+
+struct mfm_runmm; /* opaque */
+
+struct mfm_runmm_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_runs;          /* the burst resampler's capacities (mfm_runrs_get_capacity) */
+    uint32_t max_out_samples;
+    uint32_t max_decisions;     /* per call, all channels; 0 = max_out_samples / s + max_runs, cannot overflow */
+    uint32_t flags;             /* 0 */
+    float kw, km, samples_per_bit, error_min, error_max; /* mm_init's arguments */
+};
+
+int mfm_runmm_create(struct mfm_runmm **pm, const struct mfm_runmm_config *cfg);
+void mfm_runmm_destroy(struct mfm_runmm **pm);
+/*
+ * Recover the clock of the runs of one burst resampler call: d_runs, d_payload and d_totals are what mfm_runrs_device_view
+ * returned.  Work is queued on `stream` (the resampler call's, or one ordered behind it); no host synchronisation and no count
+ * read on the host: launches are sized from the capacities fixed at create, surplus workgroups return after reading the
+ * totals.  The three arrays are read until the queued work has run.
+ */
+int mfm_runmm_process_device(struct mfm_runmm *m, const struct mfm_runrs_run *d_runs, const int16_t *d_payload, const uint64_t *d_totals,
+                             void *stream);
+/*
+ * Wait for the last call, read its totals into *nr_runs and *nr_decisions and copy the used part of both arrays.  MFM_E_NOMEM
+ * when max_runs or max_decisions is too small (nothing copied, the totals say what is needed); MFM_E_STATE with a message when
+ * the call was refused (nothing copied, the state did not move: the same input in a call that is right is right again).
+ */
+int mfm_runmm_fetch(struct mfm_runmm *m, struct mfm_runmm_run *runs, size_t max_runs, size_t *nr_runs, int16_t *decisions,
+                    size_t max_decisions, size_t *nr_decisions);
+/* For consumers that stay on the device: the last call's runs, decisions and d_totals[4], valid until the next call.  Any of the
+ * three may be NULL. */
+int mfm_runmm_device_view(struct mfm_runmm *m, const struct mfm_runmm_run **d_runs, const int16_t **d_decisions, const uint64_t **d_totals);
+struct mfm_runmm_state;
+/* Wait for the last call and copy the per-channel state it left, state[nr_channels] (for tests and for moving a stream
+ * between objects: it is what the host twin carries). */
+int mfm_runmm_fetch_state(struct mfm_runmm *m, struct mfm_runmm_state *state, size_t nr_channels);
+/* The way back: waits for the queued work, validates every channel (csrc/mfm_runmm.h states the conditions) and writes what
+ * the next process call reads.  A state that fails gets MFM_E_INVAL with a message naming channel and field, and nothing is
+ * written.  The result of the last call stays readable. */
+int mfm_runmm_store_state(struct mfm_runmm *m, const struct mfm_runmm_state *state, size_t nr_channels);
+
 /* bch_code_decode (pager/bch_code.c:307-398) on n words in place; rc[i] = its return value (0 or 1). */
 int mfm_bch3121_decode_device(uint32_t *d_words, uint8_t *d_rc, size_t n, int device, void *stream);
 int mfm_bch3121_decode_host(uint32_t *words, uint8_t *rc, size_t n, int device);
@@ -2286,6 +2393,30 @@ int mfm_hosttwin_runflex_call_ends(uint32_t nr_channels, uint32_t max_runs, uint
 /* host twin of mfm_runflex_end_stretches_device and its fetch, as mfm_hosttwin_runais_end_stretches (the rings are not touched) */
 int mfm_hosttwin_runflex_end_stretches(uint32_t nr_channels, struct mfm_runflex_state *state, struct mfm_runflex_end *ends,
                                        size_t max_ends, size_t *nr_ends);
+/* the per-channel state of the burst Mueller-Muller stage, on the device and in the host twin: all zero at the start of a
+ * stream.  What a stored state must satisfy: csrc/mfm_runmm.h (mfm_runmm_state_check) */
+struct mfm_runmm_state {        /* 48 bytes */
+    uint64_t outs;              /* outputs of the stretch so far */
+    uint64_t decs;              /* decisions of the stretch so far */
+    uint64_t stretch_window;    /* first window of the stretch */
+    float w;                    /* the reference's w, m and last_sample after the last decision (mm_init's before the first) */
+    float m;
+    float last_sample;
+    uint32_t next_offset;       /* whole samples from the stretch's end so far to the next decision */
+    uint32_t has_stretch;       /* 0: nothing to continue */
+    uint32_t reserved;          /* 0 */
+};
+/* host twin of one mfm_runmm_process_device call and its fetch, no device needed (cfg->device is not read): runs / payload /
+ * totals are one burst resampler call's result (totals[4] as its d_totals), state [cfg->nr_channels] is read and updated in
+ * place.  Same refusals: MFM_E_INVAL with the message create gives; MFM_E_STATE with the message mfm_runmm_fetch gives and
+ * *flags = overflow | input error << 8; MFM_E_NOMEM when max_out_runs or max_out_decisions is too small (*nr_runs,
+ * *nr_decisions = needed); on any error nothing is written, the state included. */
+int mfm_hosttwin_runmm_call(const struct mfm_runmm_config *cfg, struct mfm_runmm_state *state, const struct mfm_runrs_run *runs,
+                            const int16_t *payload, const uint64_t *totals, struct mfm_runmm_run *out_runs, size_t max_out_runs,
+                            size_t *nr_runs, int16_t *decisions, size_t max_out_decisions, size_t *nr_decisions, uint32_t *flags);
+/* the validation mfm_runmm_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
+ * channel and field that fail (csrc/mfm_runmm.h) */
+int mfm_hosttwin_runmm_state_check(uint32_t nr_channels, const struct mfm_runmm_state *state);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

@@ -5,7 +5,7 @@
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
            [--floor-windows M --open-ratio R --close-ratio R [--warmup N]]
            [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-dc-pole POLE]
-           [--gate-ais | --gate-pocsag | --gate-flex]] | --gate-route routes.json]]
+           [--gate-ais | --gate-pocsag | --gate-flex | --gate-mm SPB[,KW,KM,MARGIN]]] | --gate-route routes.json]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -91,6 +91,26 @@ the place of the time:
     {"proto": "flex", "type": "alphanumeric", "channel": 3, "first_sample": 4000, "baud": 3200, "frameNo": 42, "cycleNo": 5,
      "phaseNo": "A", "capCode": 123456, "fragment": false, "maildrop": false, "fragSeq": 3, "message": "HELLO"}
 
+--gate-mm SPB[,KW,KM,MARGIN] (with --gate-resample; beside no other stage flag, --gate-bits or --gate-ends) queues the burst
+Mueller-Muller stage behind the burst resampler on the same stream, the flush call included: every stretch goes through a fresh
+clock recovery loop mm_init(KW, KM, SPB, SPB - MARGIN, SPB + MARGIN) (pager/mueller_muller.c; SPB is samples per bit at the
+resampler's output rate, the other three default to the reference test's 0.0001, 0.000004 and 0.05; all are taken as float32).
+DIR/chNNNN.mm.s16 gets the channel's decisions - the samples the loop picked, one per recovered symbol - appended, and DIR/mm.jsonl
+one line per run:
+
+    {"channel": 3, "first_sample": 4000, "first_dec": 0, "nr_dec": 76, "begins": 1, "file_offset": 0}
+
+(first_sample: the run's first sample, in samples of the channel at the input rate; first_dec the index of the run's first decision within its stretch,
+begins 1 on a stretch's first run, file_offset in bytes of the .mm.s16 file).  It is the product for a 2-FSK channel none of the
+three decoders understands: d > 0 ? 0 : 1 is the reference consumer's bit.
+
+    python tools/level_scan.py --bench-runmm --window 4096 [--reps 8] [--inner 10]
+
+prints one line ("runmm_stage"): burst resampler -> burst Mueller-Muller stage on a gate's device view against mfm_resampler ->
+mfm_mm on the full rows, 4/5 with 41 taps, 131 072 input samples per channel at 64 and 1024 channels, the three masks all-closed,
+scene (a squelch at the median window energy) and all-open, the two chains alternating in one process in rotating order; and
+whether a sample of the burst decisions (the first runs of a call) equalled the host twin's.
+
 --gate-ends (with --gate-ais, --gate-pocsag or --gate-flex, with or without --gate-bits, or with --gate-route, where it applies to
 every route's stage) switches the stage's stretch-end report on, ends the open stretches behind the gate's flush and writes
 DIR/ends.jsonl beside the events (under a route: DIR/NAME/ends.jsonl), one line per stretch: channel, first_sample (the stretch's
@@ -112,7 +132,9 @@ burst chain only the runs of its own channels.  FILE is JSON:
     {"routes": [{"name": "pocsag", "stage": "pocsag", "resample": "4/5", "taps": "filter.json", "channels": [0, 2, 5]},
                 {"name": "flex", "stage": "flex", "resample": "16/25", "taps": "flex.json", "dc_pole": 0.999, "channels": [1, 3]}]}
 
-up to eight routes; stage is ais, pocsag, flex or none (the resampler alone); resample and taps as --gate-resample and
+up to eight routes; stage is ais, pocsag, flex, mm or none (the resampler alone; a route of stage mm carries "mm": {"spb": 20.8333,
+"kw": 0.0001, "km": 0.000004, "margin": 0.05}, spb required, as --gate-mm, writes mm.jsonl and chNNNN.mm.s16, takes no bits and has
+no stretch-end report); resample and taps as --gate-resample and
 --resample-taps; dc_pole and bits (true / false) are optional and follow the rules of --gate-dc-pole and --gate-bits (bits only
 with ais or pocsag, never with dc_pole); a channel may stand in one route at most, and a channel in none is gated but goes no
 further.  Each route runs burst resampler -> stage on its view of the router, on the engine's stream, the flush call included, and
@@ -210,8 +232,32 @@ def read_config(path):
     return fs, centre, decim, taps, chans
 
 
-ROUTE_STAGES = ("ais", "pocsag", "flex", "none")
+ROUTE_STAGES = ("ais", "pocsag", "flex", "none")   # and "mm", which the refusal below does not name: its words are pinned
 MAX_ROUTES = 8   # MFM_RUNROUTE_MAX_ROUTES
+MM_DEFAULTS = {"kw": 0.0001, "km": 0.000004, "margin": 0.05}   # pager/test/test_mueller_muller.c:85-88
+
+
+def parse_gate_mm(text):
+    """--gate-mm SPB[,KW,KM,MARGIN] as the "mm" object of a route"""
+    parts = text.split(",")
+    if len(parts) not in (1, 4):
+        raise SystemExit(f"--gate-mm takes SPB or SPB,KW,KM,MARGIN, not {text!r}")
+    try:
+        vals = [float(x) for x in parts]
+    except ValueError:
+        raise SystemExit(f"--gate-mm takes SPB or SPB,KW,KM,MARGIN, not {text!r}")
+    mm = dict(MM_DEFAULTS, spb=vals[0])
+    if len(vals) == 4:
+        mm.update(kw=vals[1], km=vals[2], margin=vals[3])
+    return mm
+
+
+def check_mm(mm, where):
+    """the "mm" object of a route (or of --gate-mm): spb, and optionally kw, km, margin, all numbers"""
+    if not isinstance(mm, dict) or "spb" not in mm or set(mm) - {"spb", "kw", "km", "margin"} or \
+            not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in mm.values()):
+        raise SystemExit(f"{where}: \"mm\" must be an object of numbers with spb and optionally kw, km and margin, not {mm!r}")
+    return dict(MM_DEFAULTS, **mm)
 
 
 class Routes(list):
@@ -243,10 +289,17 @@ def read_routes(path, nr_channels):
         if not name or name in names or os.sep in name or name in (".", ".."):
             raise SystemExit(f"--gate-route: a route's name is its folder under --gate-out: {name!r} is empty, used twice or a path")
         names.add(name)
-        if r.get("stage") not in ROUTE_STAGES:
+        if r.get("stage") not in ROUTE_STAGES + ("mm",):
             raise SystemExit(f"--gate-route: route {name}: stage {r.get('stage')!r} is none of {', '.join(ROUTE_STAGES)}")
         if not r.get("resample") or not r.get("taps"):
             raise SystemExit(f"--gate-route: route {name} needs resample (I/D) and taps (a JSON file whose lpfCoeffs are the taps)")
+        if r["stage"] == "mm":
+            r["mm"] = check_mm(r.get("mm"), f"--gate-route: route {name}")
+            if r.get("bits"):
+                raise SystemExit(f"--gate-route: route {name}: bits needs stage ais or pocsag: the burst Mueller-Muller stage reads PCM values, "
+                                 "not sign bits")
+        elif "mm" in r:
+            raise SystemExit(f"--gate-route: route {name}: \"mm\" belongs to stage mm, not to stage {r['stage']}")
         if r.get("bits") and r["stage"] not in ("ais", "pocsag"):
             raise SystemExit(f"--gate-route: route {name}: bits needs stage ais or pocsag: the burst FLEX stage reads PCM values, not sign bits")
         if r.get("bits") and r.get("dc_pole") is not None:
@@ -272,15 +325,16 @@ ENDS_MODE_NAMES = {"ais": {1: "receive"}, "pocsag": {2: "batch", 3: "syncword"},
 
 
 class BurstChain:
-    """burst resampler -> burst stage (ais, pocsag, flex or None) behind one run list - the gate's, or with --gate-route one
+    """burst resampler -> burst stage (ais, pocsag, flex, mm or None) behind one run list - the gate's, or with --gate-route one
     route's of the run router - and the files the two write under out_dir; view() returns the run list's device view"""
 
     def __init__(self, pkg, out_dir, window, nr_channels, max_in_samples, preroll, device, view, resample, taps_file, dc_pole=None,
-                 stage=None, bits=False, caps=None, channels=None, bound=None, ends=False):
+                 stage=None, bits=False, caps=None, channels=None, bound=None, ends=False, mm=None):
         """caps and channels: behind a packed or a local route of the run router, its route_caps() - the chain is sized to the route -
         and its route_channels(), which turn the route-local channel numbers of everything fetched back into true ones.  bound:
         behind a local route, the router's bound_view(): the resampler then reads the gate's payload through its view entries.
-        ends (--gate-ends): the stage's stretch-end report, one line per stretch in ends.jsonl"""
+        ends (--gate-ends): the stage's stretch-end report, one line per stretch in ends.jsonl (the mm stage has none: nothing is
+        pending when a stretch ends).  mm: stage mm's spb, kw, km and margin"""
         b = self.b = pkg.binding
         self.out_dir, self.window, self.view, self.bound = out_dir, window, view, bound
         self.channels = None if channels is None else np.asarray(channels, np.uint32)
@@ -298,13 +352,16 @@ class BurstChain:
         self.rs_index, self.rs_started = open(os.path.join(out_dir, "resampled.jsonl"), "w"), set()
         self.stage = stage
         self.st, self.st_index, self.pages_index, self.pagers = None, None, None, {}
-        if stage:
+        if stage == "mm":
+            self.st = pkg.RunMm.behind(self.rr, mm["spb"], mm["kw"], mm["km"], margin=mm["margin"], device=device)
+            self.st_index, self.mm_started = open(os.path.join(out_dir, "mm.jsonl"), "w"), set()
+        elif stage:
             self.st = {"ais": pkg.RunAis, "pocsag": pkg.RunPocsag, "flex": pkg.RunFlex}[stage].behind(self.rr, device=device)
             self.st_index = open(os.path.join(out_dir, stage + ".jsonl"), "w")
         if stage in ("pocsag", "flex"):
             self.pages_index = open(os.path.join(out_dir, "pages.jsonl"), "w")
         self.ends_index, self.stretches, self.cut_by_mode = None, 0, {}
-        if stage and ends:
+        if stage and stage != "mm" and ends:
             self.st.set_end_report(True)
             self.ends_index = open(os.path.join(out_dir, "ends.jsonl"), "w")
         # --gate-bits: the predicate the stage behind the resampler reads
@@ -341,6 +398,9 @@ class BurstChain:
         if self.stage == "flex":
             events, frames = self.st.fetch()
             self.write_flex(self.true_channels(events), frames)
+        if self.stage == "mm":
+            runs, decisions = self.st.fetch()
+            self.write_mm(self.true_channels(runs), decisions)
         if self.ends_index:
             self.write_ends(self.true_channels(self.st.fetch_ends()))
 
@@ -418,6 +478,19 @@ class BurstChain:
                                             "sample": int(e["sample"]), "start_sample": int(e["start_sample"]), "nr_bytes": int(e["nr_bytes"]),
                                             "fcs_valid": int(e["fcs_valid"]), "bytes": bytes(e["bytes"][:int(e["nr_bytes"])]).hex()}) + "\n")
 
+    def write_mm(self, runs, decisions):
+        """the decisions of every run appended to its channel's file, and a line per run"""
+        for r in runs:
+            c = int(r["channel"])
+            path = os.path.join(self.out_dir, "ch%04d.mm.s16" % c)
+            with open(path, "ab" if c in self.mm_started else "wb") as g:
+                at = g.tell()
+                decisions[int(r["dec_offset"]):int(r["dec_offset"]) + int(r["nr_dec"])].tofile(g)
+            self.mm_started.add(c)
+            self.st_index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * self.window,
+                                            "first_dec": int(r["first_dec"]), "nr_dec": int(r["nr_dec"]), "begins": int(r["flags"]) & 1,
+                                            "file_offset": at}) + "\n")
+
     def write_resampled(self, runs, payload):
         for r in runs:
             c = int(r["channel"])
@@ -481,9 +554,10 @@ def scan(a):
     max_in = a.block // decim + 8
     router, chains = None, []   # one chain behind the gate, or with --gate-route one per route behind the run router
     if a.gate_resample:   # main() has refused --gate-flex without it or beside another stage
-        stage = "ais" if a.gate_ais else "pocsag" if a.gate_pocsag else "flex" if a.gate_flex else None
+        stage = "ais" if a.gate_ais else "pocsag" if a.gate_pocsag else "flex" if a.gate_flex else "mm" if a.gate_mm else None
         chains.append(BurstChain(pkg, a.gate_out, a.window, len(chans), max_in, int(a.gate_preroll), a.device, gate.device_view,
-                                 a.gate_resample, a.resample_taps, dc_pole=a.gate_dc_pole, stage=stage, bits=a.gate_bits, ends=a.gate_ends))
+                                 a.gate_resample, a.resample_taps, dc_pole=a.gate_dc_pole, stage=stage, bits=a.gate_bits, ends=a.gate_ends,
+                                 mm=parse_gate_mm(a.gate_mm) if a.gate_mm else None))
     if routes is not None:
         if not gate or iq_form:
             raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
@@ -506,7 +580,7 @@ def scan(a):
             chains.append(BurstChain(pkg, os.path.join(a.gate_out, r["name"]), a.window, len(chans), max_in, int(a.gate_preroll), a.device,
                                      lambda k=k: router.device_view(k), r["resample"], r["taps"], dc_pole=r.get("dc_pole"),
                                      stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits")), ends=a.gate_ends,
-                                     **sized))
+                                     mm=r.get("mm"), **sized))
 
     def run_stages():
         """the router, where there is one, and every chain on the gate's last result, all on the engine's stream"""
@@ -2028,6 +2102,129 @@ def bench_runflex_alone(a):
     bench_runflex(a, pkg, torch)
 
 
+def bench_runmm(a, pkg, torch):
+    """burst resampler -> burst Mueller-Muller stage on the device view one gate call left (every call begins every stretch anew,
+    as in bench_runrs, so every call does the same work) against mfm_resampler (v_dot2 form) -> mfm_mm on the full rows; the two
+    chains alternate in one process in rotating order.  The decisions of a call's first runs are compared with the host twin's"""
+    b = pkg.binding
+    W, I, D = a.window, 4, 5
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    taps = np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16)
+    spb = float(np.float32(38400.0) / np.float32(1200.0))   # the busy rows' 1200-baud transmissions behind the 4/5 resampler
+    mm = dict(MM_DEFAULTS, spb=spb)
+    emin, emax = float(np.float32(spb) - np.float32(mm["margin"])), float(np.float32(spb) + np.float32(mm["margin"]))
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "runmm_stage", "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I, "decimate": D,
+           "taps": int(taps.size), "reps": a.reps, "calls_per_rep": a.inner, "samples_per_bit": spb, "kw": mm["kw"], "km": mm["km"],
+           "margin": mm["margin"], "staging_unit": b.RUNMM_STAGING_UNIT}
+    sample_ok, sample_decisions = True, 0
+    for nch in (64, 1024):
+        host = _busy_pocsag_rows(pkg, nch, n)
+        d_rows = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "scene": scene["open"]}
+        keep, recs = [], {"scene": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        plain = pkg.Resampler(nch, taps, I, D, nb, device=0, force_dot2=True)
+        pm_ = pkg.MuellerMuller(nch, mm["kw"], mm["km"], spb, emin, emax, plain.max_out(), device=0)
+        rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        rm = pkg.RunMm.behind(rr, spb, mm["kw"], mm["km"], margin=mm["margin"])
+
+        def run_plain():
+            yptr, ystride, ny = plain.process_device(rows, in_stride, nb)
+            pm_.process_device(yptr, ystride, ny)
+
+        res = {}
+        for name in ("all_closed", "scene", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_burst():
+                rr.process_device(*view)
+                rm.process_device(*rr.device_view())
+
+            def run_burst_rs():
+                rr.process_device(*view)
+
+            def run_plain_rs():
+                plain.process_device(rows, in_stride, nb)
+
+            variants = [("burst", run_burst), ("plain", run_plain), ("burst_rs", run_burst_rs), ("plain_rs", run_plain_rs)]
+            for _, fn in variants:
+                timed(fn, 3)
+            run_burst()
+            mruns, decs = rm.fetch()
+            # a sample against the twin: the call's first runs (each begins its stretch, so each stands alone)
+            runs, payload = rr.fetch()
+            k = 0
+            while k < min(len(runs), 6) and int(runs["out_offset"][k]) + int(runs["nr_out"][k]) <= 1 << 20:
+                k += 1
+            if k:
+                assert (runs["flags"][:k] & 1).all()
+                wr, wd = b.hosttwin_runmm_call(b.hosttwin_runmm_state(nch), runs[:k], payload[:int(runs["out_offset"][k - 1]) + int(runs["nr_out"][k - 1])],
+                                               spb, mm["kw"], mm["km"], margin=mm["margin"])
+                sample_ok = sample_ok and mruns[:k].tobytes() == wr.tobytes() and decs[:wd.size].tobytes() == wd.tobytes()
+                sample_decisions += int(wd.size)
+            got_t = {v: [] for v, _ in variants}
+            for rep_ in range(a.reps):
+                j = rep_ % len(variants)
+                for vname, fn in variants[j:] + variants[:j]:
+                    got_t[vname].append(timed(fn, a.inner))
+            (bm, bsd), (pm, psd) = _stats(got_t["burst"]), _stats(got_t["plain"])
+            (brm, brsd), (prm, prsd) = _stats(got_t["burst_rs"]), _stats(got_t["plain_rs"])
+            ratio = bm / pm
+            ratio_se = ratio * math.sqrt(bsd * bsd / a.reps / (bm * bm) + psd * psd / a.reps / (pm * pm))
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "runs": int(len(runs)),
+                         "longest_run_out": int(runs["nr_out"].max()) if len(runs) else 0, "decisions_per_call": int(decs.size),
+                         "burst_ms": bm, "burst_sd": bsd, "plain_ms": pm, "plain_sd": psd, "burst_over_plain": ratio,
+                         "burst_over_plain_se": ratio_se, "burst_resampler_ms": brm, "burst_resampler_sd": brsd,
+                         "plain_resampler_ms": prm, "plain_resampler_sd": prsd, "burst_mm_ms": bm - brm, "plain_mm_ms": pm - prm}
+            gate.close()
+        out["channels_%d" % nch] = res
+        for o in (rm, rr, pm_, plain, sq):
+            o.close()
+        del d_rows, keep
+    out["sample_equals_twin"] = bool(sample_ok)
+    out["sample_decisions"] = int(sample_decisions)
+    print(json.dumps(out))
+
+
+def bench_runmm_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runmm needs the GPU: there is no CPU path to time")
+    bench_runmm(a, pkg, torch)
+
+
 def bench_runpocsag_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -2074,6 +2271,8 @@ def main():
     ap.add_argument("--gate-ais", action="store_true", help="demodulate AIS on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--gate-pocsag", action="store_true", help="demodulate POCSAG on the resampled runs on the device (with --gate-resample)")
     ap.add_argument("--gate-flex", action="store_true", help="decode FLEX on the resampled runs on the device (with --gate-resample to 16 000 Hz)")
+    ap.add_argument("--gate-mm", default=None, metavar="SPB[,KW,KM,MARGIN]",
+                    help="Mueller-Muller clock recovery on the resampled runs on the device (with --gate-resample): the decisions of every run")
     ap.add_argument("--gate-bits", action="store_true",
                     help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
     ap.add_argument("--gate-ends", action="store_true",
@@ -2087,6 +2286,8 @@ def main():
     ap.add_argument("--bench-runais", action="store_true", help="the runais_stage line of --bench alone")
     ap.add_argument("--bench-runpocsag", action="store_true", help="the runpocsag_stage line of --bench alone")
     ap.add_argument("--bench-runflex", action="store_true", help="the runflex_stage line alone")
+    ap.add_argument("--bench-runmm", action="store_true",
+                    help="the runmm_stage line: burst resampler -> burst Mueller-Muller against the full-row chain at 64 and 1024 channels")
     ap.add_argument("--bench-runbits", action="store_true", help="the runbits_stage line of --bench alone")
     ap.add_argument("--bench-runroute", action="store_true", help="the runroute_stage line alone: the run router at 64 and 1024 channels")
     ap.add_argument("--bench-runroute-pack", action="store_true",
@@ -2109,6 +2310,8 @@ def main():
         return bench_runpocsag_alone(a)
     if a.bench_runflex:
         return bench_runflex_alone(a)
+    if a.bench_runmm:
+        return bench_runmm_alone(a)
     if a.bench_runends:
         return bench_runends_alone(a)
     if a.bench_runbits:
@@ -2127,6 +2330,18 @@ def main():
         raise SystemExit("--floor-windows, --open-ratio and --close-ratio go together: the adaptive squelch needs all three")
     if a.warmup is not None and a.floor_windows is None:
         raise SystemExit("--warmup needs --floor-windows: it is the adaptive squelch's warm-up")
+    if a.gate_mm:
+        if a.gate_route:
+            raise SystemExit("--gate-route excludes --gate-mm: a route of stage mm names its own loop")
+        if not a.gate_resample:
+            raise SystemExit("--gate-mm needs --gate-resample: the burst Mueller-Muller stage takes the burst resampler's runs")
+        if a.gate_ais or a.gate_pocsag or a.gate_flex:
+            raise SystemExit("--gate-mm, --gate-flex, --gate-pocsag and --gate-ais exclude each other: one stage reads the burst resampler's runs")
+        if a.gate_bits:
+            raise SystemExit("--gate-mm and --gate-bits exclude each other: the burst Mueller-Muller stage reads PCM values, not sign bits")
+        if a.gate_ends:
+            raise SystemExit("--gate-mm and --gate-ends exclude each other: a decision never looks ahead, so nothing is cut when a stretch ends")
+        parse_gate_mm(a.gate_mm)
     if a.gate_route and (a.gate_resample or a.gate_ais or a.gate_pocsag or a.gate_flex or a.gate_bits or a.gate_dc_pole is not None):
         raise SystemExit("--gate-route excludes --gate-resample, --gate-ais, --gate-pocsag, --gate-flex, --gate-bits and --gate-dc-pole: "
                          "every route names its own resampler and stage")

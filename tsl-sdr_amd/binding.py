@@ -94,6 +94,8 @@ ABI_SYMBOLS = [
     "mfm_hosttwin_runroute_route_caps", "mfm_hosttwin_runroute_sets_call",
     "mfm_runroute_create_local", "mfm_runroute_bound_view", "mfm_hosttwin_runroute_local_call",
     "mfm_runrs_process_view_device", "mfm_runrs_process_bits_view_device",
+    "mfm_runmm_create", "mfm_runmm_destroy", "mfm_runmm_process_device", "mfm_runmm_fetch", "mfm_runmm_device_view",
+    "mfm_runmm_fetch_state", "mfm_runmm_store_state", "mfm_hosttwin_runmm_call", "mfm_hosttwin_runmm_state_check",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -318,6 +320,33 @@ RUNPOCSAG_STATE_DTYPE = np.dtype([("outs", "<u8"), ("stretch_window", "<u8"), ("
                                   ("skip", "<u4"), ("batch_word", "<u4"), ("batch_bit", "<u4"), ("sync_word", "<u4"),
                                   ("nr_sync_bits", "<u4"), ("nr_eye", "<u4", (3,)), ("since_reset", "<u4"), ("has_stretch", "<u4"),
                                   ("batch", "<u4", (16,)), ("tail", "<u4", (75,))])
+
+
+class RunMmConfig(C.Structure):
+    """struct mfm_runmm_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("max_runs", C.c_uint32),
+                ("max_out_samples", C.c_uint32), ("max_decisions", C.c_uint32), ("flags", C.c_uint32), ("kw", C.c_float),
+                ("km", C.c_float), ("samples_per_bit", C.c_float), ("error_min", C.c_float), ("error_max", C.c_float)]
+
+
+MFM_RUNMM_OVER_RUNS, MFM_RUNMM_OVER_DECISIONS = 1, 2                                # d_totals[2]
+MFM_RUNMM_IN_RUNRS, MFM_RUNMM_IN_OUT_OF_STEP, MFM_RUNMM_IN_BAD_RUNS = 1, 2, 4       # d_totals[3]
+RUNMM_STAGING_UNIT = 512   # samples of a run the walk holds in LDS at a time (csrc/mfm_runmm.h)
+# numpy views of struct mfm_runmm_run (40 bytes, per run) and struct mfm_runmm_state (48 bytes, per channel)
+RUNMM_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("dec_offset", "<u8"), ("first_dec", "<u8"), ("channel", "<u4"),
+                            ("nr_dec", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+RUNMM_STATE_DTYPE = np.dtype([("outs", "<u8"), ("decs", "<u8"), ("stretch_window", "<u8"), ("w", "<f4"), ("m", "<f4"),
+                              ("last_sample", "<f4"), ("next_offset", "<u4"), ("has_stretch", "<u4"), ("reserved", "<u4")])
+
+
+def runmm_min_step(km, error_min):
+    """s = floor(error_min - |km| * 32768) in float: no step of the loop is shorter (csrc/mfm_runmm.h)"""
+    return int(np.floor(np.float32(error_min) - np.abs(np.float32(km)) * np.float32(32768.0)))
+
+
+def runmm_slots(nr_out, s):
+    """the decision bound of a run of nr_out samples (mfm_runmm_slots)"""
+    return int(nr_out) // int(s) + 1
 
 
 def runpocsag_slots(nr_out):
@@ -687,6 +716,17 @@ def load_library():
     lib.mfm_runroute_create_local.argtypes = [C.POINTER(vp), C.POINTER(RunRouteConfig), vp]
     lib.mfm_runroute_bound_view.argtypes = [vp, C.POINTER(vp)]
     lib.mfm_hosttwin_runroute_local_call.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+    lib.mfm_runmm_create.argtypes = [C.POINTER(vp), C.POINTER(RunMmConfig)]
+    lib.mfm_runmm_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runmm_destroy.restype = None
+    lib.mfm_runmm_process_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mfm_runmm_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_runmm_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runmm_fetch_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_runmm_store_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_hosttwin_runmm_call.argtypes = [C.POINTER(RunMmConfig), vp, vp, vp, vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp,
+                                            C.POINTER(C.c_uint32)]
+    lib.mfm_hosttwin_runmm_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                               C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -2627,6 +2667,150 @@ class RunPocsag(_RunEnds):
         rc = self.lib.mfm_runpocsag_store_state(self.h, st.ctypes.data if st is not None else None, n)
         if rc < 0:
             self._raise(rc, "mfm_runpocsag_store_state")
+
+
+class RunMm:
+    """mfm_runmm: the runs of a RunResampler's device view through the Mueller-Muller clock recovery, one fresh loop per stretch;
+    RUNMM_RUN_DTYPE records and a dense int16 payload of decisions.  max_runs and max_out_samples are the burst resampler's
+    capacities (RunMm.behind reads them); max_decisions 0 is a bound that cannot overflow.  error_min / error_max default to
+    samples_per_bit -/+ margin in float32, as the reference's test sets them."""
+
+    def __init__(self, nr_channels, max_runs, max_out_samples, samples_per_bit, kw, km, margin=0.05, error_min=None, error_max=None,
+                 max_decisions=0, device=0, flags=0, abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        emin = float(np.float32(samples_per_bit) - np.float32(margin)) if error_min is None else error_min
+        emax = float(np.float32(samples_per_bit) + np.float32(margin)) if error_max is None else error_max
+        self.cfg = RunMmConfig(abi_version, device, nr_channels, max_runs, max_out_samples, max_decisions, flags, kw, km, samples_per_bit,
+                               emin, emax)
+        rc = self.lib.mfm_runmm_create(C.byref(self.h), C.byref(self.cfg))
+        if rc < 0:
+            self._raise(rc, "mfm_runmm_create")
+        self.nr_channels = nr_channels
+
+    @classmethod
+    def behind(cls, run_resampler, samples_per_bit, kw, km, margin=0.05, max_decisions=0, device=0, **kwargs):
+        """a stage sized for everything one call of `run_resampler` can produce"""
+        max_runs, max_out = run_resampler.capacity()
+        return cls(run_resampler.nr_channels, max_runs, max_out, samples_per_bit, kw, km, margin=margin, max_decisions=max_decisions,
+                   device=device, **kwargs)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runmm_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_payload, d_totals, stream=None):
+        """the three addresses of RunResampler.device_view(), after its process_device on the same stream"""
+        rc = self.lib.mfm_runmm_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_payload), C.c_void_p(d_totals), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runmm_process_device")
+
+    def fetch(self, max_runs=None, max_decisions=None):
+        """(runs RUNMM_RUN_DTYPE, decisions int16) of the last call.  With a buffer too small: MfmError(MFM_E_NOMEM) whose `needed`
+        attribute is the (runs, decisions) that would fit"""
+        nr, nd = C.c_size_t(), C.c_size_t()
+        if max_runs is None or max_decisions is None:
+            rc = self.lib.mfm_runmm_fetch(self.h, None, 0, C.byref(nr), None, 0, C.byref(nd))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below
+                self._raise(rc, "mfm_runmm_fetch")
+            max_runs = nr.value if max_runs is None else max_runs
+            max_decisions = nd.value if max_decisions is None else max_decisions
+        runs = np.zeros(max(max_runs, 1), RUNMM_RUN_DTYPE)
+        decs = np.zeros(max(max_decisions, 1), np.int16)
+        rc = self.lib.mfm_runmm_fetch(self.h, runs.ctypes.data, max_runs, C.byref(nr), decs.ctypes.data, max_decisions, C.byref(nd))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runmm_fetch")
+            except MfmError as err:
+                err.needed = (nr.value, nd.value)
+                raise
+        return runs[:nr.value].copy(), decs[:nd.value].copy()
+
+    def device_view(self):
+        """(d_runs, d_decisions, d_totals): device addresses of the last call's run records, its decisions and the four uint64
+        totals (runs, decisions, overflow, input error)"""
+        r, d, t = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runmm_device_view(self.h, C.byref(r), C.byref(d), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runmm_device_view")
+        return r.value, d.value, t.value
+
+    def fetch_state(self):
+        """the per-channel state the last call left (RUNMM_STATE_DTYPE [C]): what the host twin carries"""
+        out = np.zeros(self.nr_channels, RUNMM_STATE_DTYPE)
+        rc = self.lib.mfm_runmm_fetch_state(self.h, out.ctypes.data, self.nr_channels)
+        if rc < 0:
+            self._raise(rc, "mfm_runmm_fetch_state")
+        return out
+
+    def store_state(self, state, nr_channels=None):
+        """mfm_runmm_store_state: what the next process call continues from.  Validated first: MfmError(MFM_E_INVAL) with a
+        message naming channel and field, and nothing written"""
+        st = np.ascontiguousarray(state, dtype=RUNMM_STATE_DTYPE) if state is not None else None
+        n = self.nr_channels if nr_channels is None else nr_channels
+        assert st is None or st.shape == (n,)
+        rc = self.lib.mfm_runmm_store_state(self.h, st.ctypes.data if st is not None else None, n)
+        if rc < 0:
+            self._raise(rc, "mfm_runmm_store_state")
+
+
+def hosttwin_runmm_state(nr_channels):
+    """the host twin's per-channel state at the start of a stream: RUNMM_STATE_DTYPE [C], all zero (no stretch)"""
+    return np.zeros(nr_channels, RUNMM_STATE_DTYPE)
+
+
+def hosttwin_runmm_call(state, runs, payload, samples_per_bit, kw, km, margin=0.05, error_min=None, error_max=None, totals=None,
+                        max_runs=None, max_out_samples=None, max_decisions=0, max_out_runs=None, max_out_decisions=None, flags=0,
+                        abi_version=MFM_ABI_VERSION):
+    """mfm_hosttwin_runmm_call: one call of the burst Mueller-Muller stage on the CPU.  state (hosttwin_runmm_state) is updated in
+    place; runs RUNRS_RUN_DTYPE and payload int16 are one burst resampler call's result, totals its four totals (default: the
+    lengths, no flags); max_runs / max_out_samples / max_decisions are the configuration's (default: what the call needs);
+    returns (runs RUNMM_RUN_DTYPE, decisions).  A refused call raises MfmError(MFM_E_STATE) with a `flags` attribute (overflow |
+    input error << 8)"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNMM_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNRS_RUN_DTYPE).reshape(-1)
+    pl = np.ascontiguousarray(payload, dtype=np.int16).reshape(-1)
+    t = np.array([rr.size, pl.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_out_samples = max(pl.size, 1) if max_out_samples is None else max_out_samples
+    emin = float(np.float32(samples_per_bit) - np.float32(margin)) if error_min is None else error_min
+    emax = float(np.float32(samples_per_bit) + np.float32(margin)) if error_max is None else error_max
+    cfg = RunMmConfig(abi_version, 0, state.shape[0], max_runs, max_out_samples, max_decisions, flags, kw, km, samples_per_bit, emin, emax)
+    max_out_runs = rr.size if max_out_runs is None else max_out_runs
+    max_out_decisions = pl.size + rr.size if max_out_decisions is None else max_out_decisions
+    out_r = np.zeros(max(max_out_runs, 1), RUNMM_RUN_DTYPE)
+    out_d = np.zeros(max(max_out_decisions, 1), np.int16)
+    nr, nd, fl = C.c_size_t(), C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runmm_call(C.byref(cfg), state.ctypes.data, rr.ctypes.data if rr.size else None,
+                                     pl.ctypes.data if pl.size else None, t.ctypes.data, out_r.ctypes.data, max_out_runs, C.byref(nr),
+                                     out_d.ctypes.data, max_out_decisions, C.byref(nd), C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runmm_call", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.flags = (nr.value, nd.value), fl.value
+        raise err
+    return out_r[:nr.value].copy(), out_d[:nd.value].copy()
+
+
+def hosttwin_runmm_state_check(state):
+    """mfm_hosttwin_runmm_state_check: what RunMm.store_state validates, on the CPU"""
+    st = np.ascontiguousarray(state, dtype=RUNMM_STATE_DTYPE).reshape(-1)
+    lib = load_library()
+    rc = lib.mfm_hosttwin_runmm_state_check(st.shape[0], st.ctypes.data)
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runmm_state_check", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
 
 
 def hosttwin_runpocsag_state(nr_channels):
