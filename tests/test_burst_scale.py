@@ -27,7 +27,7 @@ ROOT = tg.ROOT
 MOD = {"runrs": tr, "runais": tra, "runpocsag": trp, "runflex": trf}
 STAGES = ["runrs", "runais", "runpocsag", "runflex"]
 COUNTS = [1024, 1025, 2049]
-SCAN_THREADS = 1024     # R?_SCAN_THREADS of the four .hip files: per = ceil(n / 1024) runs per thread
+SCAN_THREADS = 1024     # MFM_RUN_SCAN_THREADS of csrc/mfm_run_stage.h: per = ceil(n / 1024) runs per thread
 FRAME, BAD_BAUD = trf.FRAME, trf.BAD_BAUD
 FIGURES = {}            # scene -> the figures its guards saw, for a report
 

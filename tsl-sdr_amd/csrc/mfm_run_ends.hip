@@ -19,18 +19,14 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 
 #include "mfm_run_ends.h"
-
-extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 
 static_assert(sizeof(mfm_runais_end) == 48 && sizeof(mfm_runpocsag_end) == 184 && sizeof(mfm_runflex_end) == 64, "the stretch-end records");
 static_assert(offsetof(mfm_runpocsag_end, raw) == 56 && offsetof(mfm_runpocsag_end, corrected) == 120, "struct mfm_runpocsag_end");
 
 namespace {
 
-constexpr uint32_t RE_SCAN_THREADS = 1024;
 constexpr uint32_t RE_WRITE_THREADS = 256;
 
 template <class State>
@@ -57,34 +53,6 @@ struct ReFlush {
     uint32_t C;
 };
 
-/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
-__device__ __forceinline__ uint64_t re_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
-        if (lane >= (uint32_t)o) {
-            inc += ((uint64_t)hi << 32) | lo;
-        }
-    }
-    if (lane == 63) {
-        lds[wave] = inc;
-    }
-    __syncthreads();
-    uint64_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < RE_SCAN_THREADS / 64; i++) {
-        const uint64_t t = lds[i];
-        base += i < wave ? t : 0u;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
 /* records of run r in the low half, those with mode != 0 in the high half */
 template <class State>
 __device__ __forceinline__ uint64_t re_count(const ReCall<State> &A, uint64_t r, uint64_t n)
@@ -103,20 +71,19 @@ __device__ __forceinline__ uint64_t re_count(const ReCall<State> &A, uint64_t r,
 }
 
 template <class State>
-__global__ __launch_bounds__(RE_SCAN_THREADS) void re_place_kernel(const ReCall<State> A)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void re_place_kernel(const ReCall<State> A)
 {
-    __shared__ uint64_t lds[RE_SCAN_THREADS / 64];
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
     const uint32_t n = A.ctl[1]; /* 0 for a refused call; at most cap_runs */
     /* the counts, a run per thread and step (neighbouring threads read neighbouring runs, no step waits for another): they wait
      * in base[r], records in bits 0 - 1 and those with mode != 0 in bits 2 - 3 */
-    for (uint32_t r = threadIdx.x; r < n; r += RE_SCAN_THREADS) {
+    for (uint32_t r = threadIdx.x; r < n; r += MFM_RUN_SCAN_THREADS) {
         const uint64_t k = re_count(A, r, n);
         A.base[r] = (uint32_t)k | ((uint32_t)(k >> 32) << 2);
     }
     __syncthreads(); /* one block: what it wrote is what it reads */
-    const uint32_t per = (n + RE_SCAN_THREADS - 1) / RE_SCAN_THREADS;
-    const uint32_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint32_t r1 = r0 + per < n ? r0 + per : n;
+    uint32_t r0, r1;
+    mfm_run_slice(n, &r0, &r1);
     uint64_t s = 0;
 #pragma unroll 1
     for (uint32_t r = r0; r < r1; r++) {
@@ -124,7 +91,7 @@ __global__ __launch_bounds__(RE_SCAN_THREADS) void re_place_kernel(const ReCall<
         s += (k & 3u) | ((uint64_t)(k >> 2) << 32);
     }
     uint64_t total;
-    uint64_t base = re_block_scan(s, lds, &total); /* fewer than 2^28 runs of two records: the halves do not meet */
+    uint64_t base = mfm_run_block_scan(s, lds, &total); /* fewer than 2^28 runs of two records: the halves do not meet */
 #pragma unroll 1
     for (uint32_t r = r0; r < r1; r++) {
         const uint32_t k = A.base[r];
@@ -208,20 +175,18 @@ __global__ __launch_bounds__(64) void re_write_pocsag_kernel(const ReCall<mfm_ru
 /* ---- the end call --------------------------------------------------------------------------------------------------- */
 
 template <class State>
-__global__ __launch_bounds__(RE_SCAN_THREADS) void re_flush_place_kernel(const ReFlush<State> A)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void re_flush_place_kernel(const ReFlush<State> A)
 {
-    __shared__ uint64_t lds[RE_SCAN_THREADS / 64];
-    const uint64_t n = A.C;
-    const uint64_t per = (n + RE_SCAN_THREADS - 1) / RE_SCAN_THREADS;
-    const uint64_t c0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t c1 = c0 + per < n ? c0 + per : n;
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
+    uint64_t c0, c1;
+    mfm_run_slice<uint64_t>(A.C, &c0, &c1);
     uint64_t s = 0;
 #pragma unroll 1
     for (uint64_t c = c0; c < c1; c++) {
         s += A.chan[c].has_stretch ? 1u + ((uint64_t)(A.chan[c].mode != 0u) << 32) : 0u;
     }
     uint64_t total;
-    uint64_t base = re_block_scan(s, lds, &total);
+    uint64_t base = mfm_run_block_scan(s, lds, &total);
 #pragma unroll 1
     for (uint64_t c = c0; c < c1; c++) {
         A.base[c] = (uint32_t)base;
@@ -266,8 +231,6 @@ __global__ __launch_bounds__(64) void re_flush_write_pocsag_kernel(const ReFlush
     }
 }
 
-thread_local char g_re_error[256] = "";
-
 size_t re_record_bytes(int stage)
 {
     return stage == MFM_RUN_ENDS_AIS ? sizeof(mfm_runais_end) : stage == MFM_RUN_ENDS_POCSAG ? sizeof(mfm_runpocsag_end) : sizeof(mfm_runflex_end);
@@ -278,7 +241,7 @@ void re_launch_process(const MfmRunEnds *e, const MfmRunEndsCall *c, hipStream_t
 {
     const ReCall<State> A{ c->runs, static_cast<const State *>(c->chan_old), static_cast<const State *>(c->run_state), c->ctl, c->bch,
                            e->d_base, e->d_ends, e->d_end_totals, c->C, c->cap_runs };
-    hipLaunchKernelGGL(re_place_kernel<State>, dim3(1), dim3(RE_SCAN_THREADS), 0, s, A);
+    hipLaunchKernelGGL(re_place_kernel<State>, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
     if constexpr (sizeof(End) == sizeof(mfm_runpocsag_end)) {
         hipLaunchKernelGGL(re_write_pocsag_kernel, dim3(c->cap_runs), dim3(64), 0, s, A);
     } else {
@@ -291,7 +254,7 @@ template <class State, class End>
 void re_launch_flush(const MfmRunEnds *e, void *chan, uint64_t *totals, const MfmBchTables *bch, uint32_t C, hipStream_t s)
 {
     const ReFlush<State> A{ static_cast<State *>(chan), totals, bch, e->d_base, e->d_ends, e->d_end_totals, C };
-    hipLaunchKernelGGL(re_flush_place_kernel<State>, dim3(1), dim3(RE_SCAN_THREADS), 0, s, A);
+    hipLaunchKernelGGL(re_flush_place_kernel<State>, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
     if constexpr (sizeof(End) == sizeof(mfm_runpocsag_end)) {
         hipLaunchKernelGGL(re_flush_write_pocsag_kernel, dim3(C), dim3(64), 0, s, A);
     } else {
@@ -300,16 +263,6 @@ void re_launch_flush(const MfmRunEnds *e, void *chan, uint64_t *totals, const Mf
 }
 
 } /* namespace */
-
-#define RE_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t err_ = (expr);                                                                            \
-        if (err_ != hipSuccess) {                                                                            \
-            snprintf(g_re_error, sizeof(g_re_error), "%s failed: %s", #expr, hipGetErrorString(err_));       \
-            mfm_internal_set_error(g_re_error);                                                              \
-            return err_ == hipErrorOutOfMemory ? MFM_E_NOMEM : MFM_E_DEVICE;                                 \
-        }                                                                                                    \
-    } while (0)
 
 extern "C" {
 
@@ -327,11 +280,11 @@ int mfm_internal_run_ends_set(MfmRunEnds *e, int stage, bool on, size_t max_runs
     }
     /* a process call holds at most max_runs records, an end call at most nr_channels */
     e->cap = max_runs > nr_channels ? max_runs : nr_channels;
-    RE_TRY(hipMalloc(&e->d_ends, e->cap * re_record_bytes(stage)));
-    RE_TRY(hipMalloc(&e->d_end_totals, 2 * 8));
-    RE_TRY(hipMemset(e->d_end_totals, 0, 2 * 8));
-    RE_TRY(hipMalloc(&e->d_base, e->cap * 4));
-    RE_TRY(hipDeviceSynchronize());
+    MFM_RUN_TRY(hipMalloc(&e->d_ends, e->cap * re_record_bytes(stage)));
+    MFM_RUN_TRY(hipMalloc(&e->d_end_totals, 2 * 8));
+    MFM_RUN_TRY(hipMemset(e->d_end_totals, 0, 2 * 8));
+    MFM_RUN_TRY(hipMalloc(&e->d_base, e->cap * 4));
+    MFM_RUN_TRY(hipDeviceSynchronize());
     e->on = true;
     return MFM_OK;
 }
@@ -345,7 +298,7 @@ int mfm_internal_run_ends_process(MfmRunEnds *e, int stage, const MfmRunEndsCall
     } else {
         re_launch_process<mfm_runflex_state, mfm_runflex_end>(e, call, s);
     }
-    RE_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     return MFM_OK;
 }
 
@@ -358,20 +311,20 @@ int mfm_internal_run_ends_flush(MfmRunEnds *e, int stage, void *chan, uint64_t *
     } else {
         re_launch_flush<mfm_runflex_state, mfm_runflex_end>(e, chan, totals, bch, C, s);
     }
-    RE_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     return MFM_OK;
 }
 
 int mfm_internal_run_ends_fetch(MfmRunEnds *e, int stage, void *out, size_t max, size_t *nr)
 {
     uint64_t t[2];
-    RE_TRY(hipMemcpy(t, e->d_end_totals, sizeof(t), hipMemcpyDeviceToHost));
+    MFM_RUN_TRY(hipMemcpy(t, e->d_end_totals, sizeof(t), hipMemcpyDeviceToHost));
     *nr = (size_t)t[0];
     if (t[0] > max) {
         return MFM_E_NOMEM;
     }
     if (t[0]) {
-        RE_TRY(hipMemcpy(out, e->d_ends, (size_t)t[0] * re_record_bytes(stage), hipMemcpyDeviceToHost));
+        MFM_RUN_TRY(hipMemcpy(out, e->d_ends, (size_t)t[0] * re_record_bytes(stage), hipMemcpyDeviceToHost));
     }
     return MFM_OK;
 }

@@ -1,15 +1,14 @@
 /*
  * mfm_runais.hip - the burst AIS stage: the runs the burst resampler left in its dense payload go through the AIS
  * demodulator (ais/ais_demod.c:114-258) on the device, one fresh demodulator per stretch.  See include/multifm_hip.h for the
- * boundary and the event format, mfm_runais.h for the segment layout, the slot bound and the checks of a run, and
- * mfm_ais.hip for the row stage whose bit-sliced correlator and RECEIVE step this file restates.
+ * boundary and the event format, mfm_runais.h for the segment layout and the slot bound, mfm_run_stage.h for the checks of a
+ * run, and mfm_ais.hip for the row stage whose bit-sliced correlator and RECEIVE step this file restates.
  *
  * The input is what mfm_runrs_device_view returns; how many runs and samples a call carries is read on the device, so the
  * host never waits and every launch is sized from the capacities fixed at create.
  *
- *   ra_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_runais_check_run) before anything of the
- *                      payload is read; exclusive scans of the runs' segment words, event slots and slicer workgroups (a
- *                      thread sums a stretch of runs, the waves scan by lane shifts, the 16 wave sums go through LDS); a
+ *   ra_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_run_check_run) before anything of the
+ *                      payload is read; exclusive scans of the runs' segment words, event slots and slicer workgroups; a
  *                      channel's last run leaves its index for the state kernel; the totals and the flags.
  *   ra_slice_kernel    payload int16 -> 1 bit per sample.  A workgroup takes 256 words of one run's segment, which it finds
  *                      from its index by binary search in the scanned workgroup counts: the 8 history words (the channel's
@@ -29,19 +28,18 @@
  *                      go into the OTHER of two state buffers; a channel without a run, and every channel of a refused
  *                      call, copies its state over.
  *
- * Nothing is floating point and no atomic decides a placement (the packet bits of one RECEIVE step are OR-ed into LDS).
+ * Nothing is floating point and no atomic decides a placement (the packet bits of one RECEIVE step are OR-ed into LDS). The block scan, a thread's slice of the runs, the plan's head, the count scan and
+ * the word copy of the compaction, and the host code around a call are mfm_run_stage.h's, shared with the other burst stages.
  */
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/multifm_hip.h"
 
-extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_run_bits.h"
 #include "mfm_run_ends.h"
 #include "mfm_runais.h"
@@ -52,17 +50,13 @@ static_assert(sizeof(mfm_runais_state) == 264 && offsetof(mfm_runais_state, pack
 
 namespace {
 
-constexpr uint32_t RA_SCAN_THREADS = 1024;
 constexpr uint32_t RA_SLICE_NT = MFM_RUN_BITS_SLICE_NT;         /* slicer: threads = segment words per workgroup */
-constexpr uint32_t RA_NONE = 0xffffffffu;     /* d_chan_last: the channel has no run in this call */
-constexpr uint32_t RA_T_EVENTS = 0, RA_T_RUNS = 1, RA_T_OVERFLOW = 2, RA_T_INPUT = 3; /* d_totals[] */
-constexpr uint32_t RA_RS_RUNS = 0, RA_RS_ELEMS = 1, RA_RS_OVERFLOW = 2, RA_RS_GATE = 3; /* the resampler's */
+constexpr uint32_t RA_T_EVENTS = 0, RA_T_RUNS = 1; /* d_totals[], in front of MFM_RUN_T_OVERFLOW and MFM_RUN_T_INPUT */
 constexpr uint32_t RA_PREAMBLE = 0x5555557eu; /* ais_demod.c:136 */
 constexpr uint32_t RA_SLOW_SPAN = 165;        /* samples after a reset during which M differs from the free-running map */
 constexpr uint32_t RA_MAX_BITS = 5 * 256;     /* ais_demod.c:186 */
 constexpr uint32_t RA_PACKET_WORDS = RA_MAX_BITS / 32;
 constexpr uint32_t RA_STATE_WORDS = sizeof(mfm_runais_state) / 4, RA_TAIL_WORD0 = offsetof(mfm_runais_state, tail) / 4;
-constexpr uint64_t RA_MAX_RUNS = 1ull << 28, RA_MAX_OUT = 1ull << 31; /* per call: segment words and slots stay below 2^32 */
 
 /* ---- bit-sliced preamble correlator, after ai_q32 and ai_m32 of mfm_ais.hip ----------------------------------------------- */
 
@@ -152,67 +146,21 @@ struct RaCall {
     uint32_t C, cap_runs, cap_out, cap_events;
 };
 
-/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
-__device__ __forceinline__ uint64_t ra_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void ra_plan_kernel(const RaCall A)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
-        if (lane >= (uint32_t)o) {
-            inc += ((uint64_t)hi << 32) | lo;
-        }
-    }
-    if (lane == 63) {
-        lds[wave] = inc;
-    }
-    __syncthreads();
-    uint64_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < RA_SCAN_THREADS / 64; i++) {
-        const uint64_t t = lds[i];
-        base += i < wave ? t : 0u;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(RA_SCAN_THREADS) void ra_plan_kernel(const RaCall A)
-{
-    __shared__ uint64_t lds[RA_SCAN_THREADS / 64];
-    const uint64_t n = A.rtotals[RA_RS_RUNS], E = A.rtotals[RA_RS_ELEMS];
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
     const bool words = A.bits != nullptr; /* E and out_offset count words of the bits payload */
-    uint64_t over = 0, err = 0;
-    if (A.rtotals[RA_RS_OVERFLOW] || A.rtotals[RA_RS_GATE]) {
-        err = MFM_RUNAIS_IN_RUNRS;
-    } else if (E > (words ? (uint64_t)A.cap_out / 32u + A.cap_runs : (uint64_t)A.cap_out)) {
-        err = MFM_RUNAIS_IN_BAD_RUNS;
-    } else if (n > A.cap_runs) {
-        over = MFM_RUNAIS_OVER_RUNS;
+    uint64_t n, E, over, err, r0, r1;
+    if (!mfm_run_plan_head(A.rtotals, words ? (uint64_t)A.cap_out / 32u + A.cap_runs : (uint64_t)A.cap_out, A.cap_runs, A.totals, A.ctl, 2, &n, &E, &over, &err)) {
+        return; /* nothing may be read */
     }
-    if (over || err) { /* nothing may be read */
-        if (threadIdx.x == 0) {
-            A.totals[RA_T_EVENTS] = 0;
-            A.totals[RA_T_RUNS] = 0;
-            A.totals[RA_T_OVERFLOW] = over;
-            A.totals[RA_T_INPUT] = err;
-            A.ctl[0] = 0;
-            A.ctl[1] = 0;
-        }
-        return;
-    }
-    const uint64_t per = (n + RA_SCAN_THREADS - 1) / RA_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    mfm_run_slice(n, &r0, &r1);
     uint64_t so = 0, sw = 0, ss = 0, sb = 0;
     uint32_t bad = 0;
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         const mfm_runrs_run run = A.runs[r];
-        bad |= mfm_runais_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old, words);
+        bad |= mfm_run_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old, words);
         const uint32_t w = mfm_runais_seg_words(run.nr_out);
         so += run.nr_out;
         sw += w;
@@ -221,11 +169,11 @@ __global__ __launch_bounds__(RA_SCAN_THREADS) void ra_plan_kernel(const RaCall A
     }
     /* fewer than 2^31 runs of fewer than 2^32 outputs: every sum stays below 2^63 */
     uint64_t to, tws, tb;
-    (void)ra_block_scan(so, lds, &to);
+    (void)mfm_run_block_scan(so, lds, &to);
     /* a call that is not refused has fewer than 2^32 segment words and fewer than 2^32 slots (ra_geometry): they share a scan */
-    const uint64_t bws = ra_block_scan((sw & 0xffffffffull) | (ss << 32), lds, &tws);
+    const uint64_t bws = mfm_run_block_scan((sw & 0xffffffffull) | (ss << 32), lds, &tws);
     uint64_t bw = bws & 0xffffffffull, bs = bws >> 32, ts = tws >> 32;
-    uint64_t bb = ra_block_scan(sb, lds, &tb);
+    uint64_t bb = mfm_run_block_scan(sb, lds, &tb);
     if (__syncthreads_or((bad & MFM_RUNAIS_IN_OUT_OF_STEP) != 0)) {
         err |= MFM_RUNAIS_IN_OUT_OF_STEP;
     }
@@ -256,8 +204,8 @@ __global__ __launch_bounds__(RA_SCAN_THREADS) void ra_plan_kernel(const RaCall A
     if (threadIdx.x == 0) {
         A.totals[RA_T_EVENTS] = 0; /* the event scan */
         A.totals[RA_T_RUNS] = refused ? 0u : n;
-        A.totals[RA_T_OVERFLOW] = over;
-        A.totals[RA_T_INPUT] = err;
+        A.totals[MFM_RUN_T_OVERFLOW] = over;
+        A.totals[MFM_RUN_T_INPUT] = err;
         if (!refused) {
             A.blk_base[n] = (uint32_t)tb;
         }
@@ -535,25 +483,11 @@ __global__ __launch_bounds__(64) void ra_walk_kernel(const RaCall A)
     }
 }
 
-__global__ __launch_bounds__(RA_SCAN_THREADS) void ra_evscan_kernel(const RaCall A)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void ra_evscan_kernel(const RaCall A)
 {
-    __shared__ uint64_t lds[RA_SCAN_THREADS / 64];
-    const uint64_t n = A.ctl[1]; /* 0 for a refused call */
-    const uint64_t per = (n + RA_SCAN_THREADS - 1) / RA_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
-    uint64_t s = 0;
-#pragma unroll 1
-    for (uint64_t r = r0; r < r1; r++) {
-        s += A.count[r];
-    }
-    uint64_t total;
-    uint64_t base = ra_block_scan(s, lds, &total); /* at most the sum of the slots: within cap_events */
-#pragma unroll 1
-    for (uint64_t r = r0; r < r1; r++) {
-        A.ev_base[r] = (uint32_t)base;
-        base += A.count[r];
-    }
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
+    /* 0 runs for a refused call; the total is at most the sum of the slots: within cap_events */
+    const uint64_t total = mfm_run_count_scan(A.count, A.ev_base, A.ctl[1], lds);
     if (threadIdx.x == 0) {
         A.totals[RA_T_EVENTS] = total;
     }
@@ -568,9 +502,7 @@ __global__ __launch_bounds__(64) void ra_compact_kernel(const RaCall A)
     constexpr uint32_t EW = sizeof(mfm_runais_event) / 4;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(A.slots + A.slot_base[r]);
     uint32_t *dst = reinterpret_cast<uint32_t *>(A.events + A.ev_base[r]);
-    for (uint32_t i = threadIdx.x; i < A.count[r] * EW; i += blockDim.x) {
-        dst[i] = src[i];
-    }
+    mfm_run_copy_words(src, dst, &A.count[r], EW);
 }
 
 __global__ __launch_bounds__(64) void ra_state_kernel(const RaCall A)
@@ -579,13 +511,13 @@ __global__ __launch_bounds__(64) void ra_state_kernel(const RaCall A)
     const uint32_t c = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) {
         s_last = A.chan_last[c];
-        A.chan_last[c] = RA_NONE; /* for the next call */
+        A.chan_last[c] = MFM_RUN_NONE; /* for the next call */
     }
     __syncthreads();
     const uint32_t last = s_last;
-    const bool refused = A.totals[RA_T_OVERFLOW] != 0 || A.totals[RA_T_INPUT] != 0;
+    const bool refused = A.totals[MFM_RUN_T_OVERFLOW] != 0 || A.totals[MFM_RUN_T_INPUT] != 0;
     uint32_t *nw = reinterpret_cast<uint32_t *>(&A.chan_new[c]);
-    if (last == RA_NONE || refused) { /* the state stays */
+    if (last == MFM_RUN_NONE || refused) { /* the state stays */
         const uint32_t *old = reinterpret_cast<const uint32_t *>(&A.chan_old[c]);
         for (uint32_t i = tid; i < RA_STATE_WORDS; i += blockDim.x) {
             nw[i] = old[i];
@@ -600,29 +532,12 @@ __global__ __launch_bounds__(64) void ra_state_kernel(const RaCall A)
     }
 }
 
-thread_local char g_ra_error[256] = "";
-
-int ra_fail(int code, const char *msg)
-{
-    snprintf(g_ra_error, sizeof(g_ra_error), "%s", msg);
-    mfm_internal_set_error(g_ra_error);
-    return code;
-}
-
 /* what create checks without a device; the capacities with the default filled in */
 int ra_geometry(const mfm_runais_config &cfg, uint64_t *cap_events)
 {
-    if (cfg.abi_version != MFM_ABI_VERSION) {
-        return ra_fail(MFM_E_INVAL, "abi_version is not MFM_ABI_VERSION");
-    }
-    if (0 == cfg.nr_channels) {
-        return ra_fail(MFM_E_INVAL, "nr_channels must be at least 1");
-    }
-    if (0 == cfg.max_runs || 0 == cfg.max_out_samples || cfg.max_runs >= RA_MAX_RUNS || cfg.max_out_samples >= RA_MAX_OUT) {
-        return ra_fail(MFM_E_INVAL, "max_runs must be 1 .. 2^28 - 1 and max_out_samples 1 .. 2^31 - 1: the burst resampler's capacities (mfm_runrs_get_capacity)");
-    }
-    if (cfg.flags != 0) {
-        return ra_fail(MFM_E_INVAL, "flags must be 0");
+    const int rc = mfm_run_geometry(cfg);
+    if (rc != MFM_OK) {
+        return rc;
     }
     *cap_events = cfg.max_events ? cfg.max_events : (uint64_t)cfg.max_out_samples / MFM_RUNAIS_MIN_SPACING + cfg.max_runs;
     return MFM_OK;
@@ -631,32 +546,10 @@ int ra_geometry(const mfm_runais_config &cfg, uint64_t *cap_events)
 /* the message of a refused call, as fetch and the host twin give it */
 const char *ra_refusal(uint64_t over, uint64_t err)
 {
-    if (err & MFM_RUNAIS_IN_RUNRS) {
-        return "the burst resampler's call raised overflow or gate error";
-    }
-    if (err & MFM_RUNAIS_IN_BAD_RUNS) {
-        return "the run list is not a burst resampler's: a run names a channel or an output range that does not exist, or more than max_out_samples";
-    }
-    if (err & MFM_RUNAIS_IN_OUT_OF_STEP) {
-        return "out of step with the burst resampler: a continuing run does not follow on its channel's stretch";
-    }
-    if (over & MFM_RUNAIS_OVER_RUNS) {
-        return "the call has more runs than max_runs";
-    }
-    return "the call's event bound (the sum of nr_out / 160 + 1 over its runs) exceeds max_events";
+    return mfm_run_refusal(over, err, "the call's event bound (the sum of nr_out / 160 + 1 over its runs) exceeds max_events");
 }
 
 } /* namespace */
-
-#define RA_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t err_ = (expr);                                                                            \
-        if (err_ != hipSuccess) {                                                                            \
-            snprintf(g_ra_error, sizeof(g_ra_error), "%s failed: %s", #expr, hipGetErrorString(err_));       \
-            mfm_internal_set_error(g_ra_error);                                                              \
-            return err_ == hipErrorOutOfMemory ? MFM_E_NOMEM : MFM_E_DEVICE;                                 \
-        }                                                                                                    \
-    } while (0)
 
 struct mfm_runais {
     mfm_runais_config cfg{};
@@ -701,27 +594,27 @@ int mfm_runais_create(struct mfm_runais **pa, const struct mfm_runais_config *cf
     a->seg_words = (uint64_t)cfg->max_out_samples / 32u + 10ull * nruns;
     a->max_blocks = a->seg_words / RA_SLICE_NT + nruns;
     *pa = a; /* from here on the caller's destroy frees what was allocated */
-    RA_TRY(hipSetDevice(cfg->device));
+    MFM_RUN_TRY(hipSetDevice(cfg->device));
     for (int i = 0; i < 2; i++) {
-        RA_TRY(hipMalloc(&a->d_chan[i], C * sizeof(mfm_runais_state)));
-        RA_TRY(hipMemset(a->d_chan[i], 0, C * sizeof(mfm_runais_state))); /* no stretch */
+        MFM_RUN_TRY(hipMalloc(&a->d_chan[i], C * sizeof(mfm_runais_state)));
+        MFM_RUN_TRY(hipMemset(a->d_chan[i], 0, C * sizeof(mfm_runais_state))); /* no stretch */
     }
-    RA_TRY(hipMalloc(&a->d_run_state, nruns * sizeof(mfm_runais_state)));
-    RA_TRY(hipMalloc(&a->d_seg, (size_t)a->seg_words * 4));
-    RA_TRY(hipMalloc(&a->d_seg_base, nruns * 4));
-    RA_TRY(hipMalloc(&a->d_slot_base, nruns * 4));
-    RA_TRY(hipMalloc(&a->d_blk_base, (nruns + 1) * 4));
-    RA_TRY(hipMalloc(&a->d_count, nruns * 4));
-    RA_TRY(hipMalloc(&a->d_ev_base, nruns * 4));
-    RA_TRY(hipMalloc(&a->d_chan_last, C * 4));
-    RA_TRY(hipMemset(a->d_chan_last, 0xff, C * 4));
-    RA_TRY(hipMalloc(&a->d_ctl, 2 * 4));
-    RA_TRY(hipMemset(a->d_ctl, 0, 2 * 4));
-    RA_TRY(hipMalloc(&a->d_totals, 4 * 8));
-    RA_TRY(hipMemset(a->d_totals, 0, 4 * 8));
-    RA_TRY(hipMalloc(&a->d_slots, (size_t)cap_events * sizeof(mfm_runais_event)));
-    RA_TRY(hipMalloc(&a->d_events, (size_t)cap_events * sizeof(mfm_runais_event)));
-    RA_TRY(hipDeviceSynchronize());
+    MFM_RUN_TRY(hipMalloc(&a->d_run_state, nruns * sizeof(mfm_runais_state)));
+    MFM_RUN_TRY(hipMalloc(&a->d_seg, (size_t)a->seg_words * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_seg_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_slot_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_blk_base, (nruns + 1) * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_count, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_ev_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_chan_last, C * 4));
+    MFM_RUN_TRY(hipMemset(a->d_chan_last, 0xff, C * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_ctl, 2 * 4));
+    MFM_RUN_TRY(hipMemset(a->d_ctl, 0, 2 * 4));
+    MFM_RUN_TRY(hipMalloc(&a->d_totals, 4 * 8));
+    MFM_RUN_TRY(hipMemset(a->d_totals, 0, 4 * 8));
+    MFM_RUN_TRY(hipMalloc(&a->d_slots, (size_t)cap_events * sizeof(mfm_runais_event)));
+    MFM_RUN_TRY(hipMalloc(&a->d_events, (size_t)cap_events * sizeof(mfm_runais_event)));
+    MFM_RUN_TRY(hipDeviceSynchronize());
     return MFM_OK;
 }
 
@@ -763,34 +656,34 @@ int ra_process(mfm_runais *a, const mfm_runrs_run *d_runs, const int16_t *d_payl
         return MFM_E_INVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RA_TRY(hipSetDevice(a->cfg.device));
-    if (a->have_call && a->last_stream != s) {
-        RA_TRY(hipStreamSynchronize(a->last_stream)); /* state lives on the device; keep calls ordered */
+    const int rb = mfm_run_call_begin(a, s);
+    if (rb != MFM_OK) {
+        return rb;
     }
     const uint32_t cur = a->cur;
     const RaCall A{ d_runs,        d_payload,      d_bits,         d_totals,       a->d_chan[cur], a->d_chan[cur ^ 1u], a->d_run_state,
                     a->d_seg,      a->d_seg_base,  a->d_slot_base, a->d_blk_base,  a->d_count,          a->d_ev_base,
                     a->d_chan_last, a->d_ctl,      a->d_totals,    a->d_slots,     a->d_events,         a->cfg.nr_channels,
                     a->cfg.max_runs, a->cfg.max_out_samples, (uint32_t)a->cap_events };
-    hipLaunchKernelGGL(ra_plan_kernel, dim3(1), dim3(RA_SCAN_THREADS), 0, s, A);
-    RA_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ra_plan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     if (d_bits) { /* the word copy of mfm_run_bits.hip in the place of the slicer */
         const mfm_run_bits_slice B{ d_runs, d_bits, reinterpret_cast<const uint32_t *>(a->d_chan[cur]), a->d_blk_base, a->d_seg_base, a->d_ctl,
                                     a->d_seg, RA_STATE_WORDS, RA_TAIL_WORD0, MFM_RUNAIS_HIST_WORDS };
         if (mfm_internal_run_bits_slice(&B, (uint32_t)a->max_blocks, s) != MFM_OK) {
-            RA_TRY(hipGetLastError());
+            MFM_RUN_TRY(hipGetLastError());
             return MFM_E_DEVICE;
         }
     } else {
         hipLaunchKernelGGL(ra_slice_kernel, dim3((uint32_t)a->max_blocks), dim3(RA_SLICE_NT), 0, s, A);
-        RA_TRY(hipGetLastError());
+        MFM_RUN_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(ra_walk_kernel, dim3(a->cfg.max_runs), dim3(64), 0, s, A);
-    RA_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ra_evscan_kernel, dim3(1), dim3(RA_SCAN_THREADS), 0, s, A);
-    RA_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ra_evscan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(ra_compact_kernel, dim3(a->cfg.max_runs), dim3(64), 0, s, A);
-    RA_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     if (a->ends.on) { /* behind the walk, in front of the state kernel */
         const MfmRunEndsCall E{ d_runs, a->d_chan[cur], a->d_run_state, a->d_ctl, nullptr, a->cfg.nr_channels, a->cfg.max_runs };
         const int re = mfm_internal_run_ends_process(&a->ends, MFM_RUN_ENDS_AIS, &E, s);
@@ -799,10 +692,8 @@ int ra_process(mfm_runais *a, const mfm_runrs_run *d_runs, const int16_t *d_payl
         }
     }
     hipLaunchKernelGGL(ra_state_kernel, dim3(a->cfg.nr_channels), dim3(64), 0, s, A);
-    RA_TRY(hipGetLastError());
-    a->cur ^= 1u;
-    a->last_stream = s;
-    a->have_call = true;
+    MFM_RUN_TRY(hipGetLastError());
+    mfm_run_call_end(a, s);
     return MFM_OK;
 }
 
@@ -825,7 +716,7 @@ int mfm_runais_process_bits_device(struct mfm_runais *a, const struct mfm_runrs_
         return MFM_E_INVAL;
     }
     if (view->polarity != MFM_BITS_POS) {
-        return ra_fail(MFM_E_INVAL, "the burst AIS stage needs MFM_BITS_POS bits (bit = sample > 0)");
+        return mfm_run_fail(MFM_E_INVAL, "the burst AIS stage needs MFM_BITS_POS bits (bit = sample > 0)");
     }
     return ra_process(a, view->d_runs, nullptr, view->d_bits, view->d_totals, stream);
 }
@@ -839,19 +730,19 @@ int mfm_runais_fetch(struct mfm_runais *a, struct mfm_runais_event *events, size
     if (!a->have_call) {
         return MFM_OK;
     }
-    RA_TRY(hipSetDevice(a->cfg.device));
-    RA_TRY(hipStreamSynchronize(a->last_stream));
+    MFM_RUN_TRY(hipSetDevice(a->cfg.device));
+    MFM_RUN_TRY(hipStreamSynchronize(a->last_stream));
     uint64_t t[4];
-    RA_TRY(hipMemcpy(t, a->d_totals, sizeof(t), hipMemcpyDeviceToHost));
-    if (t[RA_T_OVERFLOW] || t[RA_T_INPUT]) {
-        return ra_fail(MFM_E_STATE, ra_refusal(t[RA_T_OVERFLOW], t[RA_T_INPUT]));
+    MFM_RUN_TRY(hipMemcpy(t, a->d_totals, sizeof(t), hipMemcpyDeviceToHost));
+    if (t[MFM_RUN_T_OVERFLOW] || t[MFM_RUN_T_INPUT]) {
+        return mfm_run_fail(MFM_E_STATE, ra_refusal(t[MFM_RUN_T_OVERFLOW], t[MFM_RUN_T_INPUT]));
     }
     *nr_events = (size_t)t[RA_T_EVENTS];
     if (t[RA_T_EVENTS] > max_events) {
         return MFM_E_NOMEM;
     }
     if (t[RA_T_EVENTS]) {
-        RA_TRY(hipMemcpy(events, a->d_events, (size_t)t[RA_T_EVENTS] * sizeof(mfm_runais_event), hipMemcpyDeviceToHost));
+        MFM_RUN_TRY(hipMemcpy(events, a->d_events, (size_t)t[RA_T_EVENTS] * sizeof(mfm_runais_event), hipMemcpyDeviceToHost));
     }
     return MFM_OK;
 }
@@ -872,69 +763,39 @@ int mfm_runais_device_view(struct mfm_runais *a, const struct mfm_runais_event *
 
 int mfm_hosttwin_runais_state_check(uint32_t nr_channels, const struct mfm_runais_state *state)
 {
-    if (!state || !nr_channels) {
-        return MFM_E_INVAL;
-    }
-    for (uint32_t c = 0; c < nr_channels; c++) {
-        if (const char *why = mfm_runais_state_check(state[c])) {
-            char msg[224];
-            snprintf(msg, sizeof(msg), "burst AIS state, channel %u: %s", c, why);
-            return ra_fail(MFM_E_INVAL, msg);
-        }
-    }
-    return MFM_OK;
+    return mfm_run_state_check(nr_channels, state, "AIS", mfm_runais_state_check);
 }
 
 int mfm_runais_fetch_state(struct mfm_runais *a, struct mfm_runais_state *state, size_t nr_channels)
 {
-    if (!a || !state || nr_channels != a->cfg.nr_channels) {
-        return MFM_E_INVAL;
-    }
-    RA_TRY(hipSetDevice(a->cfg.device));
-    if (a->have_call) {
-        RA_TRY(hipStreamSynchronize(a->last_stream));
-    }
-    RA_TRY(hipMemcpy(state, a->d_chan[a->cur], nr_channels * sizeof(mfm_runais_state), hipMemcpyDeviceToHost));
-    return MFM_OK;
+    return mfm_run_fetch_state(a, state, nr_channels);
 }
 
 int mfm_runais_store_state(struct mfm_runais *a, const struct mfm_runais_state *state, size_t nr_channels)
 {
-    if (!a || !state || nr_channels != a->cfg.nr_channels) {
-        return MFM_E_INVAL;
-    }
-    const int ok = mfm_hosttwin_runais_state_check(a->cfg.nr_channels, state);
-    if (ok != MFM_OK) {
-        return ok;
-    }
-    RA_TRY(hipSetDevice(a->cfg.device));
-    if (a->have_call) {
-        RA_TRY(hipStreamSynchronize(a->last_stream));
-    }
-    RA_TRY(hipMemcpy(a->d_chan[a->cur], state, nr_channels * sizeof(mfm_runais_state), hipMemcpyHostToDevice));
-    return MFM_OK;
+    return mfm_run_store_state(a, state, nr_channels, mfm_hosttwin_runais_state_check);
 }
 
 /* ---- the stretch-end report: kernels and launchers in mfm_run_ends.hip ---- */
 
 int mfm_runais_set_end_report(struct mfm_runais *a, int on)
 {
-    return mfm_run_ends_entry_set(a, MFM_RUN_ENDS_AIS, on, ra_fail);
+    return mfm_run_ends_entry_set(a, MFM_RUN_ENDS_AIS, on, mfm_run_fail);
 }
 
 int mfm_runais_end_stretches_device(struct mfm_runais *a, void *stream)
 {
-    return mfm_run_ends_entry_flush(a, MFM_RUN_ENDS_AIS, nullptr, stream, ra_fail);
+    return mfm_run_ends_entry_flush(a, MFM_RUN_ENDS_AIS, nullptr, stream, mfm_run_fail);
 }
 
 int mfm_runais_fetch_ends(struct mfm_runais *a, struct mfm_runais_end *ends, size_t max_ends, size_t *nr_ends)
 {
-    return mfm_run_ends_entry_fetch(a, MFM_RUN_ENDS_AIS, ends, max_ends, nr_ends, ra_fail, ra_refusal);
+    return mfm_run_ends_entry_fetch(a, MFM_RUN_ENDS_AIS, ends, max_ends, nr_ends, mfm_run_fail, ra_refusal);
 }
 
 int mfm_runais_ends_view(struct mfm_runais *a, const struct mfm_runais_end **d_ends, const uint64_t **d_end_totals)
 {
-    return mfm_run_ends_entry_view(a, d_ends, d_end_totals, ra_fail);
+    return mfm_run_ends_entry_view(a, d_ends, d_end_totals, mfm_run_fail);
 }
 
 } /* extern "C" */
@@ -1091,38 +952,16 @@ int ra_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_sampl
     if (rc != MFM_OK) {
         return rc;
     }
-    /* the plan pass */
-    const uint64_t n = totals[RA_RS_RUNS], E = totals[RA_RS_ELEMS];
-    uint64_t over = 0, err = 0;
-    if (totals[RA_RS_OVERFLOW] || totals[RA_RS_GATE]) {
-        err = MFM_RUNAIS_IN_RUNRS;
-    } else if (E > (words ? (uint64_t)max_out_samples / 32u + max_runs : (uint64_t)max_out_samples)) {
-        err = MFM_RUNAIS_IN_BAD_RUNS;
-    } else if (n > max_runs) {
-        over = MFM_RUNAIS_OVER_RUNS;
+    uint64_t n, over, err, ts = 0; /* the plan pass */
+    if (!mfm_run_twin_plan(totals, nr_channels, max_runs, max_out_samples, state, runs, words ? (const void *)bits : (const void *)payload, words,
+                           [&](uint32_t nr_out) { ts += mfm_runais_slots(nr_out); }, &n, &over, &err)) {
+        return MFM_E_INVAL;
     }
-    if (!over && !err) {
-        if ((n && !runs) || (E && !(words ? (const void *)bits : (const void *)payload))) {
-            return MFM_E_INVAL;
-        }
-        uint64_t to = 0, ts = 0;
-        for (uint64_t r = 0; r < n; r++) {
-            err |= mfm_runais_check_run(runs[r], r ? &runs[r - 1] : nullptr, nr_channels, E, state, words);
-            to += runs[r].nr_out;
-            ts += mfm_runais_slots(runs[r].nr_out);
-        }
-        if (to > max_out_samples) {
-            err |= MFM_RUNAIS_IN_BAD_RUNS;
-        }
-        if (!err && ts > cap_events) {
-            over = MFM_RUNAIS_OVER_EVENTS;
-        }
+    if (!err && ts > cap_events) {
+        over = MFM_RUNAIS_OVER_EVENTS;
     }
     if (over || err) {
-        if (flags) {
-            *flags = (uint32_t)(over | (err << 8));
-        }
-        return ra_fail(MFM_E_STATE, ra_refusal(over, err));
+        return mfm_run_twin_refuse(over, err, flags, ra_refusal(over, err));
     }
     /* every run from the state the call started with (only a channel's first run reads it); the state its last run leaves */
     std::vector<mfm_runais_event> out;
@@ -1215,7 +1054,7 @@ int mfm_hosttwin_runais_call_bits(uint32_t nr_channels, uint32_t max_runs, uint3
                                   uint32_t *flags)
 {
     if (polarity != MFM_BITS_POS) {
-        return ra_fail(MFM_E_INVAL, "the burst AIS stage needs MFM_BITS_POS bits (bit = sample > 0)");
+        return mfm_run_fail(MFM_E_INVAL, "the burst AIS stage needs MFM_BITS_POS bits (bit = sample > 0)");
     }
     return ra_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, nullptr, bits, true, totals, events, max_out,
                         nr_events, flags);

@@ -1,8 +1,8 @@
 /*
  * mfm_runflex.h - what the kernels of the burst FLEX stage (mfm_runflex_*, include/multifm_hip.h) and its host twin
  * (mfm_hosttwin_runflex_call) must state once: the layout of a run's bit segment, where a PCM sample of a stretch lives, a
- * run's share of the event and frame slots, the checks a run has to pass before anything of the payload is read, the coding
- * table and the 4-level slicer, and the canonical form of the state a run leaves.
+ * run's share of the event and frame slots, the coding table and the 4-level slicer, and the canonical form of the state a run
+ * leaves.  The checks a run has to pass before anything of the payload is read are mfm_run_stage.h's.
  *
  * A run's segment is MFM_RUNFLEX_HIST_WORDS words of history, then its nr_out sample bits (bit = sample >= 0), then one word
  * of padding: segment bit 320 + j is output j of the run, i.e. stretch sample first_out + j.  The history is the sign of the
@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "../../include/multifm_hip.h"
+#include "mfm_run_stage.h"
 
 #define MFM_RUNFLEX_HIST_WORDS 10u  /* 310 samples of register history, whole words */
 #define MFM_RUNFLEX_HIST_BITS (32u * MFM_RUNFLEX_HIST_WORDS)
@@ -41,10 +42,6 @@
 #define MFM_RUNFLEX_FRAME_SPACING 29985u /* samples between two FRAME events of a stretch at least */
 
 enum { MFM_RUNFLEX_SEARCH = 0, MFM_RUNFLEX_SYNC1 = 1, MFM_RUNFLEX_FRAME = 2 };
-
-#ifndef MFM_RUN_POS_LIMIT
-#define MFM_RUN_POS_LIMIT (1ull << 62) /* positions a stored state may hold stay below this, as the seek entries demand */
-#endif
 
 #define MFM_RUNFLEX_SYNC1_WAIT 1120u  /* SYNC1 waits while j + (1 .. 10) + 1110 >= outs: j is at most this far behind outs */
 #define MFM_RUNFLEX_FRAME_WAIT 28562u /* FRAME waits while the last block symbol, at most this far behind j, is >= outs */
@@ -136,26 +133,6 @@ __host__ __device__ inline uint32_t mfm_runflex_event_slots(uint32_t nr_out)
 __host__ __device__ inline uint32_t mfm_runflex_frame_slots(uint32_t nr_out)
 {
     return nr_out / MFM_RUNFLEX_FRAME_SPACING + 1u;
-}
-
-/*
- * The input-error flags of run `run` (0: it may be read).  prev: the run in front of it in the list (NULL for the first),
- * nr_elems: the resampler's total of output elements, state: the per-channel state the call started from.
- */
-__host__ __device__ inline uint32_t mfm_runflex_check_run(const mfm_runrs_run &run, const mfm_runrs_run *prev, uint32_t nr_channels,
-                                                          uint64_t nr_elems, const mfm_runflex_state *state)
-{
-    if (run.channel >= nr_channels || (prev && prev->channel > run.channel) || run.out_offset > nr_elems ||
-        run.nr_out > nr_elems - run.out_offset) {
-        return MFM_RUNFLEX_IN_BAD_RUNS;
-    }
-    if (run.flags & MFM_RUNRS_BEGINS) {
-        return run.first_out != 0 ? MFM_RUNFLEX_IN_BAD_RUNS : 0u;
-    }
-    /* only a channel's first run of a call can continue: a later one has a closed window in front of it */
-    const bool first = !prev || prev->channel != run.channel;
-    const mfm_runflex_state &st = state[run.channel];
-    return first && st.has_stretch && st.outs == run.first_out ? 0u : MFM_RUNFLEX_IN_OUT_OF_STEP;
 }
 
 /* _pager_codings[] (pager_flex.c:46-96) as mfm_flex.hip's fx_codings states it, in selects: no table, so host and device share

@@ -2,13 +2,13 @@
  * mfm_runflex.hip - the burst FLEX stage: the runs the burst resampler left in its dense payload go through the FLEX front
  * half (pager/pager_flex.c:129-171,264-525,1200-1345,1401-1455) on the device, one fresh decoder per stretch.  See
  * include/multifm_hip.h for the boundary and the event format, mfm_runflex.h for the segment layout, the ring, the slot
- * bounds and the checks of a run, and mfm_flex.hip for the row stage whose match words, walk from event to event and frame
+ * bounds, mfm_run_stage.h for the checks of a run, and mfm_flex.hip for the row stage whose match words, walk from event to event and frame
  * gather this file restates on ragged runs.
  *
  * The input is what mfm_runrs_device_view returns; how many runs and samples a call carries is read on the device, so the
  * host never waits and every launch is sized from the capacities fixed at create.
  *
- *   rf_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_runflex_check_run) before anything of
+ *   rf_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_run_check_run) before anything of
  *                      the payload is read; exclusive scans of the runs' segment words, event slots, frame slots and slicer
  *                      workgroups; a channel's last run leaves its index for the ring and state kernels; the totals and flags.
  *   rf_slice_kernel    PCM int16 -> 1 bit per sample (sample >= 0).  A workgroup takes 256 words of one run's segment, which
@@ -30,19 +30,18 @@
  *   rf_state_kernel    one block per channel: the record of the channel's last run goes into the OTHER of two state buffers;
  *                      a channel without a run, and every channel of a refused call, copies its state over.
  *
- * Nothing is floating point and no atomic decides a placement.
+ * Nothing is floating point and no atomic decides a placement.  The block scan, a thread's slice of the runs, the plan's head and the
+ * host code around a call are mfm_run_stage.h's, shared with the other burst stages.
  */
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/multifm_hip.h"
 
-extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_bch.h"
 #include "mfm_run_ends.h"
 #include "mfm_runflex.h"
@@ -54,16 +53,12 @@ static_assert(sizeof(mfm_runflex_state) == 88 && offsetof(mfm_runflex_state, mod
 
 namespace {
 
-constexpr uint32_t RF_SCAN_THREADS = 1024;
 constexpr uint32_t RF_SLICE_NT = 256;         /* slicer: threads = segment words per workgroup */
 constexpr uint32_t RF_GATHER_THREADS = 256;
 constexpr uint32_t RF_RING_BLOCKS = 8;        /* workgroups per channel of the ring kernel */
-constexpr uint32_t RF_NONE = 0xffffffffu;     /* d_chan_last: the channel has no run in this call */
-constexpr uint32_t RF_T_EVENTS = 0, RF_T_FRAMES = 1, RF_T_OVERFLOW = 2, RF_T_INPUT = 3; /* d_totals[] */
-constexpr uint32_t RF_RS_RUNS = 0, RF_RS_ELEMS = 1, RF_RS_OVERFLOW = 2, RF_RS_GATE = 3; /* the resampler's */
+constexpr uint32_t RF_T_EVENTS = 0, RF_T_FRAMES = 1; /* d_totals[], in front of MFM_RUN_T_OVERFLOW and MFM_RUN_T_INPUT */
 constexpr uint32_t RF_HW = MFM_RUNFLEX_HIST_WORDS;
 constexpr uint32_t RF_STATE_WORDS = sizeof(mfm_runflex_state) / 4;
-constexpr uint64_t RF_MAX_RUNS = 1ull << 28, RF_MAX_OUT = 1ull << 31; /* per call: segment words and slots stay below 2^32 */
 
 /* a collected frame, as the walk leaves it for the gather kernel */
 struct RfFrameDesc {
@@ -111,66 +106,20 @@ __device__ __forceinline__ int rf_sample(const RfCall &A, const mfm_runrs_run &r
     return *(s >= run.first_out ? in_run : in_ring);
 }
 
-/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
-__device__ __forceinline__ uint64_t rf_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void rf_plan_kernel(const RfCall A)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
-        if (lane >= (uint32_t)o) {
-            inc += ((uint64_t)hi << 32) | lo;
-        }
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
+    uint64_t n, E, over, err, r0, r1;
+    if (!mfm_run_plan_head(A.rtotals, A.cap_out, A.cap_runs, A.totals, A.ctl, 2, &n, &E, &over, &err)) {
+        return; /* nothing may be read */
     }
-    if (lane == 63) {
-        lds[wave] = inc;
-    }
-    __syncthreads();
-    uint64_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < RF_SCAN_THREADS / 64; i++) {
-        const uint64_t t = lds[i];
-        base += i < wave ? t : 0u;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(RF_SCAN_THREADS) void rf_plan_kernel(const RfCall A)
-{
-    __shared__ uint64_t lds[RF_SCAN_THREADS / 64];
-    const uint64_t n = A.rtotals[RF_RS_RUNS], E = A.rtotals[RF_RS_ELEMS];
-    uint64_t over = 0, err = 0;
-    if (A.rtotals[RF_RS_OVERFLOW] || A.rtotals[RF_RS_GATE]) {
-        err = MFM_RUNFLEX_IN_RUNRS;
-    } else if (E > A.cap_out) {
-        err = MFM_RUNFLEX_IN_BAD_RUNS;
-    } else if (n > A.cap_runs) {
-        over = MFM_RUNFLEX_OVER_RUNS;
-    }
-    if (over || err) { /* nothing may be read */
-        if (threadIdx.x == 0) {
-            A.totals[RF_T_EVENTS] = 0;
-            A.totals[RF_T_FRAMES] = 0;
-            A.totals[RF_T_OVERFLOW] = over;
-            A.totals[RF_T_INPUT] = err;
-            A.ctl[0] = 0;
-            A.ctl[1] = 0;
-        }
-        return;
-    }
-    const uint64_t per = (n + RF_SCAN_THREADS - 1) / RF_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    mfm_run_slice(n, &r0, &r1);
     uint64_t so = 0, sw = 0, ss = 0, sf = 0, sb = 0;
     uint32_t bad = 0;
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         const mfm_runrs_run run = A.runs[r];
-        bad |= mfm_runflex_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old);
+        bad |= mfm_run_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old);
         const uint32_t w = mfm_runflex_seg_words(run.nr_out);
         so += run.nr_out;
         sw += w;
@@ -180,10 +129,10 @@ __global__ __launch_bounds__(RF_SCAN_THREADS) void rf_plan_kernel(const RfCall A
     }
     /* fewer than 2^28 runs of fewer than 2^32 outputs: every sum stays below 2^63 */
     uint64_t to, tws, tfb;
-    (void)rf_block_scan(so, lds, &to);
+    (void)mfm_run_block_scan(so, lds, &to);
     /* a call that is not refused has fewer than 2^32 segment words, slots and workgroups (rf_geometry): two share a scan */
-    const uint64_t bws = rf_block_scan((sw & 0xffffffffull) | (ss << 32), lds, &tws);
-    const uint64_t bfb = rf_block_scan((sf & 0xffffffffull) | (sb << 32), lds, &tfb);
+    const uint64_t bws = mfm_run_block_scan((sw & 0xffffffffull) | (ss << 32), lds, &tws);
+    const uint64_t bfb = mfm_run_block_scan((sf & 0xffffffffull) | (sb << 32), lds, &tfb);
     uint64_t bw = bws & 0xffffffffull, bs = bws >> 32, bf = bfb & 0xffffffffull, bb = bfb >> 32;
     const uint64_t ts = tws >> 32, tf = tfb & 0xffffffffull, tb = tfb >> 32;
     if (__syncthreads_or((bad & MFM_RUNFLEX_IN_OUT_OF_STEP) != 0)) {
@@ -218,8 +167,8 @@ __global__ __launch_bounds__(RF_SCAN_THREADS) void rf_plan_kernel(const RfCall A
     if (threadIdx.x == 0) {
         A.totals[RF_T_EVENTS] = 0; /* the event scan */
         A.totals[RF_T_FRAMES] = 0;
-        A.totals[RF_T_OVERFLOW] = over;
-        A.totals[RF_T_INPUT] = err;
+        A.totals[MFM_RUN_T_OVERFLOW] = over;
+        A.totals[MFM_RUN_T_INPUT] = err;
         if (!refused) {
             A.blk_base[n] = (uint32_t)tb;
         }
@@ -582,20 +531,18 @@ __global__ __launch_bounds__(64) void rf_walk_kernel(const RfCall A)
     }
 }
 
-__global__ __launch_bounds__(RF_SCAN_THREADS) void rf_evscan_kernel(const RfCall A)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void rf_evscan_kernel(const RfCall A)
 {
-    __shared__ uint64_t lds[RF_SCAN_THREADS / 64];
-    const uint64_t n = A.ctl[1]; /* 0 for a refused call */
-    const uint64_t per = (n + RF_SCAN_THREADS - 1) / RF_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
+    uint64_t r0, r1;
+    mfm_run_slice<uint64_t>(A.ctl[1], &r0, &r1); /* 0 runs for a refused call */
     uint64_t s = 0;
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         s += (uint64_t)A.count[2 * r] | ((uint64_t)A.count[2 * r + 1] << 32);
     }
     uint64_t total;
-    uint64_t base = rf_block_scan(s, lds, &total); /* at most the sums of the slots: within cap_events and cap_frames */
+    uint64_t base = mfm_run_block_scan(s, lds, &total); /* at most the sums of the slots: within cap_events and cap_frames */
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         A.ev_base[2 * r] = (uint32_t)base;
@@ -673,7 +620,7 @@ __global__ __launch_bounds__(256) void rf_ring_kernel(const RfCall A)
 {
     const uint32_t c = blockIdx.y;
     const uint32_t last = A.chan_last[c];
-    if (last == RF_NONE || A.totals[RF_T_OVERFLOW] != 0 || A.totals[RF_T_INPUT] != 0) {
+    if (last == MFM_RUN_NONE || A.totals[MFM_RUN_T_OVERFLOW] != 0 || A.totals[MFM_RUN_T_INPUT] != 0) {
         return; /* a refused call wrote no chan_last; the test on the totals states the rule */
     }
     const mfm_runrs_run run = A.runs[last];
@@ -690,40 +637,23 @@ __global__ __launch_bounds__(64) void rf_state_kernel(const RfCall A)
 {
     const uint32_t c = blockIdx.x, tid = threadIdx.x;
     const uint32_t last = A.chan_last[c];
-    const bool refused = A.totals[RF_T_OVERFLOW] != 0 || A.totals[RF_T_INPUT] != 0;
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(last == RF_NONE || refused ? &A.chan_old[c] : &A.run_state[last]);
+    const bool refused = A.totals[MFM_RUN_T_OVERFLOW] != 0 || A.totals[MFM_RUN_T_INPUT] != 0;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(last == MFM_RUN_NONE || refused ? &A.chan_old[c] : &A.run_state[last]);
     uint32_t *nw = reinterpret_cast<uint32_t *>(&A.chan_new[c]);
     if (tid < RF_STATE_WORDS) {
         nw[tid] = src[tid];
     }
     if (tid == 0) {
-        A.chan_last[c] = RF_NONE; /* for the next call */
+        A.chan_last[c] = MFM_RUN_NONE; /* for the next call */
     }
-}
-
-thread_local char g_rf_error[256] = "";
-
-int rf_fail(int code, const char *msg)
-{
-    snprintf(g_rf_error, sizeof(g_rf_error), "%s", msg);
-    mfm_internal_set_error(g_rf_error);
-    return code;
 }
 
 /* what create checks without a device; the capacities with the defaults filled in */
 int rf_geometry(const mfm_runflex_config &cfg, uint64_t *cap_events, uint64_t *cap_frames)
 {
-    if (cfg.abi_version != MFM_ABI_VERSION) {
-        return rf_fail(MFM_E_INVAL, "abi_version is not MFM_ABI_VERSION");
-    }
-    if (0 == cfg.nr_channels) {
-        return rf_fail(MFM_E_INVAL, "nr_channels must be at least 1");
-    }
-    if (0 == cfg.max_runs || 0 == cfg.max_out_samples || cfg.max_runs >= RF_MAX_RUNS || cfg.max_out_samples >= RF_MAX_OUT) {
-        return rf_fail(MFM_E_INVAL, "max_runs must be 1 .. 2^28 - 1 and max_out_samples 1 .. 2^31 - 1: the burst resampler's capacities (mfm_runrs_get_capacity)");
-    }
-    if (cfg.flags != 0) {
-        return rf_fail(MFM_E_INVAL, "flags must be 0");
+    const int rc = mfm_run_geometry(cfg);
+    if (rc != MFM_OK) {
+        return rc;
     }
     /* the sums of the slots over max_runs runs that share max_out_samples outputs, at most */
     *cap_events = cfg.max_events ? cfg.max_events : (uint64_t)cfg.max_out_samples / MFM_RUNFLEX_EVENT_SPACING + cfg.max_runs;
@@ -734,32 +664,10 @@ int rf_geometry(const mfm_runflex_config &cfg, uint64_t *cap_events, uint64_t *c
 /* the message of a refused call, as fetch and the host twin give it */
 const char *rf_refusal(uint64_t over, uint64_t err)
 {
-    if (err & MFM_RUNFLEX_IN_RUNRS) {
-        return "the burst resampler's call raised overflow or gate error";
-    }
-    if (err & MFM_RUNFLEX_IN_BAD_RUNS) {
-        return "the run list is not a burst resampler's: a run names a channel or an output range that does not exist, or more than max_out_samples";
-    }
-    if (err & MFM_RUNFLEX_IN_OUT_OF_STEP) {
-        return "out of step with the burst resampler: a continuing run does not follow on its channel's stretch";
-    }
-    if (over & MFM_RUNFLEX_OVER_RUNS) {
-        return "the call has more runs than max_runs";
-    }
-    return "the call's event bound (the sum of nr_out / 1105 + 1 over its runs) exceeds max_events, or its frame bound (nr_out / 29985 + 1) max_frames";
+    return mfm_run_refusal(over, err, "the call's event bound (the sum of nr_out / 1105 + 1 over its runs) exceeds max_events, or its frame bound (nr_out / 29985 + 1) max_frames");
 }
 
 } /* namespace */
-
-#define RF_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t err_ = (expr);                                                                            \
-        if (err_ != hipSuccess) {                                                                            \
-            snprintf(g_rf_error, sizeof(g_rf_error), "%s failed: %s", #expr, hipGetErrorString(err_));       \
-            mfm_internal_set_error(g_rf_error);                                                              \
-            return err_ == hipErrorOutOfMemory ? MFM_E_NOMEM : MFM_E_DEVICE;                                 \
-        }                                                                                                    \
-    } while (0)
 
 struct mfm_runflex {
     mfm_runflex_config cfg{};
@@ -813,38 +721,38 @@ int mfm_runflex_create(struct mfm_runflex **pf, const struct mfm_runflex_config 
     p->max_blocks = p->seg_words / RF_SLICE_NT + nruns;
     if (p->seg_words >= (1ull << 32) || p->max_blocks >= (1ull << 31) || cap_events >= (1ull << 32) || cap_frames >= (1ull << 31)) {
         delete p;
-        return rf_fail(MFM_E_INVAL, "max_runs and max_out_samples together ask for 2^32 segment words or more");
+        return mfm_run_fail(MFM_E_INVAL, "max_runs and max_out_samples together ask for 2^32 segment words or more");
     }
     *pf = p; /* from here on the caller's destroy frees what was allocated */
-    RF_TRY(hipSetDevice(cfg->device));
+    MFM_RUN_TRY(hipSetDevice(cfg->device));
     for (int i = 0; i < 2; i++) {
-        RF_TRY(hipMalloc(&p->d_chan[i], C * sizeof(mfm_runflex_state)));
-        RF_TRY(hipMemset(p->d_chan[i], 0, C * sizeof(mfm_runflex_state))); /* no stretch */
+        MFM_RUN_TRY(hipMalloc(&p->d_chan[i], C * sizeof(mfm_runflex_state)));
+        MFM_RUN_TRY(hipMemset(p->d_chan[i], 0, C * sizeof(mfm_runflex_state))); /* no stretch */
     }
-    RF_TRY(hipMalloc(&p->d_ring, C * MFM_RUNFLEX_RING * sizeof(int16_t)));
-    RF_TRY(hipMemset(p->d_ring, 0, C * MFM_RUNFLEX_RING * sizeof(int16_t)));
-    RF_TRY(hipMalloc(&p->d_run_state, nruns * sizeof(mfm_runflex_state)));
-    RF_TRY(hipMalloc(&p->d_seg, (size_t)p->seg_words * 4));
-    RF_TRY(hipMalloc(&p->d_plane, (size_t)p->seg_words * 4));
-    RF_TRY(hipMalloc(&p->d_summ, ((size_t)p->seg_words / 32 + 2 * nruns + 1) * 4));
-    RF_TRY(hipMalloc(&p->d_seg_base, nruns * 4));
-    RF_TRY(hipMalloc(&p->d_slot_base, nruns * 4));
-    RF_TRY(hipMalloc(&p->d_fslot_base, nruns * 4));
-    RF_TRY(hipMalloc(&p->d_blk_base, (nruns + 1) * 4));
-    RF_TRY(hipMalloc(&p->d_count, nruns * 8));
-    RF_TRY(hipMalloc(&p->d_ev_base, nruns * 8));
-    RF_TRY(hipMalloc(&p->d_chan_last, C * 4));
-    RF_TRY(hipMemset(p->d_chan_last, 0xff, C * 4));
-    RF_TRY(hipMalloc(&p->d_ctl, 2 * 4));
-    RF_TRY(hipMemset(p->d_ctl, 0, 2 * 4));
-    RF_TRY(hipMalloc(&p->d_totals, 4 * 8));
-    RF_TRY(hipMemset(p->d_totals, 0, 4 * 8));
-    RF_TRY(hipMalloc(&p->d_slots, (size_t)cap_events * sizeof(mfm_runflex_event)));
-    RF_TRY(hipMalloc(&p->d_events, (size_t)cap_events * sizeof(mfm_runflex_event)));
-    RF_TRY(hipMalloc(&p->d_fslots, (size_t)cap_frames * sizeof(RfFrameDesc)));
-    RF_TRY(hipMalloc(&p->d_fdesc, (size_t)cap_frames * sizeof(RfFrameDesc)));
-    RF_TRY(hipMalloc(&p->d_frames, (size_t)cap_frames * sizeof(mfm_flex_frame_words)));
-    RF_TRY(hipDeviceSynchronize());
+    MFM_RUN_TRY(hipMalloc(&p->d_ring, C * MFM_RUNFLEX_RING * sizeof(int16_t)));
+    MFM_RUN_TRY(hipMemset(p->d_ring, 0, C * MFM_RUNFLEX_RING * sizeof(int16_t)));
+    MFM_RUN_TRY(hipMalloc(&p->d_run_state, nruns * sizeof(mfm_runflex_state)));
+    MFM_RUN_TRY(hipMalloc(&p->d_seg, (size_t)p->seg_words * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_plane, (size_t)p->seg_words * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_summ, ((size_t)p->seg_words / 32 + 2 * nruns + 1) * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_seg_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_slot_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_fslot_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_blk_base, (nruns + 1) * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_count, nruns * 8));
+    MFM_RUN_TRY(hipMalloc(&p->d_ev_base, nruns * 8));
+    MFM_RUN_TRY(hipMalloc(&p->d_chan_last, C * 4));
+    MFM_RUN_TRY(hipMemset(p->d_chan_last, 0xff, C * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_ctl, 2 * 4));
+    MFM_RUN_TRY(hipMemset(p->d_ctl, 0, 2 * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_totals, 4 * 8));
+    MFM_RUN_TRY(hipMemset(p->d_totals, 0, 4 * 8));
+    MFM_RUN_TRY(hipMalloc(&p->d_slots, (size_t)cap_events * sizeof(mfm_runflex_event)));
+    MFM_RUN_TRY(hipMalloc(&p->d_events, (size_t)cap_events * sizeof(mfm_runflex_event)));
+    MFM_RUN_TRY(hipMalloc(&p->d_fslots, (size_t)cap_frames * sizeof(RfFrameDesc)));
+    MFM_RUN_TRY(hipMalloc(&p->d_fdesc, (size_t)cap_frames * sizeof(RfFrameDesc)));
+    MFM_RUN_TRY(hipMalloc(&p->d_frames, (size_t)cap_frames * sizeof(mfm_flex_frame_words)));
+    MFM_RUN_TRY(hipDeviceSynchronize());
     return MFM_OK;
 }
 
@@ -889,9 +797,9 @@ int mfm_runflex_process_device(struct mfm_runflex *p, const struct mfm_runrs_run
         return MFM_E_INVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RF_TRY(hipSetDevice(p->cfg.device));
-    if (p->have_call && p->last_stream != s) {
-        RF_TRY(hipStreamSynchronize(p->last_stream)); /* state lives on the device; keep calls ordered */
+    const int rb = mfm_run_call_begin(p, s);
+    if (rb != MFM_OK) {
+        return rb;
     }
     const uint32_t cur = p->cur;
     const RfCall A{ d_runs,        d_payload,      d_totals,        p->d_chan[cur], p->d_chan[cur ^ 1u], p->d_run_state, p->d_ring,
@@ -899,23 +807,23 @@ int mfm_runflex_process_device(struct mfm_runflex *p, const struct mfm_runrs_run
                     p->d_count,    p->d_ev_base,   p->d_chan_last,  p->d_ctl,       p->d_totals,         p->d_slots,     p->d_events,
                     p->d_fslots,   p->d_fdesc,     p->d_frames,     p->d_bch,       p->cfg.nr_channels,  p->cfg.max_runs,
                     p->cfg.max_out_samples, (uint32_t)p->cap_events, (uint32_t)p->cap_frames };
-    hipLaunchKernelGGL(rf_plan_kernel, dim3(1), dim3(RF_SCAN_THREADS), 0, s, A);
-    RF_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rf_plan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rf_slice_kernel, dim3((uint32_t)p->max_blocks), dim3(RF_SLICE_NT), 0, s, A);
-    RF_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rf_match_kernel, dim3((uint32_t)p->max_blocks), dim3(RF_SLICE_NT), 0, s, A);
-    RF_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rf_walk_kernel, dim3(p->cfg.max_runs), dim3(64), 0, s, A);
-    RF_TRY(hipGetLastError());
-    hipLaunchKernelGGL(rf_evscan_kernel, dim3(1), dim3(RF_SCAN_THREADS), 0, s, A);
-    RF_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rf_evscan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rf_compact_kernel, dim3(p->cfg.max_runs), dim3(64), 0, s, A);
-    RF_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     /* the frames' words read the ring as the call found it: before the ring kernel */
     hipLaunchKernelGGL(rf_gather_kernel, dim3((uint32_t)p->cap_frames), dim3(RF_GATHER_THREADS), 0, s, A);
-    RF_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rf_ring_kernel, dim3(RF_RING_BLOCKS, p->cfg.nr_channels), dim3(256), 0, s, A);
-    RF_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     if (p->ends.on) { /* behind the walk, in front of the state kernel */
         const MfmRunEndsCall E{ d_runs, p->d_chan[cur], p->d_run_state, p->d_ctl, p->d_bch, p->cfg.nr_channels, p->cfg.max_runs };
         const int re = mfm_internal_run_ends_process(&p->ends, MFM_RUN_ENDS_FLEX, &E, s);
@@ -924,10 +832,8 @@ int mfm_runflex_process_device(struct mfm_runflex *p, const struct mfm_runrs_run
         }
     }
     hipLaunchKernelGGL(rf_state_kernel, dim3(p->cfg.nr_channels), dim3(64), 0, s, A);
-    RF_TRY(hipGetLastError());
-    p->cur ^= 1u;
-    p->last_stream = s;
-    p->have_call = true;
+    MFM_RUN_TRY(hipGetLastError());
+    mfm_run_call_end(p, s);
     return MFM_OK;
 }
 
@@ -942,12 +848,12 @@ int mfm_runflex_fetch(struct mfm_runflex *p, struct mfm_runflex_event *events, s
     if (!p->have_call) {
         return MFM_OK;
     }
-    RF_TRY(hipSetDevice(p->cfg.device));
-    RF_TRY(hipStreamSynchronize(p->last_stream));
+    MFM_RUN_TRY(hipSetDevice(p->cfg.device));
+    MFM_RUN_TRY(hipStreamSynchronize(p->last_stream));
     uint64_t t[4];
-    RF_TRY(hipMemcpy(t, p->d_totals, sizeof(t), hipMemcpyDeviceToHost));
-    if (t[RF_T_OVERFLOW] || t[RF_T_INPUT]) {
-        return rf_fail(MFM_E_STATE, rf_refusal(t[RF_T_OVERFLOW], t[RF_T_INPUT]));
+    MFM_RUN_TRY(hipMemcpy(t, p->d_totals, sizeof(t), hipMemcpyDeviceToHost));
+    if (t[MFM_RUN_T_OVERFLOW] || t[MFM_RUN_T_INPUT]) {
+        return mfm_run_fail(MFM_E_STATE, rf_refusal(t[MFM_RUN_T_OVERFLOW], t[MFM_RUN_T_INPUT]));
     }
     *nr_events = (size_t)t[RF_T_EVENTS];
     *nr_frames = (size_t)t[RF_T_FRAMES];
@@ -955,10 +861,10 @@ int mfm_runflex_fetch(struct mfm_runflex *p, struct mfm_runflex_event *events, s
         return MFM_E_NOMEM;
     }
     if (t[RF_T_EVENTS]) {
-        RF_TRY(hipMemcpy(events, p->d_events, (size_t)t[RF_T_EVENTS] * sizeof(mfm_runflex_event), hipMemcpyDeviceToHost));
+        MFM_RUN_TRY(hipMemcpy(events, p->d_events, (size_t)t[RF_T_EVENTS] * sizeof(mfm_runflex_event), hipMemcpyDeviceToHost));
     }
     if (t[RF_T_FRAMES]) {
-        RF_TRY(hipMemcpy(frames, p->d_frames, (size_t)t[RF_T_FRAMES] * sizeof(mfm_flex_frame_words), hipMemcpyDeviceToHost));
+        MFM_RUN_TRY(hipMemcpy(frames, p->d_frames, (size_t)t[RF_T_FRAMES] * sizeof(mfm_flex_frame_words), hipMemcpyDeviceToHost));
     }
     return MFM_OK;
 }
@@ -981,76 +887,57 @@ int mfm_runflex_device_view(struct mfm_runflex *p, const struct mfm_runflex_even
     return MFM_OK;
 }
 
-int mfm_runflex_fetch_state(struct mfm_runflex *p, struct mfm_runflex_state *state, int16_t *ring, size_t nr_channels)
-{
-    if (!p || !state || nr_channels != p->cfg.nr_channels) {
-        return MFM_E_INVAL;
-    }
-    RF_TRY(hipSetDevice(p->cfg.device));
-    if (p->have_call) {
-        RF_TRY(hipStreamSynchronize(p->last_stream));
-    }
-    RF_TRY(hipMemcpy(state, p->d_chan[p->cur], nr_channels * sizeof(mfm_runflex_state), hipMemcpyDeviceToHost));
-    if (ring) {
-        RF_TRY(hipMemcpy(ring, p->d_ring, nr_channels * MFM_RUNFLEX_RING * sizeof(int16_t), hipMemcpyDeviceToHost));
-    }
-    return MFM_OK;
-}
-
 int mfm_hosttwin_runflex_state_check(uint32_t nr_channels, const struct mfm_runflex_state *state)
 {
-    if (!state || !nr_channels) {
-        return MFM_E_INVAL;
+    return mfm_run_state_check(nr_channels, state, "FLEX", mfm_runflex_state_check);
+}
+
+/* the states as the other stages', and the ring behind them */
+int mfm_runflex_fetch_state(struct mfm_runflex *p, struct mfm_runflex_state *state, int16_t *ring, size_t nr_channels)
+{
+    const int rc = mfm_run_fetch_state(p, state, nr_channels);
+    if (rc != MFM_OK) {
+        return rc;
     }
-    for (uint32_t c = 0; c < nr_channels; c++) {
-        if (const char *why = mfm_runflex_state_check(state[c])) {
-            char msg[224];
-            snprintf(msg, sizeof(msg), "burst FLEX state, channel %u: %s", c, why);
-            return rf_fail(MFM_E_INVAL, msg);
-        }
+    if (ring) {
+        MFM_RUN_TRY(hipMemcpy(ring, p->d_ring, nr_channels * MFM_RUNFLEX_RING * sizeof(int16_t), hipMemcpyDeviceToHost));
     }
     return MFM_OK;
 }
 
 int mfm_runflex_store_state(struct mfm_runflex *p, const struct mfm_runflex_state *state, const int16_t *ring, size_t nr_channels)
 {
-    if (!p || !state || !ring || nr_channels != p->cfg.nr_channels) {
+    if (!ring) {
         return MFM_E_INVAL;
     }
-    const int ok = mfm_hosttwin_runflex_state_check(p->cfg.nr_channels, state);
-    if (ok != MFM_OK) {
-        return ok;
+    const int rc = mfm_run_store_state(p, state, nr_channels, mfm_hosttwin_runflex_state_check);
+    if (rc != MFM_OK) {
+        return rc;
     }
-    RF_TRY(hipSetDevice(p->cfg.device));
-    if (p->have_call) {
-        RF_TRY(hipStreamSynchronize(p->last_stream));
-    }
-    RF_TRY(hipMemcpy(p->d_chan[p->cur], state, nr_channels * sizeof(mfm_runflex_state), hipMemcpyHostToDevice));
-    RF_TRY(hipMemcpy(p->d_ring, ring, nr_channels * MFM_RUNFLEX_RING * sizeof(int16_t), hipMemcpyHostToDevice));
+    MFM_RUN_TRY(hipMemcpy(p->d_ring, ring, nr_channels * MFM_RUNFLEX_RING * sizeof(int16_t), hipMemcpyHostToDevice));
     return MFM_OK;
 }
-
 
 /* ---- the stretch-end report: kernels and launchers in mfm_run_ends.hip ---- */
 
 int mfm_runflex_set_end_report(struct mfm_runflex *p, int on)
 {
-    return mfm_run_ends_entry_set(p, MFM_RUN_ENDS_FLEX, on, rf_fail);
+    return mfm_run_ends_entry_set(p, MFM_RUN_ENDS_FLEX, on, mfm_run_fail);
 }
 
 int mfm_runflex_end_stretches_device(struct mfm_runflex *p, void *stream)
 {
-    return mfm_run_ends_entry_flush(p, MFM_RUN_ENDS_FLEX, p ? p->d_bch : nullptr, stream, rf_fail);
+    return mfm_run_ends_entry_flush(p, MFM_RUN_ENDS_FLEX, p ? p->d_bch : nullptr, stream, mfm_run_fail);
 }
 
 int mfm_runflex_fetch_ends(struct mfm_runflex *p, struct mfm_runflex_end *ends, size_t max_ends, size_t *nr_ends)
 {
-    return mfm_run_ends_entry_fetch(p, MFM_RUN_ENDS_FLEX, ends, max_ends, nr_ends, rf_fail, rf_refusal);
+    return mfm_run_ends_entry_fetch(p, MFM_RUN_ENDS_FLEX, ends, max_ends, nr_ends, mfm_run_fail, rf_refusal);
 }
 
 int mfm_runflex_ends_view(struct mfm_runflex *p, const struct mfm_runflex_end **d_ends, const uint64_t **d_end_totals)
 {
-    return mfm_run_ends_entry_view(p, d_ends, d_end_totals, rf_fail);
+    return mfm_run_ends_entry_view(p, d_ends, d_end_totals, mfm_run_fail);
 }
 
 } /* extern "C" */
@@ -1295,39 +1182,16 @@ int rf_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_sampl
     if (rc != MFM_OK) {
         return rc;
     }
-    /* the plan pass */
-    const uint64_t n = totals[RF_RS_RUNS], E = totals[RF_RS_ELEMS];
-    uint64_t over = 0, err = 0;
-    if (totals[RF_RS_OVERFLOW] || totals[RF_RS_GATE]) {
-        err = MFM_RUNFLEX_IN_RUNRS;
-    } else if (E > max_out_samples) {
-        err = MFM_RUNFLEX_IN_BAD_RUNS;
-    } else if (n > max_runs) {
-        over = MFM_RUNFLEX_OVER_RUNS;
+    uint64_t n, over, err, ts = 0, tf = 0; /* the plan pass */
+    if (!mfm_run_twin_plan(totals, nr_channels, max_runs, max_out_samples, state, runs, payload, false,
+                           [&](uint32_t nr_out) { ts += mfm_runflex_event_slots(nr_out); tf += mfm_runflex_frame_slots(nr_out); }, &n, &over, &err)) {
+        return MFM_E_INVAL;
     }
-    if (!over && !err) {
-        if ((n && !runs) || (E && !payload)) {
-            return MFM_E_INVAL;
-        }
-        uint64_t to = 0, ts = 0, tf = 0;
-        for (uint64_t r = 0; r < n; r++) {
-            err |= mfm_runflex_check_run(runs[r], r ? &runs[r - 1] : nullptr, nr_channels, E, state);
-            to += runs[r].nr_out;
-            ts += mfm_runflex_event_slots(runs[r].nr_out);
-            tf += mfm_runflex_frame_slots(runs[r].nr_out);
-        }
-        if (to > max_out_samples) {
-            err |= MFM_RUNFLEX_IN_BAD_RUNS;
-        }
-        if (!err && (ts > cap_events || tf > cap_frames)) {
-            over = MFM_RUNFLEX_OVER_EVENTS;
-        }
+    if (!err && (ts > cap_events || tf > cap_frames)) {
+        over = MFM_RUNFLEX_OVER_EVENTS;
     }
     if (over || err) {
-        if (flags) {
-            *flags = (uint32_t)(over | (err << 8));
-        }
-        return rf_fail(MFM_E_STATE, rf_refusal(over, err));
+        return mfm_run_twin_refuse(over, err, flags, rf_refusal(over, err));
     }
     /* every run from the state and the ring the call started with (only a channel's first run reads them) */
     std::vector<mfm_runflex_event> out;

@@ -1,7 +1,8 @@
 /*
  * mfm_runmm.h - what the kernels of the burst Mueller-Muller stage (mfm_runmm_*, include/multifm_hip.h) and its host twin
- * (mfm_hosttwin_runmm_call) must state once: the loop's parameters, what a run starts from, the checks a run has to pass before
- * anything of the payload is read, one decision of the loop, what a run leaves behind and what a stored state must satisfy.
+ * (mfm_hosttwin_runmm_call) must state once: the loop's parameters, what a run starts from, one decision of the loop, what a run
+ * leaves behind and what a stored state must satisfy.  The checks a run has to pass before anything of the payload is read are
+ * mfm_run_stage.h's.
  *
  * The position.  The reference keeps the position of the next decision as a float (cur_sample, pager/mueller_muller.c:56-66,
  * :96, :108-109).  It starts at 0 and only ever has floorf() of something added and the whole block length taken away, so it
@@ -20,10 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/multifm_hip.h"
-
-#ifndef MFM_RUN_POS_LIMIT
-#define MFM_RUN_POS_LIMIT (1ull << 62) /* positions a stored state may hold stay below this, as the seek entries demand */
-#endif
+#include "mfm_run_stage.h"
 
 #define MFM_RUNMM_STAGING_UNIT 512u /* samples of a run the walk holds in LDS at a time (rm_walk_kernel, mfm_runmm.hip) */
 #define MFM_RUNMM_MAX_STEP (1u << 21) /* no step reaches this: floor(m + w + km * x) < 1 + 2^20 (and 2^20 more for a stored m) */
@@ -113,27 +111,6 @@ inline const char *mfm_runmm_state_check(const mfm_runmm_state &st)
         return "reserved must be 0";
     }
     return nullptr;
-}
-
-/*
- * The input-error flags of run `run` (0: it may be read): mfm_runpocsag_check_run's conditions.  prev: the run in front of it in
- * the list (NULL for the first), nr_elems: the resampler's total of output elements, state: the per-channel state the call
- * started from.
- */
-__host__ __device__ inline uint32_t mfm_runmm_check_run(const mfm_runrs_run &run, const mfm_runrs_run *prev, uint32_t nr_channels,
-                                                        uint64_t nr_elems, const mfm_runmm_state *state)
-{
-    if (run.channel >= nr_channels || (prev && prev->channel > run.channel) || run.out_offset > nr_elems ||
-        run.nr_out > nr_elems - run.out_offset) {
-        return MFM_RUNMM_IN_BAD_RUNS;
-    }
-    if (run.flags & MFM_RUNRS_BEGINS) {
-        return run.first_out != 0 ? MFM_RUNMM_IN_BAD_RUNS : 0u;
-    }
-    /* only a channel's first run of a call can continue: a later one has a closed window in front of it */
-    const bool first = !prev || prev->channel != run.channel;
-    const mfm_runmm_state &st = state[run.channel];
-    return first && st.has_stretch && st.outs == run.first_out ? 0u : MFM_RUNMM_IN_OUT_OF_STEP;
 }
 
 /* the loop between two decisions: the reference's w, m and last_sample, and sign(last_sample), which :76 takes again */

@@ -1,13 +1,13 @@
 /*
  * mfm_runmm.hip - the burst Mueller-Muller stage: the runs the burst resampler left in its dense payload go through the clock
  * recovery loop (pager/mueller_muller.c:10-115) on the device, one fresh loop per stretch.  See include/multifm_hip.h for the
- * boundary and the result, mfm_runmm.h for the position, the checks of a run, the slot bound and the arithmetic of a decision,
- * and mfm_mm.hip for the row stage whose walk this file restates.
+ * boundary and the result, mfm_runmm.h for the position, the slot bound and the arithmetic of a decision, mfm_run_stage.h for
+ * the checks of a run, and mfm_mm.hip for the row stage whose walk this file restates.
  *
  * The input is what mfm_runrs_device_view returns; how many runs and samples a call carries is read on the device, so the
  * host never waits and every launch is sized from the capacities fixed at create.
  *
- *   rm_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_runmm_check_run) before anything of the
+ *   rm_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_run_check_run) before anything of the
  *                      payload is read; exclusive scan of the runs' decision slots; a channel's last run leaves its index for
  *                      the state kernel; the totals and the flags.
  *   rm_walk_kernel     The loop is a feedback loop: the time of a run is the length of its dependent chain, and the runs of a
@@ -27,19 +27,18 @@
  *   rm_state_kernel    one lane per channel: the state of the channel's last run goes into the OTHER of two state buffers; a
  *                      channel without a run, and every channel of a refused call, copies its state over.
  *
- * No atomic decides a placement and nothing is read behind a run.
+ * No atomic decides a placement and nothing is read behind a run.  The block scan, a thread's slice of the runs, the plan's
+ * head and the host code around a call are mfm_run_stage.h's, shared with the other burst stages.
  */
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/multifm_hip.h"
 
-extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_runmm.h"
 
 static_assert(sizeof(mfm_runmm_run) == 40 && offsetof(mfm_runmm_run, first_dec) == 16 && offsetof(mfm_runmm_run, channel) == 24,
@@ -49,11 +48,7 @@ static_assert(sizeof(mfm_runmm_state) == 48 && offsetof(mfm_runmm_state, w) == 2
 
 namespace {
 
-constexpr uint32_t RM_SCAN_THREADS = 1024;
-constexpr uint32_t RM_NONE = 0xffffffffu; /* d_chan_last: the channel has no run in this call */
-constexpr uint32_t RM_T_RUNS = 0, RM_T_DECS = 1, RM_T_OVERFLOW = 2, RM_T_INPUT = 3;     /* d_totals[] */
-constexpr uint32_t RM_RS_RUNS = 0, RM_RS_ELEMS = 1, RM_RS_OVERFLOW = 2, RM_RS_GATE = 3; /* the resampler's */
-constexpr uint64_t RM_MAX_RUNS = 1ull << 28, RM_MAX_OUT = 1ull << 31; /* per call: slots and positions within a run stay below 2^32 */
+constexpr uint32_t RM_T_RUNS = 0, RM_T_DECS = 1; /* d_totals[], in front of MFM_RUN_T_OVERFLOW and MFM_RUN_T_INPUT */
 constexpr uint32_t RM_RUNS = 16;                  /* runs (walking lanes) per one-wave workgroup */
 constexpr uint32_t RM_U = MFM_RUNMM_STAGING_UNIT; /* samples of a run in its strip: the walk's staging unit */
 constexpr uint32_t RM_PITCH = RM_U * 2u + 16u;    /* bytes per strip: the 8-byte candidate read may start at the last sample */
@@ -82,72 +77,27 @@ struct RmCall {
     mfm_runmm_params P;
 };
 
-/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
-__device__ __forceinline__ uint64_t rm_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void rm_plan_kernel(const RmCall A)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
-        if (lane >= (uint32_t)o) {
-            inc += ((uint64_t)hi << 32) | lo;
-        }
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
+    uint64_t n, E, over, err, r0, r1;
+    if (!mfm_run_plan_head(A.rtotals, A.cap_out, A.cap_runs, A.totals, A.ctl, 1, &n, &E, &over, &err)) {
+        return; /* nothing may be read */
     }
-    if (lane == 63) {
-        lds[wave] = inc;
-    }
-    __syncthreads();
-    uint64_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < RM_SCAN_THREADS / 64; i++) {
-        const uint64_t t = lds[i];
-        base += i < wave ? t : 0u;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(RM_SCAN_THREADS) void rm_plan_kernel(const RmCall A)
-{
-    __shared__ uint64_t lds[RM_SCAN_THREADS / 64];
-    const uint64_t n = A.rtotals[RM_RS_RUNS], E = A.rtotals[RM_RS_ELEMS];
-    uint64_t over = 0, err = 0;
-    if (A.rtotals[RM_RS_OVERFLOW] || A.rtotals[RM_RS_GATE]) {
-        err = MFM_RUNMM_IN_RUNRS;
-    } else if (E > (uint64_t)A.cap_out) {
-        err = MFM_RUNMM_IN_BAD_RUNS;
-    } else if (n > A.cap_runs) {
-        over = MFM_RUNMM_OVER_RUNS;
-    }
-    if (over || err) { /* nothing may be read */
-        if (threadIdx.x == 0) {
-            A.totals[RM_T_RUNS] = 0;
-            A.totals[RM_T_DECS] = 0;
-            A.totals[RM_T_OVERFLOW] = over;
-            A.totals[RM_T_INPUT] = err;
-            A.ctl[0] = 0;
-        }
-        return;
-    }
-    const uint64_t per = (n + RM_SCAN_THREADS - 1) / RM_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    mfm_run_slice(n, &r0, &r1);
     uint64_t so = 0, ss = 0;
     uint32_t bad = 0;
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         const mfm_runrs_run run = A.runs[r];
-        bad |= mfm_runmm_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old);
+        bad |= mfm_run_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old);
         so += run.nr_out;
         ss += mfm_runmm_slots(run.nr_out, A.P.s);
     }
     /* fewer than 2^28 runs of fewer than 2^32 outputs: every sum stays below 2^63 */
     uint64_t to, ts;
-    (void)rm_block_scan(so, lds, &to);
-    uint64_t bs = rm_block_scan(ss, lds, &ts);
+    (void)mfm_run_block_scan(so, lds, &to);
+    uint64_t bs = mfm_run_block_scan(ss, lds, &ts);
     if (__syncthreads_or((bad & MFM_RUNMM_IN_OUT_OF_STEP) != 0)) {
         err |= MFM_RUNMM_IN_OUT_OF_STEP;
     }
@@ -173,8 +123,8 @@ __global__ __launch_bounds__(RM_SCAN_THREADS) void rm_plan_kernel(const RmCall A
     if (threadIdx.x == 0) {
         A.totals[RM_T_RUNS] = refused ? 0u : n;
         A.totals[RM_T_DECS] = 0; /* the decision scan */
-        A.totals[RM_T_OVERFLOW] = over;
-        A.totals[RM_T_INPUT] = err;
+        A.totals[MFM_RUN_T_OVERFLOW] = over;
+        A.totals[MFM_RUN_T_INPUT] = err;
         A.ctl[0] = refused ? 0u : (uint32_t)n;
     }
 }
@@ -324,20 +274,18 @@ __global__ __launch_bounds__(64) void rm_walk_kernel(const RmCall A)
     }
 }
 
-__global__ __launch_bounds__(RM_SCAN_THREADS) void rm_scan_kernel(const RmCall A)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void rm_scan_kernel(const RmCall A)
 {
-    __shared__ uint64_t lds[RM_SCAN_THREADS / 64];
-    const uint64_t n = A.ctl[0]; /* 0 for a refused call */
-    const uint64_t per = (n + RM_SCAN_THREADS - 1) / RM_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
+    uint64_t r0, r1;
+    mfm_run_slice<uint64_t>(A.ctl[0], &r0, &r1); /* 0 runs for a refused call */
     uint64_t s = 0;
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         s += A.out_runs[r].nr_dec;
     }
     uint64_t total;
-    uint64_t base = rm_block_scan(s, lds, &total); /* at most the sum of the slots: within cap_decs */
+    uint64_t base = mfm_run_block_scan(s, lds, &total); /* at most the sum of the slots: within cap_decs */
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         A.out_runs[r].dec_offset = base;
@@ -369,37 +317,20 @@ __global__ __launch_bounds__(256) void rm_state_kernel(const RmCall A)
         return;
     }
     const uint32_t last = A.chan_last[c];
-    A.chan_last[c] = RM_NONE; /* for the next call */
-    const bool refused = A.totals[RM_T_OVERFLOW] != 0 || A.totals[RM_T_INPUT] != 0;
-    A.chan_new[c] = last == RM_NONE || refused ? A.chan_old[c] : A.run_state[last]; /* else the state stays */
-}
-
-thread_local char g_rm_error[256] = "";
-
-int rm_fail(int code, const char *msg)
-{
-    snprintf(g_rm_error, sizeof(g_rm_error), "%s", msg);
-    mfm_internal_set_error(g_rm_error);
-    return code;
+    A.chan_last[c] = MFM_RUN_NONE; /* for the next call */
+    const bool refused = A.totals[MFM_RUN_T_OVERFLOW] != 0 || A.totals[MFM_RUN_T_INPUT] != 0;
+    A.chan_new[c] = last == MFM_RUN_NONE || refused ? A.chan_old[c] : A.run_state[last]; /* else the state stays */
 }
 
 /* what create checks without a device; the loop's constants and the decision capacity with the default filled in */
 int rm_geometry(const mfm_runmm_config &cfg, mfm_runmm_params *P, uint64_t *cap_decs)
 {
-    if (cfg.abi_version != MFM_ABI_VERSION) {
-        return rm_fail(MFM_E_INVAL, "abi_version is not MFM_ABI_VERSION");
-    }
-    if (0 == cfg.nr_channels) {
-        return rm_fail(MFM_E_INVAL, "nr_channels must be at least 1");
-    }
-    if (0 == cfg.max_runs || 0 == cfg.max_out_samples || cfg.max_runs >= RM_MAX_RUNS || cfg.max_out_samples >= RM_MAX_OUT) {
-        return rm_fail(MFM_E_INVAL, "max_runs must be 1 .. 2^28 - 1 and max_out_samples 1 .. 2^31 - 1: the burst resampler's capacities (mfm_runrs_get_capacity)");
-    }
-    if (cfg.flags != 0) {
-        return rm_fail(MFM_E_INVAL, "flags must be 0");
+    const int rc = mfm_run_geometry(cfg);
+    if (rc != MFM_OK) {
+        return rc;
     }
     if (const char *why = mfm_runmm_params_check(cfg.kw, cfg.km, cfg.samples_per_bit, cfg.error_min, cfg.error_max, P)) {
-        return rm_fail(MFM_E_INVAL, why);
+        return mfm_run_fail(MFM_E_INVAL, why);
     }
     /* the sum of mfm_runmm_slots over max_runs runs that share max_out_samples outputs, at most */
     *cap_decs = cfg.max_decisions ? cfg.max_decisions : (uint64_t)cfg.max_out_samples / P->s + cfg.max_runs;
@@ -409,32 +340,10 @@ int rm_geometry(const mfm_runmm_config &cfg, mfm_runmm_params *P, uint64_t *cap_
 /* the message of a refused call, as fetch and the host twin give it */
 const char *rm_refusal(uint64_t over, uint64_t err)
 {
-    if (err & MFM_RUNMM_IN_RUNRS) {
-        return "the burst resampler's call raised overflow or gate error";
-    }
-    if (err & MFM_RUNMM_IN_BAD_RUNS) {
-        return "the run list is not a burst resampler's: a run names a channel or an output range that does not exist, or more than max_out_samples";
-    }
-    if (err & MFM_RUNMM_IN_OUT_OF_STEP) {
-        return "out of step with the burst resampler: a continuing run does not follow on its channel's stretch";
-    }
-    if (over & MFM_RUNMM_OVER_RUNS) {
-        return "the call has more runs than max_runs";
-    }
-    return "the call's decision bound (the sum of nr_out / s + 1 over its runs, s = floor(error_min - |km| * 32768)) exceeds max_decisions";
+    return mfm_run_refusal(over, err, "the call's decision bound (the sum of nr_out / s + 1 over its runs, s = floor(error_min - |km| * 32768)) exceeds max_decisions");
 }
 
 } /* namespace */
-
-#define RM_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t err_ = (expr);                                                                            \
-        if (err_ != hipSuccess) {                                                                            \
-            snprintf(g_rm_error, sizeof(g_rm_error), "%s failed: %s", #expr, hipGetErrorString(err_));       \
-            mfm_internal_set_error(g_rm_error);                                                              \
-            return err_ == hipErrorOutOfMemory ? MFM_E_NOMEM : MFM_E_DEVICE;                                 \
-        }                                                                                                    \
-    } while (0)
 
 struct mfm_runmm {
     mfm_runmm_config cfg{};
@@ -478,23 +387,23 @@ int mfm_runmm_create(struct mfm_runmm **pm, const struct mfm_runmm_config *cfg)
     m->cap_decs = cap_decs;
     const size_t C = cfg->nr_channels, nruns = cfg->max_runs;
     *pm = m; /* from here on the caller's destroy frees what was allocated */
-    RM_TRY(hipSetDevice(cfg->device));
+    MFM_RUN_TRY(hipSetDevice(cfg->device));
     for (int i = 0; i < 2; i++) {
-        RM_TRY(hipMalloc(&m->d_chan[i], C * sizeof(mfm_runmm_state)));
-        RM_TRY(hipMemset(m->d_chan[i], 0, C * sizeof(mfm_runmm_state))); /* no stretch */
+        MFM_RUN_TRY(hipMalloc(&m->d_chan[i], C * sizeof(mfm_runmm_state)));
+        MFM_RUN_TRY(hipMemset(m->d_chan[i], 0, C * sizeof(mfm_runmm_state))); /* no stretch */
     }
-    RM_TRY(hipMalloc(&m->d_run_state, nruns * sizeof(mfm_runmm_state)));
-    RM_TRY(hipMalloc(&m->d_out_runs, nruns * sizeof(mfm_runmm_run)));
-    RM_TRY(hipMalloc(&m->d_slot_base, nruns * 4));
-    RM_TRY(hipMalloc(&m->d_chan_last, C * 4));
-    RM_TRY(hipMemset(m->d_chan_last, 0xff, C * 4));
-    RM_TRY(hipMalloc(&m->d_ctl, 2 * 4));
-    RM_TRY(hipMemset(m->d_ctl, 0, 2 * 4));
-    RM_TRY(hipMalloc(&m->d_totals, 4 * 8));
-    RM_TRY(hipMemset(m->d_totals, 0, 4 * 8));
-    RM_TRY(hipMalloc(&m->d_slots, (size_t)cap_decs * 2));
-    RM_TRY(hipMalloc(&m->d_decs, (size_t)cap_decs * 2));
-    RM_TRY(hipDeviceSynchronize());
+    MFM_RUN_TRY(hipMalloc(&m->d_run_state, nruns * sizeof(mfm_runmm_state)));
+    MFM_RUN_TRY(hipMalloc(&m->d_out_runs, nruns * sizeof(mfm_runmm_run)));
+    MFM_RUN_TRY(hipMalloc(&m->d_slot_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&m->d_chan_last, C * 4));
+    MFM_RUN_TRY(hipMemset(m->d_chan_last, 0xff, C * 4));
+    MFM_RUN_TRY(hipMalloc(&m->d_ctl, 2 * 4));
+    MFM_RUN_TRY(hipMemset(m->d_ctl, 0, 2 * 4));
+    MFM_RUN_TRY(hipMalloc(&m->d_totals, 4 * 8));
+    MFM_RUN_TRY(hipMemset(m->d_totals, 0, 4 * 8));
+    MFM_RUN_TRY(hipMalloc(&m->d_slots, (size_t)cap_decs * 2));
+    MFM_RUN_TRY(hipMalloc(&m->d_decs, (size_t)cap_decs * 2));
+    MFM_RUN_TRY(hipDeviceSynchronize());
     return MFM_OK;
 }
 
@@ -527,27 +436,25 @@ int mfm_runmm_process_device(struct mfm_runmm *m, const struct mfm_runrs_run *d_
         return MFM_E_INVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RM_TRY(hipSetDevice(m->cfg.device));
-    if (m->have_call && m->last_stream != s) {
-        RM_TRY(hipStreamSynchronize(m->last_stream)); /* state lives on the device; keep calls ordered */
+    const int rb = mfm_run_call_begin(m, s);
+    if (rb != MFM_OK) {
+        return rb;
     }
     const uint32_t cur = m->cur;
     const RmCall A{ d_runs,        d_payload,      d_totals,      m->d_chan[cur], m->d_chan[cur ^ 1u], m->d_run_state, m->d_out_runs,
                     m->d_slot_base, m->d_chan_last, m->d_ctl,      m->d_totals,    m->d_slots,          m->d_decs,
                     m->cfg.nr_channels, m->cfg.max_runs, m->cfg.max_out_samples, (uint32_t)m->cap_decs, m->P };
-    hipLaunchKernelGGL(rm_plan_kernel, dim3(1), dim3(RM_SCAN_THREADS), 0, s, A);
-    RM_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rm_plan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rm_walk_kernel, dim3((m->cfg.max_runs + RM_RUNS - 1u) / RM_RUNS), dim3(64), 0, s, A);
-    RM_TRY(hipGetLastError());
-    hipLaunchKernelGGL(rm_scan_kernel, dim3(1), dim3(RM_SCAN_THREADS), 0, s, A);
-    RM_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rm_scan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rm_compact_kernel, dim3(m->cfg.max_runs), dim3(64), 0, s, A);
-    RM_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rm_state_kernel, dim3((m->cfg.nr_channels + 255u) / 256u), dim3(256), 0, s, A);
-    RM_TRY(hipGetLastError());
-    m->cur ^= 1u;
-    m->last_stream = s;
-    m->have_call = true;
+    MFM_RUN_TRY(hipGetLastError());
+    mfm_run_call_end(m, s);
     return MFM_OK;
 }
 
@@ -562,12 +469,12 @@ int mfm_runmm_fetch(struct mfm_runmm *m, struct mfm_runmm_run *runs, size_t max_
     if (!m->have_call) {
         return MFM_OK;
     }
-    RM_TRY(hipSetDevice(m->cfg.device));
-    RM_TRY(hipStreamSynchronize(m->last_stream));
+    MFM_RUN_TRY(hipSetDevice(m->cfg.device));
+    MFM_RUN_TRY(hipStreamSynchronize(m->last_stream));
     uint64_t t[4];
-    RM_TRY(hipMemcpy(t, m->d_totals, sizeof(t), hipMemcpyDeviceToHost));
-    if (t[RM_T_OVERFLOW] || t[RM_T_INPUT]) {
-        return rm_fail(MFM_E_STATE, rm_refusal(t[RM_T_OVERFLOW], t[RM_T_INPUT]));
+    MFM_RUN_TRY(hipMemcpy(t, m->d_totals, sizeof(t), hipMemcpyDeviceToHost));
+    if (t[MFM_RUN_T_OVERFLOW] || t[MFM_RUN_T_INPUT]) {
+        return mfm_run_fail(MFM_E_STATE, rm_refusal(t[MFM_RUN_T_OVERFLOW], t[MFM_RUN_T_INPUT]));
     }
     *nr_runs = (size_t)t[RM_T_RUNS];
     *nr_decisions = (size_t)t[RM_T_DECS];
@@ -575,10 +482,10 @@ int mfm_runmm_fetch(struct mfm_runmm *m, struct mfm_runmm_run *runs, size_t max_
         return MFM_E_NOMEM;
     }
     if (t[RM_T_RUNS]) {
-        RM_TRY(hipMemcpy(runs, m->d_out_runs, (size_t)t[RM_T_RUNS] * sizeof(mfm_runmm_run), hipMemcpyDeviceToHost));
+        MFM_RUN_TRY(hipMemcpy(runs, m->d_out_runs, (size_t)t[RM_T_RUNS] * sizeof(mfm_runmm_run), hipMemcpyDeviceToHost));
     }
     if (t[RM_T_DECS]) {
-        RM_TRY(hipMemcpy(decisions, m->d_decs, (size_t)t[RM_T_DECS] * 2, hipMemcpyDeviceToHost));
+        MFM_RUN_TRY(hipMemcpy(decisions, m->d_decs, (size_t)t[RM_T_DECS] * 2, hipMemcpyDeviceToHost));
     }
     return MFM_OK;
 }
@@ -602,47 +509,17 @@ int mfm_runmm_device_view(struct mfm_runmm *m, const struct mfm_runmm_run **d_ru
 
 int mfm_runmm_fetch_state(struct mfm_runmm *m, struct mfm_runmm_state *state, size_t nr_channels)
 {
-    if (!m || !state || nr_channels != m->cfg.nr_channels) {
-        return MFM_E_INVAL;
-    }
-    RM_TRY(hipSetDevice(m->cfg.device));
-    if (m->have_call) {
-        RM_TRY(hipStreamSynchronize(m->last_stream));
-    }
-    RM_TRY(hipMemcpy(state, m->d_chan[m->cur], nr_channels * sizeof(mfm_runmm_state), hipMemcpyDeviceToHost));
-    return MFM_OK;
+    return mfm_run_fetch_state(m, state, nr_channels);
 }
 
 int mfm_hosttwin_runmm_state_check(uint32_t nr_channels, const struct mfm_runmm_state *state)
 {
-    if (!state || !nr_channels) {
-        return MFM_E_INVAL;
-    }
-    for (uint32_t c = 0; c < nr_channels; c++) {
-        if (const char *why = mfm_runmm_state_check(state[c])) {
-            char msg[224];
-            snprintf(msg, sizeof(msg), "burst Mueller-Muller state, channel %u: %s", c, why);
-            return rm_fail(MFM_E_INVAL, msg);
-        }
-    }
-    return MFM_OK;
+    return mfm_run_state_check(nr_channels, state, "Mueller-Muller", mfm_runmm_state_check);
 }
 
 int mfm_runmm_store_state(struct mfm_runmm *m, const struct mfm_runmm_state *state, size_t nr_channels)
 {
-    if (!m || !state || nr_channels != m->cfg.nr_channels) {
-        return MFM_E_INVAL;
-    }
-    const int ok = mfm_hosttwin_runmm_state_check(m->cfg.nr_channels, state);
-    if (ok != MFM_OK) {
-        return ok;
-    }
-    RM_TRY(hipSetDevice(m->cfg.device));
-    if (m->have_call) {
-        RM_TRY(hipStreamSynchronize(m->last_stream));
-    }
-    RM_TRY(hipMemcpy(m->d_chan[m->cur], state, nr_channels * sizeof(mfm_runmm_state), hipMemcpyHostToDevice));
-    return MFM_OK;
+    return mfm_run_store_state(m, state, nr_channels, mfm_hosttwin_runmm_state_check);
 }
 
 /* ---- the host twin: the same plan, the loop one decision at a time ---- */
@@ -665,38 +542,16 @@ int mfm_hosttwin_runmm_call(const struct mfm_runmm_config *cfg, struct mfm_runmm
     if (rc != MFM_OK) {
         return rc;
     }
-    /* the plan pass */
-    const uint64_t n = totals[RM_RS_RUNS], E = totals[RM_RS_ELEMS];
-    uint64_t over = 0, err = 0;
-    if (totals[RM_RS_OVERFLOW] || totals[RM_RS_GATE]) {
-        err = MFM_RUNMM_IN_RUNRS;
-    } else if (E > (uint64_t)cfg->max_out_samples) {
-        err = MFM_RUNMM_IN_BAD_RUNS;
-    } else if (n > cfg->max_runs) {
-        over = MFM_RUNMM_OVER_RUNS;
+    uint64_t n, over, err, ts = 0; /* the plan pass */
+    if (!mfm_run_twin_plan(totals, cfg->nr_channels, cfg->max_runs, cfg->max_out_samples, state, runs, payload, false,
+                           [&](uint32_t nr_out) { ts += mfm_runmm_slots(nr_out, P.s); }, &n, &over, &err)) {
+        return MFM_E_INVAL;
     }
-    if (!over && !err) {
-        if ((n && !runs) || (E && !payload)) {
-            return MFM_E_INVAL;
-        }
-        uint64_t to = 0, ts = 0;
-        for (uint64_t r = 0; r < n; r++) {
-            err |= mfm_runmm_check_run(runs[r], r ? &runs[r - 1] : nullptr, cfg->nr_channels, E, state);
-            to += runs[r].nr_out;
-            ts += mfm_runmm_slots(runs[r].nr_out, P.s);
-        }
-        if (to > cfg->max_out_samples) {
-            err |= MFM_RUNMM_IN_BAD_RUNS;
-        }
-        if (!err && ts > cap_decs) {
-            over = MFM_RUNMM_OVER_DECISIONS;
-        }
+    if (!err && ts > cap_decs) {
+        over = MFM_RUNMM_OVER_DECISIONS;
     }
     if (over || err) {
-        if (flags) {
-            *flags = (uint32_t)(over | (err << 8));
-        }
-        return rm_fail(MFM_E_STATE, rm_refusal(over, err));
+        return mfm_run_twin_refuse(over, err, flags, rm_refusal(over, err));
     }
     /* every run from the state the call started with (only a channel's first run reads it); the state its last run leaves */
     std::vector<mfm_runmm_run> recs(n);

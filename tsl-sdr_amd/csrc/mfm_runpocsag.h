@@ -1,7 +1,7 @@
 /*
  * mfm_runpocsag.h - what the kernels of the burst POCSAG stage (mfm_runpocsag_*, include/multifm_hip.h) and its host twin
- * (mfm_hosttwin_runpocsag_call) must state once: the layout of a run's bit segment, its share of the event slots, the
- * checks a run has to pass before anything of the payload is read, and the bits a stretch leaves behind.
+ * (mfm_hosttwin_runpocsag_call) must state once: the layout of a run's bit segment, its share of the event slots and the
+ * bits a stretch leaves behind.  The checks a run has to pass before anything of the payload is read are mfm_run_stage.h's.
  *
  * A run's segment is MFM_RUNPOCSAG_HIST_WORDS words of history, then its nr_out sample bits (bit = sample < 0), then one
  * word of padding: segment bit 2400 + j is output j of the run, i.e. stretch sample first_out + j.  The history is the
@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/multifm_hip.h"
+#include "mfm_run_stage.h"
 
 #define MFM_RUNPOCSAG_HIST_WORDS 75u /* 32 bits * 75 samples per bit of register history = 2400 samples, whole words */
 #define MFM_RUNPOCSAG_HIST_BITS (32u * MFM_RUNPOCSAG_HIST_WORDS)
@@ -33,10 +34,6 @@
 #define MFM_RUNPOCSAG_SYNC 0x7cd215d8u         /* pager_pocsag_priv.h:40 */
 
 enum { MFM_RUNPOCSAG_SEARCH = 0, MFM_RUNPOCSAG_BATCH = 2, MFM_RUNPOCSAG_SYNCWORD = 3 };
-
-#ifndef MFM_RUN_POS_LIMIT
-#define MFM_RUN_POS_LIMIT (1ull << 62) /* positions a stored state may hold stay below this, as the seek entries demand */
-#endif
 
 /*
  * What a state handed in from outside (mfm_runpocsag_store_state) must satisfy before a kernel reads it; NULL when it does,
@@ -129,28 +126,6 @@ __host__ __device__ inline uint32_t mfm_runpocsag_seg_words(uint32_t nr_out)
 __host__ __device__ inline uint32_t mfm_runpocsag_slots(uint32_t nr_out)
 {
     return 3u * (nr_out / MFM_RUNPOCSAG_MIN_SPACING + 1u) + 2u;
-}
-
-/*
- * The input-error flags of run `run` (0: it may be read).  prev: the run in front of it in the list (NULL for the first),
- * nr_elems: the resampler's total of output elements, state: the per-channel state the call started from.  words: the
- * resampler's bits form, where out_offset and nr_elems count 32-bit words and the run owns (nr_out + 31) / 32 of them.
- */
-__host__ __device__ inline uint32_t mfm_runpocsag_check_run(const mfm_runrs_run &run, const mfm_runrs_run *prev, uint32_t nr_channels,
-                                                            uint64_t nr_elems, const mfm_runpocsag_state *state, bool words = false)
-{
-    const uint64_t owned = words ? ((uint64_t)run.nr_out + 31u) / 32u : run.nr_out;
-    if (run.channel >= nr_channels || (prev && prev->channel > run.channel) || run.out_offset > nr_elems ||
-        owned > nr_elems - run.out_offset) {
-        return MFM_RUNPOCSAG_IN_BAD_RUNS;
-    }
-    if (run.flags & MFM_RUNRS_BEGINS) {
-        return run.first_out != 0 ? MFM_RUNPOCSAG_IN_BAD_RUNS : 0u;
-    }
-    /* only a channel's first run of a call can continue: a later one has a closed window in front of it */
-    const bool first = !prev || prev->channel != run.channel;
-    const mfm_runpocsag_state &st = state[run.channel];
-    return first && st.has_stretch && st.outs == run.first_out ? 0u : MFM_RUNPOCSAG_IN_OUT_OF_STEP;
 }
 
 /* word k (0 .. 74) of the tail a run leaves: segment bits [nr_out + 32 k, nr_out + 32 k + 32), which end with the run's last

@@ -2,13 +2,13 @@
  * mfm_runpocsag.hip - the burst POCSAG stage: the runs the burst resampler left in its dense payload go through the POCSAG
  * demodulator (pager/pager_pocsag.c:81-117,434-543) on the device, one fresh demodulator per stretch.  See
  * include/multifm_hip.h for the boundary and the event format, mfm_runpocsag.h for the segment layout, the tail, the slot
- * bound and the checks of a run, and mfm_pocsag.hip for the row stage whose bit-sliced correlator, segmented eye scan and
+ * bound, mfm_run_stage.h for the checks of a run, and mfm_pocsag.hip for the row stage whose bit-sliced correlator, segmented eye scan and
  * strided gathers this file restates.
  *
  * The input is what mfm_runrs_device_view returns; how many runs and samples a call carries is read on the device, so the
  * host never waits and every launch is sized from the capacities fixed at create.
  *
- *   rp_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_runpocsag_check_run) before anything of
+ *   rp_plan_kernel     one block.  One pass over the runs: every run is checked (mfm_run_check_run) before anything of
  *                      the payload is read; exclusive scans of the runs' segment words, event slots and slicer workgroups; a
  *                      channel's last run leaves its index for the state kernel; the totals and the flags.
  *   rp_slice_kernel    payload int16 -> 1 bit per sample (sample < 0).  A workgroup takes 256 words of one run's segment,
@@ -37,19 +37,18 @@
  *                      go into the OTHER of two state buffers; a channel without a run, and every channel of a refused
  *                      call, copies its state over.
  *
- * Nothing is floating point and no atomic decides a placement.
+ * Nothing is floating point and no atomic decides a placement. The block scan, a thread's slice of the runs, the plan's head, the count scan and
+ * the word copy of the compaction, and the host code around a call are mfm_run_stage.h's, shared with the other burst stages.
  */
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/multifm_hip.h"
 
-extern "C" __attribute__((visibility("hidden"))) void mfm_internal_set_error(const char *msg);
 #include "mfm_bch.h"
 #include "mfm_run_bits.h"
 #include "mfm_run_ends.h"
@@ -64,16 +63,12 @@ static_assert(sizeof(mfm_runpocsag_state) == 432 && offsetof(mfm_runpocsag_state
 
 namespace {
 
-constexpr uint32_t RP_SCAN_THREADS = 1024;
 constexpr uint32_t RP_SLICE_NT = MFM_RUN_BITS_SLICE_NT;         /* slicer: threads = segment words per workgroup */
-constexpr uint32_t RP_NONE = 0xffffffffu;     /* d_chan_last: the channel has no run in this call */
-constexpr uint32_t RP_T_EVENTS = 0, RP_T_RUNS = 1, RP_T_OVERFLOW = 2, RP_T_INPUT = 3; /* d_totals[] */
-constexpr uint32_t RP_RS_RUNS = 0, RP_RS_ELEMS = 1, RP_RS_OVERFLOW = 2, RP_RS_GATE = 3; /* the resampler's */
+constexpr uint32_t RP_T_EVENTS = 0, RP_T_RUNS = 1; /* d_totals[], in front of MFM_RUN_T_OVERFLOW and MFM_RUN_T_INPUT */
 constexpr uint32_t RP_SYNC = MFM_RUNPOCSAG_SYNC;
 constexpr uint32_t RP_BACK = 76;              /* 31 * 75 bits = 72.7 words of history, plus the funnel-shift neighbour */
 constexpr uint32_t RP_TILE = RP_BACK + 64 + 2;
 constexpr uint32_t RP_STATE_WORDS = sizeof(mfm_runpocsag_state) / 4, RP_TAIL_WORD0 = offsetof(mfm_runpocsag_state, tail) / 4;
-constexpr uint64_t RP_MAX_RUNS = 1ull << 28, RP_MAX_OUT = 1ull << 31; /* per call: segment words and slots stay below 2^32 */
 static_assert(MFM_RUNPOCSAG_HIST_WORDS + 1 >= RP_BACK, "a step's tile starts at most one word in front of the segment");
 
 /* ---- bit-sliced sync-word correlator, after pg_count_le4 and pg_match32 of mfm_pocsag.hip --------------------------------- */
@@ -206,67 +201,21 @@ struct RpCall {
     uint32_t C, cap_runs, cap_out, cap_events, seg_cap;
 };
 
-/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
-__device__ __forceinline__ uint64_t rp_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void rp_plan_kernel(const RpCall A)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
-        if (lane >= (uint32_t)o) {
-            inc += ((uint64_t)hi << 32) | lo;
-        }
-    }
-    if (lane == 63) {
-        lds[wave] = inc;
-    }
-    __syncthreads();
-    uint64_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < RP_SCAN_THREADS / 64; i++) {
-        const uint64_t t = lds[i];
-        base += i < wave ? t : 0u;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(RP_SCAN_THREADS) void rp_plan_kernel(const RpCall A)
-{
-    __shared__ uint64_t lds[RP_SCAN_THREADS / 64];
-    const uint64_t n = A.rtotals[RP_RS_RUNS], E = A.rtotals[RP_RS_ELEMS];
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
     const bool words = A.bits != nullptr; /* E and out_offset count words of the bits payload */
-    uint64_t over = 0, err = 0;
-    if (A.rtotals[RP_RS_OVERFLOW] || A.rtotals[RP_RS_GATE]) {
-        err = MFM_RUNPOCSAG_IN_RUNRS;
-    } else if (E > (words ? (uint64_t)A.cap_out / 32u + A.cap_runs : (uint64_t)A.cap_out)) {
-        err = MFM_RUNPOCSAG_IN_BAD_RUNS;
-    } else if (n > A.cap_runs) {
-        over = MFM_RUNPOCSAG_OVER_RUNS;
+    uint64_t n, E, over, err, r0, r1;
+    if (!mfm_run_plan_head(A.rtotals, words ? (uint64_t)A.cap_out / 32u + A.cap_runs : (uint64_t)A.cap_out, A.cap_runs, A.totals, A.ctl, 2, &n, &E, &over, &err)) {
+        return; /* nothing may be read */
     }
-    if (over || err) { /* nothing may be read */
-        if (threadIdx.x == 0) {
-            A.totals[RP_T_EVENTS] = 0;
-            A.totals[RP_T_RUNS] = 0;
-            A.totals[RP_T_OVERFLOW] = over;
-            A.totals[RP_T_INPUT] = err;
-            A.ctl[0] = 0;
-            A.ctl[1] = 0;
-        }
-        return;
-    }
-    const uint64_t per = (n + RP_SCAN_THREADS - 1) / RP_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    mfm_run_slice(n, &r0, &r1);
     uint64_t so = 0, sw = 0, ss = 0, sb = 0;
     uint32_t bad = 0;
 #pragma unroll 1
     for (uint64_t r = r0; r < r1; r++) {
         const mfm_runrs_run run = A.runs[r];
-        bad |= mfm_runpocsag_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old, words);
+        bad |= mfm_run_check_run(run, r ? &A.runs[r - 1] : nullptr, A.C, E, A.chan_old, words);
         const uint32_t w = mfm_runpocsag_seg_words(run.nr_out);
         so += run.nr_out;
         sw += w;
@@ -275,11 +224,11 @@ __global__ __launch_bounds__(RP_SCAN_THREADS) void rp_plan_kernel(const RpCall A
     }
     /* fewer than 2^28 runs of fewer than 2^32 outputs: every sum stays below 2^63 */
     uint64_t to, tws, tb;
-    (void)rp_block_scan(so, lds, &to);
+    (void)mfm_run_block_scan(so, lds, &to);
     /* a call that is not refused has fewer than 2^32 segment words and fewer than 2^32 slots (rp_geometry): they share a scan */
-    const uint64_t bws = rp_block_scan((sw & 0xffffffffull) | (ss << 32), lds, &tws);
+    const uint64_t bws = mfm_run_block_scan((sw & 0xffffffffull) | (ss << 32), lds, &tws);
     uint64_t bw = bws & 0xffffffffull, bs = bws >> 32, ts = tws >> 32;
-    uint64_t bb = rp_block_scan(sb, lds, &tb);
+    uint64_t bb = mfm_run_block_scan(sb, lds, &tb);
     if (__syncthreads_or((bad & MFM_RUNPOCSAG_IN_OUT_OF_STEP) != 0)) {
         err |= MFM_RUNPOCSAG_IN_OUT_OF_STEP;
     }
@@ -310,8 +259,8 @@ __global__ __launch_bounds__(RP_SCAN_THREADS) void rp_plan_kernel(const RpCall A
     if (threadIdx.x == 0) {
         A.totals[RP_T_EVENTS] = 0; /* the event scan */
         A.totals[RP_T_RUNS] = refused ? 0u : n;
-        A.totals[RP_T_OVERFLOW] = over;
-        A.totals[RP_T_INPUT] = err;
+        A.totals[MFM_RUN_T_OVERFLOW] = over;
+        A.totals[MFM_RUN_T_INPUT] = err;
         if (!refused) {
             A.blk_base[n] = (uint32_t)tb;
         }
@@ -747,25 +696,11 @@ __global__ __launch_bounds__(64) void rp_walk_kernel(const RpCall A)
     }
 }
 
-__global__ __launch_bounds__(RP_SCAN_THREADS) void rp_evscan_kernel(const RpCall A)
+__global__ __launch_bounds__(MFM_RUN_SCAN_THREADS) void rp_evscan_kernel(const RpCall A)
 {
-    __shared__ uint64_t lds[RP_SCAN_THREADS / 64];
-    const uint64_t n = A.ctl[1]; /* 0 for a refused call */
-    const uint64_t per = (n + RP_SCAN_THREADS - 1) / RP_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
-    uint64_t s = 0;
-#pragma unroll 1
-    for (uint64_t r = r0; r < r1; r++) {
-        s += A.count[r];
-    }
-    uint64_t total;
-    uint64_t base = rp_block_scan(s, lds, &total); /* at most the sum of the slots: within cap_events */
-#pragma unroll 1
-    for (uint64_t r = r0; r < r1; r++) {
-        A.ev_base[r] = (uint32_t)base;
-        base += A.count[r];
-    }
+    __shared__ uint64_t lds[MFM_RUN_SCAN_THREADS / 64];
+    /* 0 runs for a refused call; the total is at most the sum of the slots: within cap_events */
+    const uint64_t total = mfm_run_count_scan(A.count, A.ev_base, A.ctl[1], lds);
     if (threadIdx.x == 0) {
         A.totals[RP_T_EVENTS] = total;
     }
@@ -780,9 +715,7 @@ __global__ __launch_bounds__(64) void rp_compact_kernel(const RpCall A)
     constexpr uint32_t EW = sizeof(mfm_runpocsag_event) / 4;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(A.slots + A.slot_base[r]);
     uint32_t *dst = reinterpret_cast<uint32_t *>(A.events + A.ev_base[r]);
-    for (uint32_t i = threadIdx.x; i < A.count[r] * EW; i += blockDim.x) {
-        dst[i] = src[i];
-    }
+    mfm_run_copy_words(src, dst, &A.count[r], EW);
 }
 
 __global__ __launch_bounds__(128) void rp_state_kernel(const RpCall A)
@@ -791,13 +724,13 @@ __global__ __launch_bounds__(128) void rp_state_kernel(const RpCall A)
     const uint32_t c = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) {
         s_last = A.chan_last[c];
-        A.chan_last[c] = RP_NONE; /* for the next call */
+        A.chan_last[c] = MFM_RUN_NONE; /* for the next call */
     }
     __syncthreads();
     const uint32_t last = s_last;
-    const bool refused = A.totals[RP_T_OVERFLOW] != 0 || A.totals[RP_T_INPUT] != 0;
+    const bool refused = A.totals[MFM_RUN_T_OVERFLOW] != 0 || A.totals[MFM_RUN_T_INPUT] != 0;
     uint32_t *nw = reinterpret_cast<uint32_t *>(&A.chan_new[c]);
-    if (last == RP_NONE || refused) { /* the state stays */
+    if (last == MFM_RUN_NONE || refused) { /* the state stays */
         const uint32_t *old = reinterpret_cast<const uint32_t *>(&A.chan_old[c]);
         for (uint32_t i = tid; i < RP_STATE_WORDS; i += blockDim.x) {
             nw[i] = old[i];
@@ -812,29 +745,12 @@ __global__ __launch_bounds__(128) void rp_state_kernel(const RpCall A)
     }
 }
 
-thread_local char g_rp_error[256] = "";
-
-int rp_fail(int code, const char *msg)
-{
-    snprintf(g_rp_error, sizeof(g_rp_error), "%s", msg);
-    mfm_internal_set_error(g_rp_error);
-    return code;
-}
-
 /* what create checks without a device; the capacities with the default filled in */
 int rp_geometry(const mfm_runpocsag_config &cfg, uint64_t *cap_events)
 {
-    if (cfg.abi_version != MFM_ABI_VERSION) {
-        return rp_fail(MFM_E_INVAL, "abi_version is not MFM_ABI_VERSION");
-    }
-    if (0 == cfg.nr_channels) {
-        return rp_fail(MFM_E_INVAL, "nr_channels must be at least 1");
-    }
-    if (0 == cfg.max_runs || 0 == cfg.max_out_samples || cfg.max_runs >= RP_MAX_RUNS || cfg.max_out_samples >= RP_MAX_OUT) {
-        return rp_fail(MFM_E_INVAL, "max_runs must be 1 .. 2^28 - 1 and max_out_samples 1 .. 2^31 - 1: the burst resampler's capacities (mfm_runrs_get_capacity)");
-    }
-    if (cfg.flags != 0) {
-        return rp_fail(MFM_E_INVAL, "flags must be 0");
+    const int rc = mfm_run_geometry(cfg);
+    if (rc != MFM_OK) {
+        return rc;
     }
     /* the sum of mfm_runpocsag_slots over max_runs runs that share max_out_samples outputs, at most */
     *cap_events = cfg.max_events ? cfg.max_events : 3ull * (cfg.max_out_samples / MFM_RUNPOCSAG_MIN_SPACING) + 5ull * cfg.max_runs;
@@ -844,32 +760,10 @@ int rp_geometry(const mfm_runpocsag_config &cfg, uint64_t *cap_events)
 /* the message of a refused call, as fetch and the host twin give it */
 const char *rp_refusal(uint64_t over, uint64_t err)
 {
-    if (err & MFM_RUNPOCSAG_IN_RUNRS) {
-        return "the burst resampler's call raised overflow or gate error";
-    }
-    if (err & MFM_RUNPOCSAG_IN_BAD_RUNS) {
-        return "the run list is not a burst resampler's: a run names a channel or an output range that does not exist, or more than max_out_samples";
-    }
-    if (err & MFM_RUNPOCSAG_IN_OUT_OF_STEP) {
-        return "out of step with the burst resampler: a continuing run does not follow on its channel's stretch";
-    }
-    if (over & MFM_RUNPOCSAG_OVER_RUNS) {
-        return "the call has more runs than max_runs";
-    }
-    return "the call's event bound (the sum of 3 * (nr_out / 8704 + 1) + 2 over its runs) exceeds max_events";
+    return mfm_run_refusal(over, err, "the call's event bound (the sum of 3 * (nr_out / 8704 + 1) + 2 over its runs) exceeds max_events");
 }
 
 } /* namespace */
-
-#define RP_TRY(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t err_ = (expr);                                                                            \
-        if (err_ != hipSuccess) {                                                                            \
-            snprintf(g_rp_error, sizeof(g_rp_error), "%s failed: %s", #expr, hipGetErrorString(err_));       \
-            mfm_internal_set_error(g_rp_error);                                                              \
-            return err_ == hipErrorOutOfMemory ? MFM_E_NOMEM : MFM_E_DEVICE;                                 \
-        }                                                                                                    \
-    } while (0)
 
 struct mfm_runpocsag {
     mfm_runpocsag_config cfg{};
@@ -919,32 +813,32 @@ int mfm_runpocsag_create(struct mfm_runpocsag **pp, const struct mfm_runpocsag_c
     p->max_blocks = p->seg_words / RP_SLICE_NT + nruns;
     if (p->seg_words >= (1ull << 32) || p->max_blocks >= (1ull << 31)) {
         delete p;
-        return rp_fail(MFM_E_INVAL, "max_runs and max_out_samples together ask for 2^32 segment words or more");
+        return mfm_run_fail(MFM_E_INVAL, "max_runs and max_out_samples together ask for 2^32 segment words or more");
     }
     *pp = p; /* from here on the caller's destroy frees what was allocated */
-    RP_TRY(hipSetDevice(cfg->device));
+    MFM_RUN_TRY(hipSetDevice(cfg->device));
     for (int i = 0; i < 2; i++) {
-        RP_TRY(hipMalloc(&p->d_chan[i], C * sizeof(mfm_runpocsag_state)));
-        RP_TRY(hipMemset(p->d_chan[i], 0, C * sizeof(mfm_runpocsag_state))); /* no stretch */
+        MFM_RUN_TRY(hipMalloc(&p->d_chan[i], C * sizeof(mfm_runpocsag_state)));
+        MFM_RUN_TRY(hipMemset(p->d_chan[i], 0, C * sizeof(mfm_runpocsag_state))); /* no stretch */
     }
-    RP_TRY(hipMalloc(&p->d_run_state, nruns * sizeof(mfm_runpocsag_state)));
-    RP_TRY(hipMalloc(&p->d_seg, (size_t)p->seg_words * 4));
-    RP_TRY(hipMalloc(&p->d_plane, (size_t)p->seg_words * 12));
-    RP_TRY(hipMalloc(&p->d_summ, ((size_t)p->seg_words / 32 + 2 * nruns + 1) * 4));
-    RP_TRY(hipMalloc(&p->d_seg_base, nruns * 4));
-    RP_TRY(hipMalloc(&p->d_slot_base, nruns * 4));
-    RP_TRY(hipMalloc(&p->d_blk_base, (nruns + 1) * 4));
-    RP_TRY(hipMalloc(&p->d_count, nruns * 4));
-    RP_TRY(hipMalloc(&p->d_ev_base, nruns * 4));
-    RP_TRY(hipMalloc(&p->d_chan_last, C * 4));
-    RP_TRY(hipMemset(p->d_chan_last, 0xff, C * 4));
-    RP_TRY(hipMalloc(&p->d_ctl, 2 * 4));
-    RP_TRY(hipMemset(p->d_ctl, 0, 2 * 4));
-    RP_TRY(hipMalloc(&p->d_totals, 4 * 8));
-    RP_TRY(hipMemset(p->d_totals, 0, 4 * 8));
-    RP_TRY(hipMalloc(&p->d_slots, (size_t)cap_events * sizeof(mfm_runpocsag_event)));
-    RP_TRY(hipMalloc(&p->d_events, (size_t)cap_events * sizeof(mfm_runpocsag_event)));
-    RP_TRY(hipDeviceSynchronize());
+    MFM_RUN_TRY(hipMalloc(&p->d_run_state, nruns * sizeof(mfm_runpocsag_state)));
+    MFM_RUN_TRY(hipMalloc(&p->d_seg, (size_t)p->seg_words * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_plane, (size_t)p->seg_words * 12));
+    MFM_RUN_TRY(hipMalloc(&p->d_summ, ((size_t)p->seg_words / 32 + 2 * nruns + 1) * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_seg_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_slot_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_blk_base, (nruns + 1) * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_count, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_ev_base, nruns * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_chan_last, C * 4));
+    MFM_RUN_TRY(hipMemset(p->d_chan_last, 0xff, C * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_ctl, 2 * 4));
+    MFM_RUN_TRY(hipMemset(p->d_ctl, 0, 2 * 4));
+    MFM_RUN_TRY(hipMalloc(&p->d_totals, 4 * 8));
+    MFM_RUN_TRY(hipMemset(p->d_totals, 0, 4 * 8));
+    MFM_RUN_TRY(hipMalloc(&p->d_slots, (size_t)cap_events * sizeof(mfm_runpocsag_event)));
+    MFM_RUN_TRY(hipMalloc(&p->d_events, (size_t)cap_events * sizeof(mfm_runpocsag_event)));
+    MFM_RUN_TRY(hipDeviceSynchronize());
     return MFM_OK;
 }
 
@@ -989,36 +883,36 @@ int rp_process(mfm_runpocsag *p, const mfm_runrs_run *d_runs, const int16_t *d_p
         return MFM_E_INVAL;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RP_TRY(hipSetDevice(p->cfg.device));
-    if (p->have_call && p->last_stream != s) {
-        RP_TRY(hipStreamSynchronize(p->last_stream)); /* state lives on the device; keep calls ordered */
+    const int rb = mfm_run_call_begin(p, s);
+    if (rb != MFM_OK) {
+        return rb;
     }
     const uint32_t cur = p->cur;
     const RpCall A{ d_runs,         d_payload,     d_bits,         d_totals,       p->d_chan[cur], p->d_chan[cur ^ 1u], p->d_run_state,
                     p->d_seg,       p->d_plane,    p->d_summ,      p->d_seg_base, p->d_slot_base, p->d_blk_base,  p->d_count,          p->d_ev_base,
                     p->d_chan_last, p->d_ctl,      p->d_totals,    p->d_slots,     p->d_events,         p->d_bch,
                     p->cfg.nr_channels, p->cfg.max_runs, p->cfg.max_out_samples, (uint32_t)p->cap_events, (uint32_t)p->seg_words };
-    hipLaunchKernelGGL(rp_plan_kernel, dim3(1), dim3(RP_SCAN_THREADS), 0, s, A);
-    RP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rp_plan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     if (d_bits) { /* the word copy of mfm_run_bits.hip in the place of the slicer */
         const mfm_run_bits_slice B{ d_runs, d_bits, reinterpret_cast<const uint32_t *>(p->d_chan[cur]), p->d_blk_base, p->d_seg_base, p->d_ctl,
                                     p->d_seg, RP_STATE_WORDS, RP_TAIL_WORD0, MFM_RUNPOCSAG_HIST_WORDS };
         if (mfm_internal_run_bits_slice(&B, (uint32_t)p->max_blocks, s) != MFM_OK) {
-            RP_TRY(hipGetLastError());
+            MFM_RUN_TRY(hipGetLastError());
             return MFM_E_DEVICE;
         }
     } else {
         hipLaunchKernelGGL(rp_slice_kernel, dim3((uint32_t)p->max_blocks), dim3(RP_SLICE_NT), 0, s, A);
-        RP_TRY(hipGetLastError());
+        MFM_RUN_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(rp_match_kernel, dim3((uint32_t)p->max_blocks), dim3(RP_SLICE_NT), 0, s, A);
-    RP_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rp_walk_kernel, dim3(p->cfg.max_runs), dim3(64), 0, s, A);
-    RP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(rp_evscan_kernel, dim3(1), dim3(RP_SCAN_THREADS), 0, s, A);
-    RP_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rp_evscan_kernel, dim3(1), dim3(MFM_RUN_SCAN_THREADS), 0, s, A);
+    MFM_RUN_TRY(hipGetLastError());
     hipLaunchKernelGGL(rp_compact_kernel, dim3(p->cfg.max_runs), dim3(64), 0, s, A);
-    RP_TRY(hipGetLastError());
+    MFM_RUN_TRY(hipGetLastError());
     if (p->ends.on) { /* behind the walk, in front of the state kernel */
         const MfmRunEndsCall E{ d_runs, p->d_chan[cur], p->d_run_state, p->d_ctl, p->d_bch, p->cfg.nr_channels, p->cfg.max_runs };
         const int re = mfm_internal_run_ends_process(&p->ends, MFM_RUN_ENDS_POCSAG, &E, s);
@@ -1027,10 +921,8 @@ int rp_process(mfm_runpocsag *p, const mfm_runrs_run *d_runs, const int16_t *d_p
         }
     }
     hipLaunchKernelGGL(rp_state_kernel, dim3(p->cfg.nr_channels), dim3(128), 0, s, A);
-    RP_TRY(hipGetLastError());
-    p->cur ^= 1u;
-    p->last_stream = s;
-    p->have_call = true;
+    MFM_RUN_TRY(hipGetLastError());
+    mfm_run_call_end(p, s);
     return MFM_OK;
 }
 
@@ -1053,7 +945,7 @@ int mfm_runpocsag_process_bits_device(struct mfm_runpocsag *p, const struct mfm_
         return MFM_E_INVAL;
     }
     if (view->polarity != MFM_BITS_NEG) {
-        return rp_fail(MFM_E_INVAL, "the burst POCSAG stage needs MFM_BITS_NEG bits (bit = sample < 0)");
+        return mfm_run_fail(MFM_E_INVAL, "the burst POCSAG stage needs MFM_BITS_NEG bits (bit = sample < 0)");
     }
     return rp_process(p, view->d_runs, nullptr, view->d_bits, view->d_totals, stream);
 }
@@ -1067,19 +959,19 @@ int mfm_runpocsag_fetch(struct mfm_runpocsag *p, struct mfm_runpocsag_event *eve
     if (!p->have_call) {
         return MFM_OK;
     }
-    RP_TRY(hipSetDevice(p->cfg.device));
-    RP_TRY(hipStreamSynchronize(p->last_stream));
+    MFM_RUN_TRY(hipSetDevice(p->cfg.device));
+    MFM_RUN_TRY(hipStreamSynchronize(p->last_stream));
     uint64_t t[4];
-    RP_TRY(hipMemcpy(t, p->d_totals, sizeof(t), hipMemcpyDeviceToHost));
-    if (t[RP_T_OVERFLOW] || t[RP_T_INPUT]) {
-        return rp_fail(MFM_E_STATE, rp_refusal(t[RP_T_OVERFLOW], t[RP_T_INPUT]));
+    MFM_RUN_TRY(hipMemcpy(t, p->d_totals, sizeof(t), hipMemcpyDeviceToHost));
+    if (t[MFM_RUN_T_OVERFLOW] || t[MFM_RUN_T_INPUT]) {
+        return mfm_run_fail(MFM_E_STATE, rp_refusal(t[MFM_RUN_T_OVERFLOW], t[MFM_RUN_T_INPUT]));
     }
     *nr_events = (size_t)t[RP_T_EVENTS];
     if (t[RP_T_EVENTS] > max_events) {
         return MFM_E_NOMEM;
     }
     if (t[RP_T_EVENTS]) {
-        RP_TRY(hipMemcpy(events, p->d_events, (size_t)t[RP_T_EVENTS] * sizeof(mfm_runpocsag_event), hipMemcpyDeviceToHost));
+        MFM_RUN_TRY(hipMemcpy(events, p->d_events, (size_t)t[RP_T_EVENTS] * sizeof(mfm_runpocsag_event), hipMemcpyDeviceToHost));
     }
     return MFM_OK;
 }
@@ -1098,71 +990,41 @@ int mfm_runpocsag_device_view(struct mfm_runpocsag *p, const struct mfm_runpocsa
     return MFM_OK;
 }
 
-int mfm_runpocsag_fetch_state(struct mfm_runpocsag *p, struct mfm_runpocsag_state *state, size_t nr_channels)
-{
-    if (!p || !state || nr_channels != p->cfg.nr_channels) {
-        return MFM_E_INVAL;
-    }
-    RP_TRY(hipSetDevice(p->cfg.device));
-    if (p->have_call) {
-        RP_TRY(hipStreamSynchronize(p->last_stream));
-    }
-    RP_TRY(hipMemcpy(state, p->d_chan[p->cur], nr_channels * sizeof(mfm_runpocsag_state), hipMemcpyDeviceToHost));
-    return MFM_OK;
-}
-
 int mfm_hosttwin_runpocsag_state_check(uint32_t nr_channels, const struct mfm_runpocsag_state *state)
 {
-    if (!state || !nr_channels) {
-        return MFM_E_INVAL;
-    }
-    for (uint32_t c = 0; c < nr_channels; c++) {
-        if (const char *why = mfm_runpocsag_state_check(state[c])) {
-            char msg[224];
-            snprintf(msg, sizeof(msg), "burst POCSAG state, channel %u: %s", c, why);
-            return rp_fail(MFM_E_INVAL, msg);
-        }
-    }
-    return MFM_OK;
+    return mfm_run_state_check(nr_channels, state, "POCSAG", mfm_runpocsag_state_check);
+}
+
+int mfm_runpocsag_fetch_state(struct mfm_runpocsag *p, struct mfm_runpocsag_state *state, size_t nr_channels)
+{
+    return mfm_run_fetch_state(p, state, nr_channels);
 }
 
 int mfm_runpocsag_store_state(struct mfm_runpocsag *p, const struct mfm_runpocsag_state *state, size_t nr_channels)
 {
-    if (!p || !state || nr_channels != p->cfg.nr_channels) {
-        return MFM_E_INVAL;
-    }
-    const int ok = mfm_hosttwin_runpocsag_state_check(p->cfg.nr_channels, state);
-    if (ok != MFM_OK) {
-        return ok;
-    }
-    RP_TRY(hipSetDevice(p->cfg.device));
-    if (p->have_call) {
-        RP_TRY(hipStreamSynchronize(p->last_stream));
-    }
-    RP_TRY(hipMemcpy(p->d_chan[p->cur], state, nr_channels * sizeof(mfm_runpocsag_state), hipMemcpyHostToDevice));
-    return MFM_OK;
+    return mfm_run_store_state(p, state, nr_channels, mfm_hosttwin_runpocsag_state_check);
 }
 
 /* ---- the stretch-end report: kernels and launchers in mfm_run_ends.hip ---- */
 
 int mfm_runpocsag_set_end_report(struct mfm_runpocsag *p, int on)
 {
-    return mfm_run_ends_entry_set(p, MFM_RUN_ENDS_POCSAG, on, rp_fail);
+    return mfm_run_ends_entry_set(p, MFM_RUN_ENDS_POCSAG, on, mfm_run_fail);
 }
 
 int mfm_runpocsag_end_stretches_device(struct mfm_runpocsag *p, void *stream)
 {
-    return mfm_run_ends_entry_flush(p, MFM_RUN_ENDS_POCSAG, p ? p->d_bch : nullptr, stream, rp_fail);
+    return mfm_run_ends_entry_flush(p, MFM_RUN_ENDS_POCSAG, p ? p->d_bch : nullptr, stream, mfm_run_fail);
 }
 
 int mfm_runpocsag_fetch_ends(struct mfm_runpocsag *p, struct mfm_runpocsag_end *ends, size_t max_ends, size_t *nr_ends)
 {
-    return mfm_run_ends_entry_fetch(p, MFM_RUN_ENDS_POCSAG, ends, max_ends, nr_ends, rp_fail, rp_refusal);
+    return mfm_run_ends_entry_fetch(p, MFM_RUN_ENDS_POCSAG, ends, max_ends, nr_ends, mfm_run_fail, rp_refusal);
 }
 
 int mfm_runpocsag_ends_view(struct mfm_runpocsag *p, const struct mfm_runpocsag_end **d_ends, const uint64_t **d_end_totals)
 {
-    return mfm_run_ends_entry_view(p, d_ends, d_end_totals, rp_fail);
+    return mfm_run_ends_entry_view(p, d_ends, d_end_totals, mfm_run_fail);
 }
 
 } /* extern "C" */
@@ -1320,38 +1182,16 @@ int rp_twin_call(uint32_t nr_channels, uint32_t max_runs, uint32_t max_out_sampl
     if (rc != MFM_OK) {
         return rc;
     }
-    /* the plan pass */
-    const uint64_t n = totals[RP_RS_RUNS], E = totals[RP_RS_ELEMS];
-    uint64_t over = 0, err = 0;
-    if (totals[RP_RS_OVERFLOW] || totals[RP_RS_GATE]) {
-        err = MFM_RUNPOCSAG_IN_RUNRS;
-    } else if (E > (words ? (uint64_t)max_out_samples / 32u + max_runs : (uint64_t)max_out_samples)) {
-        err = MFM_RUNPOCSAG_IN_BAD_RUNS;
-    } else if (n > max_runs) {
-        over = MFM_RUNPOCSAG_OVER_RUNS;
+    uint64_t n, over, err, ts = 0; /* the plan pass */
+    if (!mfm_run_twin_plan(totals, nr_channels, max_runs, max_out_samples, state, runs, words ? (const void *)bits : (const void *)payload, words,
+                           [&](uint32_t nr_out) { ts += mfm_runpocsag_slots(nr_out); }, &n, &over, &err)) {
+        return MFM_E_INVAL;
     }
-    if (!over && !err) {
-        if ((n && !runs) || (E && !(words ? (const void *)bits : (const void *)payload))) {
-            return MFM_E_INVAL;
-        }
-        uint64_t to = 0, ts = 0;
-        for (uint64_t r = 0; r < n; r++) {
-            err |= mfm_runpocsag_check_run(runs[r], r ? &runs[r - 1] : nullptr, nr_channels, E, state, words);
-            to += runs[r].nr_out;
-            ts += mfm_runpocsag_slots(runs[r].nr_out);
-        }
-        if (to > max_out_samples) {
-            err |= MFM_RUNPOCSAG_IN_BAD_RUNS;
-        }
-        if (!err && ts > cap_events) {
-            over = MFM_RUNPOCSAG_OVER_EVENTS;
-        }
+    if (!err && ts > cap_events) {
+        over = MFM_RUNPOCSAG_OVER_EVENTS;
     }
     if (over || err) {
-        if (flags) {
-            *flags = (uint32_t)(over | (err << 8));
-        }
-        return rp_fail(MFM_E_STATE, rp_refusal(over, err));
+        return mfm_run_twin_refuse(over, err, flags, rp_refusal(over, err));
     }
     /* every run from the state the call started with (only a channel's first run reads it); the state its last run leaves */
     std::vector<mfm_runpocsag_event> out;
@@ -1445,7 +1285,7 @@ int mfm_hosttwin_runpocsag_call_bits(uint32_t nr_channels, uint32_t max_runs, ui
                                      size_t *nr_events, uint32_t *flags)
 {
     if (polarity != MFM_BITS_NEG) {
-        return rp_fail(MFM_E_INVAL, "the burst POCSAG stage needs MFM_BITS_NEG bits (bit = sample < 0)");
+        return mfm_run_fail(MFM_E_INVAL, "the burst POCSAG stage needs MFM_BITS_NEG bits (bit = sample < 0)");
     }
     return rp_twin_call(nr_channels, max_runs, max_out_samples, max_events, state, runs, nullptr, bits, true, totals, events, max_out,
                         nr_events, flags);

@@ -13,12 +13,13 @@
 
 #include "../../include/multifm_hip.h"
 #include "mfm_numerics.h"
+#include "mfm_run_stage.h"
 #include "mfm_runrs.h"
 
 namespace {
 
 constexpr uint32_t RR_NT = 256, RR_OPT = 4, RR_OPB = RR_NT * RR_OPT; /* FIR kernel: threads, outputs per thread / per workgroup */
-constexpr uint32_t RR_SCAN_THREADS = 1024;
+constexpr uint32_t RR_SCAN_THREADS = MFM_RUN_SCAN_THREADS; /* the block scan and a thread's slice are mfm_run_stage.h's */
 constexpr uint32_t RR_NONE = 0xffffffffu;                            /* d_chan_last: the channel has no run in this call */
 constexpr uint32_t RR_T_RUNS = 0, RR_T_ELEMS = 1, RR_T_OVERFLOW = 2, RR_T_GATE = 3; /* d_totals[], ours and the gate's */
 
@@ -112,34 +113,6 @@ __device__ __forceinline__ void rr_plan_body(const RrCall &A, const uint64_t *pa
     }
 }
 
-/* scan over the block (1024 threads); returns this thread's EXCLUSIVE prefix, *total = the block's sum */
-__device__ __forceinline__ uint64_t rr_block_scan(uint64_t v, uint64_t *lds, uint64_t *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), o);
-        if (lane >= (uint32_t)o) {
-            inc += ((uint64_t)hi << 32) | lo;
-        }
-    }
-    if (lane == 63) {
-        lds[wave] = inc;
-    }
-    __syncthreads();
-    uint64_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < RR_SCAN_THREADS / 64; i++) {
-        const uint64_t t = lds[i];
-        base += i < wave ? t : 0u;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
 /* BITS: out_offset and the total count 32-bit words of the bits payload (mfm_runrs_bit_words per run), not int16 elements */
 template <bool BITS>
 __device__ __forceinline__ void rr_scan_body(const RrCall &A)
@@ -158,9 +131,8 @@ __device__ __forceinline__ void rr_scan_body(const RrCall &A)
         return;
     }
     const uint64_t n = A.gtotals[RR_T_RUNS]; /* <= cap_runs < 2^32 */
-    const uint64_t per = (n + RR_SCAN_THREADS - 1) / RR_SCAN_THREADS;
-    const uint64_t r0 = threadIdx.x * per < n ? threadIdx.x * per : n;
-    const uint64_t r1 = r0 + per < n ? r0 + per : n;
+    uint64_t r0, r1;
+    mfm_run_slice(n, &r0, &r1);
     uint64_t so = 0, sb = 0, sq = 0;
     uint32_t sw = 0;
 #pragma unroll 1
@@ -173,18 +145,18 @@ __device__ __forceinline__ void rr_scan_body(const RrCall &A)
     /* the workgroup counts ride in the scan of the outputs: a run has at most nr_out / 1024 + 1 of them, so their sum over
      * fewer than 2^31 runs of fewer than 2^31 outputs stays below 2^32, and the outputs' sum below 2^62 */
     uint64_t to, tb, tq = 0;
-    uint64_t bo = rr_block_scan(so, lds, &to);
+    uint64_t bo = mfm_run_block_scan(so, lds, &to);
     uint64_t bb;
     if (BITS) {
         /* the words ride with the workgroup counts: both sums stay below 2^32 (at most to / 32 + n words, which is also why
          * they fit the bits payload when to is within out_cap; a sum beyond that is a refused call and never used) */
-        bb = rr_block_scan((sb & 0xffffffffull) | (sq << 32), lds, &tb);
+        bb = mfm_run_block_scan((sb & 0xffffffffull) | (sq << 32), lds, &tb);
         bo = bb >> 32;
         tq = tb >> 32;
         bb &= 0xffffffffull;
         tb &= 0xffffffffull;
     } else {
-        bb = rr_block_scan(sb, lds, &tb);
+        bb = mfm_run_block_scan(sb, lds, &tb);
     }
     /* run lists that are not a gate's (overlapping payload ranges) could ask for more than the output holds */
     const bool wrong = __syncthreads_or(sw != 0) != 0 || to > A.out_cap;
