@@ -2035,6 +2035,150 @@ int mfm_runmm_fetch_state(struct mfm_runmm *m, struct mfm_runmm_state *state, si
  * the next process call reads.  A state that fails gets MFM_E_INVAL with a message naming channel and field, and nothing is
  * written.  The result of the last call stays readable. */
 int mfm_runmm_store_state(struct mfm_runmm *m, const struct mfm_runmm_state *state, size_t nr_channels);
+/* The capacities fixed at create: max_runs as given, and max_decisions with the default filled in (max_out_samples / s +
+ * max_runs where the configuration said 0).  What a stage behind this one sizes itself from.  Either pointer may be NULL. */
+int mfm_runmm_get_capacity(struct mfm_runmm *m, uint32_t *max_runs, uint64_t *max_decisions);
+
+/*
+ * ---- Burst sync stage: sync words in the burst Mueller-Muller stage's decisions, on the device ------------------------------
+ * The consumer of the stage above: its input is what mfm_runmm_device_view returns (the run records, the dense int16 decisions,
+ * the totals), all read on the device, and its output is one bit per decision and one event wherever the last 32 bits of a
+ * stretch are a sync word of a small table, or nearly one.  One pass says per stretch which word was seen, where and in which
+ * polarity; the bits let a consumer cut the frames behind a sync out of 1/16 of the bytes.
+ *
+ * Stretch means what it means for the burst Mueller-Muller stage.  Run r continues its channel's stretch exactly when
+ * MFM_RUNRS_BEGINS is clear in runs[r].flags, otherwise it begins a new one.
+ *
+ * Rule.  The reference's only consumer of mm_process, pager/test/test_mueller_muller.c:130-136, with a table and the
+ * complement.  Per stretch a fresh register shr = 0; for every decision d of the stretch, in order, shr = (shr << 1) | bit,
+ * where bit = !(d > 0) with MFM_RUNSYNC_BIT_NOT_POS (the reference's, :132) and bit = (d > 0) with MFM_RUNSYNC_BIT_POS.
+ * MFM_RUNSYNC_BIT_NOT_POS is not the sign bit MFM_BITS_NEG takes: d == 0 is the one value where the two differ (bit 1 here, 0
+ * there).  After decision number n (counted from 0 within the stretch) the lowest word index k that matches is looked for, the
+ * word itself before its complement: words[k] matches when popcount(words[k] ^ shr) <= max_distance, and with
+ * MFM_RUNSYNC_F_EITHER its complement when popcount(~words[k] ^ shr) <= max_distance.  max_distance <= 15 keeps a register from
+ * matching a word and its complement at once.  A match is one event; there is at most one event per decision.  The reference
+ * compares with "< 4": max_distance = 3.
+ *
+ * The register is tested from the stretch's first decision on, with zeros above the bits shifted in so far, exactly as the
+ * reference's loop tests it: there is no warm-up of 32 decisions, and a word with leading zeros can match before 32 decisions
+ * have passed.
+ *
+ * No lag.  Events do not depend on how the stream was cut into calls or runs; an event is reported by the call and run that
+ * holds decision n.
+ *
+ * State.  Per channel, on the device (struct mfm_runsync_state below, which the host twin carries too): the register, the
+ * decisions of the stretch so far and the stretch's first window.  Two state buffers are used in turn: a channel's first run of
+ * a call reads the old state, its last run leaves the new one.  A channel without a run keeps its state.  A run with nr_dec == 0
+ * changes nothing and still begins or continues its stretch.
+ *
+ * Result.  It replaces the previous call's.
+ *   run records  one struct mfm_runsync_run per input run, in the Mueller-Muller stage's order
+ *   bits         one bit per decision: decision j of a run is bit j % 32 of word word_offset + j / 32.  A run owns (nr_dec + 31) /
+ *                32 words, ascending and without gaps; a run with nr_dec == 0 owns none; the bits at and above nr_dec in a run's
+ *                last word are 0 - the convention of mfm_runrs_process_bits_device.  Capacity: max_decisions / 32 + max_runs words.
+ *   events       struct mfm_runsync_event, dense, in run order and ascending in dec within a run; a run's events are contiguous
+ *                (nr_events of them, behind those of the runs in front).  Order and offsets come from a scan, never from atomics.
+ *   totals       d_totals[4] = { runs, events, overflow, input error }
+ *
+ * Refused calls produce nothing, leave the per-channel state untouched and raise a flag that mfm_runsync_fetch reports as
+ * MFM_E_STATE with a message:
+ *   overflow     MFM_RUNSYNC_OVER_RUNS: more runs than max_runs; MFM_RUNSYNC_OVER_DECISIONS: more decisions than max_decisions;
+ *                MFM_RUNSYNC_OVER_EVENTS: the call's events exceed a caller-chosen max_events - by the count, which is known
+ *                before an event is placed, so nothing is written past the capacity
+ *   input error  MFM_RUNSYNC_IN_RUNMM: the Mueller-Muller stage's totals carry overflow or an input error;
+ *                MFM_RUNSYNC_IN_OUT_OF_STEP: a continuing run that is not its channel's first of the call, or whose first_dec is
+ *                not the state's decs, or whose channel has no stretch; MFM_RUNSYNC_IN_BAD_RUNS: a channel >= nr_channels,
+ *                channels not ascending, a beginning run whose first_dec is not 0, a dec_offset that is not the running sum of
+ *                nr_dec or a range that ends past the totals.  All of these are checked before a decision is read.
+ *
+ * Refusals at create (MFM_E_INVAL with a message, before a device is looked for): nr_words of 0 or above 8, max_distance above
+ * 15, an unknown bit_rule, flags other than MFM_RUNSYNC_F_EITHER, capacities that are zero or reach 2^28 runs or 2^31 decisions
+ * or events.
+ */
+#define MFM_RUNSYNC_BIT_NOT_POS 0u     /* bit = !(d > 0): test_mueller_muller.c:132 */
+#define MFM_RUNSYNC_BIT_POS 1u         /* bit = (d > 0) */
+#define MFM_RUNSYNC_F_EITHER 1u        /* mfm_runsync_config.flags: the complement of every word is tested too */
+#define MFM_RUNSYNC_OVER_RUNS 1u
+#define MFM_RUNSYNC_OVER_DECISIONS 2u
+#define MFM_RUNSYNC_OVER_EVENTS 4u
+#define MFM_RUNSYNC_IN_RUNMM 1u
+#define MFM_RUNSYNC_IN_OUT_OF_STEP 2u
+#define MFM_RUNSYNC_IN_BAD_RUNS 4u
+
+struct mfm_runsync_run {        /* 40 bytes */
+    uint64_t first_window;      /* the Mueller-Muller run's */
+    uint64_t word_offset;       /* in 32-bit words of the bits */
+    uint64_t first_dec;         /* index of the run's first decision within its stretch */
+    uint32_t channel;
+    uint32_t nr_dec;
+    uint32_t flags;             /* MFM_RUNRS_BEGINS, copied */
+    uint32_t nr_events;
+};
+
+struct mfm_runsync_event {      /* 32 bytes */
+    uint64_t dec;               /* the decision that completed the word, counted within its stretch */
+    uint32_t channel;
+    uint32_t run;               /* index in this call's run list */
+    uint32_t seen;              /* the register */
+    uint32_t word_index;
+    uint32_t distance;          /* bits that differ from the word, or from its complement */
+    uint32_t inverted;          /* 0: the word, 1: its complement */
+};
+
+/* the per-channel state, on the device and in the host twin: all zero at the start of a stream.  What a stored state must
+ * satisfy: csrc/mfm_runsync.h (mfm_runsync_state_check) */
+struct mfm_runsync_state {      /* 24 bytes */
+    uint64_t stretch_window;    /* first window of the stretch */
+    uint64_t decs;              /* decisions of the stretch so far */
+    uint32_t shr;               /* the register after the last of them */
+    uint32_t has_stretch;       /* 0: nothing to continue */
+};
+
+struct mfm_runsync; /* opaque */
+
+struct mfm_runsync_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_runs;          /* the burst Mueller-Muller stage's capacities (mfm_runmm_get_capacity) */
+    uint32_t max_decisions;
+    uint32_t max_events;        /* per call, all channels; 0 = max_decisions, cannot overflow: at most one event per decision */
+    uint32_t nr_words;          /* 1 .. 8 */
+    uint32_t words[8];
+    uint32_t max_distance;      /* 0 .. 15 */
+    uint32_t bit_rule;          /* MFM_RUNSYNC_BIT_NOT_POS or MFM_RUNSYNC_BIT_POS */
+    uint32_t flags;             /* 0 or MFM_RUNSYNC_F_EITHER */
+};
+
+int mfm_runsync_create(struct mfm_runsync **ps, const struct mfm_runsync_config *cfg);
+void mfm_runsync_destroy(struct mfm_runsync **ps);
+/*
+ * Search the decisions of one burst Mueller-Muller call: d_runs, d_decisions and d_totals are what mfm_runmm_device_view
+ * returned.  Work is queued on `stream` (the Mueller-Muller call's, or one ordered behind it); no host synchronisation and no
+ * count read on the host: launches are sized from the capacities fixed at create, surplus workgroups return after reading the
+ * totals.  The three arrays are read until the queued work has run.
+ */
+int mfm_runsync_process_device(struct mfm_runsync *s, const struct mfm_runmm_run *d_runs, const int16_t *d_decisions, const uint64_t *d_totals,
+                               void *stream);
+/*
+ * Wait for the last call, read its totals and copy the used part of the three arrays.  MFM_E_NOMEM when max_runs, max_words or
+ * max_events is too small (nothing copied, *nr_runs, *nr_words and *nr_events say what is needed); MFM_E_STATE with a message
+ * when the call was refused (nothing copied, the state did not move: the same input in a call that is right is right again).
+ */
+int mfm_runsync_fetch(struct mfm_runsync *s, struct mfm_runsync_run *runs, size_t max_runs, size_t *nr_runs, uint32_t *bits, size_t max_words,
+                      size_t *nr_words, struct mfm_runsync_event *events, size_t max_events, size_t *nr_events);
+/* For consumers that stay on the device: the last call's run records, bits, events and d_totals[4], valid until the next call.
+ * Any of the four may be NULL. */
+int mfm_runsync_device_view(struct mfm_runsync *s, const struct mfm_runsync_run **d_runs, const uint32_t **d_bits,
+                            const struct mfm_runsync_event **d_events, const uint64_t **d_totals);
+/* The capacities fixed at create: runs, bit words (max_decisions / 32 + max_runs) and events.  Any pointer may be NULL. */
+int mfm_runsync_get_capacity(struct mfm_runsync *s, uint32_t *max_runs, uint64_t *max_words, uint64_t *max_events);
+/* Wait for the last call and copy the per-channel state it left, state[nr_channels]: what the host twin carries. */
+int mfm_runsync_fetch_state(struct mfm_runsync *s, struct mfm_runsync_state *state, size_t nr_channels);
+/* The way back: waits for the queued work, validates every channel (csrc/mfm_runsync.h states the conditions) and writes what
+ * the next process call reads.  A state that fails gets MFM_E_INVAL with a message naming channel and field, and nothing is
+ * written.  The result of the last call stays readable. */
+int mfm_runsync_store_state(struct mfm_runsync *s, const struct mfm_runsync_state *state, size_t nr_channels);
 
 /* bch_code_decode (pager/bch_code.c:307-398) on n words in place; rc[i] = its return value (0 or 1). */
 int mfm_bch3121_decode_device(uint32_t *d_words, uint8_t *d_rc, size_t n, int device, void *stream);
@@ -2417,6 +2561,18 @@ int mfm_hosttwin_runmm_call(const struct mfm_runmm_config *cfg, struct mfm_runmm
 /* the validation mfm_runmm_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
  * channel and field that fail (csrc/mfm_runmm.h) */
 int mfm_hosttwin_runmm_state_check(uint32_t nr_channels, const struct mfm_runmm_state *state);
+/* host twin of one mfm_runsync_process_device call and its fetch, no device needed (cfg->device is not read): runs / decisions /
+ * totals are one burst Mueller-Muller call's result (totals[4] as its d_totals), state [cfg->nr_channels] is read and updated in
+ * place.  Same refusals: MFM_E_INVAL with the message create gives; MFM_E_STATE with the message mfm_runsync_fetch gives and
+ * *flags = overflow | input error << 8; MFM_E_NOMEM when max_out_runs, max_out_words or max_out_events is too small (*nr_runs,
+ * *nr_words, *nr_events = needed); on any error nothing is written, the state included. */
+int mfm_hosttwin_runsync_call(const struct mfm_runsync_config *cfg, struct mfm_runsync_state *state, const struct mfm_runmm_run *runs,
+                              const int16_t *decisions, const uint64_t *totals, struct mfm_runsync_run *out_runs, size_t max_out_runs,
+                              size_t *nr_runs, uint32_t *bits, size_t max_out_words, size_t *nr_words, struct mfm_runsync_event *events,
+                              size_t max_out_events, size_t *nr_events, uint32_t *flags);
+/* the validation mfm_runsync_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
+ * channel and field that fail (csrc/mfm_runsync.h) */
+int mfm_hosttwin_runsync_state_check(uint32_t nr_channels, const struct mfm_runsync_state *state);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

@@ -5,7 +5,7 @@
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
            [--floor-windows M --open-ratio R --close-ratio R [--warmup N]]
            [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-dc-pole POLE]
-           [--gate-ais | --gate-pocsag | --gate-flex | --gate-mm SPB[,KW,KM,MARGIN]]] | --gate-route routes.json]]
+           [--gate-ais | --gate-pocsag | --gate-flex | --gate-mm SPB[,KW,KM,MARGIN] [--gate-sync WORDS]]] | --gate-route routes.json]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -111,6 +111,28 @@ mfm_mm on the full rows, 4/5 with 41 taps, 131 072 input samples per channel at 
 scene (a squelch at the median window energy) and all-open, the two chains alternating in one process in rotating order; and
 whether a sample of the burst decisions (the first runs of a call) equalled the host twin's.
 
+--gate-sync WORD[,WORD...][/DIST][,either] (only with --gate-mm) queues the burst sync stage (mfm_runsync_*) behind the burst
+Mueller-Muller stage on the same stream: per stretch a fresh 32-bit register takes d > 0 ? 0 : 1 of every decision
+(pager/test/test_mueller_muller.c:130-136), and wherever it is within DIST bits (default 3, at most 15) of one of the one to eight
+words - with ",either" of a word's complement too - DIR/sync.jsonl gets a line:
+
+    {"channel": 3, "first_window": 4, "first_sample": 4000, "dec": 331, "word": "7cd215d8", "distance": 0, "inverted": 0, "seen": "7cd215d8"}
+
+(first_window and first_sample: where the stretch began; dec: the decision that completed the word, counted within the stretch), and
+once a stretch is over - the channel's next one begins, or the run ends - a summary line with its decisions and the count per word:
+
+    {"channel": 3, "first_window": 4, "first_sample": 4000, "decisions": 1210, "events": {"7cd215d8": 2}}
+
+A route of stage mm may carry "sync": {"words": [2094142936], "distance": 3, "either": false} with the same meaning (words required).
+Without the flag nothing the tool writes changes.
+
+    python tools/level_scan.py --bench-runsync --window 4096 [--reps 6] [--inner 10]
+
+prints one line ("runsync_stage"): the chain of --bench-runmm with and without the sync stage behind it, and the resampler alone, on
+the same three masks at 64 and 1024 channels, alternating in one process: means, standard deviations, the sync stage's cost as
+the difference with its standard error and the verdict of tools/exp/ab.py's two-standard-error rule, and that cost over the
+Mueller-Muller stage's own call (the chain minus the resampler); and whether every call's result equalled the host twin's.
+
 --gate-ends (with --gate-ais, --gate-pocsag or --gate-flex, with or without --gate-bits, or with --gate-route, where it applies to
 every route's stage) switches the stage's stretch-end report on, ends the open stretches behind the gate's flush and writes
 DIR/ends.jsonl beside the events (under a route: DIR/NAME/ends.jsonl), one line per stretch: channel, first_sample (the stretch's
@@ -134,7 +156,7 @@ burst chain only the runs of its own channels.  FILE is JSON:
 
 up to eight routes; stage is ais, pocsag, flex, mm or none (the resampler alone; a route of stage mm carries "mm": {"spb": 20.8333,
 "kw": 0.0001, "km": 0.000004, "margin": 0.05}, spb required, as --gate-mm, writes mm.jsonl and chNNNN.mm.s16, takes no bits and has
-no stretch-end report); resample and taps as --gate-resample and
+no stretch-end report, and may carry "sync" as --gate-sync); resample and taps as --gate-resample and
 --resample-taps; dc_pole and bits (true / false) are optional and follow the rules of --gate-dc-pole and --gate-bits (bits only
 with ais or pocsag, never with dc_pole); a channel may stand in one route at most, and a channel in none is gated but goes no
 further.  Each route runs burst resampler -> stage on its view of the router, on the engine's stream, the flush call included, and
@@ -260,6 +282,31 @@ def check_mm(mm, where):
     return dict(MM_DEFAULTS, **mm)
 
 
+def parse_gate_sync(text):
+    """--gate-sync WORD[,WORD...][/DIST][,either] as the "sync" object of a route of stage mm"""
+    either = text.endswith(",either")
+    body = text[:-len(",either")] if either else text
+    words, _, dist = body.partition("/")
+    try:
+        sync = {"words": [int(w, 0) for w in words.split(",")], "distance": int(dist) if dist else 3, "either": either}
+    except ValueError:
+        raise SystemExit(f"--gate-sync takes WORD[,WORD...][/DIST][,either], not {text!r}")
+    return check_sync(sync, "--gate-sync")
+
+
+def check_sync(sync, where):
+    """the "sync" object of a route of stage mm (or of --gate-sync): words, 1 .. 8 of 32 bits, and optionally distance (0 .. 15) and
+    either"""
+    ok = isinstance(sync, dict) and "words" in sync and not set(sync) - {"words", "distance", "either"}
+    ok = ok and isinstance(sync["words"], list) and 1 <= len(sync["words"]) <= 8
+    ok = ok and all(isinstance(w, int) and not isinstance(w, bool) and 0 <= w <= 0xFFFFFFFF for w in sync["words"])
+    ok = ok and isinstance(sync.get("distance", 3), int) and 0 <= sync.get("distance", 3) <= 15 and isinstance(sync.get("either", False), bool)
+    if not ok:
+        raise SystemExit(f"{where}: \"sync\" must be an object with words (1 .. 8 numbers of 32 bits) and optionally distance (0 .. 15) "
+                         f"and either (true or false), not {sync!r}")
+    return {"words": list(sync["words"]), "distance": sync.get("distance", 3), "either": sync.get("either", False)}
+
+
 class Routes(list):
     """the routes of a --gate-route file; `local` is the file's "local" key"""
     local = False
@@ -295,11 +342,15 @@ def read_routes(path, nr_channels):
             raise SystemExit(f"--gate-route: route {name} needs resample (I/D) and taps (a JSON file whose lpfCoeffs are the taps)")
         if r["stage"] == "mm":
             r["mm"] = check_mm(r.get("mm"), f"--gate-route: route {name}")
+            if "sync" in r:
+                r["sync"] = check_sync(r["sync"], f"--gate-route: route {name}")
             if r.get("bits"):
                 raise SystemExit(f"--gate-route: route {name}: bits needs stage ais or pocsag: the burst Mueller-Muller stage reads PCM values, "
                                  "not sign bits")
         elif "mm" in r:
             raise SystemExit(f"--gate-route: route {name}: \"mm\" belongs to stage mm, not to stage {r['stage']}")
+        elif "sync" in r:
+            raise SystemExit(f"--gate-route: route {name}: \"sync\" belongs to stage mm, not to stage {r['stage']}")
         if r.get("bits") and r["stage"] not in ("ais", "pocsag"):
             raise SystemExit(f"--gate-route: route {name}: bits needs stage ais or pocsag: the burst FLEX stage reads PCM values, not sign bits")
         if r.get("bits") and r.get("dc_pole") is not None:
@@ -329,12 +380,13 @@ class BurstChain:
     route's of the run router - and the files the two write under out_dir; view() returns the run list's device view"""
 
     def __init__(self, pkg, out_dir, window, nr_channels, max_in_samples, preroll, device, view, resample, taps_file, dc_pole=None,
-                 stage=None, bits=False, caps=None, channels=None, bound=None, ends=False, mm=None):
+                 stage=None, bits=False, caps=None, channels=None, bound=None, ends=False, mm=None, sync=None):
         """caps and channels: behind a packed or a local route of the run router, its route_caps() - the chain is sized to the route -
         and its route_channels(), which turn the route-local channel numbers of everything fetched back into true ones.  bound:
         behind a local route, the router's bound_view(): the resampler then reads the gate's payload through its view entries.
         ends (--gate-ends): the stage's stretch-end report, one line per stretch in ends.jsonl (the mm stage has none: nothing is
-        pending when a stretch ends).  mm: stage mm's spb, kw, km and margin"""
+        pending when a stretch ends).  mm: stage mm's spb, kw, km and margin.  sync (--gate-sync): the burst sync stage behind
+        stage mm, its words, distance and either"""
         b = self.b = pkg.binding
         self.out_dir, self.window, self.view, self.bound = out_dir, window, view, bound
         self.channels = None if channels is None else np.asarray(channels, np.uint32)
@@ -358,6 +410,10 @@ class BurstChain:
         elif stage:
             self.st = {"ais": pkg.RunAis, "pocsag": pkg.RunPocsag, "flex": pkg.RunFlex}[stage].behind(self.rr, device=device)
             self.st_index = open(os.path.join(out_dir, stage + ".jsonl"), "w")
+        self.sy, self.sy_index, self.sy_words, self.sy_stretch = None, None, [], {}
+        if stage == "mm" and sync:
+            self.sy = pkg.RunSync.behind(self.st, sync["words"], max_distance=sync["distance"], either=sync["either"], device=device)
+            self.sy_index, self.sy_words = open(os.path.join(out_dir, "sync.jsonl"), "w"), ["%08x" % w for w in sync["words"]]
         if stage in ("pocsag", "flex"):
             self.pages_index = open(os.path.join(out_dir, "pages.jsonl"), "w")
         self.ends_index, self.stretches, self.cut_by_mode = None, 0, {}
@@ -383,6 +439,8 @@ class BurstChain:
             rr.process_device(*self.view(), stream=stream)
         if st:
             st.process_device(*rr.device_view(), stream=stream)
+        if self.sy:
+            self.sy.process_device(*st.device_view(), stream=stream)
 
     def write(self):
         """fetch the last call's results and append them to the files"""
@@ -401,6 +459,9 @@ class BurstChain:
         if self.stage == "mm":
             runs, decisions = self.st.fetch()
             self.write_mm(self.true_channels(runs), decisions)
+        if self.sy:
+            runs, _, events = self.sy.fetch()
+            self.write_sync(self.true_channels(runs), self.true_channels(events))
         if self.ends_index:
             self.write_ends(self.true_channels(self.st.fetch_ends()))
 
@@ -436,6 +497,11 @@ class BurstChain:
     def close(self):
         for hp in self.pagers.values():
             hp.close()
+        if self.sy:
+            for c in sorted(self.sy_stretch):
+                self.write_sync_summary(c)
+            self.sy_index.close()
+            self.sy.close()
         for f in (self.rs_index, self.st_index, self.pages_index, self.ends_index):
             if f:
                 f.close()
@@ -490,6 +556,30 @@ class BurstChain:
             self.st_index.write(json.dumps({"channel": c, "first_sample": int(r["first_window"]) * self.window,
                                             "first_dec": int(r["first_dec"]), "nr_dec": int(r["nr_dec"]), "begins": int(r["flags"]) & 1,
                                             "file_offset": at}) + "\n")
+
+    def write_sync(self, runs, events):
+        """a line per event, and a summary line per stretch once the channel's next stretch begins (or the run ends)"""
+        at = 0
+        for r in runs:
+            c = int(r["channel"])
+            if int(r["flags"]) & 1:
+                if c in self.sy_stretch:
+                    self.write_sync_summary(c)
+                self.sy_stretch[c] = [int(r["first_window"]), 0, [0] * len(self.sy_words)]
+            st = self.sy_stretch[c]
+            st[1] += int(r["nr_dec"])
+            for e in events[at:at + int(r["nr_events"])]:
+                k = int(e["word_index"])
+                st[2][k] += 1
+                self.sy_index.write(json.dumps({"channel": c, "first_window": st[0], "first_sample": st[0] * self.window, "dec": int(e["dec"]),
+                                                "word": self.sy_words[k], "distance": int(e["distance"]), "inverted": int(e["inverted"]),
+                                                "seen": "%08x" % int(e["seen"])}) + "\n")
+            at += int(r["nr_events"])
+
+    def write_sync_summary(self, c):
+        fw, nd, counts = self.sy_stretch.pop(c)
+        self.sy_index.write(json.dumps({"channel": c, "first_window": fw, "first_sample": fw * self.window, "decisions": nd,
+                                        "events": dict(zip(self.sy_words, counts))}) + "\n")
 
     def write_resampled(self, runs, payload):
         for r in runs:
@@ -557,7 +647,8 @@ def scan(a):
         stage = "ais" if a.gate_ais else "pocsag" if a.gate_pocsag else "flex" if a.gate_flex else "mm" if a.gate_mm else None
         chains.append(BurstChain(pkg, a.gate_out, a.window, len(chans), max_in, int(a.gate_preroll), a.device, gate.device_view,
                                  a.gate_resample, a.resample_taps, dc_pole=a.gate_dc_pole, stage=stage, bits=a.gate_bits, ends=a.gate_ends,
-                                 mm=parse_gate_mm(a.gate_mm) if a.gate_mm else None))
+                                 mm=parse_gate_mm(a.gate_mm) if a.gate_mm else None,
+                                 sync=parse_gate_sync(a.gate_sync) if a.gate_sync else None))
     if routes is not None:
         if not gate or iq_form:
             raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
@@ -580,7 +671,7 @@ def scan(a):
             chains.append(BurstChain(pkg, os.path.join(a.gate_out, r["name"]), a.window, len(chans), max_in, int(a.gate_preroll), a.device,
                                      lambda k=k: router.device_view(k), r["resample"], r["taps"], dc_pole=r.get("dc_pole"),
                                      stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits")), ends=a.gate_ends,
-                                     mm=r.get("mm"), **sized))
+                                     mm=r.get("mm"), sync=r.get("sync"), **sized))
 
     def run_stages():
         """the router, where there is one, and every chain on the gate's last result, all on the engine's stream"""
@@ -2216,6 +2307,116 @@ def bench_runmm(a, pkg, torch):
     print(json.dumps(out))
 
 
+def bench_runsync(a, pkg, torch):
+    """burst resampler -> burst Mueller-Muller stage with and without the burst sync stage behind it, on the device view one gate
+    call left (the masks and shapes of bench_runmm); the variants alternate in one process in rotating order.  The yardstick is the
+    Mueller-Muller stage's own call on the same mask: chain with it minus the resampler alone.  The events of a call are compared
+    with the host twin's on the decisions fetched"""
+    b = pkg.binding
+    W, I, D = a.window, 4, 5
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    taps = np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16)
+    spb = float(np.float32(38400.0) / np.float32(1200.0))
+    mm = dict(MM_DEFAULTS, spb=spb)
+    words = [0x7CD215D8, 0xA6C6AAAA, 0x870C78F3, 0xB0684E97]   # POCSAG's sync word and three more, as FLEX's would stand beside it
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "runsync_stage", "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I, "decimate": D,
+           "reps": a.reps, "calls_per_rep": a.inner, "samples_per_bit": spb, "words": ["%08x" % w for w in words], "max_distance": 3,
+           "either": True, "segment": b.RUNSYNC_SEGMENT}
+    twin_ok = True
+    for nch in (64, 1024):
+        host = _busy_pocsag_rows(pkg, nch, n)
+        d_rows = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "scene": scene["open"]}
+        keep, recs = [], {"scene": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        rm = pkg.RunMm.behind(rr, spb, mm["kw"], mm["km"], margin=mm["margin"])
+        rs = pkg.RunSync.behind(rm, words, max_distance=3, either=True)
+        res = {}
+        for name in ("all_closed", "scene", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_rs():
+                rr.process_device(*view)
+
+            def run_mm():
+                rr.process_device(*view)
+                rm.process_device(*rr.device_view())
+
+            def run_sync():
+                rr.process_device(*view)
+                rm.process_device(*rr.device_view())
+                rs.process_device(*rm.device_view())
+
+            variants = [("sync", run_sync), ("mm", run_mm), ("rs", run_rs)]
+            for _, fn in variants:
+                timed(fn, 3)
+            run_sync()
+            sruns, sbits, sev = rs.fetch()
+            mruns, decs = rm.fetch()
+            wr, wb, we = b.hosttwin_runsync_call(b.hosttwin_runsync_state(nch), mruns, decs, words, max_distance=3, either=True)
+            twin_ok = twin_ok and sruns.tobytes() == wr.tobytes() and sbits.tobytes() == wb.tobytes() and sev.tobytes() == we.tobytes()
+            got_t = {v: [] for v, _ in variants}
+            for rep_ in range(a.reps):
+                j = rep_ % len(variants)
+                for vname, fn in variants[j:] + variants[:j]:
+                    got_t[vname].append(timed(fn, a.inner))
+            (sm, ssd), (mmm, msd), (rm_, rsd) = _stats(got_t["sync"]), _stats(got_t["mm"]), _stats(got_t["rs"])
+            diff, diff_se = sm - mmm, math.sqrt((ssd * ssd + msd * msd) / a.reps)
+            mm_call = mmm - rm_
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "runs": int(len(mruns)), "decisions_per_call": int(decs.size),
+                         "events_per_call": int(sev.size), "chain_with_sync_ms": sm, "chain_with_sync_sd": ssd, "chain_ms": mmm, "chain_sd": msd,
+                         "resampler_ms": rm_, "resampler_sd": rsd, "sync_ms": diff, "sync_se": diff_se,
+                         "verdict": "costs" if diff > 2 * diff_se else "neutral" if abs(diff) <= 2 * diff_se else "faster",
+                         "mm_call_ms": mm_call, "sync_over_mm_call": diff / mm_call if mm_call > 0 else None}
+            gate.close()
+        out["channels_%d" % nch] = res
+        for o in (rs, rm, rr, sq):
+            o.close()
+        del d_rows, keep
+    out["equals_twin"] = bool(twin_ok)
+    print(json.dumps(out))
+
+
+def bench_runsync_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runsync needs the GPU: there is no CPU path to time")
+    bench_runsync(a, pkg, torch)
+
+
 def bench_runmm_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -2273,6 +2474,8 @@ def main():
     ap.add_argument("--gate-flex", action="store_true", help="decode FLEX on the resampled runs on the device (with --gate-resample to 16 000 Hz)")
     ap.add_argument("--gate-mm", default=None, metavar="SPB[,KW,KM,MARGIN]",
                     help="Mueller-Muller clock recovery on the resampled runs on the device (with --gate-resample): the decisions of every run")
+    ap.add_argument("--gate-sync", default=None, metavar="WORD[,WORD...][/DIST][,either]",
+                    help="with --gate-mm: the burst sync stage behind it, sync words in the decisions; one line per event in sync.jsonl")
     ap.add_argument("--gate-bits", action="store_true",
                     help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
     ap.add_argument("--gate-ends", action="store_true",
@@ -2288,6 +2491,8 @@ def main():
     ap.add_argument("--bench-runflex", action="store_true", help="the runflex_stage line alone")
     ap.add_argument("--bench-runmm", action="store_true",
                     help="the runmm_stage line: burst resampler -> burst Mueller-Muller against the full-row chain at 64 and 1024 channels")
+    ap.add_argument("--bench-runsync", action="store_true",
+                    help="the runsync_stage line: the burst Mueller-Muller chain with and without the burst sync stage at 64 and 1024 channels")
     ap.add_argument("--bench-runbits", action="store_true", help="the runbits_stage line of --bench alone")
     ap.add_argument("--bench-runroute", action="store_true", help="the runroute_stage line alone: the run router at 64 and 1024 channels")
     ap.add_argument("--bench-runroute-pack", action="store_true",
@@ -2312,6 +2517,8 @@ def main():
         return bench_runflex_alone(a)
     if a.bench_runmm:
         return bench_runmm_alone(a)
+    if a.bench_runsync:
+        return bench_runsync_alone(a)
     if a.bench_runends:
         return bench_runends_alone(a)
     if a.bench_runbits:
@@ -2330,6 +2537,10 @@ def main():
         raise SystemExit("--floor-windows, --open-ratio and --close-ratio go together: the adaptive squelch needs all three")
     if a.warmup is not None and a.floor_windows is None:
         raise SystemExit("--warmup needs --floor-windows: it is the adaptive squelch's warm-up")
+    if a.gate_sync:
+        if not a.gate_mm:
+            raise SystemExit("--gate-sync needs --gate-mm: the burst sync stage takes the burst Mueller-Muller stage's decisions")
+        parse_gate_sync(a.gate_sync)
     if a.gate_mm:
         if a.gate_route:
             raise SystemExit("--gate-route excludes --gate-mm: a route of stage mm names its own loop")

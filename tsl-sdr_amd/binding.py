@@ -96,6 +96,10 @@ ABI_SYMBOLS = [
     "mfm_runrs_process_view_device", "mfm_runrs_process_bits_view_device",
     "mfm_runmm_create", "mfm_runmm_destroy", "mfm_runmm_process_device", "mfm_runmm_fetch", "mfm_runmm_device_view",
     "mfm_runmm_fetch_state", "mfm_runmm_store_state", "mfm_hosttwin_runmm_call", "mfm_hosttwin_runmm_state_check",
+    "mfm_runmm_get_capacity",
+    "mfm_runsync_create", "mfm_runsync_destroy", "mfm_runsync_process_device", "mfm_runsync_fetch", "mfm_runsync_device_view",
+    "mfm_runsync_get_capacity", "mfm_runsync_fetch_state", "mfm_runsync_store_state", "mfm_hosttwin_runsync_call",
+    "mfm_hosttwin_runsync_state_check",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -337,6 +341,26 @@ RUNMM_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("dec_offset", "<u8"), ("fi
                             ("nr_dec", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 RUNMM_STATE_DTYPE = np.dtype([("outs", "<u8"), ("decs", "<u8"), ("stretch_window", "<u8"), ("w", "<f4"), ("m", "<f4"),
                               ("last_sample", "<f4"), ("next_offset", "<u4"), ("has_stretch", "<u4"), ("reserved", "<u4")])
+
+
+class RunSyncConfig(C.Structure):
+    """struct mfm_runsync_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("max_runs", C.c_uint32),
+                ("max_decisions", C.c_uint32), ("max_events", C.c_uint32), ("nr_words", C.c_uint32), ("words", C.c_uint32 * 8),
+                ("max_distance", C.c_uint32), ("bit_rule", C.c_uint32), ("flags", C.c_uint32)]
+
+
+MFM_RUNSYNC_BIT_NOT_POS, MFM_RUNSYNC_BIT_POS = 0, 1                                 # bit = !(d > 0) / bit = (d > 0)
+MFM_RUNSYNC_F_EITHER = 1                                                            # the complement of every word too
+MFM_RUNSYNC_OVER_RUNS, MFM_RUNSYNC_OVER_DECISIONS, MFM_RUNSYNC_OVER_EVENTS = 1, 2, 4    # d_totals[2]
+MFM_RUNSYNC_IN_RUNMM, MFM_RUNSYNC_IN_OUT_OF_STEP, MFM_RUNSYNC_IN_BAD_RUNS = 1, 2, 4     # d_totals[3]
+RUNSYNC_SEGMENT = 1024   # decisions of a run one wave packs and matches (csrc/mfm_runsync.h)
+# numpy views of struct mfm_runsync_run (40 bytes, per run), mfm_runsync_event (32 bytes) and mfm_runsync_state (24 bytes, per channel)
+RUNSYNC_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("word_offset", "<u8"), ("first_dec", "<u8"), ("channel", "<u4"),
+                              ("nr_dec", "<u4"), ("flags", "<u4"), ("nr_events", "<u4")])
+RUNSYNC_EVENT_DTYPE = np.dtype([("dec", "<u8"), ("channel", "<u4"), ("run", "<u4"), ("seen", "<u4"), ("word_index", "<u4"),
+                                ("distance", "<u4"), ("inverted", "<u4")])
+RUNSYNC_STATE_DTYPE = np.dtype([("stretch_window", "<u8"), ("decs", "<u8"), ("shr", "<u4"), ("has_stretch", "<u4")])
 
 
 def runmm_min_step(km, error_min):
@@ -727,6 +751,19 @@ def load_library():
     lib.mfm_hosttwin_runmm_call.argtypes = [C.POINTER(RunMmConfig), vp, vp, vp, vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp,
                                             C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runmm_state_check.argtypes = [C.c_uint32, vp]
+    lib.mfm_runmm_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.mfm_runsync_create.argtypes = [C.POINTER(vp), C.POINTER(RunSyncConfig)]
+    lib.mfm_runsync_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runsync_destroy.restype = None
+    lib.mfm_runsync_process_device.argtypes = [vp, vp, vp, vp, vp]
+    lib.mfm_runsync_fetch.argtypes = [vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp, vp, C.c_size_t, szp]
+    lib.mfm_runsync_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runsync_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.mfm_runsync_fetch_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_runsync_store_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_hosttwin_runsync_call.argtypes = [C.POINTER(RunSyncConfig), vp, vp, vp, vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp,
+                                              vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
+    lib.mfm_hosttwin_runsync_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                               C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -2745,6 +2782,14 @@ class RunMm:
             self._raise(rc, "mfm_runmm_device_view")
         return r.value, d.value, t.value
 
+    def capacity(self):
+        """(max_runs, max_decisions) fixed at create, the default filled in: what a stage behind this one sizes itself from"""
+        r, d = C.c_uint32(), C.c_uint64()
+        rc = self.lib.mfm_runmm_get_capacity(self.h, C.byref(r), C.byref(d))
+        if rc < 0:
+            self._raise(rc, "mfm_runmm_get_capacity")
+        return r.value, d.value
+
     def fetch_state(self):
         """the per-channel state the last call left (RUNMM_STATE_DTYPE [C]): what the host twin carries"""
         out = np.zeros(self.nr_channels, RUNMM_STATE_DTYPE)
@@ -2811,6 +2856,165 @@ def hosttwin_runmm_state_check(state):
     rc = lib.mfm_hosttwin_runmm_state_check(st.shape[0], st.ctypes.data)
     if rc < 0:
         raise MfmError(rc, "mfm_hosttwin_runmm_state_check", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
+
+
+def _runsync_config(nr_channels, max_runs, max_decisions, words, max_distance, bit_rule, either, max_events, device, flags, abi_version):
+    ws = [int(w) & 0xFFFFFFFF for w in words]
+    arr = (C.c_uint32 * 8)(*ws[:8])
+    fl = (MFM_RUNSYNC_F_EITHER if either else 0) if flags is None else flags
+    return RunSyncConfig(abi_version, device, nr_channels, max_runs, max_decisions, max_events, len(ws), arr, max_distance, bit_rule, fl)
+
+
+class RunSync:
+    """mfm_runsync: the decisions of a RunMm's device view against a table of sync words, a fresh 32-bit register per stretch;
+    RUNSYNC_RUN_DTYPE records, one bit per decision in words aligned per run, and RUNSYNC_EVENT_DTYPE events.  max_runs and
+    max_decisions are the burst Mueller-Muller stage's capacities (RunSync.behind reads them); max_events 0 cannot overflow."""
+
+    def __init__(self, nr_channels, max_runs, max_decisions, words, max_distance=3, bit_rule=MFM_RUNSYNC_BIT_NOT_POS, either=False,
+                 max_events=0, device=0, flags=None, abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        self.cfg = _runsync_config(nr_channels, max_runs, max_decisions, words, max_distance, bit_rule, either, max_events, device, flags,
+                                   abi_version)
+        rc = self.lib.mfm_runsync_create(C.byref(self.h), C.byref(self.cfg))
+        if rc < 0:
+            self._raise(rc, "mfm_runsync_create")
+        self.nr_channels = nr_channels
+
+    @classmethod
+    def behind(cls, run_mm, words, **kwargs):
+        """a stage sized for everything one call of `run_mm` can produce"""
+        max_runs, max_decisions = run_mm.capacity()
+        return cls(run_mm.nr_channels, max_runs, max_decisions, words, **kwargs)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runsync_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_decisions, d_totals, stream=None):
+        """the three addresses of RunMm.device_view(), after its process_device on the same stream"""
+        rc = self.lib.mfm_runsync_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_decisions), C.c_void_p(d_totals), C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runsync_process_device")
+
+    def fetch(self, max_runs=None, max_words=None, max_events=None):
+        """(runs RUNSYNC_RUN_DTYPE, bits uint32, events RUNSYNC_EVENT_DTYPE) of the last call.  With a buffer too small:
+        MfmError(MFM_E_NOMEM) whose `needed` attribute is the (runs, words, events) that would fit"""
+        nr, nw, ne = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        if max_runs is None or max_words is None or max_events is None:
+            rc = self.lib.mfm_runsync_fetch(self.h, None, 0, C.byref(nr), None, 0, C.byref(nw), None, 0, C.byref(ne))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below
+                self._raise(rc, "mfm_runsync_fetch")
+            max_runs = nr.value if max_runs is None else max_runs
+            max_words = nw.value if max_words is None else max_words
+            max_events = ne.value if max_events is None else max_events
+        runs = np.zeros(max(max_runs, 1), RUNSYNC_RUN_DTYPE)
+        bits = np.zeros(max(max_words, 1), np.uint32)
+        evs = np.zeros(max(max_events, 1), RUNSYNC_EVENT_DTYPE)
+        rc = self.lib.mfm_runsync_fetch(self.h, runs.ctypes.data, max_runs, C.byref(nr), bits.ctypes.data, max_words, C.byref(nw),
+                                        evs.ctypes.data, max_events, C.byref(ne))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runsync_fetch")
+            except MfmError as err:
+                err.needed = (nr.value, nw.value, ne.value)
+                raise
+        return runs[:nr.value].copy(), bits[:nw.value].copy(), evs[:ne.value].copy()
+
+    def device_view(self):
+        """(d_runs, d_bits, d_events, d_totals): device addresses of the last call's run records, bit words, events and the four
+        uint64 totals (runs, events, overflow, input error)"""
+        r, b, e, t = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runsync_device_view(self.h, C.byref(r), C.byref(b), C.byref(e), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runsync_device_view")
+        return r.value, b.value, e.value, t.value
+
+    def capacity(self):
+        """(max_runs, max_words, max_events) fixed at create"""
+        r, w, e = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.mfm_runsync_get_capacity(self.h, C.byref(r), C.byref(w), C.byref(e))
+        if rc < 0:
+            self._raise(rc, "mfm_runsync_get_capacity")
+        return r.value, w.value, e.value
+
+    def fetch_state(self):
+        """the per-channel state the last call left (RUNSYNC_STATE_DTYPE [C]): what the host twin carries"""
+        out = np.zeros(self.nr_channels, RUNSYNC_STATE_DTYPE)
+        rc = self.lib.mfm_runsync_fetch_state(self.h, out.ctypes.data, self.nr_channels)
+        if rc < 0:
+            self._raise(rc, "mfm_runsync_fetch_state")
+        return out
+
+    def store_state(self, state, nr_channels=None):
+        """mfm_runsync_store_state: what the next process call continues from.  Validated first: MfmError(MFM_E_INVAL) with a
+        message naming channel and field, and nothing written"""
+        st = np.ascontiguousarray(state, dtype=RUNSYNC_STATE_DTYPE) if state is not None else None
+        n = self.nr_channels if nr_channels is None else nr_channels
+        assert st is None or st.shape == (n,)
+        rc = self.lib.mfm_runsync_store_state(self.h, st.ctypes.data if st is not None else None, n)
+        if rc < 0:
+            self._raise(rc, "mfm_runsync_store_state")
+
+
+def hosttwin_runsync_state(nr_channels):
+    """the host twin's per-channel state at the start of a stream: RUNSYNC_STATE_DTYPE [C], all zero (no stretch)"""
+    return np.zeros(nr_channels, RUNSYNC_STATE_DTYPE)
+
+
+def hosttwin_runsync_call(state, runs, decisions, words, max_distance=3, bit_rule=MFM_RUNSYNC_BIT_NOT_POS, either=False, totals=None,
+                          max_runs=None, max_decisions=None, max_events=0, max_out_runs=None, max_out_words=None, max_out_events=None,
+                          flags=None, abi_version=MFM_ABI_VERSION):
+    """mfm_hosttwin_runsync_call: one call of the burst sync stage on the CPU.  state (hosttwin_runsync_state) is updated in place;
+    runs RUNMM_RUN_DTYPE and decisions int16 are one burst Mueller-Muller call's result, totals its four totals (default: the
+    lengths, no flags); max_runs / max_decisions / max_events are the configuration's (default: what the call needs); returns
+    (runs RUNSYNC_RUN_DTYPE, bits, events).  A refused call raises MfmError(MFM_E_STATE) with a `flags` attribute (overflow | input
+    error << 8)"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNSYNC_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNMM_RUN_DTYPE).reshape(-1)
+    dd = np.ascontiguousarray(decisions, dtype=np.int16).reshape(-1)
+    t = np.array([rr.size, dd.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_decisions = max(dd.size, 1) if max_decisions is None else max_decisions
+    cfg = _runsync_config(state.shape[0], max_runs, max_decisions, words, max_distance, bit_rule, either, max_events, 0, flags, abi_version)
+    max_out_runs = rr.size if max_out_runs is None else max_out_runs
+    max_out_words = dd.size // 32 + rr.size if max_out_words is None else max_out_words
+    max_out_events = dd.size if max_out_events is None else max_out_events
+    out_r = np.zeros(max(max_out_runs, 1), RUNSYNC_RUN_DTYPE)
+    out_b = np.zeros(max(max_out_words, 1), np.uint32)
+    out_e = np.zeros(max(max_out_events, 1), RUNSYNC_EVENT_DTYPE)
+    nr, nw, ne, fl = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runsync_call(C.byref(cfg), state.ctypes.data, rr.ctypes.data if rr.size else None,
+                                       dd.ctypes.data if dd.size else None, t.ctypes.data, out_r.ctypes.data, max_out_runs, C.byref(nr),
+                                       out_b.ctypes.data, max_out_words, C.byref(nw), out_e.ctypes.data, max_out_events, C.byref(ne),
+                                       C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runsync_call", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.flags = (nr.value, nw.value, ne.value), fl.value
+        raise err
+    return out_r[:nr.value].copy(), out_b[:nw.value].copy(), out_e[:ne.value].copy()
+
+
+def hosttwin_runsync_state_check(state):
+    """mfm_hosttwin_runsync_state_check: what RunSync.store_state validates, on the CPU"""
+    st = np.ascontiguousarray(state, dtype=RUNSYNC_STATE_DTYPE).reshape(-1)
+    lib = load_library()
+    rc = lib.mfm_hosttwin_runsync_state_check(st.shape[0], st.ctypes.data)
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runsync_state_check", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
 
 
 def hosttwin_runpocsag_state(nr_channels):

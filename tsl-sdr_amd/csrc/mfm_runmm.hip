@@ -507,6 +507,20 @@ int mfm_runmm_device_view(struct mfm_runmm *m, const struct mfm_runmm_run **d_ru
     return MFM_OK;
 }
 
+int mfm_runmm_get_capacity(struct mfm_runmm *m, uint32_t *max_runs, uint64_t *max_decisions)
+{
+    if (!m) {
+        return MFM_E_INVAL;
+    }
+    if (max_runs) {
+        *max_runs = m->cfg.max_runs;
+    }
+    if (max_decisions) {
+        *max_decisions = m->cap_decs;
+    }
+    return MFM_OK;
+}
+
 int mfm_runmm_fetch_state(struct mfm_runmm *m, struct mfm_runmm_state *state, size_t nr_channels)
 {
     return mfm_run_fetch_state(m, state, nr_channels);
