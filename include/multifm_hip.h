@@ -63,7 +63,8 @@ extern "C" {
 
 /* flags for mfm_engine_config::flags */
 #define MFM_F_DEVICE_ONLY 0x1u /* keep outputs in HBM; no host mirror, fetch() unavailable */
-#define MFM_F_TIMING 0x2u      /* bracket every kernel launch with HIP events */
+#define MFM_F_TIMING 0x2u      /* bracket every kernel launch with HIP events (an engine with two compute streams reads the
+                                  kernel's own stamps instead: mfm_stats::kernel_ms) */
 #define MFM_F_FORCE_DOT2 0x4u  /* run the v_dot2 (packed int16 VALU) kernel even where the matrix-core kernel applies:
                                   both produce the same bits; parity tests and A/B timing select it here */
 #define MFM_F_FORCE_MFMA_V1 0x8u /* where both matrix-core kernels apply, run the first-generation one (31-output column
@@ -86,8 +87,13 @@ extern "C" {
                                   it and finds its rotator position from the stream's output count), so the next launch's
                                   workgroups take the slots the current one's shorter chunks free up instead of waiting for
                                   its last tile and a dispatch.  mfm_engine_stream() then returns the stream of the most
-                                  recent launch; per-launch durations (MFM_F_TIMING) include the time a launch waits for
-                                  slots and are no longer kernel time.  Ignored by the other kernels. */
+                                  recent launch, and the engine goes on alternating after the stream has been handed out
+                                  (without the flag it alternates only until then: mfm_engine_stream).  The carry of an
+                                  alternating launch of int16 blocks on mfm_kernel_v3.hip is copied at submit time, behind the
+                                  block's producer and behind no channel kernel, into a ring of the engine's own from which the
+                                  next launch reads it; 8-bit blocks and the long-filter kernels copy it on the next launch's
+                                  stream.  Per-launch durations (MFM_F_TIMING) of an engine with two streams are the kernel's
+                                  own stamps (mfm_stats::kernel_ms).  Ignored by the other kernels. */
 #define MFM_F_V3L_ONE_ROW_BLOCK 0x400u /* long filters on the second generation (mfm_kernel_v3l.hip): one row block (8 channels) per
                                   wave - slices of 64 channels - also where two would fit (slices of 128: the default for more
                                   than 64 channels when two row blocks' taps fit 128 registers); same bits; parity tests, A/B timing */
@@ -142,7 +148,15 @@ struct mfm_stats {
     uint64_t samples_in;       /* wideband samples accepted */
     uint64_t outputs;          /* outputs produced per channel */
     uint64_t launches;         /* kernel launches */
-    double kernel_ms;          /* sum of the durations of `timed_launches` launches (MFM_F_TIMING), HIP events */
+    double kernel_ms;          /* sum of the durations of `timed_launches` launches (MFM_F_TIMING): HIP event pairs on an engine
+                                  with one compute stream.  On an engine with two (MFM_F_OVERLAP, or by itself:
+                                  mfm_engine_stream) no event pairs are recorded - a pair around a launch that shares the chip
+                                  with the one before it measures its wait for workgroup slots - and a duration is what the
+                                  kernel stamped itself: the 100 MHz reference ticks of its LONGEST WORKGROUP'S own run time
+                                  (mfm_engine_get_launch_cycles), not a span on a stream.  Consecutive launches overlap by
+                                  their ragged ends, so the mean of these may exceed the step period; a speed claim rests on
+                                  the step time (bench.py: ms_per_step), not on kernel_ms.  A stamp that left the readable
+                                  half of the stamp ring before it was folded is not counted in timed_launches. */
     uint32_t nr_channels;
     uint32_t nr_taps;
     uint32_t outputs_per_tile; /* kernel geometry, informational */
@@ -170,6 +184,12 @@ struct mfm_stats {
                                   MFM_F_SLICE_128); 0: the v_dot2 kernel */
     uint64_t submits;          /* blocks accepted (mfm_engine_submit / push); with coalesce_samples several of them share a launch */
     uint64_t pending_samples;  /* samples accepted and not yet launched (coalesce_samples; mfm_engine_flush launches them) */
+    uint64_t overlapped_launches; /* of `launches`: those that went to the other compute stream than the launch before them
+                                  and left their carry to a copy of the engine's own, so that the next launch's workgroups
+                                  moved into their ragged end (MFM_F_OVERLAP, or by itself: mfm_engine_stream) */
+    uint32_t pinned;           /* 1: the engine's stream has been handed out (mfm_engine_stream) or the engine belongs to a
+                                  device group, and MFM_F_OVERLAP is not set: one compute stream */
+    uint32_t reserved2;        /* 0 */
 };
 
 /* Size in bytes of one input staging buffer for this configuration and tap count (coalesce_samples = 0). */
@@ -268,7 +288,9 @@ int mfm_engine_last_output_device(struct mfm_engine *e, void **d_pcm, size_t *st
                                   void **d_iq);
 
 /* What the most recent launch read: device address of its [history tail | blocks] and the sample count (self-checks that
- * re-run a launch's input through a reference; valid until nbuf - 1 further launches have been queued). */
+ * re-run a launch's input through a reference; valid until nbuf - 1 further launches have been queued).  A launch that took
+ * its first samples from the engine's carry ring (MFM_F_OVERLAP) leaves the buffer's front stale: the call then waits for that
+ * launch and puts them there before it returns.  Producer-side call. */
 int mfm_engine_last_launch_input(struct mfm_engine *e, void **d_in, size_t *nr_samples, int *format);
 
 /* coalesce_samples: launch what has been accepted and not yet launched (MFM_E_BUSY when every output slot holds an
@@ -303,8 +325,9 @@ int mfm_engine_seek(struct mfm_engine *e, uint64_t outputs_before);
 
 int mfm_engine_get_stats(struct mfm_engine *e, struct mfm_stats *st);
 
-/* MFM_F_TIMING: durations (ms, HIP events on the compute stream) of the most recent launches, oldest first; at most
- * `cap` and at most the last 4096.  Returns how many were written. */
+/* MFM_F_TIMING: durations (ms; HIP events on the compute stream, or - on an engine with two compute streams - the kernel's
+ * own stamps, mfm_stats::kernel_ms) of the most recent timed launches, oldest first; at most `cap` and at most the last
+ * 4096.  Returns how many were written. */
 size_t mfm_engine_get_launch_ms(struct mfm_engine *e, float *dst, size_t cap);
 /* MFM_F_TIMING, second-generation kernels: the last launches' durations in the shader's own clocks, oldest first - the
  * longest workgroup's s_memtime (shader-clock ticks) and s_memrealtime (100 MHz reference ticks) difference, stamped by the
@@ -315,8 +338,18 @@ size_t mfm_engine_get_launch_ms(struct mfm_engine *e, float *dst, size_t cap);
  * kernels).  Either array may be NULL. */
 size_t mfm_engine_get_launch_cycles(struct mfm_engine *e, uint64_t *shader_ticks, uint64_t *ref_ticks, size_t cap);
 
-/* The engine's compute stream (hipStream_t) - with MFM_F_OVERLAP the one the most recent launch went to - for callers that
- * order their own work after it. */
+/* The engine's compute stream (hipStream_t), for callers that order their own work after it: THE stream every later launch
+ * is ordered on (with MFM_F_OVERLAP: the one the most recent launch went to, and the next call may return the other).
+ *
+ * Handing the stream out PINS the engine.  An engine alternates its launches between two compute streams without being
+ * asked (as MFM_F_OVERLAP does, early carry included) while nobody can tell: int16 blocks on mfm_kernel_v3.hip,
+ * MFM_F_DEVICE_ONLY, two input buffers (no coalesce_samples), a launch that fills the workgroup slots more than once, not a
+ * member of a device group - and this function not called yet.  Such an engine can only be observed through
+ * mfm_engine_sync(), fetch and the stats calls, which wait for both streams.  The first call here joins the two (the stream
+ * returned waits for the other one's last launch), and from then on the engine launches on that one stream, with the carry
+ * in the kernel.  A caller that asks before its first submit gets an engine that never alternated; mfm_stats::pinned and
+ * ::overlapped_launches tell.  (mfm_engine_last_output_device() returns no stream and pins nothing: order consumers through
+ * this call.)  Producer-side call. */
 void *mfm_engine_stream(struct mfm_engine *e);
 
 const char *mfm_strerror(int err);

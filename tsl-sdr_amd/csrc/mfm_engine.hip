@@ -135,8 +135,9 @@ struct mfm_engine {
                                                           in_free[i], or the timing event recorded at the same point of
                                                           the stream.  acquire_input() waits on it, the coalescing policy
                                                           queries it */
+    hipStream_t in_free_on[kMaxInBufs] = { nullptr, nullptr, nullptr }; /* the stream in_free_wait[i] was recorded on */
     hipEvent_t in_ready = nullptr;
-    int nbuf = 2;      /* 3 with coalesce_samples: one being read, one queued behind it, one being filled */
+    int nbuf = 2;     /* 3 with coalesce_samples: one being read, one queued behind it, one being filled */
     int cur_in = 0;
     uint32_t tail = 0; /* unconsumed samples at the front of d_in[cur_in] (behind `hist`): the history the next outputs need */
     uint32_t hist = 0; /* second-generation kernel: already consumed samples kept in front of them - the decimation once the
@@ -184,6 +185,26 @@ struct mfm_engine {
     hipEvent_t tail_done[kMaxInBufs] = { nullptr, nullptr, nullptr }; /* overlap: the carry out of buffer i has been copied */
     bool tail_pending[kMaxInBufs] = { false, false, false };
     hipEvent_t kernel_done = nullptr;
+    /* Two streams without being asked (include/multifm_hip.h, mfm_engine_stream): an engine whose stream nobody has been
+     * handed can only be observed through sync / stats, which wait for both streams.  `pinned`: the stream has been handed
+     * out (or the engine belongs to a device group) - one stream from then on, unless MFM_F_OVERLAP asks for two. */
+    bool auto_alt = false, pinned = false;
+    uint64_t overlapped = 0; /* launches that left their carry to the copy below and so did not hold back the next one */
+    /* Early carry (int16 blocks on mfm_kernel_v3.hip): when a launch alternates, the next launch's [hist | history tail] is
+     * copied at submit time by a one-workgroup kernel on s_in - behind the producer of this block and behind no channel
+     * kernel - into a slot of d_ring, and the next launch reads it from there (mfm_launch_v3::head).  Pass r of
+     * launch_locked() reads buffer r % nbuf and, if its head is in the ring, slot r % (nbuf + 1).
+     * NO EVENT GUARDS A SLOT: pass r writes slot (r + 1) % (nbuf + 1), which pass r + 1 - (nbuf + 1) = r - nbuf read last;
+     * that pass also read buffer (r - nbuf) % nbuf = r % nbuf, the buffer of pass r, and acquire_input() has waited on the
+     * host for its kernel's end (in_free) before the producer of pass r's block was allowed to write - so before this
+     * submit.  (Two buffers: slot (r + 1) % 3 was last read by launch r - 2.) */
+    uint32_t *d_ring = nullptr;
+    uint32_t ring_slot = 0;          /* samples per slot: 2 * D + T + 16 */
+    uint64_t pass = 0;               /* launch_locked() passes since the stream's start: buffer pass % nbuf is being filled */
+    const uint32_t *head = nullptr;  /* the [hist | tail] of the buffer being filled is here, not at its front ... */
+    hipEvent_t head_ev = nullptr;    /* ... once this has happened */
+    const uint32_t *last_head = nullptr; /* the most recent launch read its first last_head_n samples from here */
+    uint32_t last_head_n = 0;
 
     /* stream bookkeeping */
     int parity = 0;
@@ -203,6 +224,10 @@ struct mfm_engine {
     unsigned long long *d_cyc = nullptr; /* [kCycleRing][2] */
     std::vector<float> launch_ms; /* ring of the last kLaunchRing launch durations */
     uint64_t launch_ms_n = 0;     /* durations folded so far */
+    /* An event pair around a launch that shares the chip with the one before it measures its wait for workgroup slots: an
+     * engine with two compute streams records none, and a timed launch's duration is the kernel's own stamp in d_cyc (100 MHz
+     * reference ticks of its longest workgroup).  The 0-based numbers of the timed launches not yet folded, oldest first. */
+    std::vector<uint64_t> stamp_pending;
 };
 
 namespace {
@@ -385,19 +410,62 @@ int division_selftest(int device, int variant)
 }
 
 
+void fold_duration(mfm_engine *e, float ms)
+{
+    e->kernel_ms += ms;
+    if (e->launch_ms.size() < kLaunchRing) {
+        e->launch_ms.resize(kLaunchRing);
+    }
+    e->launch_ms[e->launch_ms_n % kLaunchRing] = ms;
+    e->launch_ms_n++;
+}
+
+/* the stamps of the timed launches of a two-stream engine (mfm_engine::stamp_pending).  all: every one of them, after waiting
+ * for the compute streams; else those of launches that are known to have ended - a launch eight launches back has, since
+ * acquire_input() waits for the launch nbuf passes back.  A stamp that has left the readable half of the ring (its slot is
+ * zeroed by the launch kCycleRing / 2 behind its own) is dropped: that launch is not counted as timed. */
+int fold_stamps(mfm_engine *e, bool all)
+{
+    if (e->stamp_pending.empty() || !e->d_cyc) {
+        e->stamp_pending.clear();
+        return MFM_OK;
+    }
+    if (all) {
+        HIP_TRY(hipStreamSynchronize(e->cs[0]));
+        if (e->cs[1] != e->cs[0]) {
+            HIP_TRY(hipStreamSynchronize(e->cs[1]));
+        }
+    }
+    std::vector<unsigned long long> ring(kCycleRing * 2);
+    HIP_TRY(hipMemcpy(ring.data(), e->d_cyc, ring.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    size_t done = 0;
+    for (; done < e->stamp_pending.size(); done++) {
+        const uint64_t seq = e->stamp_pending[done];
+        if (!all && seq + 8u > e->launches) {
+            break;
+        }
+        const uint64_t tag = ((seq + 1u) & 0xffffffu) << 40, mask = (1ull << 40) - 1ull;
+        const unsigned long long b = ring[2 * (seq % kCycleRing) + 1];
+        if (seq + kCycleRing / 2u >= e->launches && (b & ~mask) == tag) {
+            fold_duration(e, (float)((double)(b & mask) / 1e5));
+        }
+    }
+    e->stamp_pending.erase(e->stamp_pending.begin(), e->stamp_pending.begin() + (ptrdiff_t)done);
+    return MFM_OK;
+}
+
 int fold_timing(mfm_engine *e, bool all)
 {
+    /* (stamps are older than event pairs: an engine goes from two streams to one - when it is pinned - and never back) */
+    if (all || (!e->stamp_pending.empty() && e->launches - e->stamp_pending.front() >= kCycleRing / 4u)) {
+        MFM_TRY(fold_stamps(e, all));
+    }
     while (e->t_tail < e->t_head && (all || e->t_head - e->t_tail >= (uint64_t)kTimingPairs)) {
         const int i = (int)(e->t_tail % kTimingPairs);
         HIP_TRY(hipEventSynchronize(e->t1[i]));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, e->t0[i], e->t1[i]));
-        e->kernel_ms += ms;
-        if (e->launch_ms.size() < kLaunchRing) {
-            e->launch_ms.resize(kLaunchRing);
-        }
-        e->launch_ms[e->launch_ms_n % kLaunchRing] = ms;
-        e->launch_ms_n++;
+        fold_duration(e, ms);
         e->t_tail++;
     }
     return MFM_OK;
@@ -453,6 +521,11 @@ void free_device(mfm_engine *e)
     free_dev(e->d_info);
     free_dev(e->d_rot);
     free_dev(e->d_cyc);
+    free_dev(e->d_ring);
+    e->head = e->last_head = nullptr;
+    e->head_ev = nullptr; /* (one of tail_done[]) */
+    e->last_head_n = 0;
+    e->stamp_pending.clear();
     free_dev(e->d_lut);
     for (mfm_chan_state *&s : e->d_state) {
         free_dev(s);
@@ -565,6 +638,16 @@ __global__ __launch_bounds__(256) void mfm_unpack_kernel(const uint16_t *raw, ui
             out = mfm_pack16((int8_t)(two & 0xffu), (int8_t)(two >> 8));
         }
         dst[s] = out;
+    }
+}
+
+/* The early carry's copy (mfm_engine::d_ring) and its way back to a buffer's front: n samples - about a kilobyte -, one
+ * workgroup, no LDS, a few registers, so that it finds a place on a chip whose every SIMD is full of channel-kernel waves as
+ * soon as one of them leaves.  (A hipMemcpyAsync is a shader copy as well, with a dispatch and a barrier packet around it.) */
+__global__ __launch_bounds__(256) void mfm_carry_kernel(const uint32_t *src, uint32_t *dst, uint32_t n)
+{
+    for (uint32_t i = threadIdx.x; i < n; i += 256u) {
+        dst[i] = src[i];
     }
 }
 
@@ -785,14 +868,30 @@ static int commit_locked(struct mfm_engine *e)
     HIP_TRY(hipStreamCreateWithFlags(&e->s_compute, hipStreamNonBlocking));
     e->cs[0] = e->cs[1] = e->s_last = e->s_compute;
     e->ncs = 1;
-    if ((e->cfg.flags & MFM_F_OVERLAP) && v3) {
+    e->si = 0;
+    e->pinned = false;
+    e->overlapped = 0;
+    e->pass = 0;
+    /* int16 blocks run on mfm_kernel_v3.hip (not the long-filter file): the early carry applies */
+    const bool v3s = v3 && p.fmt[MFM_IN_CS16].kfn && p.fmt[MFM_IN_CS16].V.layout != 3u;
+    /* two streams by itself: where nobody can tell (the stream has not been handed out: mfm_engine_stream) and the other
+     * conditions of include/multifm_hip.h hold; the per-launch ones are launch_locked()'s */
+    e->auto_alt = v3s && dev_only && 2 == e->nbuf && !(e->cfg.flags & MFM_F_OVERLAP);
+    if (((e->cfg.flags & MFM_F_OVERLAP) && v3) || e->auto_alt) {
         HIP_TRY(hipStreamCreateWithFlags(&e->cs[1], hipStreamNonBlocking));
         e->ncs = 2;
         for (int i = 0; i < kMaxInBufs; i++) {
             HIP_TRY(hipEventCreateWithFlags(&e->tail_done[i], hipEventDisableTiming));
         }
+        if (v3s) {
+            e->ring_slot = 2u * p.D + p.T + 16u;
+            HIP_TRY(hipMalloc(&e->d_ring, (size_t)(e->nbuf + 1) * e->ring_slot * sizeof(uint32_t)));
+        }
     }
-    HIP_TRY(hipStreamCreateWithFlags(&e->s_out, hipStreamNonBlocking));
+    /* (the process has few hardware queues, and streams that share one serialise: a device-only engine copies nothing out) */
+    if (!dev_only) {
+        HIP_TRY(hipStreamCreateWithFlags(&e->s_out, hipStreamNonBlocking));
+    }
     HIP_TRY(hipEventCreateWithFlags(&e->in_ready, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&e->kernel_done, hipEventDisableTiming));
 
@@ -970,7 +1069,8 @@ int launch_locked(mfm_engine *e)
      * moves into); a launch of one tile per slot or less costs more in the extra packets of the carry (a copy, two events)
      * than it gains: it keeps the carry in the kernel and the next launch stays behind it on the same stream. */
     bool two = false;
-    if (e->ncs > 1u && v3 && n_new) {
+    /* (an engine that alternates without having been asked to does so for int16 blocks only: 8-bit blocks keep one stream) */
+    if (e->ncs > 1u && v3 && n_new && !(e->auto_alt && raw8)) {
         const uint32_t ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT, slots = 256u * e->plan.v_wg_per_cu;
         /* ... and only when what its carry copy reads - the last consumed row and the unconsumed samples behind it - lies
          * behind the [hist | tail] front of this buffer, which the previous launch's carry wrote on the OTHER stream: the
@@ -979,7 +1079,43 @@ int launch_locked(mfm_engine *e)
         two = (uint64_t)ntiles * e->plan.v_nslices > slots && (uint64_t)n_new * D >= (uint64_t)e->tail + D;
     }
     hipStream_t S_after = two ? e->cs[e->si ^ 1u] : S;
-    if (e->ncs > 1u && !two && e->in_free_wait[nxt]) {
+    /* early carry: an alternating launch of int16 blocks on mfm_kernel_v3.hip leaves the next launch's [hist | tail] in the
+     * carry ring instead of at the front of the next buffer (mfm_engine::d_ring) */
+    const bool early = two && !raw8 && e->d_ring != nullptr;
+    /* chunks of consecutive tiles, `rounds` per workgroup slot and slice, lengths equal to within one tile
+     * (a chunk pays one extra column group) */
+    uint32_t v_ntiles = 0, v_nchunks = 0, v_nitems = 0, v_slots = 0;
+    if (v3 && n_new) {
+        const FormatPlan &f = e->plan.fmt[fmt];
+        v_ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT;
+        v_slots = 256u * f.wg_per_cu;
+        /* (a multiple of 8: the items are dealt chunk-major over the eight XCDs - item = 8 * (chunk / 8 * nslices + slice) +
+         * chunk % 8, mfm3_decode_item - so a chunk count that is not one leaves holes in the last group of eight, the grid
+         * overflows the slots and a few workgroups run a SECOND chunk while the others are done: with 3, 5, 6 or 12 slices
+         * (130-192, 257-320, ... channels) a launch took up to twice as long as its work, profiles/r06_ab_chunking.txt) */
+        uint32_t per_slice = std::max(1u, v_slots / f.V.nslices);
+        per_slice = per_slice >= 8u ? per_slice & ~7u : per_slice;
+        /* one chunk per slot: shorter chunks (3..10 tiles, several rounds) were 2-6 % slower on MI355X */
+        v_nchunks = std::min(v_ntiles, per_slice);
+        v_nitems = ((v_nchunks + 7u) / 8u) * 8u * f.V.nslices;
+    }
+    if (e->head) {
+        /* this buffer's [hist | tail] is in the ring: whoever reads it - the kernel or the copy below - comes behind its copy */
+        HIP_TRY(hipStreamWaitEvent(S, e->head_ev, 0));
+        /* The kernel takes it from there when it alternates (a launch that does not carries the tail itself, out of the
+         * buffer's front, or there is no kernel at all) and when nothing but the prologue of a first chunk's workgroup reads
+         * the first head_n samples: the second tile's image starts (OT - LEAD) rows into the buffer, and no workgroup comes
+         * to a first chunk as its second item.  Both hold wherever `two` does today; spelled out so that the kernel's
+         * assumption does not rest on that.  Otherwise the samples go where they would have been: nobody reads this
+         * buffer's front any more, acquire_input() has waited for the launch that did. */
+        const uint32_t head_n = e->hist + e->tail;
+        if (!(two && !raw8 && head_n <= (MFM_V3_OT - MFM_V3_LEAD) * D && v_nitems <= v_slots)) {
+            hipLaunchKernelGGL(mfm_carry_kernel, dim3(1), dim3(256), 0, S, e->head, e->d_in[cur], head_n);
+            HIP_TRY(hipGetLastError());
+            e->head = nullptr;
+        }
+    }
+    if (e->ncs > 1u && !two && e->in_free_wait[nxt] && e->in_free_on[nxt] != S) {
         /* this launch (or its stream's copy) writes the carry into the next buffer: whoever read that one last - possibly on
          * the other stream - must be through */
         HIP_TRY(hipStreamWaitEvent(S, e->in_free_wait[nxt], 0));
@@ -1015,14 +1151,23 @@ int launch_locked(mfm_engine *e)
         /* MFM_F_TIMING_SPARSE: every fourth launch carries the event pair.  An event record is a packet the command
          * processor handles between two kernels (~4 us each on MI355X): bracketing every launch of a back-to-back
          * stream costs 6 % of a 0.12 ms step, a sample of them costs under 1 % and measures the same kernel. */
-        const bool timing = (e->cfg.flags & MFM_F_TIMING) != 0 &&
-                            (!(e->cfg.flags & MFM_F_TIMING_SPARSE) || (e->launches % kSparseTiming) == 0);
+        const bool timed = (e->cfg.flags & MFM_F_TIMING) != 0 &&
+                           (!(e->cfg.flags & MFM_F_TIMING_SPARSE) || (e->launches % kSparseTiming) == 0);
+        /* two compute streams: no event pairs - a pair around a launch that shares the chip with the one before it measures
+         * its wait for slots -, the kernel's own stamp is the duration (mfm_engine::stamp_pending) */
+        const bool stamped = timed && e->ncs > 1u && e->d_cyc != nullptr;
+        const bool timing = timed && e->ncs <= 1u;
         int ti = 0;
-        if (timing) {
+        if (timed) {
             int rc = fold_timing(e, false);
             if (rc != MFM_OK) {
                 return rc;
             }
+        }
+        if (stamped) {
+            e->stamp_pending.push_back(e->launches);
+        }
+        if (timing) {
             ti = (int)(e->t_head % kTimingPairs);
             HIP_TRY(hipEventRecord(e->t0[ti], S));
         }
@@ -1036,20 +1181,11 @@ int launch_locked(mfm_engine *e)
             V.n_new = n_new;
             V.hist = e->hist;
             V.k_base = e->outputs;
-            V.ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT;
-            /* chunks of consecutive tiles, `rounds` per workgroup slot and slice, lengths equal to within one tile
-             * (a chunk pays one extra column group) */
-            const uint32_t slots = 256u * f.wg_per_cu;
-            /* (a multiple of 8: the items are dealt chunk-major over the eight XCDs - item = 8 * (chunk / 8 * nslices + slice) +
-             * chunk % 8, mfm3_decode_item - so a chunk count that is not one leaves holes in the last group of eight, the grid
-             * overflows the slots and a few workgroups run a SECOND chunk while the others are done: with 3, 5, 6 or 12 slices
-             * (130-192, 257-320, ... channels) a launch took up to twice as long as its work, profiles/r06_ab_chunking.txt) */
-            uint32_t per_slice = std::max(1u, slots / V.nslices);
-            per_slice = per_slice >= 8u ? per_slice & ~7u : per_slice;
-            /* one chunk per slot: shorter chunks (3..10 tiles, several rounds) were 2-6 % slower on MI355X */
-            V.nchunks = std::min(V.ntiles, per_slice);
+            V.ntiles = v_ntiles;
+            const uint32_t slots = v_slots;
+            V.nchunks = v_nchunks;
             V.cl = (V.ntiles + V.nchunks - 1u) / V.nchunks;
-            V.nitems = ((V.nchunks + 7u) / 8u) * 8u * V.nslices;
+            V.nitems = v_nitems;
             /* the next launch's [hist | history tail]: the last consumed row and what was not consumed */
             V.tail_src = e->hist + n_new * D - D;
             V.tail_n = D + n_avail - n_new * D;
@@ -1058,6 +1194,11 @@ int launch_locked(mfm_engine *e)
             if (two) {
                 V.tail_n = 0; /* the next launch must not wait for this kernel: the carry is copied on its own stream below */
                 tail_in_kernel = false;
+                e->overlapped++;
+            }
+            if (e->head) {
+                V.head = e->head;
+                V.head_n = e->hist + e->tail;
             }
             V.pcm = slot->d_pcm;
             V.iq_dbg = iq_dbg;
@@ -1115,7 +1256,26 @@ int launch_locked(mfm_engine *e)
     const uint32_t consumed = n_new * D;
     const uint32_t new_tail = n_avail - consumed;
     const uint32_t new_hist = (v3 && n_new) ? D : e->hist;
-    if (new_hist + new_tail && !tail_in_kernel) {
+    e->last_head = e->head;
+    e->last_head_n = e->head ? e->hist + e->tail : 0u;
+    e->head = nullptr;
+    if (early) {
+        /* (early implies a launch that consumed at least the old tail: what is copied lies behind this buffer's first
+         * hist + tail samples, in what the producer of this block wrote, and s_in is behind that producer - submit_impl.)
+         * The slot: see mfm_engine::d_ring for why nobody reads it any more. */
+        uint32_t *const dst = e->d_ring + (size_t)((e->pass + 1u) % (uint64_t)(e->nbuf + 1)) * e->ring_slot;
+        if (new_hist + new_tail > e->ring_slot) {
+            return fail(MFM_E_STATE, "carry of %u samples, ring slots of %u", new_hist + new_tail, e->ring_slot);
+        }
+        hipLaunchKernelGGL(mfm_carry_kernel, dim3(1), dim3(256), 0, e->s_in, e->d_in[cur] + e->hist + consumed - new_hist, dst,
+                           new_hist + new_tail);
+        HIP_TRY(hipGetLastError());
+        /* this buffer is free once its kernel AND this copy are through (acquire_input waits for both) */
+        HIP_TRY(hipEventRecord(e->tail_done[cur], e->s_in));
+        e->tail_pending[cur] = true;
+        e->head = dst;
+        e->head_ev = e->tail_done[cur];
+    } else if (new_hist + new_tail && !tail_in_kernel) {
         const size_t ss = raw8 ? 2 : 4;
         if (two && e->in_free_wait[nxt]) {
             /* the launch that last read the next buffer may be on the other stream */
@@ -1144,6 +1304,7 @@ int launch_locked(mfm_engine *e)
         HIP_TRY(hipEventRecord(e->in_free[cur], S));
         e->in_free_wait[cur] = e->in_free[cur];
     }
+    e->in_free_on[cur] = S; /* (a later launch on the same stream is behind it anyway) */
 
     if (n_new) {
         slot->first_output = e->outputs;
@@ -1172,6 +1333,7 @@ int launch_locked(mfm_engine *e)
     if (two) {
         e->si ^= 1u;
     }
+    e->pass++;
     e->last_launch_samples = n_avail;
     e->last_launch_buf = cur;
     e->last_launch_fmt = fmt;
@@ -1337,6 +1499,9 @@ static int submit_impl(struct mfm_engine *e, size_t nr_samples, void *producer_s
         }
         if (static_cast<hipStream_t>(producer_stream) == e->s_in) {
             e->wait_copy_stream = false; /* everything staged before is covered too */
+        } else if (e->d_ring && e->ncs > 1u) {
+            /* the early carry's copy runs on s_in and reads what this producer writes: behind it, and behind nothing else */
+            HIP_TRY(hipStreamWaitEvent(e->s_in, e->in_ready, 0));
         }
     }
 
@@ -1803,6 +1968,16 @@ int mfm_engine_last_launch_input(struct mfm_engine *e, void **d_in, size_t *nr_s
     if (!e || !e->committed || e->last_launch_buf < 0) {
         return fail(MFM_E_STATE, "no launch yet");
     }
+    if (e->last_head) {
+        /* the launch read its first samples from the carry ring: they go where this call promises them, once the launch
+         * (the only reader of the buffer's front, if it looked there at all) is through */
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(hipStreamSynchronize(e->s_last));
+        HIP_TRY(hipMemcpyAsync(e->d_in[e->last_launch_buf], e->last_head, (size_t)e->last_head_n * 4, hipMemcpyDeviceToDevice,
+                               e->s_last));
+        HIP_TRY(hipStreamSynchronize(e->s_last));
+        e->last_head = nullptr;
+    }
     if (d_in) {
         /* the first sample the launch had not consumed before (the second-generation kernel keeps a row in front of it) */
         *d_in = reinterpret_cast<uint8_t *>(e->d_in[e->last_launch_buf]) +
@@ -1923,10 +2098,12 @@ int mfm_engine_sync(struct mfm_engine *e)
     }
     HIP_TRY(hipStreamSynchronize(e->s_in));
     HIP_TRY(hipStreamSynchronize(e->s_compute));
-    if (e->ncs > 1u) {
+    if (e->cs[1] != e->s_compute) {
         HIP_TRY(hipStreamSynchronize(e->cs[1]));
     }
-    HIP_TRY(hipStreamSynchronize(e->s_out));
+    if (e->s_out) {
+        HIP_TRY(hipStreamSynchronize(e->s_out));
+    }
     return MFM_OK;
 }
 
@@ -1955,6 +2132,13 @@ int mfm_engine_reset(struct mfm_engine *e)
     e->tail_fmt = MFM_IN_CS16;
     e->in_fmt[0] = e->in_fmt[1] = e->in_fmt[2] = MFM_IN_CS16;
     e->cur_in = 0;
+    e->pass = 0; /* (buffer pass % nbuf again; the carry ring's slots are all free: everything has ended) */
+    e->head = e->last_head = nullptr;
+    e->last_head_n = 0;
+    for (int i = 0; i < kMaxInBufs; i++) {
+        e->in_free_wait[i] = nullptr;
+        e->tail_pending[i] = false;
+    }
     e->wait_copy_stream = false;
     e->last_launch_samples = 0;
     e->last_launch_buf = -1;
@@ -1995,6 +2179,7 @@ int mfm_engine_get_stats(struct mfm_engine *e, struct mfm_stats *st)
     memset(st, 0, sizeof(*st));
     if (e->committed && (e->cfg.flags & MFM_F_TIMING)) {
         HIP_TRY(hipSetDevice(e->cfg.device));
+        std::lock_guard<std::mutex> guard(e->mu); /* (the producer appends to what is folded here) */
         int rc = fold_timing(e, true);
         if (rc != MFM_OK) {
             return rc;
@@ -2014,6 +2199,8 @@ int mfm_engine_get_stats(struct mfm_engine *e, struct mfm_stats *st)
         st->pending_blocks = (uint32_t)(e->submit_seq - e->fetch_seq);
         st->pending_samples = e->pend; /* written under the lock by submit / launch */
         st->launches_8bit = e->launches_8bit;
+        st->overlapped_launches = e->overlapped;
+        st->pinned = e->pinned ? 1u : 0u;
     }
     st->grid_last = e->grid_last;
     st->tail_samples = e->tail;
@@ -2026,6 +2213,7 @@ size_t mfm_engine_get_launch_ms(struct mfm_engine *e, float *dst, size_t cap)
     if (!e || !e->committed || !(e->cfg.flags & MFM_F_TIMING)) {
         return 0;
     }
+    std::lock_guard<std::mutex> guard(e->mu);
     if (hipSetDevice(e->cfg.device) != hipSuccess || fold_timing(e, true) != MFM_OK) {
         return 0;
     }
@@ -2046,7 +2234,7 @@ size_t mfm_engine_get_launch_cycles(struct mfm_engine *e, uint64_t *shader_ticks
      * thread looks at the figures) - a flush from here would launch one shard of a gathering group by itself and take the
      * shards out of step. */
     if (hipSetDevice(e->cfg.device) != hipSuccess || hipStreamSynchronize(e->s_compute) != hipSuccess ||
-        (e->ncs > 1u && hipStreamSynchronize(e->cs[1]) != hipSuccess)) {
+        (e->cs[1] != e->s_compute && hipStreamSynchronize(e->cs[1]) != hipSuccess)) {
         return 0;
     }
     std::vector<unsigned long long> ring(kCycleRing * 2);
@@ -2070,9 +2258,39 @@ size_t mfm_engine_get_launch_cycles(struct mfm_engine *e, uint64_t *shader_ticks
     return n;
 }
 
+/* The stream is handed out (or a device group takes the engine): one compute stream from here on, unless MFM_F_OVERLAP asked
+ * for two.  s_compute waits for the other stream's last launch and becomes the stream of every later one; a head that is
+ * still in the carry ring goes to its buffer's front with the next launch (launch_locked). */
+int mfm_engine_pin(struct mfm_engine *e)
+{
+    if (!e || !e->committed) {
+        return fail(MFM_E_STATE, "commit first");
+    }
+    std::lock_guard<std::mutex> guard(e->mu);
+    if (e->pinned || (e->cfg.flags & MFM_F_OVERLAP)) {
+        return MFM_OK;
+    }
+    e->pinned = true;
+    if (e->ncs > 1u) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(hipEventRecord(e->kernel_done, e->cs[1])); /* (device-only engines have no other use for this event) */
+        HIP_TRY(hipStreamWaitEvent(e->cs[0], e->kernel_done, 0));
+        e->ncs = 1;
+        e->si = 0;
+        e->s_last = e->cs[0];
+    }
+    return MFM_OK;
+}
+
 void *mfm_engine_stream(struct mfm_engine *e)
 {
-    return (e && e->committed) ? e->s_last : nullptr;
+    if (!e || !e->committed) {
+        return nullptr;
+    }
+    if (mfm_engine_pin(e) != MFM_OK) {
+        return nullptr;
+    }
+    return e->s_last;
 }
 
 /* ---- host twins (see include/multifm_hip.h) ---- */

@@ -35,6 +35,9 @@ __attribute__((visibility("hidden"))) int mfm_engine_pending_samples(struct mfm_
 __attribute__((visibility("hidden"))) int mfm_engine_plan(struct mfm_engine *e, size_t nr_samples, int *must, int *may, int *want);
 /* 1 when the buffer being filled holds accepted blocks of another format than fmt (they have to be flushed first) */
 __attribute__((visibility("hidden"))) int mfm_engine_format_conflict(struct mfm_engine *e, int fmt);
+/* what the first mfm_engine_stream() does, for a caller that orders work on the engine's streams without asking for them
+ * (a device group, at commit): one compute stream from here on, unless MFM_F_OVERLAP is set */
+__attribute__((visibility("hidden"))) int mfm_engine_pin(struct mfm_engine *e);
 #define MFM_SUBMIT_AUTO 0
 #define MFM_SUBMIT_DEFER 1
 #define MFM_SUBMIT_LAUNCH 2

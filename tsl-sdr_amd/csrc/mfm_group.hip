@@ -372,6 +372,8 @@ int mfm_group_commit(struct mfm_group *g)
             rc = mfm_engine_add_channel(e, d.offset_hz, d.taps.data(), d.taps.size(), d.gain, d.want_iq);
         }
         rc = rc < 0 ? rc : mfm_engine_commit(e);
+        /* the shards run in step on their engines' streams: no engine of a group alternates streams by itself */
+        rc = rc < 0 ? rc : mfm_engine_pin(e);
     }
     if (rc != MFM_OK) {
         group_release(g);

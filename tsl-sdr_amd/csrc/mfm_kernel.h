@@ -274,4 +274,11 @@ struct mfm_launch_v3 {
     const float2 *lut;
     int16_t *pcm;
     uint32_t *iq_dbg;
+    /* Early carry (mfm_kernel_v3.hip, int16 input): the first head_n samples of the buffer - this launch's [hist | history
+     * tail], which the launch before it would have put at the front of x through tail_n / tail_dst - lie at `head` instead
+     * (a slot of the engine's carry ring, written by a copy that did not wait for any channel kernel).  Only the first tile's
+     * image reaches that far into the buffer ((MFM_V3_OT - MFM_V3_LEAD) * decim >= head_n; the engine checks), so only the
+     * workgroups whose first chunk starts at tile 0 look at it, in their prologue.  NULL / 0: everything is read from x. */
+    const uint32_t *head;
+    uint32_t head_n, pad3;
 };

@@ -496,19 +496,23 @@ __global__ __launch_bounds__(MFM3_NT, 4) void mfm_channel_kernel_v3(const mfm_la
     }
     const uint32_t lb0 = chunk_rows ? 16u * n + 16u * t_pitch * kg : n * rs + 16u * kg;
 
-    auto stage_load = [&](uint32_t tile, int j) -> uint4 {
-        /* 4 samples of the image of `tile`, which starts LEAD rows in front of the tile's first output (the first
-         * unconsumed sample sits L.hist samples into the buffer).  Only a readable address is needed: samples before
-         * the buffer feed nothing but outputs in front of the recomputed one (and, at the start of a stream, that one:
-         * replaced by the zero history), samples past n_avail only outputs >= n_new (never stored) or zero-padded
-         * taps.  Chunks past the image all read the tile's first line (one cache line per wave). */
+    /* the buffer index of the first of the 4 samples (8 as bytes) that chunk j of this thread holds of the image of `tile` */
+    auto stage_index = [&](uint32_t tile, int j) -> int {
         const uint32_t q = tid + (uint32_t)j * MFM3_NT;
         int gs = (int)(tile * MFM_V3_OT * D + L.hist) - (int)(MFM_V3_LEAD * D) + (IN8 ? 8 : 4) * (int)(q < L.nstage4 ? q : 0u);
         if constexpr (PADDED) {
             gs -= ((int)L.hist - (int)(MFM_V3_LEAD * 25u)) & ((IN8 ? 8 : 4) - 1); /* chunks are 16-byte aligned in the buffer */
         }
         gs = gs < 0 ? 0 : gs;
-        gs = gs > (int)L.x_last4 ? (int)L.x_last4 : gs;
+        return gs > (int)L.x_last4 ? (int)L.x_last4 : gs;
+    };
+    auto stage_load = [&](uint32_t tile, int j) -> uint4 {
+        /* 4 samples of the image of `tile`, which starts LEAD rows in front of the tile's first output (the first
+         * unconsumed sample sits L.hist samples into the buffer).  Only a readable address is needed: samples before
+         * the buffer feed nothing but outputs in front of the recomputed one (and, at the start of a stream, that one:
+         * replaced by the zero history), samples past n_avail only outputs >= n_new (never stored) or zero-padded
+         * taps.  Chunks past the image all read the tile's first line (one cache line per wave). */
+        const int gs = stage_index(tile, j);
 #if MFM3_NONTEMPORAL & 1
         const mfm_v4i ld = __builtin_nontemporal_load(
             reinterpret_cast<const mfm_v4i *>(reinterpret_cast<const uint8_t *>(L.x) + ((uint32_t)gs << (IN8 ? 1 : 2))));
@@ -622,6 +626,25 @@ __global__ __launch_bounds__(MFM3_NT, 4) void mfm_channel_kernel_v3(const mfm_la
         }
         reinterpret_cast<uint32_t *>(smem + L.lut_off)[MFM3_LUT_SLOT(tid)] = lut_v;
 #endif
+        if constexpr (IN8 == 0) {
+            /* early carry (mfm_launch_v3::head): the launch's first head_n samples are in the engine's carry ring, not at
+             * the front of the buffer.  Sample by sample - head_n is any number, a 16-byte chunk can straddle the seam.  A
+             * wave-uniform branch that the workgroups of the launch's first chunk take, once. */
+            if (L.head_n != 0u && tile == 0u) {
+#pragma unroll
+                for (int j = 0; j < NCH; j++) {
+                    const uint32_t gs = (uint32_t)stage_index(0u, j);
+                    uint32_t w[4] = { v[j].x, v[j].y, v[j].z, v[j].w };
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        if (gs + (uint32_t)k < L.head_n) {
+                            w[k] = L.head[gs + (uint32_t)k];
+                        }
+                    }
+                    v[j] = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < NCH; j++) {
             stage_store(0, j, v[j]);
