@@ -53,7 +53,10 @@ SIZES = [1, 1, 100, 26, 1, 4096, 4096, 4096, 131072, 16384, 7919, 5, 127, 128, 1
 def test_coalesced_ragged_buffers_against_the_oracle(pkg, ora, kernel, policy):
     """Front-end sized buffers (file_if 4096, rtl_sdr 131072, uhd 16384, airspy 262144), single samples and blocks shorter
     than the filter, gathered into launches of up to 300 000 samples: same PCM and filtered IQ as the oracle on the whole
-    stream; with MFM_F_GATHER the launch boundaries are those of the gathered sample count, not of the blocks."""
+    stream; with MFM_F_GATHER the launch boundaries are those of the gathered sample count, not of the blocks.  The
+    `*overlap` policies set MFM_F_OVERLAP at sizes that stay on ONE stream (at most 92 tiles on one slice, against 512 workgroup
+    slots: launch_locked() alternates only beyond a tile per slot): they exercise the flag's bookkeeping - the second stream, its
+    events, the carry ring's allocation.  Launches that do alternate: tests/test_overlap_forms.py."""
     b = pkg.binding
     fs, decim, taps, offs, gains = pkg.synth.plan("cfg2_64ch", nr_channels=9)
     n = 1200000
@@ -87,7 +90,7 @@ def test_coalesced_ragged_buffers_against_the_oracle(pkg, ora, kernel, policy):
     assert parts[0][0] == 0 and pcm.shape == ref.shape
     assert np.array_equal(pcm, ref) and np.array_equal(q, refq)
     assert st["samples_in"] == n and st["outputs"] == ref.shape[1] and st["submits"] == k and st["pending_samples"] == 0
-    assert st["launches"] <= st["submits"]
+    assert st["launches"] <= st["submits"] and st["overlapped_launches"] == 0
     if policy.startswith("gather"):
         # a launch per 300 000 gathered samples (plus the block that crossed the mark), and the flush at the end
         assert st["launches"] <= n // 300000 + 1, st["launches"]
@@ -222,11 +225,14 @@ def test_coalescing_group_of_several_shards_through_a_fake_transport(tmp_path, s
 @pytest.mark.parametrize("want_iq", [False, True])
 @pytest.mark.parametrize("plan,nch", [("cfg2_64ch", 64), ("cfg2_64ch_grid", 64), ("cfg3_1024ch", 200), ("multifm_1ch", 20)])
 def test_overlapped_launches_against_the_oracle(pkg, ora, plan, nch, want_iq):
-    """MFM_F_OVERLAP: consecutive launches on two streams.  A launch takes nothing from the one before it but input samples
-    (the output in front of it is recomputed from the row kept in front of the first unconsumed sample, the rotator position
-    folded from the stream's output count), so whatever order the device runs their workgroups in, the stream is the
-    oracle's: general, quarter-turn, sign-flip and identity rotators (filter/direct_fir.c:151-172), filtered IQ on and off
-    (different kernel instances), blocks of 20 tiles and of less than one, 16 slices of channels."""
+    """MFM_F_OVERLAP at sizes that stay on ONE stream: blocks of at most 2^17 samples are at most 22 tiles (52 at D = 40) on at
+    most 4 slices, against 512 workgroup slots, and launch_locked() alternates only beyond a tile per slot - asserted below
+    (overlapped_launches == 0).  What runs is the flag's bookkeeping (the second stream and its events, the carry ring's
+    allocation, the waits a launch that does not alternate issues) and, as on any engine, that a launch takes nothing from the
+    one before it but input samples (the output in front of it is recomputed from the row kept in front of the first
+    unconsumed sample, the rotator position folded from the stream's output count): general, quarter-turn, sign-flip and
+    identity rotators (filter/direct_fir.c:151-172), filtered IQ on and off (different kernel instances), blocks of 20 tiles and
+    of less than one.  Launches that do alternate, on every layout, slice count and input format: tests/test_overlap_forms.py."""
     b = pkg.binding
     fs, decim, taps, offs, gains = pkg.synth.plan(plan, nr_channels=nch)
     n = decim * 40000 + 777
@@ -252,7 +258,9 @@ def test_overlapped_launches_against_the_oracle(pkg, ora, plan, nch, want_iq):
         pos += m
         k += 1
     _finish(eng, parts, qparts)
+    st = eng.stats()
     eng.close()
+    assert st["overlapped_launches"] == 0, st
     pcm = np.concatenate([p[1] for p in parts], axis=1)
     assert pcm.shape == ref.shape
     if not np.array_equal(pcm, ref):
@@ -268,7 +276,9 @@ def test_seek_resumes_the_rotators_also_beyond_2_to_the_32(pkg, ora, kernel, bef
     """mfm_engine_seek: a stream resumed at output `before` - the derotators where that many steps of the recurrence leave
     them (filter/direct_fir.c:166-167), history and discriminator empty.  Counts inside the pre-period of the 101 kHz
     rotator (53 105 steps), across 2^32 (the kernels fold a 64-bit output count; a stream at the bench's rate gets there
-    within a second) and far beyond.  Oracle: the same channel stepped to `before` (mfmo_chan_skip_outputs)."""
+    within a second) and far beyond.  Oracle: the same channel stepped to `before` (mfmo_chan_skip_outputs).  The
+    `auto+overlap` rows set MFM_F_OVERLAP on blocks of 30 000 samples - 5 tiles, one stream: seek with the flag's bookkeeping in
+    place; seek with a carry in the ring of an alternating stream is in tests/test_overlap_forms.py and test_launch_overlap.py."""
     b = pkg.binding
     fs, decim = 2400000, 96
     taps = pkg.synth.design_lpf(128, 12500.0, fs)

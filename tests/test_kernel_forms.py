@@ -375,8 +375,10 @@ def test_pcm_store_policy(pkg, ora, geom):
 @pytest.mark.gpu
 
 def test_slice128_gathered_and_overlapped(pkg, ora):
-    """MFM_F_GATHER | MFM_F_OVERLAP with coalesce_samples on 128-channel slices: launch boundaries at the gathered counts,
-    consecutive launches on two streams, each recomputing the output in front of it."""
+    """MFM_F_GATHER | MFM_F_OVERLAP with coalesce_samples on 128-channel slices: launch boundaries at the gathered counts, each
+    launch recomputing the output in front of it.  The launches stay on ONE stream (at most 38 tiles on 4 slices, against the
+    256 slots of one workgroup per CU: overlapped_launches == 0 below) - this is the flag's bookkeeping on the long-filter
+    kernel; launches of that kernel that do alternate are in tests/test_overlap_forms.py."""
     b = pkg.binding
     fs, decim, taps, _, _ = pkg.synth.plan("cfg3_1024ch", nr_channels=512)
     offs = _mixed_offsets(pkg, 512)
@@ -417,6 +419,7 @@ def test_slice128_gathered_and_overlapped(pkg, ora):
     ref, _ = ora.run_channels(iq, cre, cim, incr, decim, threads=THREADS)
     _assert_equal(pcm, ref, "gathered + overlapped, 512 channels")
     assert st["submits"] == k and st["pending_samples"] == 0 and 2 <= st["launches"] <= n // 100000 + 1, st
+    assert st["overlapped_launches"] == 0, st
 
 
 @pytest.mark.gpu
