@@ -2213,6 +2213,142 @@ int mfm_runsync_fetch_state(struct mfm_runsync *s, struct mfm_runsync_state *sta
  * written.  The result of the last call stays readable. */
 int mfm_runsync_store_state(struct mfm_runsync *s, const struct mfm_runsync_state *state, size_t nr_channels);
 
+/*
+ * ---- Burst batch stage: POCSAG batches behind the burst sync stage's events, on the device ----------------------------------
+ * The consumer of the stage above: its input is what mfm_runsync_device_view returns (the run records, the bit words, the
+ * events, the totals), all read on the device.  Behind a sync event it cuts batches of 16 codewords out of the bit words, runs
+ * BCH(31,21) on them and follows sync kept / sync lost exactly as pager/pager_pocsag.c:468-538 does at one sample per bit; the
+ * events carry the types the host pager consumes (MFM_POCSAG_EV_*), so the clock-recovery branch of the burst chain reaches
+ * pages at any symbol rate the Mueller-Muller stage follows.
+ *
+ * Rule.  Per stretch (the sync stage's: MFM_RUNRS_BEGINS decides where one begins).  Let b[n] be the sync stage's bit of
+ * decision n of the stretch.  A fresh automaton starts every stretch in SEARCH with mark = 0.
+ *   SEARCH   the stretch's first sync event with dec >= mark whose word is enabled (word_mask bit word_index set, or word_mask
+ *            == 0), at decision n0: FOUND with dec = n0, aux = seen, word_index, the distance in nr_ok, inverted.  The automaton
+ *            keeps word_index and inverted for this transmission; mark = p = n0 + 1; RECEIVE.
+ *   RECEIVE  word z (0 .. 15) of the batch is filled LSB first (the reference's bit << bit_count): bit i of word z is
+ *            b[p + 32 z + i] ^ inverted, the sync stage's own packing.  When decision p + 511 exists: BATCH with dec = p + 511
+ *            and raw[16], corrected[z] = BCH(raw[z] & 0x7fffffff), fail_mask (bit z: word z is uncorrectable) and nr_ok (the
+ *            words in front of the first failure) - struct mfm_pocsag_event's convention.  SLOT.
+ *   SLOT     the 32 bits of decisions p + 512 .. p + 543 as a register, shifted in MSB first as the sync stage's, complemented
+ *            when inverted: seen.  popcount(seen ^ words[word_index]) <= keep_distance (the reference: 4): KEPT with dec = p +
+ *            543 and aux = seen, p += 544, RECEIVE.  Otherwise LOST with the same dec and aux, mark = p + 575, SEARCH: the next
+ *            sync lies wholly behind the failed slot, as the reference searches from scratch after
+ *            _pager_pocsag_baud_search_reset, and the next FOUND decides the polarity anew.
+ * Sync events seen in RECEIVE or SLOT are ignored.  A batch or slot still being collected when its stretch ends is dropped
+ * without an event.  A run with nr_dec == 0 changes nothing and still begins or continues its stretch.
+ *
+ * No lag.  Events do not depend on how the stream was cut into calls or runs; an event is reported by the call and run that
+ * holds decision dec.
+ *
+ * State.  Per channel, on the device (struct mfm_runbatch_state below, which the host twin carries too), two buffers used in
+ * turn.  In RECEIVE and SLOT kept holds the bits of the decisions [mark, decs), nr_kept = decs - mark < 544 of them, LSB first
+ * and zero above: the previous call's bit words are gone by then.  In SEARCH nr_kept, kept, word_index and inverted are 0; a
+ * channel without a stretch is all zero.  The form is canonical: device and twin states compare as bytes.
+ *
+ * Result.  It replaces the previous call's: struct mfm_runbatch_event, dense, in run order and ascending in dec within a run,
+ * placed by a scan and never by atomics; d_totals[4] = { events, runs, overflow, input error }.  A run of nr_dec decisions has
+ * at most 3 (nr_dec / 544) + 5 events (derived in csrc/mfm_runbatch.h), so the default max_events cannot overflow.
+ *
+ * Refused calls produce nothing, leave every state untouched and raise a flag that mfm_runbatch_fetch reports as MFM_E_STATE
+ * with a message:
+ *   overflow     MFM_RUNBATCH_OVER_RUNS: more runs than max_runs; MFM_RUNBATCH_OVER_EVENTS: the call's events exceed a
+ *                caller-chosen max_events - by the count, which is known before an event is placed
+ *   input error  MFM_RUNBATCH_IN_RUNSYNC: the sync stage's totals carry a flag; MFM_RUNBATCH_IN_OUT_OF_STEP and _IN_BAD_RUNS: the
+ *                burst stages' shared run checks, a word_offset that is not the running sum of the runs' words, or runs
+ *                that hold more bit words or event slots than max_decisions and max_runs allow; MFM_RUNBATCH_IN_BAD_EVENTS: an event whose dec lies outside its run, events not
+ *                ascending, word_index >= nr_words, inverted > 1, or the sum of nr_events past the sync stage's totals.  All of
+ *                these are checked before any state moves.
+ *
+ * Refusals at create (MFM_E_INVAL with a message, before a device is looked for): nr_words of 0 or above 8, keep_distance above
+ * 15, word_mask bits at or above nr_words, flags other than 0, capacities that are zero or reach 2^28 runs or 2^31 decisions or
+ * events.
+ */
+#define MFM_RUNBATCH_SEARCH 0u         /* mfm_runbatch_state.mode */
+#define MFM_RUNBATCH_RECEIVE 1u
+#define MFM_RUNBATCH_SLOT 2u
+#define MFM_RUNBATCH_OVER_RUNS 1u
+#define MFM_RUNBATCH_OVER_EVENTS 2u
+#define MFM_RUNBATCH_IN_RUNSYNC 1u
+#define MFM_RUNBATCH_IN_OUT_OF_STEP 2u
+#define MFM_RUNBATCH_IN_BAD_RUNS 4u
+#define MFM_RUNBATCH_IN_BAD_EVENTS 8u
+
+struct mfm_runbatch_event {     /* 176 bytes */
+    uint32_t type;              /* MFM_POCSAG_EV_* */
+    uint32_t channel;
+    uint32_t run;               /* index in this call's run list */
+    uint32_t aux;               /* SYNC_FOUND: the sync stage's register; SYNC_KEPT / SYNC_LOST: the 32 bits seen in the slot, upright */
+    uint32_t word_index;        /* the transmission's sync word */
+    uint32_t inverted;          /* ... and polarity */
+    uint32_t nr_ok;             /* SYNC_FOUND: the sync event's distance; BATCH: words in front of the first BCH failure (16: all) */
+    uint32_t fail_mask;         /* BATCH: bit z set when word z is uncorrectable */
+    uint64_t stretch_window;    /* first window of the stretch */
+    uint64_t dec;               /* the decision that completed the event, counted within its stretch */
+    uint32_t raw[16];           /* BATCH: the words as collected, upright */
+    uint32_t corrected[16];     /* BATCH: (raw & 0x7fffffff) after BCH correction */
+};
+
+/* the per-channel state, on the device and in the host twin: all zero at the start of a stream.  What a stored state must
+ * satisfy: csrc/mfm_runbatch.h (mfm_runbatch_state_check) */
+struct mfm_runbatch_state {     /* 120 bytes */
+    uint64_t stretch_window;    /* first window of the stretch */
+    uint64_t decs;              /* decisions of the stretch so far */
+    uint64_t mark;              /* SEARCH: the first decision a sync may end on; RECEIVE / SLOT: p, the frame's first decision */
+    uint32_t has_stretch;       /* 0: nothing to continue */
+    uint32_t mode;              /* MFM_RUNBATCH_SEARCH / _RECEIVE / _SLOT */
+    uint32_t word_index;
+    uint32_t inverted;
+    uint32_t nr_kept;           /* decs - mark in RECEIVE and SLOT, else 0 */
+    uint32_t reserved;          /* 0 */
+    uint32_t kept[17];          /* the bits of the decisions [mark, decs), LSB first, 0 above */
+    uint32_t reserved2;         /* 0 */
+};
+
+struct mfm_runbatch; /* opaque */
+
+struct mfm_runbatch_config {
+    uint32_t abi_version;       /* MFM_ABI_VERSION */
+    int32_t device;
+    uint32_t nr_channels;
+    uint32_t max_runs;          /* the burst sync stage's (its max_runs and max_decisions) */
+    uint32_t max_decisions;
+    uint32_t max_events;        /* per call, all channels; 0 = 3 * (max_decisions / 544) + 5 * max_runs, cannot overflow */
+    uint32_t nr_words;          /* 1 .. 8: the sync stage's table */
+    uint32_t words[8];
+    uint32_t word_mask;         /* the words that start a transmission; 0 = all */
+    uint32_t keep_distance;     /* 0 .. 15; the reference: 4 */
+    uint32_t flags;             /* 0 */
+};
+
+int mfm_runbatch_create(struct mfm_runbatch **pb, const struct mfm_runbatch_config *cfg);
+void mfm_runbatch_destroy(struct mfm_runbatch **pb);
+/*
+ * Follow the sync events of one burst sync call: the four arrays are what mfm_runsync_device_view returned.  Work is queued on
+ * `stream` (the sync call's, or one ordered behind it); no host synchronisation and no count read on the host: launches are
+ * sized from the capacities fixed at create, surplus workgroups return after reading the totals.  The arrays are read until the
+ * queued work has run.
+ */
+int mfm_runbatch_process_device(struct mfm_runbatch *b, const struct mfm_runsync_run *d_runs, const uint32_t *d_bits,
+                                const struct mfm_runsync_event *d_events, const uint64_t *d_totals, void *stream);
+/*
+ * Wait for the last call, read its totals and copy its events.  MFM_E_NOMEM when max_events is too small (nothing copied,
+ * *nr_events says what is needed); MFM_E_STATE with a message when the call was refused (nothing copied, no state moved: the
+ * same input in a call that is right is right again).
+ */
+int mfm_runbatch_fetch(struct mfm_runbatch *b, struct mfm_runbatch_event *events, size_t max_events, size_t *nr_events);
+/* For consumers that stay on the device: the last call's events and d_totals[4], valid until the next call.  Either may be
+ * NULL. */
+int mfm_runbatch_device_view(struct mfm_runbatch *b, const struct mfm_runbatch_event **d_events, const uint64_t **d_totals);
+/* The capacities fixed at create: runs and events (the default filled in).  Either pointer may be NULL. */
+int mfm_runbatch_get_capacity(struct mfm_runbatch *b, uint32_t *max_runs, uint64_t *max_events);
+/* Wait for the last call and copy the per-channel state it left, state[nr_channels]: what the host twin carries. */
+int mfm_runbatch_fetch_state(struct mfm_runbatch *b, struct mfm_runbatch_state *state, size_t nr_channels);
+/* The way back: waits for the queued work, validates every channel (csrc/mfm_runbatch.h states the conditions) and writes what
+ * the next process call reads.  A state that fails gets MFM_E_INVAL with a message naming channel and field, and nothing is
+ * written.  The result of the last call stays readable. */
+int mfm_runbatch_store_state(struct mfm_runbatch *b, const struct mfm_runbatch_state *state, size_t nr_channels);
+
 /* bch_code_decode (pager/bch_code.c:307-398) on n words in place; rc[i] = its return value (0 or 1). */
 int mfm_bch3121_decode_device(uint32_t *d_words, uint8_t *d_rc, size_t n, int device, void *stream);
 int mfm_bch3121_decode_host(uint32_t *words, uint8_t *rc, size_t n, int device);
@@ -2606,6 +2742,17 @@ int mfm_hosttwin_runsync_call(const struct mfm_runsync_config *cfg, struct mfm_r
 /* the validation mfm_runsync_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
  * channel and field that fail (csrc/mfm_runsync.h) */
 int mfm_hosttwin_runsync_state_check(uint32_t nr_channels, const struct mfm_runsync_state *state);
+/* host twin of one mfm_runbatch_process_device call and its fetch, no device needed (cfg->device is not read): runs / bits /
+ * sync_events / totals are one burst sync call's result as mfm_runsync_fetch gives it, with its four totals; state[nr_channels]
+ * is read and, where the call is right and fits, updated in place.  Same refusals: MFM_E_INVAL with the message create gives;
+ * MFM_E_STATE with the message mfm_runbatch_fetch gives and *flags = overflow | input error << 8; MFM_E_NOMEM with *nr_events
+ * what is needed.  Either way nothing is written and no state moves. */
+int mfm_hosttwin_runbatch_call(const struct mfm_runbatch_config *cfg, struct mfm_runbatch_state *state, const struct mfm_runsync_run *runs,
+                               const uint32_t *bits, const struct mfm_runsync_event *sync_events, const uint64_t *totals,
+                               struct mfm_runbatch_event *events, size_t max_out_events, size_t *nr_events, uint32_t *flags);
+/* the validation mfm_runbatch_store_state applies, no device needed: MFM_OK, or MFM_E_INVAL with a message naming the first
+ * channel and field that fail (csrc/mfm_runbatch.h) */
+int mfm_hosttwin_runbatch_state_check(uint32_t nr_channels, const struct mfm_runbatch_state *state);
 /* The form mfm_resampler_create() would choose for this configuration and these taps, planned on the host by the same function
  * and without looking for a device (cfg->device is not read).  MFM_E_INVAL for what create refuses: its argument checks, a ratio
  * whose walk steps past a phase (ceil(D / I) > phase length), a call whose phase walk does not fit 32 bits, more than 150 KB

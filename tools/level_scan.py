@@ -5,7 +5,7 @@
            [--window 1000] [--metric energy|diff] [--sense above|below] [--open-thr N --close-thr N] [--hang 0]
            [--floor-windows M --open-ratio R --close-ratio R [--warmup N]]
            [--block 1048576] [--summary] [--gate-out DIR [--gate-preroll P] [--gate-resample I/D --resample-taps FILE [--gate-dc-pole POLE]
-           [--gate-ais | --gate-pocsag | --gate-flex | --gate-mm SPB[,KW,KM,MARGIN] [--gate-sync WORDS]]] | --gate-route routes.json]]
+           [--gate-ais | --gate-pocsag | --gate-flex | --gate-mm SPB[,KW,KM,MARGIN] [--gate-sync WORDS [--gate-batch [KEEP[,BAUD]]]]]] | --gate-route routes.json]]
 
 receiver.json has the reference's shape (multifm/receiver.c:138-230): sampleRateHz, centerFreqHz, decimationFactor,
 lpfTaps, channels[].chanCenterFreq (and the optional dBGain).  One JSON line per channel and completed window:
@@ -133,6 +133,26 @@ the same three masks at 64 and 1024 channels, alternating in one process: means,
 the difference with its standard error and the verdict of tools/exp/ab.py's two-standard-error rule, and that cost over the
 Mueller-Muller stage's own call (the chain minus the resampler); and whether every call's result equalled the host twin's.
 
+--gate-batch [KEEP[,BAUD]] (only with --gate-sync) queues the burst batch stage (mfm_runbatch_*) behind the burst sync stage on the
+same stream: behind a sync event it cuts batches of 16 codewords out of the sync stage's bit words, runs BCH(31,21) on them and
+holds the 32 bits behind every batch against the word that was found, within KEEP bits (default 4, at most 15), as
+pager/pager_pocsag.c:468-538 does at one sample per bit.  DIR/batch.jsonl gets a line per event:
+
+    {"channel": 3, "first_window": 4, "first_sample": 4000, "type": 2, "dec": 843, "aux": "00000000", "word": "7cd215d8", "inverted": 0,
+     "nr_ok": 16, "fail_mask": 0, "corrected": ["7a89c197", ...]}
+
+(type: MFM_POCSAG_EV_*, 1 sync found, 2 batch, 3 sync lost, 4 sync kept; dec: the decision that completed the event, counted within
+the stretch; corrected only on a batch), and the pages of a fresh host pager per stretch go to DIR/pages.jsonl in the shape
+--gate-pocsag writes, with BAUD (default 1200: the stage counts decisions and does not know the rate) in the place of the baud rate.
+A route of stage mm that carries "sync" may carry "batch": {"keep": 4, "baud": 1200} with the same meaning (both optional).
+
+    python tools/level_scan.py --bench-runbatch --window 4096 [--reps 6] [--inner 10]
+
+prints one line ("runbatch_stage"): the chain of --bench-runsync with and without the batch stage behind it on the same three masks
+at 64 and 1024 channels, alternating in one process in rotating order: means, standard deviations, the batch stage's cost as the
+difference with its standard error and the verdict of tools/exp/ab.py's two-standard-error rule, beside the sync stage's cost
+measured the same way; and whether every call's events equalled the host twin's.
+
 --gate-ends (with --gate-ais, --gate-pocsag or --gate-flex, with or without --gate-bits, or with --gate-route, where it applies to
 every route's stage) switches the stage's stretch-end report on, ends the open stretches behind the gate's flush and writes
 DIR/ends.jsonl beside the events (under a route: DIR/NAME/ends.jsonl), one line per stretch: channel, first_sample (the stretch's
@@ -156,7 +176,7 @@ burst chain only the runs of its own channels.  FILE is JSON:
 
 up to eight routes; stage is ais, pocsag, flex, mm or none (the resampler alone; a route of stage mm carries "mm": {"spb": 20.8333,
 "kw": 0.0001, "km": 0.000004, "margin": 0.05}, spb required, as --gate-mm, writes mm.jsonl and chNNNN.mm.s16, takes no bits and has
-no stretch-end report, and may carry "sync" as --gate-sync); resample and taps as --gate-resample and
+no stretch-end report, and may carry "sync" as --gate-sync and, with it, "batch" as --gate-batch); resample and taps as --gate-resample and
 --resample-taps; dc_pole and bits (true / false) are optional and follow the rules of --gate-dc-pole and --gate-bits (bits only
 with ais or pocsag, never with dc_pole); a channel may stand in one route at most, and a channel in none is gated but goes no
 further.  Each route runs burst resampler -> stage on its view of the router, on the engine's stream, the flush call included, and
@@ -307,6 +327,27 @@ def check_sync(sync, where):
     return {"words": list(sync["words"]), "distance": sync.get("distance", 3), "either": sync.get("either", False)}
 
 
+def parse_gate_batch(text):
+    """--gate-batch [KEEP[,BAUD]] as the "batch" object of a route of stage mm"""
+    keep, _, baud = text.partition(",")
+    try:
+        batch = {"keep": int(keep) if keep else 4, "baud": int(baud) if baud else 1200}
+    except ValueError:
+        raise SystemExit(f"--gate-batch takes [KEEP[,BAUD]], not {text!r}")
+    return check_batch(batch, "--gate-batch")
+
+
+def check_batch(batch, where):
+    """the "batch" object of a route of stage mm (or of --gate-batch): optionally keep (0 .. 15) and baud (1 .. 65535, what the
+    pages carry)"""
+    ok = isinstance(batch, dict) and not set(batch) - {"keep", "baud"}
+    ok = ok and all(isinstance(v, int) and not isinstance(v, bool) for v in batch.values())
+    ok = ok and 0 <= batch.get("keep", 4) <= 15 and 1 <= batch.get("baud", 1200) <= 65535
+    if not ok:
+        raise SystemExit(f"{where}: \"batch\" must be an object with optionally keep (0 .. 15) and baud (1 .. 65535), not {batch!r}")
+    return {"keep": batch.get("keep", 4), "baud": batch.get("baud", 1200)}
+
+
 class Routes(list):
     """the routes of a --gate-route file; `local` is the file's "local" key"""
     local = False
@@ -344,6 +385,11 @@ def read_routes(path, nr_channels):
             r["mm"] = check_mm(r.get("mm"), f"--gate-route: route {name}")
             if "sync" in r:
                 r["sync"] = check_sync(r["sync"], f"--gate-route: route {name}")
+            if "batch" in r:
+                if "sync" not in r:
+                    raise SystemExit(f"--gate-route: route {name}: \"batch\" needs \"sync\": the burst batch stage takes the burst sync "
+                                     "stage's events and bits")
+                r["batch"] = check_batch(r["batch"], f"--gate-route: route {name}")
             if r.get("bits"):
                 raise SystemExit(f"--gate-route: route {name}: bits needs stage ais or pocsag: the burst Mueller-Muller stage reads PCM values, "
                                  "not sign bits")
@@ -351,6 +397,8 @@ def read_routes(path, nr_channels):
             raise SystemExit(f"--gate-route: route {name}: \"mm\" belongs to stage mm, not to stage {r['stage']}")
         elif "sync" in r:
             raise SystemExit(f"--gate-route: route {name}: \"sync\" belongs to stage mm, not to stage {r['stage']}")
+        elif "batch" in r:
+            raise SystemExit(f"--gate-route: route {name}: \"batch\" belongs to stage mm, not to stage {r['stage']}")
         if r.get("bits") and r["stage"] not in ("ais", "pocsag"):
             raise SystemExit(f"--gate-route: route {name}: bits needs stage ais or pocsag: the burst FLEX stage reads PCM values, not sign bits")
         if r.get("bits") and r.get("dc_pole") is not None:
@@ -380,13 +428,14 @@ class BurstChain:
     route's of the run router - and the files the two write under out_dir; view() returns the run list's device view"""
 
     def __init__(self, pkg, out_dir, window, nr_channels, max_in_samples, preroll, device, view, resample, taps_file, dc_pole=None,
-                 stage=None, bits=False, caps=None, channels=None, bound=None, ends=False, mm=None, sync=None):
+                 stage=None, bits=False, caps=None, channels=None, bound=None, ends=False, mm=None, sync=None, batch=None):
         """caps and channels: behind a packed or a local route of the run router, its route_caps() - the chain is sized to the route -
         and its route_channels(), which turn the route-local channel numbers of everything fetched back into true ones.  bound:
         behind a local route, the router's bound_view(): the resampler then reads the gate's payload through its view entries.
         ends (--gate-ends): the stage's stretch-end report, one line per stretch in ends.jsonl (the mm stage has none: nothing is
         pending when a stretch ends).  mm: stage mm's spb, kw, km and margin.  sync (--gate-sync): the burst sync stage behind
-        stage mm, its words, distance and either"""
+        stage mm, its words, distance and either.  batch (--gate-batch): the burst batch stage behind the sync stage, its keep
+        distance and the baud rate its pages carry"""
         b = self.b = pkg.binding
         self.out_dir, self.window, self.view, self.bound = out_dir, window, view, bound
         self.channels = None if channels is None else np.asarray(channels, np.uint32)
@@ -414,7 +463,11 @@ class BurstChain:
         if stage == "mm" and sync:
             self.sy = pkg.RunSync.behind(self.st, sync["words"], max_distance=sync["distance"], either=sync["either"], device=device)
             self.sy_index, self.sy_words = open(os.path.join(out_dir, "sync.jsonl"), "w"), ["%08x" % w for w in sync["words"]]
-        if stage in ("pocsag", "flex"):
+        self.bt, self.bt_index, self.bt_baud = None, None, 0
+        if self.sy and batch:
+            self.bt = pkg.RunBatch.behind(self.sy, keep_distance=batch["keep"], device=device)
+            self.bt_index, self.bt_baud = open(os.path.join(out_dir, "batch.jsonl"), "w"), batch["baud"]
+        if stage in ("pocsag", "flex") or self.bt:
             self.pages_index = open(os.path.join(out_dir, "pages.jsonl"), "w")
         self.ends_index, self.stretches, self.cut_by_mode = None, 0, {}
         if stage and stage != "mm" and ends:
@@ -441,6 +494,8 @@ class BurstChain:
             st.process_device(*rr.device_view(), stream=stream)
         if self.sy:
             self.sy.process_device(*st.device_view(), stream=stream)
+        if self.bt:
+            self.bt.process_device(*self.sy.device_view(), stream=stream)
 
     def write(self):
         """fetch the last call's results and append them to the files"""
@@ -462,6 +517,8 @@ class BurstChain:
         if self.sy:
             runs, _, events = self.sy.fetch()
             self.write_sync(self.true_channels(runs), self.true_channels(events))
+        if self.bt:
+            self.write_batch(self.true_channels(self.bt.fetch()))
         if self.ends_index:
             self.write_ends(self.true_channels(self.st.fetch_ends()))
 
@@ -501,6 +558,10 @@ class BurstChain:
             for c in sorted(self.sy_stretch):
                 self.write_sync_summary(c)
             self.sy_index.close()
+        if self.bt:
+            self.bt_index.close()
+            self.bt.close()
+        if self.sy:
             self.sy.close()
         for f in (self.rs_index, self.st_index, self.pages_index, self.ends_index):
             if f:
@@ -576,6 +637,24 @@ class BurstChain:
                                                 "seen": "%08x" % int(e["seen"])}) + "\n")
             at += int(r["nr_events"])
 
+    def write_batch(self, events):
+        """a line per event, and the pages of a fresh host pager per (channel, stretch)"""
+        b, pagers = self.b, self.pagers
+        for e in events:
+            c, fw = int(e["channel"]), int(e["stretch_window"])
+            first = fw * self.window
+            line = {"channel": c, "first_window": fw, "first_sample": first, "type": int(e["type"]), "dec": int(e["dec"]),
+                    "aux": "%08x" % int(e["aux"]), "word": self.sy_words[int(e["word_index"])], "inverted": int(e["inverted"]),
+                    "nr_ok": int(e["nr_ok"]), "fail_mask": int(e["fail_mask"])}
+            if int(e["type"]) == 2:
+                line["corrected"] = ["%08x" % int(w) for w in e["corrected"]]
+            self.bt_index.write(json.dumps(line) + "\n")
+            if c not in pagers or pagers[c].first != first:
+                if c in pagers:
+                    pagers[c].close()
+                pagers[c] = HostPager(c, first, self.pages_index)
+            pagers[c].on_events(b.runbatch_to_pocsag_events(np.array([e], b.RUNBATCH_EVENT_DTYPE), self.bt_baud))
+
     def write_sync_summary(self, c):
         fw, nd, counts = self.sy_stretch.pop(c)
         self.sy_index.write(json.dumps({"channel": c, "first_window": fw, "first_sample": fw * self.window, "decisions": nd,
@@ -648,7 +727,8 @@ def scan(a):
         chains.append(BurstChain(pkg, a.gate_out, a.window, len(chans), max_in, int(a.gate_preroll), a.device, gate.device_view,
                                  a.gate_resample, a.resample_taps, dc_pole=a.gate_dc_pole, stage=stage, bits=a.gate_bits, ends=a.gate_ends,
                                  mm=parse_gate_mm(a.gate_mm) if a.gate_mm else None,
-                                 sync=parse_gate_sync(a.gate_sync) if a.gate_sync else None))
+                                 sync=parse_gate_sync(a.gate_sync) if a.gate_sync else None,
+                                 batch=parse_gate_batch(a.gate_batch) if a.gate_batch is not None else None))
     if routes is not None:
         if not gate or iq_form:
             raise SystemExit("--gate-route needs --gate-out and --form pcm: the burst resamplers take PCM payloads only")
@@ -671,7 +751,7 @@ def scan(a):
             chains.append(BurstChain(pkg, os.path.join(a.gate_out, r["name"]), a.window, len(chans), max_in, int(a.gate_preroll), a.device,
                                      lambda k=k: router.device_view(k), r["resample"], r["taps"], dc_pole=r.get("dc_pole"),
                                      stage=None if r["stage"] == "none" else r["stage"], bits=bool(r.get("bits")), ends=a.gate_ends,
-                                     mm=r.get("mm"), sync=r.get("sync"), **sized))
+                                     mm=r.get("mm"), sync=r.get("sync"), batch=r.get("batch"), **sized))
 
     def run_stages():
         """the router, where there is one, and every chain on the gate's last result, all on the engine's stream"""
@@ -2408,6 +2488,119 @@ def bench_runsync(a, pkg, torch):
     print(json.dumps(out))
 
 
+def bench_runbatch(a, pkg, torch):
+    """burst resampler -> burst Mueller-Muller -> burst sync with and without the burst batch stage behind it, on the device view
+    one gate call left (the masks and shapes of bench_runsync); the variants alternate in one process in rotating order.  The batch
+    stage's cost is the difference of the two chains, beside the sync stage's, measured the same way against the chain without it.
+    The events of a call are compared with the host twin's on the sync stage's result fetched"""
+    b = pkg.binding
+    W, I, D = a.window, 4, 5
+    n = 1 << 17
+    nw = n // W
+    nb = nw * W
+    taps = np.round(pkg.synth.design_lpf(41, 0.45 / 5, 1.0) * 4 * 16384.0).astype(np.int16)
+    spb = float(np.float32(38400.0) / np.float32(1200.0))
+    mm = dict(MM_DEFAULTS, spb=spb)
+    words = [0x7CD215D8, 0xA6C6AAAA, 0x870C78F3, 0xB0684E97]   # as bench_runsync
+
+    def timed(fn, inner):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / inner
+
+    out = {"bench": "runbatch_stage", "window": W, "samples_per_channel": nb, "windows_per_channel": nw, "interpolate": I, "decimate": D,
+           "reps": a.reps, "calls_per_rep": a.inner, "samples_per_bit": spb, "words": ["%08x" % w for w in words], "max_distance": 3,
+           "either": True, "keep_distance": 4, "frame": b.RUNBATCH_FRAME}
+    twin_ok = True
+    for nch in (64, 1024):
+        host = _busy_pocsag_rows(pkg, nch, n)
+        d_rows = torch.from_numpy(np.ascontiguousarray(host)).cuda()
+        rows, in_stride = d_rows.data_ptr(), n
+        probe = pkg.Level(nch, n, W, device=0)
+        probe.process_device(rows, in_stride, nb)
+        thr = int(np.median(probe.fetch()["energy"]))
+        probe.close()
+        sq = pkg.Level(nch, n, W, sense=b.MFM_LEVEL_OPEN_ABOVE, open_thr=thr, close_thr=thr, device=0)
+        sq.process_device(rows, in_stride, nb)
+        scene = sq.fetch()
+        d_scene, scene_stride, _, _ = sq.device_view()
+        masks = {"all_closed": np.zeros((nch, nw), np.uint32), "all_open": np.ones((nch, nw), np.uint32), "scene": scene["open"]}
+        keep, recs = [], {"scene": (d_scene, scene_stride)}
+        for name in ("all_closed", "all_open"):
+            r = np.zeros((nch, nw), b.LEVEL_RECORD_DTYPE)
+            r["window"] = np.arange(nw, dtype=np.uint64)[None, :]
+            r["open"] = masks[name]
+            t = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).cuda()
+            keep.append(t)
+            recs[name] = (t.data_ptr(), nw)
+        rr = pkg.RunResampler(nch, taps, I, D, W, max_in_samples=n, device=0)
+        rm = pkg.RunMm.behind(rr, spb, mm["kw"], mm["km"], margin=mm["margin"])
+        rs = pkg.RunSync.behind(rm, words, max_distance=3, either=True)
+        rb = pkg.RunBatch.behind(rs, keep_distance=4)
+        res = {}
+        for name in ("all_closed", "scene", "all_open"):
+            gate = pkg.Gate(nch, n, W, device=0)
+            gate.process_device(rows, in_stride, nb, recs[name][0], recs[name][1], nw)
+            view = gate.device_view()
+
+            def run_mm():
+                rr.process_device(*view)
+                rm.process_device(*rr.device_view())
+
+            def run_sync():
+                run_mm()
+                rs.process_device(*rm.device_view())
+
+            def run_batch():
+                run_sync()
+                rb.process_device(*rs.device_view())
+
+            variants = [("batch", run_batch), ("sync", run_sync), ("mm", run_mm)]
+            for _, fn in variants:
+                timed(fn, 3)
+            run_batch()
+            bev = rb.fetch()
+            sruns, sbits, sev = rs.fetch()
+            want = b.hosttwin_runbatch_call(b.hosttwin_runbatch_state(nch), sruns, sbits, sev, words, keep_distance=4)
+            twin_ok = twin_ok and bev.tobytes() == want.tobytes()
+            got_t = {v: [] for v, _ in variants}
+            for rep_ in range(a.reps):
+                j = rep_ % len(variants)
+                for vname, fn in variants[j:] + variants[:j]:
+                    got_t[vname].append(timed(fn, a.inner))
+            (bm, bsd), (sm, ssd), (mmm, msd) = _stats(got_t["batch"]), _stats(got_t["sync"]), _stats(got_t["mm"])
+            diff, diff_se = bm - sm, math.sqrt((bsd * bsd + ssd * ssd) / a.reps)
+            sdiff, sdiff_se = sm - mmm, math.sqrt((ssd * ssd + msd * msd) / a.reps)
+            res[name] = {"open_share": float(masks[name].astype(bool).mean()), "runs": int(len(sruns)),
+                         "decisions_per_call": int(sruns["nr_dec"].astype(np.uint64).sum()), "sync_events_per_call": int(sev.size),
+                         "events_per_call": int(bev.size), "batches_per_call": int((bev["type"] == 2).sum()),
+                         "chain_with_batch_ms": bm, "chain_with_batch_sd": bsd, "chain_ms": sm, "chain_sd": ssd, "batch_ms": diff,
+                         "batch_se": diff_se,
+                         "verdict": "costs" if diff > 2 * diff_se else "neutral" if abs(diff) <= 2 * diff_se else "faster",
+                         "sync_ms": sdiff, "sync_se": sdiff_se, "batch_over_sync": diff / sdiff if sdiff > 0 else None}
+            gate.close()
+        out["channels_%d" % nch] = res
+        for o in (rb, rs, rm, rr, sq):
+            o.close()
+        del d_rows, keep
+    out["equals_twin"] = bool(twin_ok)
+    print(json.dumps(out))
+
+
+def bench_runbatch_alone(a):
+    import torch
+    from __graft_entry__ import load_package
+    pkg = load_package()
+    if not torch.cuda.is_available():
+        raise SystemExit("--bench-runbatch needs the GPU: there is no CPU path to time")
+    bench_runbatch(a, pkg, torch)
+
+
 def bench_runsync_alone(a):
     import torch
     from __graft_entry__ import load_package
@@ -2476,6 +2669,9 @@ def main():
                     help="Mueller-Muller clock recovery on the resampled runs on the device (with --gate-resample): the decisions of every run")
     ap.add_argument("--gate-sync", default=None, metavar="WORD[,WORD...][/DIST][,either]",
                     help="with --gate-mm: the burst sync stage behind it, sync words in the decisions; one line per event in sync.jsonl")
+    ap.add_argument("--gate-batch", default=None, nargs="?", const="", metavar="KEEP[,BAUD]",
+                    help="with --gate-sync: the burst batch stage behind it, POCSAG batches behind the sync events; one line per event in "
+                         "batch.jsonl and the pages in pages.jsonl")
     ap.add_argument("--gate-bits", action="store_true",
                     help="with --gate-ais or --gate-pocsag: sign bits instead of PCM between the burst resampler and the stage")
     ap.add_argument("--gate-ends", action="store_true",
@@ -2493,6 +2689,8 @@ def main():
                     help="the runmm_stage line: burst resampler -> burst Mueller-Muller against the full-row chain at 64 and 1024 channels")
     ap.add_argument("--bench-runsync", action="store_true",
                     help="the runsync_stage line: the burst Mueller-Muller chain with and without the burst sync stage at 64 and 1024 channels")
+    ap.add_argument("--bench-runbatch", action="store_true",
+                    help="the runbatch_stage line: the burst sync chain with and without the burst batch stage at 64 and 1024 channels")
     ap.add_argument("--bench-runbits", action="store_true", help="the runbits_stage line of --bench alone")
     ap.add_argument("--bench-runroute", action="store_true", help="the runroute_stage line alone: the run router at 64 and 1024 channels")
     ap.add_argument("--bench-runroute-pack", action="store_true",
@@ -2519,6 +2717,8 @@ def main():
         return bench_runmm_alone(a)
     if a.bench_runsync:
         return bench_runsync_alone(a)
+    if a.bench_runbatch:
+        return bench_runbatch_alone(a)
     if a.bench_runends:
         return bench_runends_alone(a)
     if a.bench_runbits:
@@ -2537,6 +2737,10 @@ def main():
         raise SystemExit("--floor-windows, --open-ratio and --close-ratio go together: the adaptive squelch needs all three")
     if a.warmup is not None and a.floor_windows is None:
         raise SystemExit("--warmup needs --floor-windows: it is the adaptive squelch's warm-up")
+    if a.gate_batch is not None:
+        if not a.gate_sync:
+            raise SystemExit("--gate-batch needs --gate-sync: the burst batch stage takes the burst sync stage's events and bits")
+        parse_gate_batch(a.gate_batch)
     if a.gate_sync:
         if not a.gate_mm:
             raise SystemExit("--gate-sync needs --gate-mm: the burst sync stage takes the burst Mueller-Muller stage's decisions")

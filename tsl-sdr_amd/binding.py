@@ -100,6 +100,9 @@ ABI_SYMBOLS = [
     "mfm_runsync_create", "mfm_runsync_destroy", "mfm_runsync_process_device", "mfm_runsync_fetch", "mfm_runsync_device_view",
     "mfm_runsync_get_capacity", "mfm_runsync_fetch_state", "mfm_runsync_store_state", "mfm_hosttwin_runsync_call",
     "mfm_hosttwin_runsync_state_check",
+    "mfm_runbatch_create", "mfm_runbatch_destroy", "mfm_runbatch_process_device", "mfm_runbatch_fetch", "mfm_runbatch_device_view",
+    "mfm_runbatch_get_capacity", "mfm_runbatch_fetch_state", "mfm_runbatch_store_state", "mfm_hosttwin_runbatch_call",
+    "mfm_hosttwin_runbatch_state_check",
 ]
 
 class ExchangeDetail(C.Structure):
@@ -362,6 +365,26 @@ RUNSYNC_RUN_DTYPE = np.dtype([("first_window", "<u8"), ("word_offset", "<u8"), (
 RUNSYNC_EVENT_DTYPE = np.dtype([("dec", "<u8"), ("channel", "<u4"), ("run", "<u4"), ("seen", "<u4"), ("word_index", "<u4"),
                                 ("distance", "<u4"), ("inverted", "<u4")])
 RUNSYNC_STATE_DTYPE = np.dtype([("stretch_window", "<u8"), ("decs", "<u8"), ("shr", "<u4"), ("has_stretch", "<u4")])
+
+
+class RunBatchConfig(C.Structure):
+    """struct mfm_runbatch_config"""
+    _fields_ = [("abi_version", C.c_uint32), ("device", C.c_int32), ("nr_channels", C.c_uint32), ("max_runs", C.c_uint32),
+                ("max_decisions", C.c_uint32), ("max_events", C.c_uint32), ("nr_words", C.c_uint32), ("words", C.c_uint32 * 8),
+                ("word_mask", C.c_uint32), ("keep_distance", C.c_uint32), ("flags", C.c_uint32)]
+
+
+MFM_RUNBATCH_SEARCH, MFM_RUNBATCH_RECEIVE, MFM_RUNBATCH_SLOT = 0, 1, 2                   # mfm_runbatch_state.mode
+MFM_RUNBATCH_OVER_RUNS, MFM_RUNBATCH_OVER_EVENTS = 1, 2                                 # d_totals[2]
+MFM_RUNBATCH_IN_RUNSYNC, MFM_RUNBATCH_IN_OUT_OF_STEP, MFM_RUNBATCH_IN_BAD_RUNS, MFM_RUNBATCH_IN_BAD_EVENTS = 1, 2, 4, 8   # d_totals[3]
+RUNBATCH_FRAME = 544     # decisions of a batch and the sync slot behind it (csrc/mfm_runbatch.h)
+# numpy views of struct mfm_runbatch_event (176 bytes) and mfm_runbatch_state (120 bytes, per channel)
+RUNBATCH_EVENT_DTYPE = np.dtype([("type", "<u4"), ("channel", "<u4"), ("run", "<u4"), ("aux", "<u4"), ("word_index", "<u4"),
+                                 ("inverted", "<u4"), ("nr_ok", "<u4"), ("fail_mask", "<u4"), ("stretch_window", "<u8"), ("dec", "<u8"),
+                                 ("raw", "<u4", (16,)), ("corrected", "<u4", (16,))])
+RUNBATCH_STATE_DTYPE = np.dtype([("stretch_window", "<u8"), ("decs", "<u8"), ("mark", "<u8"), ("has_stretch", "<u4"), ("mode", "<u4"),
+                                 ("word_index", "<u4"), ("inverted", "<u4"), ("nr_kept", "<u4"), ("reserved", "<u4"),
+                                 ("kept", "<u4", (17,)), ("reserved2", "<u4")])
 
 
 def runmm_min_step(km, error_min):
@@ -765,6 +788,17 @@ def load_library():
     lib.mfm_hosttwin_runsync_call.argtypes = [C.POINTER(RunSyncConfig), vp, vp, vp, vp, vp, C.c_size_t, szp, vp, C.c_size_t, szp,
                                               vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runsync_state_check.argtypes = [C.c_uint32, vp]
+    lib.mfm_runbatch_create.argtypes = [C.POINTER(vp), C.POINTER(RunBatchConfig)]
+    lib.mfm_runbatch_destroy.argtypes = [C.POINTER(vp)]
+    lib.mfm_runbatch_destroy.restype = None
+    lib.mfm_runbatch_process_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.mfm_runbatch_fetch.argtypes = [vp, vp, C.c_size_t, szp]
+    lib.mfm_runbatch_device_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.mfm_runbatch_get_capacity.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.mfm_runbatch_fetch_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_runbatch_store_state.argtypes = [vp, vp, C.c_size_t]
+    lib.mfm_hosttwin_runbatch_call.argtypes = [C.POINTER(RunBatchConfig), vp, vp, vp, vp, vp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
+    lib.mfm_hosttwin_runbatch_state_check.argtypes = [C.c_uint32, vp]
     lib.mfm_hosttwin_runflex_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
                                               C.c_size_t, szp, vp, C.c_size_t, szp, C.POINTER(C.c_uint32)]
     lib.mfm_hosttwin_runpocsag_call.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_size_t, szp,
@@ -3016,6 +3050,169 @@ def hosttwin_runsync_state_check(state):
     rc = lib.mfm_hosttwin_runsync_state_check(st.shape[0], st.ctypes.data)
     if rc < 0:
         raise MfmError(rc, "mfm_hosttwin_runsync_state_check", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
+
+
+def _runbatch_config(nr_channels, max_runs, max_decisions, words, word_mask, keep_distance, max_events, device, flags, abi_version):
+    ws = [int(w) & 0xFFFFFFFF for w in words]
+    arr = (C.c_uint32 * 8)(*ws[:8])
+    return RunBatchConfig(abi_version, device, nr_channels, max_runs, max_decisions, max_events, len(ws), arr, word_mask, keep_distance, flags)
+
+
+class RunBatch:
+    """mfm_runbatch: behind the sync events of a RunSync's device view, POCSAG batches of 16 codewords cut from its bit words, BCH
+    on them, and sync kept / sync lost in the slot behind every batch (pager/pager_pocsag.c:468-538 at one sample per bit);
+    RUNBATCH_EVENT_DTYPE events of the MFM_POCSAG_EV_* types.  max_runs and max_decisions are the burst sync stage's (RunBatch.behind
+    reads them), words its table; max_events 0 cannot overflow."""
+
+    def __init__(self, nr_channels, max_runs, max_decisions, words, word_mask=0, keep_distance=4, max_events=0, device=0, flags=0,
+                 abi_version=MFM_ABI_VERSION):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        self.cfg = _runbatch_config(nr_channels, max_runs, max_decisions, words, word_mask, keep_distance, max_events, device, flags, abi_version)
+        rc = self.lib.mfm_runbatch_create(C.byref(self.h), C.byref(self.cfg))
+        if rc < 0:
+            self._raise(rc, "mfm_runbatch_create")
+        self.nr_channels = nr_channels
+
+    @classmethod
+    def behind(cls, run_sync, **kwargs):
+        """a stage sized for everything one call of `run_sync` can produce, with its table of words"""
+        cfg = run_sync.cfg
+        return cls(run_sync.nr_channels, cfg.max_runs, cfg.max_decisions, list(cfg.words)[:cfg.nr_words], **kwargs)
+
+    def close(self):
+        if self.h:
+            self.lib.mfm_runbatch_destroy(C.byref(self.h))
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        raise MfmError(rc, what, self.lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else self.lib.mfm_strerror(rc).decode())
+
+    def process_device(self, d_runs, d_bits, d_events, d_totals, stream=None):
+        """the four addresses of RunSync.device_view(), after its process_device on the same stream"""
+        rc = self.lib.mfm_runbatch_process_device(self.h, C.c_void_p(d_runs), C.c_void_p(d_bits), C.c_void_p(d_events), C.c_void_p(d_totals),
+                                                  C.c_void_p(stream or 0))
+        if rc < 0:
+            self._raise(rc, "mfm_runbatch_process_device")
+
+    def fetch(self, max_events=None):
+        """the RUNBATCH_EVENT_DTYPE events of the last call.  With a buffer too small: MfmError(MFM_E_NOMEM) whose `needed`
+        attribute is the number that would fit"""
+        ne = C.c_size_t()
+        if max_events is None:
+            rc = self.lib.mfm_runbatch_fetch(self.h, None, 0, C.byref(ne))
+            if rc not in (MFM_OK, MFM_E_NOMEM, MFM_E_STATE):  # MFM_E_STATE comes again below
+                self._raise(rc, "mfm_runbatch_fetch")
+            max_events = ne.value
+        evs = np.zeros(max(max_events, 1), RUNBATCH_EVENT_DTYPE)
+        rc = self.lib.mfm_runbatch_fetch(self.h, evs.ctypes.data, max_events, C.byref(ne))
+        if rc < 0:
+            try:
+                self._raise(rc, "mfm_runbatch_fetch")
+            except MfmError as err:
+                err.needed = ne.value
+                raise
+        return evs[:ne.value].copy()
+
+    def device_view(self):
+        """(d_events, d_totals): device addresses of the last call's events and the four uint64 totals (events, runs, overflow,
+        input error)"""
+        e, t = C.c_void_p(), C.c_void_p()
+        rc = self.lib.mfm_runbatch_device_view(self.h, C.byref(e), C.byref(t))
+        if rc < 0:
+            self._raise(rc, "mfm_runbatch_device_view")
+        return e.value, t.value
+
+    def capacity(self):
+        """(max_runs, max_events) fixed at create"""
+        r, e = C.c_uint32(), C.c_uint64()
+        rc = self.lib.mfm_runbatch_get_capacity(self.h, C.byref(r), C.byref(e))
+        if rc < 0:
+            self._raise(rc, "mfm_runbatch_get_capacity")
+        return r.value, e.value
+
+    def fetch_state(self):
+        """the per-channel state the last call left (RUNBATCH_STATE_DTYPE [C]): what the host twin carries"""
+        out = np.zeros(self.nr_channels, RUNBATCH_STATE_DTYPE)
+        rc = self.lib.mfm_runbatch_fetch_state(self.h, out.ctypes.data, self.nr_channels)
+        if rc < 0:
+            self._raise(rc, "mfm_runbatch_fetch_state")
+        return out
+
+    def store_state(self, state, nr_channels=None):
+        """mfm_runbatch_store_state: what the next process call continues from.  Validated first: MfmError(MFM_E_INVAL) with a
+        message naming channel and field, and nothing written"""
+        st = np.ascontiguousarray(state, dtype=RUNBATCH_STATE_DTYPE) if state is not None else None
+        n = self.nr_channels if nr_channels is None else nr_channels
+        assert st is None or st.shape == (n,)
+        rc = self.lib.mfm_runbatch_store_state(self.h, st.ctypes.data if st is not None else None, n)
+        if rc < 0:
+            self._raise(rc, "mfm_runbatch_store_state")
+
+
+def hosttwin_runbatch_state(nr_channels):
+    """the host twin's per-channel state at the start of a stream: RUNBATCH_STATE_DTYPE [C], all zero (no stretch)"""
+    return np.zeros(nr_channels, RUNBATCH_STATE_DTYPE)
+
+
+def hosttwin_runbatch_call(state, runs, bits, sync_events, words, word_mask=0, keep_distance=4, totals=None, max_runs=None,
+                           max_decisions=None, max_events=0, max_out_events=None, flags=0, abi_version=MFM_ABI_VERSION):
+    """mfm_hosttwin_runbatch_call: one call of the burst batch stage on the CPU.  state (hosttwin_runbatch_state) is updated in
+    place; runs RUNSYNC_RUN_DTYPE, bits uint32 and sync_events RUNSYNC_EVENT_DTYPE are one burst sync call's result, totals its four
+    totals (default: the lengths, no flags); max_runs / max_decisions / max_events are the configuration's (default: what the call
+    needs); returns the RUNBATCH_EVENT_DTYPE events.  A refused call raises MfmError(MFM_E_STATE) with a `flags` attribute (overflow
+    | input error << 8)"""
+    lib = load_library()
+    state = np.asarray(state)
+    assert state.dtype == RUNBATCH_STATE_DTYPE and state.flags.c_contiguous and state.ndim == 1
+    rr = np.ascontiguousarray(runs, dtype=RUNSYNC_RUN_DTYPE).reshape(-1)
+    bb = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+    ee = np.ascontiguousarray(sync_events, dtype=RUNSYNC_EVENT_DTYPE).reshape(-1)
+    t = np.array([rr.size, ee.size, 0, 0] if totals is None else totals, np.uint64)
+    assert t.shape == (4,)
+    max_runs = max(rr.size, 1) if max_runs is None else max_runs
+    max_decisions = max(int(rr["nr_dec"].astype(np.uint64).sum()), 1) if max_decisions is None else max_decisions
+    cfg = _runbatch_config(state.shape[0], max_runs, max_decisions, words, word_mask, keep_distance, max_events, 0, flags, abi_version)
+    max_out_events = int((3 * (rr["nr_dec"].astype(np.uint64) // RUNBATCH_FRAME) + 5).sum()) if max_out_events is None else max_out_events
+    out_e = np.zeros(max(max_out_events, 1), RUNBATCH_EVENT_DTYPE)
+    ne, fl = C.c_size_t(), C.c_uint32()
+    rc = lib.mfm_hosttwin_runbatch_call(C.byref(cfg), state.ctypes.data, rr.ctypes.data if rr.size else None, bb.ctypes.data if bb.size else None,
+                                        ee.ctypes.data if ee.size else None, t.ctypes.data, out_e.ctypes.data, max_out_events, C.byref(ne),
+                                        C.byref(fl))
+    if rc < 0:
+        err = MfmError(rc, "mfm_hosttwin_runbatch_call", lib.mfm_last_error().decode() if rc in (MFM_E_INVAL, MFM_E_STATE) else lib.mfm_strerror(rc).decode())
+        err.needed, err.flags = ne.value, fl.value
+        raise err
+    return out_e[:ne.value].copy()
+
+
+def hosttwin_runbatch_state_check(state):
+    """mfm_hosttwin_runbatch_state_check: what RunBatch.store_state validates, on the CPU"""
+    st = np.ascontiguousarray(state, dtype=RUNBATCH_STATE_DTYPE).reshape(-1)
+    lib = load_library()
+    rc = lib.mfm_hosttwin_runbatch_state_check(st.shape[0], st.ctypes.data)
+    if rc < 0:
+        raise MfmError(rc, "mfm_hosttwin_runbatch_state_check", lib.mfm_last_error().decode() if rc == MFM_E_INVAL else lib.mfm_strerror(rc).decode())
+
+
+def runbatch_to_pocsag_events(events, baud):
+    """mfm_pocsag_event records (POCSAG_EVENT_DTYPE, what host/mfm_pager_pocsag.c's pager_pocsag_on_events takes) from the burst
+    batch stage's: `baud` is the caller's (the stage counts decisions, not samples) and sample = dec, stretch-relative: one pager
+    object per (channel, stretch), a fresh one at every new stretch_window, as the stage has a fresh automaton there"""
+    ev = np.asarray(events)
+    assert ev.dtype == RUNBATCH_EVENT_DTYPE
+    out = np.zeros(ev.shape, POCSAG_EVENT_DTYPE)
+    for f in ("type", "channel", "aux", "nr_ok", "fail_mask", "raw", "corrected"):
+        out[f] = ev[f]
+    out["baud"] = baud
+    out["sample"] = ev["dec"]
+    return out
 
 
 def hosttwin_runpocsag_state(nr_channels):
