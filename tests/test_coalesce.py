@@ -55,7 +55,7 @@ def test_coalesced_ragged_buffers_against_the_oracle(pkg, ora, kernel, policy):
     than the filter, gathered into launches of up to 300 000 samples: same PCM and filtered IQ as the oracle on the whole
     stream; with MFM_F_GATHER the launch boundaries are those of the gathered sample count, not of the blocks.  The
     `*overlap` policies set MFM_F_OVERLAP at sizes that stay on ONE stream (at most 92 tiles on one slice, against 512 workgroup
-    slots: launch_locked() alternates only beyond a tile per slot): they exercise the flag's bookkeeping - the second stream, its
+    slots: launch_plan() alternates only beyond a tile per slot): they exercise the flag's bookkeeping - the second stream, its
     events, the carry ring's allocation.  Launches that do alternate: tests/test_overlap_forms.py."""
     b = pkg.binding
     fs, decim, taps, offs, gains = pkg.synth.plan("cfg2_64ch", nr_channels=9)
@@ -226,7 +226,7 @@ def test_coalescing_group_of_several_shards_through_a_fake_transport(tmp_path, s
 @pytest.mark.parametrize("plan,nch", [("cfg2_64ch", 64), ("cfg2_64ch_grid", 64), ("cfg3_1024ch", 200), ("multifm_1ch", 20)])
 def test_overlapped_launches_against_the_oracle(pkg, ora, plan, nch, want_iq):
     """MFM_F_OVERLAP at sizes that stay on ONE stream: blocks of at most 2^17 samples are at most 22 tiles (52 at D = 40) on at
-    most 4 slices, against 512 workgroup slots, and launch_locked() alternates only beyond a tile per slot - asserted below
+    most 4 slices, against 512 workgroup slots, and launch_plan() alternates only beyond a tile per slot - asserted below
     (overlapped_launches == 0).  What runs is the flag's bookkeeping (the second stream and its events, the carry ring's
     allocation, the waits a launch that does not alternate issues) and, as on any engine, that a launch takes nothing from the
     one before it but input samples (the output in front of it is recomputed from the row kept in front of the first

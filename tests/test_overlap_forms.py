@@ -1,5 +1,5 @@
 """Two-stream launches and the early carry on every form they run on (include/multifm_hip.h: MFM_F_OVERLAP,
-mfm_engine_stream; mfm_engine.hip launch_locked; mfm_kernel_v3.hip, the `L.head_n != 0 && tile == 0` block).
+mfm_engine_stream; mfm_launch_plan.h launch_plan, which mfm_engine.hip's launch_locked queues; mfm_kernel_v3.hip, the `L.head_n != 0 && tile == 0` block).
 
 tests/test_launch_overlap.py runs the path on one form (D 96, 128 taps, one slice, the sub-plane layout, no filtered IQ).  Here:
 the three layouts of the second-generation kernel at every k-step count, 64 and 65 channels, several slices, filtered IQ, the
@@ -48,7 +48,7 @@ CS16, CS8, RTLSDR_U8 = 0, 1, 3
 # ------------------------------------------------------------------------------------------------ the rule, restated
 
 def _rule(st, nch):
-    """(slots, nslices, outputs per tile) of launch_locked()'s alternation rule, from stats() alone"""
+    """(slots, nslices, outputs per tile) of launch_plan()'s alternation rule (mfm_launch_plan.h), from stats() alone"""
     slots = 256 * max(1, min(2, LDS_PER_CU // st["lds_bytes"]))
     return slots, -(-nch // st["slice_channels"]), st["outputs_per_tile"]
 

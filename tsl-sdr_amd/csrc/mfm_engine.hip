@@ -26,6 +26,7 @@
 #include "mfm_numerics.h"
 #include "mfm_taps.h"
 #include "mfm_plan.h"
+#include "mfm_launch_plan.h"
 #include "mfm_engine_internal.h"
 
 /* every kernel file exports a pair: select (which template instance runs a launch description: mfm_plan.hip, at commit) and
@@ -193,11 +194,8 @@ struct mfm_engine {
     /* Early carry (int16 blocks on mfm_kernel_v3.hip): when a launch alternates, the next launch's [hist | history tail] is
      * copied at submit time by a one-workgroup kernel on s_in - behind the producer of this block and behind no channel
      * kernel - into a slot of d_ring, and the next launch reads it from there (mfm_launch_v3::head).  Pass r of
-     * launch_locked() reads buffer r % nbuf and, if its head is in the ring, slot r % (nbuf + 1).
-     * NO EVENT GUARDS A SLOT: pass r writes slot (r + 1) % (nbuf + 1), which pass r + 1 - (nbuf + 1) = r - nbuf read last;
-     * that pass also read buffer (r - nbuf) % nbuf = r % nbuf, the buffer of pass r, and acquire_input() has waited on the
-     * host for its kernel's end (in_free) before the producer of pass r's block was allowed to write - so before this
-     * submit.  (Two buffers: slot (r + 1) % 3 was last read by launch r - 2.) */
+     * launch_locked() reads buffer r % nbuf and, if its head is in the ring, slot r % (nbuf + 1).  No event guards a slot:
+     * why none is needed stands with the decision, at LaunchPlan::early (mfm_launch_plan.h). */
     uint32_t *d_ring = nullptr;
     uint32_t ring_slot = 0;          /* samples per slot: 2 * D + T + 16 */
     uint64_t pass = 0;               /* launch_locked() passes since the stream's start: buffer pass % nbuf is being filled */
@@ -875,7 +873,7 @@ static int commit_locked(struct mfm_engine *e)
     /* int16 blocks run on mfm_kernel_v3.hip (not the long-filter file): the early carry applies */
     const bool v3s = v3 && p.fmt[MFM_IN_CS16].kfn && p.fmt[MFM_IN_CS16].V.layout != 3u;
     /* two streams by itself: where nobody can tell (the stream has not been handed out: mfm_engine_stream) and the other
-     * conditions of include/multifm_hip.h hold; the per-launch ones are launch_locked()'s */
+     * conditions of include/multifm_hip.h hold; the per-launch ones are launch_plan()'s (mfm_launch_plan.h) */
     e->auto_alt = v3s && dev_only && 2 == e->nbuf && !(e->cfg.flags & MFM_F_OVERLAP);
     if (((e->cfg.flags & MFM_F_OVERLAP) && v3) || e->auto_alt) {
         HIP_TRY(hipStreamCreateWithFlags(&e->cs[1], hipStreamNonBlocking));
@@ -1028,11 +1026,10 @@ struct SubmitPlan {
 /* what accepting nr_samples more (0: what is there) would mean.  Takes the lock for the slot's state. */
 void plan_block(mfm_engine *e, size_t nr_samples, SubmitPlan *p, bool locked)
 {
-    const uint32_t T = e->nr_taps, D = e->cfg.decimation, co = e->cfg.coalesce_samples;
-    const uint64_t pend_after = (uint64_t)e->pend + nr_samples;
-    const uint64_t n_avail = (uint64_t)e->tail + pend_after;
-    p->n_new = n_avail >= T ? (uint32_t)((n_avail - T) / D + 1) : 0;
-    p->must = 0 == co || pend_after >= co;
+    const AcceptPlan a = accept_plan(e->nr_taps, e->cfg.decimation, e->tail, e->pend, nr_samples, e->cfg.coalesce_samples,
+                                     (e->cfg.flags & MFM_F_GATHER) != 0);
+    p->n_new = a.n_new;
+    p->must = a.must;
     if (e->cfg.flags & MFM_F_DEVICE_ONLY) {
         p->may = true;
     } else if (locked) {
@@ -1041,92 +1038,236 @@ void plan_block(mfm_engine *e, size_t nr_samples, SubmitPlan *p, bool locked)
         std::lock_guard<std::mutex> guard(e->mu);
         p->may = 0 == p->n_new || e->slots[e->submit_seq % e->nslots].state == OutSlot::FREE;
     }
-    p->want = false;
-    if (!p->must && p->n_new && !(e->cfg.flags & MFM_F_GATHER)) {
-        const int fl = launches_in_flight(e);
-        p->want = 0 == fl || (1 == fl && 4u * pend_after >= e->last_launch_samples);
+    /* (the launches in flight are asked for - event queries - only where the policy has a say) */
+    p->want = a.policy && accept_wants(a, launches_in_flight(e), e->last_launch_samples);
+}
+
+static_assert(LP_V3_OT == MFM_V3_OT && LP_V3_LEAD == MFM_V3_LEAD, "mfm_launch_plan.h restates mfm_kernel.h's tile");
+
+/* what launch_plan() decides a pass over d_in[cur_in] from */
+LaunchInput launch_input(const mfm_engine *e)
+{
+    const int fmt = e->in_fmt[e->cur_in];
+    const FormatPlan &f = e->plan.fmt[fmt];
+    LaunchInput in;
+    in.T = e->nr_taps;
+    in.D = e->cfg.decimation;
+    in.variant = e->plan.variant;
+    in.raw8 = fmt != MFM_IN_CS16;
+    in.hist = e->hist;
+    in.tail = e->tail;
+    in.pend = e->pend;
+    in.ncs = e->ncs;
+    in.auto_alt = e->auto_alt;
+    in.ring = e->d_ring != nullptr;
+    in.head = e->head != nullptr;
+    in.alt_wg_per_cu = e->plan.v_wg_per_cu;
+    in.wg_per_cu = f.wg_per_cu;
+    in.nslices = 2u == in.variant ? f.V.nslices : 1u == in.variant ? f.M.nslices : f.L.nslices;
+    in.opl = (uint32_t)e->plan.opl;
+    in.ot = f.M.ot;
+    return in;
+}
+
+/* The channel kernel of a launch with outputs, on S, into `slot`.  *timing_end: the event that stamps its end, if it has one. */
+int queue_kernel(mfm_engine *e, const LaunchPlan &lp, const FormatPlan &f, OutSlot *slot, hipStream_t S, hipEvent_t *timing_end)
+{
+    const int cur = e->cur_in, nxt = (cur + 1) % e->nbuf;
+    mfm_chan_state *const st_in = e->d_state[e->parity], *const st_out = e->d_state[e->parity ^ 1];
+    uint32_t *const iq_dbg = e->plan.any_iq ? slot->d_iq : nullptr;
+    if (!(e->cfg.flags & MFM_F_DEVICE_ONLY)) {
+        /* the previous D2H out of this slot must have drained before the kernel rewrites it */
+        HIP_TRY(hipStreamWaitEvent(S, slot->ready, 0));
     }
+    /* MFM_F_TIMING_SPARSE: every fourth launch carries the event pair.  An event record is a packet the command
+     * processor handles between two kernels (~4 us each on MI355X): bracketing every launch of a back-to-back
+     * stream costs 6 % of a 0.12 ms step, a sample of them costs under 1 % and measures the same kernel. */
+    const bool timed = (e->cfg.flags & MFM_F_TIMING) != 0 &&
+                       (!(e->cfg.flags & MFM_F_TIMING_SPARSE) || (e->launches % kSparseTiming) == 0);
+    /* two compute streams: no event pairs - a pair around a launch that shares the chip with the one before it measures
+     * its wait for slots -, the kernel's own stamp is the duration (mfm_engine::stamp_pending) */
+    const bool stamped = timed && e->ncs > 1u && e->d_cyc != nullptr;
+    const bool timing = timed && e->ncs <= 1u;
+    int ti = 0;
+    if (timed) {
+        int rc = fold_timing(e, false);
+        if (rc != MFM_OK) {
+            return rc;
+        }
+    }
+    if (stamped) {
+        e->stamp_pending.push_back(e->launches);
+    }
+    if (timing) {
+        ti = (int)(e->t_head % kTimingPairs);
+        HIP_TRY(hipEventRecord(e->t0[ti], S));
+    }
+    if (e->in_fmt[cur] != MFM_IN_CS16) {
+        e->launches_8bit++; /* (8-bit blocks stay bytes on the matrix kernels only) */
+    }
+    e->grid_last = lp.grid;
+    if (2u == e->plan.variant) {
+        mfm_launch_v3 V = f.V;
+        V.x = e->d_in[cur];
+        V.n_avail = lp.n_avail;
+        V.n_new = lp.n_new;
+        V.hist = e->hist;
+        V.k_base = e->outputs;
+        V.ntiles = lp.ntiles;
+        V.nchunks = lp.nchunks;
+        V.cl = lp.cl;
+        V.nitems = lp.nitems;
+        V.tail_src = lp.tail_src;
+        V.tail_n = lp.tail_n;
+        V.tail_dst = e->d_in[nxt];
+        if (lp.two) {
+            e->overlapped++;
+        }
+        if (LP_HEAD_KERNEL == lp.head) {
+            V.head = e->head;
+            V.head_n = lp.head_n;
+        }
+        V.pcm = slot->d_pcm;
+        V.iq_dbg = iq_dbg;
+        if (e->d_cyc) {
+            V.cyc = e->d_cyc + 2u * (e->launches % kCycleRing);
+            V.cyc_tag = (uint32_t)((e->launches + 1u) & 0xffffffu);
+            /* ... and zeroes the slot half a ring ahead, long before that launch folds its maxima into it: a slot never
+             * holds an older launch's stamp when its turn comes, whatever the 24-bit tags compare like after 2^24 launches */
+            V.cyc_clear = e->d_cyc + 2u * ((e->launches + kCycleRing / 2u) % kCycleRing);
+        }
+        HIP_TRY(mfm_launch_channel_kernel_v3(f.kfn, &V, f.lds_bytes, lp.grid, S));
+    } else if (1u == e->plan.variant) {
+        mfm_launch_mfma M = f.M;
+        M.x = e->d_in[cur];
+        M.n_avail = lp.n_avail;
+        M.n_new = lp.n_new;
+        M.ntiles = lp.ntiles;
+        M.nitems = lp.nitems;
+        M.tail_src = lp.tail_src;
+        M.tail_n = lp.tail_n;
+        M.tail_dst = e->d_in[nxt];
+        M.st_in = st_in;
+        M.st_out = st_out;
+        M.pcm = slot->d_pcm;
+        M.iq_dbg = iq_dbg;
+        HIP_TRY(mfm_launch_channel_kernel_mfma(f.kfn, &M, f.lds_bytes, lp.grid, S));
+    } else {
+        mfm_launch L = f.L;
+        L.x = e->d_in[cur];
+        L.n_avail = lp.n_avail;
+        L.n_new = lp.n_new;
+        L.ntiles = lp.ntiles;
+        L.st_in = st_in;
+        L.st_out = st_out;
+        L.pcm = slot->d_pcm;
+        L.iq_dbg = iq_dbg;
+        HIP_TRY(mfm_launch_channel_kernel(f.kfn, &L, f.lds_bytes, S));
+    }
+    if (timing) {
+        HIP_TRY(hipEventRecord(e->t1[ti], S));
+        *timing_end = e->t1[ti];
+        e->t_head++;
+    }
+    e->parity ^= 1;
+    e->launches++;
+    return MFM_OK;
+}
+
+/* The next launch's [hist | history tail], where the kernel has not taken it along: into the next pass's ring slot on s_in, or
+ * to the front of the next buffer on S_after, the stream of the next launch. */
+int queue_carry(mfm_engine *e, const LaunchPlan &lp, hipStream_t S_after)
+{
+    const int cur = e->cur_in, nxt = (cur + 1) % e->nbuf;
+    if (LP_CARRY_RING == lp.carrier) {
+        /* the slot: see LaunchPlan::early for why nobody reads it any more */
+        uint32_t *const dst = e->d_ring + (size_t)((e->pass + 1u) % (uint64_t)(e->nbuf + 1)) * e->ring_slot;
+        if (lp.carry_n > e->ring_slot) {
+            return fail(MFM_E_STATE, "carry of %u samples, ring slots of %u", lp.carry_n, e->ring_slot);
+        }
+        hipLaunchKernelGGL(mfm_carry_kernel, dim3(1), dim3(256), 0, e->s_in, e->d_in[cur] + lp.carry_src, dst, lp.carry_n);
+        HIP_TRY(hipGetLastError());
+        /* this buffer is free once its kernel AND this copy are through (acquire_input waits for both) */
+        HIP_TRY(hipEventRecord(e->tail_done[cur], e->s_in));
+        e->tail_pending[cur] = true;
+        e->head = dst;
+        e->head_ev = e->tail_done[cur];
+    } else if (LP_CARRY_COPY == lp.carrier) {
+        const size_t ss = e->in_fmt[cur] != MFM_IN_CS16 ? 2 : 4;
+        if (lp.two && e->in_free_wait[nxt]) {
+            /* the launch that last read the next buffer may be on the other stream */
+            HIP_TRY(hipStreamWaitEvent(S_after, e->in_free_wait[nxt], 0));
+        }
+        if (lp.two && e->tail_pending[nxt]) {
+            /* ... and so may the carry copy OUT of that buffer, when a launch in between did not alternate (ADVICE r4):
+             * a wait on a completed event costs nothing */
+            HIP_TRY(hipStreamWaitEvent(S_after, e->tail_done[nxt], 0));
+        }
+        HIP_TRY(hipMemcpyAsync(e->d_in[nxt], reinterpret_cast<const uint8_t *>(e->d_in[cur]) + lp.carry_src * ss, lp.carry_n * ss,
+                               hipMemcpyDeviceToDevice, S_after));
+        if (lp.two) {
+            /* this buffer is free once its kernel AND this copy are through (acquire_input waits for both) */
+            HIP_TRY(hipEventRecord(e->tail_done[cur], S_after));
+            e->tail_pending[cur] = true;
+        }
+    }
+    return MFM_OK;
+}
+
+/* the outputs of the launch just queued on S: to the slot's host mirror on s_out, unless they stay on the device */
+int queue_output(mfm_engine *e, const LaunchPlan &lp, OutSlot *slot, hipStream_t S)
+{
+    slot->first_output = e->outputs;
+    slot->nr_outputs = lp.n_new;
+    if (e->cfg.flags & MFM_F_DEVICE_ONLY) {
+        /* nothing waits on slot->ready in device-only mode: consumers are ordered by the stream */
+        return MFM_OK;
+    }
+    HIP_TRY(hipEventRecord(e->kernel_done, S));
+    HIP_TRY(hipStreamWaitEvent(e->s_out, e->kernel_done, 0));
+    const size_t row = (size_t)e->plan.out_stride * sizeof(int16_t), C = e->chans.size();
+    HIP_TRY(hipMemcpy2DAsync(slot->h_pcm, row, slot->d_pcm, row, lp.n_new * sizeof(int16_t), C, hipMemcpyDeviceToHost, e->s_out));
+    if (e->plan.any_iq) {
+        HIP_TRY(hipMemcpy2DAsync(slot->h_iq, row * 2, slot->d_iq, row * 2, lp.n_new * sizeof(uint32_t), C, hipMemcpyDeviceToHost,
+                                 e->s_out));
+    }
+    HIP_TRY(hipEventRecord(slot->ready, e->s_out));
+    slot->state = OutSlot::INFLIGHT;
+    return MFM_OK;
 }
 
 /*
  * One pass over d_in[cur_in] = [history tail | the blocks accepted since the last launch]: the kernel, the carry of the
- * unconsumed samples to the front of the next buffer, the copy of the outputs to the host mirror.  Caller holds e->mu and
- * has checked that an output slot is free.
+ * unconsumed samples to where the next launch reads them, the copy of the outputs to the host mirror - queued as
+ * launch_plan() (mfm_launch_plan.h) decides; every count and every choice of a stream is that plan's.  Caller holds e->mu
+ * and has checked that an output slot is free.
  */
 int launch_locked(mfm_engine *e)
 {
-    const uint32_t T = e->nr_taps, D = e->cfg.decimation, C = (uint32_t)e->chans.size();
-    const bool dev_only = (e->cfg.flags & MFM_F_DEVICE_ONLY) != 0, v3 = 2u == e->plan.variant;
-    const int cur = e->cur_in, nxt = (cur + 1) % e->nbuf;
-    const uint32_t n_avail = e->tail + e->pend;
-    const uint32_t n_new = n_avail >= T ? (n_avail - T) / D + 1 : 0;
-    const int fmt = e->in_fmt[cur];
-    const bool raw8 = fmt != MFM_IN_CS16;
-    /* the stream of this launch, and of the one after it (the same one unless MFM_F_OVERLAP alternates them): what the
-     * next launch needs from this buffer - the carry - is queued there */
-    hipStream_t S = e->cs[e->si];
-    /* Two streams pay off when a launch fills the workgroup slots more than once (its ragged end is what the next launch
-     * moves into); a launch of one tile per slot or less costs more in the extra packets of the carry (a copy, two events)
-     * than it gains: it keeps the carry in the kernel and the next launch stays behind it on the same stream. */
-    bool two = false;
-    /* (an engine that alternates without having been asked to does so for int16 blocks only: 8-bit blocks keep one stream) */
-    if (e->ncs > 1u && v3 && n_new && !(e->auto_alt && raw8)) {
-        const uint32_t ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT, slots = 256u * e->plan.v_wg_per_cu;
-        /* ... and only when what its carry copy reads - the last consumed row and the unconsumed samples behind it - lies
-         * behind the [hist | tail] front of this buffer, which the previous launch's carry wrote on the OTHER stream: the
-         * copy below is then ordered behind everything it reads (the H2D copies, through in_ready) without a wait of its
-         * own.  True for every launch of more than a tile per slot; spelled out so that it does not rest on that. */
-        two = (uint64_t)ntiles * e->plan.v_nslices > slots && (uint64_t)n_new * D >= (uint64_t)e->tail + D;
-    }
-    hipStream_t S_after = two ? e->cs[e->si ^ 1u] : S;
-    /* early carry: an alternating launch of int16 blocks on mfm_kernel_v3.hip leaves the next launch's [hist | tail] in the
-     * carry ring instead of at the front of the next buffer (mfm_engine::d_ring) */
-    const bool early = two && !raw8 && e->d_ring != nullptr;
-    /* chunks of consecutive tiles, `rounds` per workgroup slot and slice, lengths equal to within one tile
-     * (a chunk pays one extra column group) */
-    uint32_t v_ntiles = 0, v_nchunks = 0, v_nitems = 0, v_slots = 0;
-    if (v3 && n_new) {
-        const FormatPlan &f = e->plan.fmt[fmt];
-        v_ntiles = (n_new + MFM_V3_OT - 1u) / MFM_V3_OT;
-        v_slots = 256u * f.wg_per_cu;
-        /* (a multiple of 8: the items are dealt chunk-major over the eight XCDs - item = 8 * (chunk / 8 * nslices + slice) +
-         * chunk % 8, mfm3_decode_item - so a chunk count that is not one leaves holes in the last group of eight, the grid
-         * overflows the slots and a few workgroups run a SECOND chunk while the others are done: with 3, 5, 6 or 12 slices
-         * (130-192, 257-320, ... channels) a launch took up to twice as long as its work, profiles/r06_ab_chunking.txt) */
-        uint32_t per_slice = std::max(1u, v_slots / f.V.nslices);
-        per_slice = per_slice >= 8u ? per_slice & ~7u : per_slice;
-        /* one chunk per slot: shorter chunks (3..10 tiles, several rounds) were 2-6 % slower on MI355X */
-        v_nchunks = std::min(v_ntiles, per_slice);
-        v_nitems = ((v_nchunks + 7u) / 8u) * 8u * f.V.nslices;
-    }
+    const LaunchPlan lp = launch_plan(launch_input(e));
+    const int cur = e->cur_in, nxt = (cur + 1) % e->nbuf, fmt = e->in_fmt[cur];
+    /* the stream of this launch, and of the one after it (the same one unless they alternate): what the next launch needs
+     * from this buffer - the carry - is queued there */
+    hipStream_t S = e->cs[e->si], S_after = lp.two ? e->cs[e->si ^ 1u] : S;
     if (e->head) {
         /* this buffer's [hist | tail] is in the ring: whoever reads it - the kernel or the copy below - comes behind its copy */
         HIP_TRY(hipStreamWaitEvent(S, e->head_ev, 0));
-        /* The kernel takes it from there when it alternates (a launch that does not carries the tail itself, out of the
-         * buffer's front, or there is no kernel at all) and when nothing but the prologue of a first chunk's workgroup reads
-         * the first head_n samples: the second tile's image starts (OT - LEAD) rows into the buffer, and no workgroup comes
-         * to a first chunk as its second item.  Both hold wherever `two` does today; spelled out so that the kernel's
-         * assumption does not rest on that.  Otherwise the samples go where they would have been: nobody reads this
-         * buffer's front any more, acquire_input() has waited for the launch that did. */
-        const uint32_t head_n = e->hist + e->tail;
-        if (!(two && !raw8 && head_n <= (MFM_V3_OT - MFM_V3_LEAD) * D && v_nitems <= v_slots)) {
-            hipLaunchKernelGGL(mfm_carry_kernel, dim3(1), dim3(256), 0, S, e->head, e->d_in[cur], head_n);
+        if (LP_HEAD_COPY_BACK == lp.head) {
+            hipLaunchKernelGGL(mfm_carry_kernel, dim3(1), dim3(256), 0, S, e->head, e->d_in[cur], lp.head_n);
             HIP_TRY(hipGetLastError());
             e->head = nullptr;
         }
     }
-    if (e->ncs > 1u && !two && e->in_free_wait[nxt] && e->in_free_on[nxt] != S) {
-        /* this launch (or its stream's copy) writes the carry into the next buffer: whoever read that one last - possibly on
-         * the other stream - must be through */
+    if (lp.wait_next_reader && e->in_free_wait[nxt] && e->in_free_on[nxt] != S) {
         HIP_TRY(hipStreamWaitEvent(S, e->in_free_wait[nxt], 0));
     }
 
     OutSlot *slot = nullptr;
     int slot_idx = -1;
-    if (n_new) {
+    if (lp.n_new) {
         slot_idx = (int)(e->submit_seq % e->nslots);
         slot = &e->slots[slot_idx];
-        if (!dev_only && slot->state != OutSlot::FREE) {
+        if (!(e->cfg.flags & MFM_F_DEVICE_ONLY) && slot->state != OutSlot::FREE) {
             return fail(MFM_E_BUSY, "all %d output slots hold unfetched blocks", e->nslots);
         }
     }
@@ -1138,167 +1279,25 @@ int launch_locked(mfm_engine *e)
         e->wait_copy_stream = false;
     }
 
-    bool tail_in_kernel = false;
     hipEvent_t timing_end = nullptr;
-    if (n_new) {
-        const FormatPlan &f = e->plan.fmt[fmt]; /* (8-bit blocks stay bytes on the matrix kernels only) */
-        mfm_chan_state *const st_in = e->d_state[e->parity], *const st_out = e->d_state[e->parity ^ 1];
-        uint32_t *const iq_dbg = e->plan.any_iq ? slot->d_iq : nullptr;
-        if (!dev_only) {
-            /* the previous D2H out of this slot must have drained before the kernel rewrites it */
-            HIP_TRY(hipStreamWaitEvent(S, slot->ready, 0));
+    if (lp.n_new) {
+        int rc = queue_kernel(e, lp, e->plan.fmt[fmt], slot, S, &timing_end);
+        if (rc != MFM_OK) {
+            return rc;
         }
-        /* MFM_F_TIMING_SPARSE: every fourth launch carries the event pair.  An event record is a packet the command
-         * processor handles between two kernels (~4 us each on MI355X): bracketing every launch of a back-to-back
-         * stream costs 6 % of a 0.12 ms step, a sample of them costs under 1 % and measures the same kernel. */
-        const bool timed = (e->cfg.flags & MFM_F_TIMING) != 0 &&
-                           (!(e->cfg.flags & MFM_F_TIMING_SPARSE) || (e->launches % kSparseTiming) == 0);
-        /* two compute streams: no event pairs - a pair around a launch that shares the chip with the one before it measures
-         * its wait for slots -, the kernel's own stamp is the duration (mfm_engine::stamp_pending) */
-        const bool stamped = timed && e->ncs > 1u && e->d_cyc != nullptr;
-        const bool timing = timed && e->ncs <= 1u;
-        int ti = 0;
-        if (timed) {
-            int rc = fold_timing(e, false);
-            if (rc != MFM_OK) {
-                return rc;
-            }
-        }
-        if (stamped) {
-            e->stamp_pending.push_back(e->launches);
-        }
-        if (timing) {
-            ti = (int)(e->t_head % kTimingPairs);
-            HIP_TRY(hipEventRecord(e->t0[ti], S));
-        }
-        if (raw8) {
-            e->launches_8bit++;
-        }
-        if (v3) {
-            mfm_launch_v3 V = f.V;
-            V.x = e->d_in[cur];
-            V.n_avail = n_avail;
-            V.n_new = n_new;
-            V.hist = e->hist;
-            V.k_base = e->outputs;
-            V.ntiles = v_ntiles;
-            const uint32_t slots = v_slots;
-            V.nchunks = v_nchunks;
-            V.cl = (V.ntiles + V.nchunks - 1u) / V.nchunks;
-            V.nitems = v_nitems;
-            /* the next launch's [hist | history tail]: the last consumed row and what was not consumed */
-            V.tail_src = e->hist + n_new * D - D;
-            V.tail_n = D + n_avail - n_new * D;
-            V.tail_dst = e->d_in[nxt];
-            tail_in_kernel = true;
-            if (two) {
-                V.tail_n = 0; /* the next launch must not wait for this kernel: the carry is copied on its own stream below */
-                tail_in_kernel = false;
-                e->overlapped++;
-            }
-            if (e->head) {
-                V.head = e->head;
-                V.head_n = e->hist + e->tail;
-            }
-            V.pcm = slot->d_pcm;
-            V.iq_dbg = iq_dbg;
-            if (e->d_cyc) {
-                V.cyc = e->d_cyc + 2u * (e->launches % kCycleRing);
-                V.cyc_tag = (uint32_t)((e->launches + 1u) & 0xffffffu);
-                /* ... and zeroes the slot half a ring ahead, long before that launch folds its maxima into it: a slot never
-                 * holds an older launch's stamp when its turn comes, whatever the 24-bit tags compare like after 2^24 launches */
-                V.cyc_clear = e->d_cyc + 2u * ((e->launches + kCycleRing / 2u) % kCycleRing);
-            }
-            e->grid_last = std::min(V.nitems, slots);
-            HIP_TRY(mfm_launch_channel_kernel_v3(f.kfn, &V, f.lds_bytes, e->grid_last, S));
-        } else if (1u == e->plan.variant) {
-            mfm_launch_mfma M = f.M;
-            M.x = e->d_in[cur];
-            M.n_avail = n_avail;
-            M.n_new = n_new;
-            M.ntiles = (n_new + M.ot - 1u) / M.ot;
-            M.nitems = ((M.ntiles + 7u) / 8u) * 8u * M.nslices;
-            M.tail_src = n_new * D;
-            M.tail_n = n_avail - n_new * D;
-            M.tail_dst = e->d_in[nxt];
-            tail_in_kernel = true;
-            M.st_in = st_in;
-            M.st_out = st_out;
-            M.pcm = slot->d_pcm;
-            M.iq_dbg = iq_dbg;
-            e->grid_last = std::min(M.nitems, 256u * f.wg_per_cu);
-            HIP_TRY(mfm_launch_channel_kernel_mfma(f.kfn, &M, f.lds_bytes, e->grid_last, S));
-        } else {
-            mfm_launch L = f.L;
-            const uint32_t ot = 64u * e->plan.opl;
-            L.x = e->d_in[cur];
-            L.n_avail = n_avail;
-            L.n_new = n_new;
-            L.ntiles = (n_new + ot - 2) / (ot - 1);
-            L.st_in = st_in;
-            L.st_out = st_out;
-            L.pcm = slot->d_pcm;
-            L.iq_dbg = iq_dbg;
-            e->grid_last = ((L.ntiles + 7) / 8) * 8 * L.nslices;
-            HIP_TRY(mfm_launch_channel_kernel(f.kfn, &L, f.lds_bytes, S));
-        }
-        if (timing) {
-            HIP_TRY(hipEventRecord(e->t1[ti], S));
-            timing_end = e->t1[ti];
-            e->t_head++;
-        }
-        e->parity ^= 1;
-        e->launches++;
     }
 
-    /* carry the unconsumed tail (and, for the second-generation kernel, the last consumed row in front of it) to the front
-     * of the next staging buffer (the MFMA kernels have done it themselves) */
-    const uint32_t consumed = n_new * D;
-    const uint32_t new_tail = n_avail - consumed;
-    const uint32_t new_hist = (v3 && n_new) ? D : e->hist;
     e->last_head = e->head;
-    e->last_head_n = e->head ? e->hist + e->tail : 0u;
+    e->last_head_n = e->head ? lp.head_n : 0u;
     e->head = nullptr;
-    if (early) {
-        /* (early implies a launch that consumed at least the old tail: what is copied lies behind this buffer's first
-         * hist + tail samples, in what the producer of this block wrote, and s_in is behind that producer - submit_impl.)
-         * The slot: see mfm_engine::d_ring for why nobody reads it any more. */
-        uint32_t *const dst = e->d_ring + (size_t)((e->pass + 1u) % (uint64_t)(e->nbuf + 1)) * e->ring_slot;
-        if (new_hist + new_tail > e->ring_slot) {
-            return fail(MFM_E_STATE, "carry of %u samples, ring slots of %u", new_hist + new_tail, e->ring_slot);
-        }
-        hipLaunchKernelGGL(mfm_carry_kernel, dim3(1), dim3(256), 0, e->s_in, e->d_in[cur] + e->hist + consumed - new_hist, dst,
-                           new_hist + new_tail);
-        HIP_TRY(hipGetLastError());
-        /* this buffer is free once its kernel AND this copy are through (acquire_input waits for both) */
-        HIP_TRY(hipEventRecord(e->tail_done[cur], e->s_in));
-        e->tail_pending[cur] = true;
-        e->head = dst;
-        e->head_ev = e->tail_done[cur];
-    } else if (new_hist + new_tail && !tail_in_kernel) {
-        const size_t ss = raw8 ? 2 : 4;
-        if (two && e->in_free_wait[nxt]) {
-            /* the launch that last read the next buffer may be on the other stream */
-            HIP_TRY(hipStreamWaitEvent(S_after, e->in_free_wait[nxt], 0));
-        }
-        if (two && e->tail_pending[nxt]) {
-            /* ... and so may the carry copy OUT of that buffer, when a launch in between did not alternate (ADVICE r4):
-             * a wait on a completed event costs nothing */
-            HIP_TRY(hipStreamWaitEvent(S_after, e->tail_done[nxt], 0));
-        }
-        HIP_TRY(hipMemcpyAsync(e->d_in[nxt],
-                               reinterpret_cast<const uint8_t *>(e->d_in[cur]) + ((size_t)e->hist + consumed - new_hist) * ss,
-                               ((size_t)new_hist + new_tail) * ss, hipMemcpyDeviceToDevice, S_after));
-        if (two) {
-            /* this buffer is free once its kernel AND this copy are through (acquire_input waits for both) */
-            HIP_TRY(hipEventRecord(e->tail_done[cur], S_after));
-            e->tail_pending[cur] = true;
-        }
+    int rc = queue_carry(e, lp, S_after);
+    if (rc != MFM_OK) {
+        return rc;
     }
     /* Every event record is a packet the command processor handles between two kernels (about 4 us each on
      * MI355X).  When the kernel carried the tail itself and its end is already stamped by the timing event, that
      * event also says "this input buffer is free". */
-    if (tail_in_kernel && timing_end) {
+    if (LP_CARRY_KERNEL == lp.carrier && timing_end) {
         e->in_free_wait[cur] = timing_end;
     } else {
         HIP_TRY(hipEventRecord(e->in_free[cur], S));
@@ -1306,40 +1305,27 @@ int launch_locked(mfm_engine *e)
     }
     e->in_free_on[cur] = S; /* (a later launch on the same stream is behind it anyway) */
 
-    if (n_new) {
-        slot->first_output = e->outputs;
-        slot->nr_outputs = n_new;
-        if (dev_only) {
-            /* nothing waits on slot->ready in device-only mode: consumers are ordered by the stream */
-        } else {
-            HIP_TRY(hipEventRecord(e->kernel_done, S));
-            HIP_TRY(hipStreamWaitEvent(e->s_out, e->kernel_done, 0));
-            const size_t row = (size_t)e->plan.out_stride * sizeof(int16_t);
-            HIP_TRY(hipMemcpy2DAsync(slot->h_pcm, row, slot->d_pcm, row, (size_t)n_new * sizeof(int16_t), C,
-                                     hipMemcpyDeviceToHost, e->s_out));
-            if (e->plan.any_iq) {
-                HIP_TRY(hipMemcpy2DAsync(slot->h_iq, row * 2, slot->d_iq, row * 2, (size_t)n_new * 4, C,
-                                         hipMemcpyDeviceToHost, e->s_out));
-            }
-            HIP_TRY(hipEventRecord(slot->ready, e->s_out));
-            slot->state = OutSlot::INFLIGHT;
+    if (lp.n_new) {
+        rc = queue_output(e, lp, slot, S);
+        if (rc != MFM_OK) {
+            return rc;
         }
         e->last_slot = slot_idx;
         e->s_last = S;
         e->submit_seq++;
-        e->outputs += n_new;
+        e->outputs += lp.n_new;
     }
 
-    if (two) {
+    if (lp.two) {
         e->si ^= 1u;
     }
     e->pass++;
-    e->last_launch_samples = n_avail;
+    e->last_launch_samples = lp.n_avail;
     e->last_launch_buf = cur;
     e->last_launch_fmt = fmt;
     e->last_launch_hist = e->hist;
-    e->hist = new_hist;
-    e->tail = new_tail;
+    e->hist = lp.new_hist;
+    e->tail = lp.new_tail;
     e->tail_fmt = fmt;
     e->in_fmt[cur] = MFM_IN_CS16;
     e->pend = 0;
